@@ -7,7 +7,11 @@ dropout ON, STN ON) on synthetic 16x64 -> 32x128 batches, B = 48 per GPU, fp32 (
         bench.py --gpus N --steps K --warmup W
 
 Prints ONE JSON line on rank 0.  `value` is the whole-job aggregate (weak scaling: 48 images per GPU per step).
-Extra objects: `roofline` -- the step's DOMINANT kernel, chosen from the committed per-step kernel table of the last rocprofv3 trace
+A plain run sets up, warms up, times `--steps` steps and prints the line (`ms_per_step`: one timed step).  `--dump-outputs DIR` writes
+what the last timed step computed (its loss, gradient norm and the model state it left) as DIR/<name>.npy.
+Everything else is measured or checked with `--full` only: the known-answer loss against the reference's, the sustained replay, the
+exact-fp32 step, the roofline kernel timings, the collective profile of the data-parallel step and the CPU baseline.
+Extra objects (`--full`): `roofline` -- the step's DOMINANT kernel, chosen from the committed per-step kernel table of the last rocprofv3 trace
 (profiles/step_kernel_table.json) and timed live with HIP events on the launch stream after the timed region; `frac` = ALGORITHMIC
 FLOPs (or bytes) / time / the peak of the unit the kernel actually issues on (the bf16 matrix cores for the split-bf16 kernels: the two
 extra products per fp32 product are reported separately as `mfma_pipe_util`); `roofline_hbm` / `roofline_mfma` -- the same for the
@@ -41,8 +45,12 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=50)       # >= 10 warm-up + >= 50 timed steps
     ap.add_argument("--warmup", type=int, default=10)
-    ap.add_argument("--sustain", type=int, default=450, help="steps replayed AFTER the timed region for `sustained_ms_per_step` (0: skip)")
-    ap.add_argument("--no-exact-fp32", action="store_true", help="skip the second Trainer under set_arithmetic('fp32') (`exact_fp32`)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the known-answer check, sustained replay, exact-fp32 step, roofline timings, collective profile and CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float32, at most 64 MB in all)")
+    ap.add_argument("--sustain", type=int, default=450, help="(--full) steps replayed AFTER the timed region for `sustained_ms_per_step` (0: skip)")
+    ap.add_argument("--no-exact-fp32", action="store_true", help="(--full) skip the second Trainer under set_arithmetic('fp32') (`exact_fp32`)")
     ap.add_argument("--tile", default="std", choices=sorted(TILES), help="std: 16x64 LR (headline); large: 32x128 LR, B=16, STN off")
     ap.add_argument("--batch", type=int, default=None, help="LR images per GPU per step (default: 48 std / 16 large)")
     ap.add_argument("--dp-selftest", action="store_true",
@@ -83,6 +91,62 @@ def first_step_loss(model, x, tp, hr):
         loss = float(image_loss_mean(sr, hr, scale=100.0))
     Fh.seed_tensor(x.device).copy_(seed)
     return loss
+
+
+def library_current():
+    """True when the in-tree HIP library is what tatt_amd.build would produce from the sources now (same content-hash test as the
+    build: every object's source digest and the link digest in its manifest), decided without writing anything."""
+    from tatt_amd import build as B
+    objdir = os.path.join(B.LIBDIR, "obj")
+    try:
+        with open(os.path.join(objdir, "manifest.json")) as f:
+            manifest = json.load(f)
+    except (OSError, ValueError):
+        return False
+    common = os.path.join(B.CSRC, "common.h")
+    objs = [os.path.join(objdir, s.replace(".hip", ".o")) for s in B.SOURCES]
+    if not os.path.exists(B.LIB) or not all(os.path.exists(o) for o in objs):
+        return False
+    if any(manifest.get(s) != B._digest([os.path.join(B.CSRC, s), common], B.EXTRA_FLAGS.get(s, ())) for s in B.SOURCES):
+        return False
+    return manifest.get("__lib__") == B._digest(objs)
+
+
+def load_library():
+    """Load the HIP library the build left in the tree.  The benchmark may run where the tree is read-only (built beforehand by
+    another user): it only builds -- which takes the build's lock file in the tree -- when the library is missing or stale."""
+    if not library_current():
+        from __graft_entry__ import build
+        build()
+    from tatt_amd._lib import LIB
+    LIB.load()
+
+
+DUMP_BUDGET = 60 * 2 ** 20          # bytes of array data --dump-outputs may write (the .npy headers stay well inside 64 MB)
+
+
+def dump_outputs(out_dir, loss, tr, model):
+    """What the last timed step handed its caller: the loss it returned, the gradient norm before clipping and the model state it
+    left (updated parameters, BatchNorm running statistics), as float32 DIR/<name>.npy.  Over the budget (the large tile, tatt_tpg)
+    every array of more than 4096 entries keeps the same fixed, seeded random subset of its flattened entries from run to run."""
+    import zlib
+    import numpy as np
+    arrays = {"loss": loss.detach().float().cpu().numpy(), "grad_norm": tr.last_grad_norm.detach().float().reshape(()).cpu().numpy()}
+    for k, v in model.state_dict().items():
+        if v.is_floating_point():
+            arrays["state." + k] = v.detach().float().cpu().numpy()
+    total = sum(v.nbytes for v in arrays.values())
+    if total > DUMP_BUDGET:
+        small = sum(v.nbytes for v in arrays.values() if v.size <= 4096)
+        frac = (DUMP_BUDGET - small) / (total - small)
+        for k, v in arrays.items():
+            if v.size > 4096:
+                rng = np.random.default_rng(zlib.crc32(k.encode()))
+                idx = np.sort(rng.choice(v.size, int(v.size * frac), replace=False))
+                arrays[k] = v.reshape(-1)[idx]
+    os.makedirs(out_dir, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), np.asarray(v, dtype=np.float32))
 
 
 def dominant_kernel_traffic(key, kernel):
@@ -454,8 +518,7 @@ def main():
 
     import tatt_amd
     from tatt_amd.train import Trainer
-    from __graft_entry__ import build
-    build()
+    load_library()
 
     torch.manual_seed(1234)
     model = make_model(a.arch, a.tile).to(dev).train()
@@ -463,7 +526,7 @@ def main():
     x, tp, hr = make_batch(a.batch, rank, dev, tile["H"], tile["W"])
     # known-answer check of the workload before anything is timed: this model, this batch, dropout off -> the reference's loss
     kat = None
-    if a.arch == "tatt" and rank == 0 and a.batch == tile["batch"]:
+    if a.full and a.arch == "tatt" and rank == 0 and a.batch == tile["batch"]:
         want = json.load(open(LOSS_FILE))[tile["loss_key"]]
         got = first_step_loss(model, x, tp, hr)
         assert abs(got - want) < 2e-4 * want, "first-step loss %.6f differs from the reference's %.6f" % (got, want)
@@ -499,9 +562,11 @@ def main():
     assert loss_v == loss_v, "loss is NaN"
     from tatt_amd import functional as _Fh
     _Fh.sync_check()                                 # launches that synchronise their work-groups in flight bound every spin: an expired one voids the run
-    # after the timed region: a long replay (>= 2 s of GPU time: clocks and thermals settle, the driver's busy sampler sees it) ...
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, loss, tr, model)
+    # after the timed region (--full): a long replay (>= 2 s of GPU time: clocks and thermals settle, the driver's busy sampler sees it) ...
     coll = None
-    if pg is not None:
+    if a.full and pg is not None:
         # collectives profiled OUTSIDE the timed region, over a bounded number of steps: an event pair around every wait for a collective
         # (the time the step's stream sat blocked behind it) and around every pass group
         tr.profile_collectives = True
@@ -511,7 +576,7 @@ def main():
         coll = tr.collective_report()
         tr.profile_collectives = False
     sustained = None
-    if a.sustain > 0:
+    if a.full and a.sustain > 0:
         barrier()
         t1 = time.perf_counter()
         for _ in range(a.sustain):
@@ -522,7 +587,7 @@ def main():
     # ... and the same step with exact fp32 products everywhere (the reference's arithmetic: model/tsrn.py:877,885,1071 are plain
     # nn.Conv2d / nn.GRU): a second model + Trainer built under set_arithmetic("fp32") -- captured graphs keep their kernels
     exact = None
-    if world == 1 and pg is None and not a.no_exact_fp32 and a.arch in ("tatt", "tsrn") and tatt_amd.get_arithmetic() == "split_bf16":
+    if a.full and world == 1 and pg is None and not a.no_exact_fp32 and a.arch in ("tatt", "tsrn") and tatt_amd.get_arithmetic() == "split_bf16":
         tatt_amd.set_arithmetic("fp32")
         try:
             torch.manual_seed(1234)
@@ -555,8 +620,8 @@ def main():
         ips = a.batch * world * a.steps / dt
         from tatt_amd import ops as _ops
         shape_key = "B%d_%dx%d" % (a.batch, tile["H"], tile["W"])
-        roof_other = None
-        if a.arch == "tbsrn":
+        roof, roof_other = None, None
+        if a.full and a.arch == "tbsrn":
             tf, tb, ff, fb, kbytes = time_tbsrn_attention(dev, a.batch, tile["H"] * tile["W"])
             kms, kflops = tf + tb, ff + fb
             ach = kflops / (kms * 1e-3) / 1e12
@@ -579,7 +644,7 @@ def main():
                     "mfma_pipe_util": round((3.0 if sb else 1.0) * ach / peak, 4),
                     "kernel_ms": round(kms, 4), "fwd_ms": round(tf, 4), "bwd_ms": round(tb, 4), "flops_per_launch": kflops,
                     "fwd_tflops": round(ff / (tf * 1e-3) / 1e12, 2), "bwd_tflops": round(fb / (tb * 1e-3) / 1e12, 2)}
-        else:
+        elif a.full:
             cands = pick_kernels(step_table() if (a.arch == "tatt" and a.tile == "std") else None)
             name, fn, us, nl = cands[0]
             k0 = fn(dev, a.batch, tile["H"], tile["W"])
@@ -589,7 +654,7 @@ def main():
                 if k2["bound"] != k0["bound"]:
                     roof_other = ("roofline_" + k2["bound"], roofline_block(name2, k2, us2, nl2, shape_key))
                     break
-        attn = time_tp_layer(dev, a.batch, tile["H"] * tile["W"]) if a.arch in ("tatt", "tatt_tpg") else None
+        attn = time_tp_layer(dev, a.batch, tile["H"] * tile["W"]) if a.full and a.arch in ("tatt", "tatt_tpg") else None
         out = {
             "metric": "LR images/s (train fwd+bwd+clip+Adam) at %dx%d->%dx%d" % (tile["H"], tile["W"], 2 * tile["H"], 2 * tile["W"]),
             "value": round(ips, 2), "unit": "LR images/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
@@ -631,7 +696,7 @@ def main():
             out["roofline_attn"] = attn
         if coll is not None:
             out["collectives"] = coll
-        if world == 1 and not a.no_cpu_baseline and a.arch != "tatt_tpg":
+        if a.full and world == 1 and not a.no_cpu_baseline and a.arch != "tatt_tpg":
             out["cpu_baseline"] = cpu_baseline(a.arch, a.cpu_batch if a.tile == "std" else min(a.cpu_batch, a.batch), a.tile)
         line = json.dumps(out)
     if pg is not None:

@@ -176,6 +176,57 @@ def test_bench_cpu_baseline_leg_runs_without_a_gpu():
     assert d["kind"] == "port" and d["unit"] == "LR images/s" and d["value"] > 0 and 1 <= d["cores"] <= 32
 
 
+@pytest.mark.parametrize("arch,tile", [("tatt", "std"), ("tatt", "large")])
+def test_bench_dump_outputs_bounded_and_repeatable(tmp_path, arch, tile):
+    """`bench.py --dump-outputs`: float32 .npy files, at most 64 MB in all (the large tile's 80 MB of state is sampled), the same
+    entries from call to call."""
+    import types
+    import bench
+    torch.manual_seed(1234)
+    m = bench.make_model(arch, tile)
+    tr = types.SimpleNamespace(last_grad_norm=torch.tensor([0.75]))
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), torch.tensor(37.5), tr, m)
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == sorted(os.listdir(tmp_path / "b"))
+    assert {"loss.npy", "grad_norm.npy", "state.block1.0.weight.npy"} <= set(names)
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in names) <= 64 * 2 ** 20
+    for f in names:
+        x, y = np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)
+        assert x.dtype == np.float32 and np.array_equal(x, y), f
+    assert float(np.load(tmp_path / "a" / "loss.npy")) == 37.5 and float(np.load(tmp_path / "a" / "grad_norm.npy")) == 0.75
+    if tile == "std":                                   # under the budget: every entry, in its own shape
+        w = m.state_dict()["block1.0.weight"].numpy()
+        assert np.array_equal(np.load(tmp_path / "a" / "state.block1.0.weight.npy"), w)
+
+
+def test_bench_loads_a_current_library_without_building(monkeypatch, tmp_path):
+    """bench.py may run in a tree it cannot write (built beforehand by another user): a library that is up to date is loaded without
+    the build's lock file; a stale one (a source digest that no longer matches) is rebuilt."""
+    import json
+    import shutil
+    import bench
+    import __graft_entry__
+    from tatt_amd import build as B
+    assert bench.library_current()
+    calls = []
+    monkeypatch.setattr(__graft_entry__, "build", lambda: calls.append(1))
+    bench.load_library()
+    assert calls == []
+    objdir = tmp_path / "lib" / "obj"
+    shutil.copytree(os.path.join(B.LIBDIR, "obj"), objdir)
+    shutil.copy(B.LIB, tmp_path / "lib")
+    monkeypatch.setattr(B, "LIBDIR", str(tmp_path / "lib"))
+    monkeypatch.setattr(B, "LIB", str(tmp_path / "lib" / os.path.basename(B.LIB)))
+    assert bench.library_current()
+    m = json.loads((objdir / "manifest.json").read_text())
+    m[B.SOURCES[0]] = "0" * 64
+    (objdir / "manifest.json").write_text(json.dumps(m))
+    assert not bench.library_current()
+    bench.load_library()
+    assert calls == [1]
+
+
 def test_sync_kernels_fit_beside_each_other():
     """The persistent query-GRU launches occupy EVERY CU (256 work-groups of 8 waves) while the STN head's launches -- which also wait
     for their own work-groups in flight -- run on the other lane.  A kernel of one family whose waves do not fit into the registers a
