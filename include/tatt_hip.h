@@ -650,7 +650,7 @@ int tatt_tplayer2_reduce_kv(const float* kvpart, const int* kvflags, float* dK, 
 int tatt_qgru_chain_capacity(int* out);
 int tatt_stn_capacity(int* out);
 /* Every wait inside those launches is bounded by the wall clock (2 s); one that expires raises the launch's own error word AND ORs a code
- * (1: query GRU, 2: STN head) into the device's sticky word -- one zero-initialised 32-bit word in device memory registered here, which the
+ * (1: query GRU, 2: STN head, 4: LSTM chain) into the device's sticky word -- one zero-initialised 32-bit word in device memory registered here, which the
  * library never resets (NULL unregisters). */
 int tatt_set_sticky(unsigned* word);
 /* One-thread launch that traps (GPU exception: the process dies) if the sticky word is non-zero; no-op without a registered word.  Issued
@@ -708,6 +708,26 @@ int tatt_lstm_fwd_step(const float* gi, const float* whh_f, const float* whh_r, 
  * dccarry (2,Bt,H) scratch carried between steps */
 int tatt_lstm_bwd_step(const float* dout, const float* whhT_f, const float* whhT_r, const float* cseq, const float* gsave,
                        float* dgates, float* dccarry, int T, int Bt, int H, int s, hipStream_t st);
+/* ---- eval-only kernels of the inference session (csrc/infer.hip, tatt_amd/infer.py) ---------------------------------------------- */
+/* One bidirectional LSTM layer (H = 256), forward only, all T steps in ONE launch: same tiling, products and reduction order as
+ * tatt_lstm_fwd_step (bitwise equal `out`), W_hh slice / b_hh / c state resident per work-group, h_{t-1} handed between the 16
+ * work-groups of a (row block, direction) group with bounded waits (sticky code 4).  Writes only out (T,Bt,2H); gi as for
+ * tatt_lstm_fwd_step; sync: 1024 words of workspace (zeroed by the call, word 1023 = this launch's error word).  Returns 1 for
+ * geometries it does not take (H != 256, more than 256 work-groups = cdiv(Bt,16)*32, or more than the device holds at once). */
+int tatt_lstm_fwd_chain(const float* gi, const float* whh_f, const float* whh_r, const float* bhh_f, const float* bhh_r,
+                        float* out, unsigned* sync, int T, int Bt, int H, hipStream_t st);
+/* out[0]: work-groups of the chain kernel the current device holds at once */
+int tatt_lstm_chain_capacity(int* out);
+/* eval BatchNorm folded into the preceding convolution: s_o = gamma_o / sqrt(var_o + eps), w_out[o,:] = w[o,:] s_o,
+ * b_out[o] = (bias[o] - mean[o]) s_o + beta[o] (bias may be NULL: 0).  w, w_out (Cout, K) contiguous. */
+int tatt_bn_fold(const float* w, const float* bias, const float* gamma, const float* beta, const float* mean,
+                 const float* var, float eps, float* w_out, float* b_out, int Cout, int K, hipStream_t st);
+/* greedy CTC decoding (arg-max per step, ties to the lower class; repeats merged, blank 0 dropped; classes with keep[c] == 0 dropped)
+ * of logits (T,B,C) by element strides, C <= 64, T <= 256, compared with label (B,T) int class indices / label_len (B) (< 0: cannot
+ * match).  correct (B) 0/1, counter (+= correct images), dec (B,T) padded with -1, dec_len (B): each may be NULL. */
+int tatt_ctc_greedy_match(const float* logits, long st_t, long st_b, long st_c, int T, int B, int C, const int* keep,
+                          const int* label, const int* label_len, int* correct, int* counter, int* dec, int* dec_len,
+                          hipStream_t st);
 /* out (B,OH,OW) = 0.299 R + 0.587 G + 0.114 B of F.interpolate(img[:, :3], (OH,OW), mode='bicubic') (interfaces/base.py:797-815);
  * img (B,C>=3,H,W) by element strides */
 int tatt_bicubic_luma(const float* img, long sn, long sc, long sh, long sw, float* out, int B, int H, int W, int OH,

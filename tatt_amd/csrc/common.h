@@ -31,6 +31,7 @@ static inline void tatt_per_device(TattPerDevice& s, F f) {
 unsigned* tatt_sticky_ptr();
 #define TATT_STICKY_QGRU 1u
 #define TATT_STICKY_STN 2u
+#define TATT_STICKY_LSTM 4u
 __device__ __forceinline__ void tatt_raise_sticky(unsigned* sticky, unsigned code) {
     if (sticky) __hip_atomic_fetch_or(sticky, code, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }

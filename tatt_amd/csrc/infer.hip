@@ -1,0 +1,260 @@
+// Eval-only kernels of the inference session (tatt_amd/infer.py): the CRNN's bidirectional LSTM layer as one launch, eval BatchNorm
+// folded into the preceding convolution, and greedy CTC decoding compared with the labels on the device.
+#include "common.h"
+
+// ------------------------------------------------------------------------------------------------
+// One bidirectional LSTM layer, forward only, all T steps in ONE launch (H = 256).
+//
+// Tiling and arithmetic are those of lstm_fwd_step_kernel (lstm.hip): one work-group per (16 batch rows x 16 hidden units x
+// direction), h_{t-1} W_hh^T on v_mfma_f32_16x16x4_f32 with the contraction split over the 4 waves and reduced in the same order,
+// the cell update in the epilogue -- so `out` is bitwise equal to the per-step launches.  Here the work-group keeps its W_hh slice
+// (4 gates x 16 units x this wave's 64 columns: 64 VGPRs per lane), its b_hh and its c state in registers for the whole chain, and
+// writes nothing but `out` (no cell sequence, no gate saves: there is no backward).
+//
+// What crosses work-groups per step is h_{t-1}: a tile's contraction reads the 16 rows x 256 units its (row block, direction) GROUP
+// of 16 members produced one step earlier.  Hand-off as in qgru_fwd_chain_kernel (gru.hip): the producer writes its h tile with
+// 16-byte `sc1` (write-through) stores -> s_waitcnt vmcnt(0) -> barrier -> ONE relaxed agent-scope flag store (flags[group][member] =
+// steps published); the consumer's wave 0 polls the group's 16 flags -> barrier -> `sc1` loads of the rows.  Every spin is bounded
+// by the wall clock: on expiry the launch raises flags[LCH_ERR] and the device's sticky word (TATT_STICKY_LSTM) and runs on.
+// No grid-wide barrier: only the members of one group wait on one another.  Residency: the whole grid (cdiv(Bt,16) x 16 x 2 <= 256
+// work-groups of 256 threads) must be co-resident -- tatt_lstm_fwd_chain refuses larger grids (the caller takes the step kernels).
+// ------------------------------------------------------------------------------------------------
+#define LCH_ERR 1023                       // index of the error word in the sync buffer (1024 words)
+#define LCH_SPIN_TICKS 200000000L          // 2 s of the 100 MHz wall clock
+#define LCH_H 256
+struct LstmChainP {
+    const float* gi;            // (T, Bt, 8H): [dir][gate][H] along the last axis, b_ih included
+    const float* whh[2];        // (4H, H)
+    const float* bhh[2];        // (4H)
+    float* out;                 // (T, Bt, 2H)
+    unsigned* flags;            // 1024 words, zeroed by the entry
+    unsigned* sticky;           // the device's sticky error word (common.h), may be null
+    int T, Bt;
+};
+typedef unsigned lch_u32x4 __attribute__((ext_vector_type(4)));
+__global__ __launch_bounds__(256) void lstm_fwd_chain_kernel(LstmChainP p) {
+    constexpr int H = LCH_H;
+    __shared__ float red[4][4][16][17];
+    __shared__ __attribute__((aligned(16))) float stage[16][16];
+    __shared__ int s_dead;
+    const int d = blockIdx.z, mem = blockIdx.y;
+    const int m0 = blockIdx.x * 16, j0 = mem * 16;
+    const int grp = d * gridDim.x + blockIdx.x;
+    const int t = threadIdx.x, lane = t & 63, wave = __builtin_amdgcn_readfirstlane(t >> 6);
+    const int T = p.T, Bt = p.Bt;
+    const int i = lane & 15, q = lane >> 4;
+    const int kb = wave * (H / 4);
+    const int arow = min(m0 + i, Bt - 1);
+    f32x4 b[4][4];                                                   // this wave's W_hh slice, resident for the chain
+#pragma unroll
+    for (int ss = 0; ss < 4; ++ss)
+#pragma unroll
+        for (int g = 0; g < 4; ++g)
+            b[g][ss] = *reinterpret_cast<const f32x4*>(p.whh[d] + ((long)g * H + j0 + i) * H + kb + 16 * ss + 4 * q);
+    const int m = t >> 4, j = t & 15;
+    const bool live = m0 + m < Bt;
+    const long row = m0 + m;
+    float bh[4];
+#pragma unroll
+    for (int g = 0; g < 4; ++g) bh[g] = p.bhh[d][g * H + j0 + j];
+    float c = 0.f;
+    if (t == 0) s_dead = 0;
+    __syncthreads();
+    unsigned* flags = p.flags + grp * 64;
+    const long plane = (long)Bt * 2 * H;                            // floats of one time slice of `out`
+    for (int s = 0; s < T; ++s) {
+        const int tt = d ? T - 1 - s : s, tp = d ? tt + 1 : tt - 1;
+        f32x4 acc[4];
+#pragma unroll
+        for (int g = 0; g < 4; ++g) acc[g] = (f32x4){0.f, 0.f, 0.f, 0.f};
+        if (s > 0) {
+            if (wave == 0 && !s_dead) {
+                const long t0 = wall_clock64();
+                int it = 0;
+                for (;;) {
+                    const unsigned f = lane < 16 ? __hip_atomic_load(flags + lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0xffffffffu;
+                    if (__builtin_amdgcn_ballot_w64(f < (unsigned)s) == 0) break;
+                    __builtin_amdgcn_s_sleep(1);
+                    if ((++it & 63) == 0 && wall_clock64() - t0 > LCH_SPIN_TICKS) {
+                        if (lane == 0) {
+                            s_dead = 1;
+                            __hip_atomic_store(p.flags + LCH_ERR, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                            tatt_raise_sticky(p.sticky, TATT_STICKY_LSTM);
+                        }
+                        break;
+                    }
+                }
+            }
+            __syncthreads();
+            f32x4 a[4];
+            {
+                const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(p.out + (long)tp * plane, 0, (int)(plane * 4), 0x00020000);
+                const int off = (arow * 2 * H + d * H + kb + 4 * q) * 4;
+#pragma unroll
+                for (int ss = 0; ss < 4; ++ss)
+                    a[ss] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, off + 64 * ss, 0, 16 /* sc1 */));
+            }
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int ss = 0; ss < 4; ++ss)
+#pragma unroll
+                for (int u = 0; u < 4; ++u)
+#pragma unroll
+                    for (int g = 0; g < 4; ++g)
+                        acc[g] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[ss][u], b[g][ss][u], acc[g], 0, 0, 0);
+        }
+        {
+            const int col = lane & 15, rb = (lane >> 4) * 4;
+#pragma unroll
+            for (int g = 0; g < 4; ++g)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) red[wave][g][rb + r][col] = acc[g][r];
+        }
+        __syncthreads();
+        if (live) {
+            float pre[4];
+#pragma unroll
+            for (int g = 0; g < 4; ++g)
+                pre[g] = (red[0][g][m][j] + red[1][g][m][j]) + (red[2][g][m][j] + red[3][g][m][j]) + bh[g] +
+                         p.gi[((long)tt * Bt + row) * 8 * H + (d * 4 + g) * H + j0 + j];
+            const float ig = sigmoid_f(pre[0]), fg = sigmoid_f(pre[1]), gg = tanhf(pre[2]), og = sigmoid_f(pre[3]);
+            c = __builtin_fmaf(ig, gg, fg * c);          // the contraction hipcc picks for the step kernel's fg * cp + ig * gg
+            stage[m][j] = og * tanhf(c);
+        }
+        __syncthreads();
+        if (t < 64) {                                                // 16 rows x 4 sixteen-byte pieces
+            const int r = t >> 2, j4 = (t & 3) * 4;
+            if (m0 + r < Bt) {
+                const f32x4 v = *reinterpret_cast<const f32x4*>(&stage[r][j4]);
+                const __amdgpu_buffer_rsrc_t ws = __builtin_amdgcn_make_buffer_rsrc(p.out + (long)tt * plane, 0, (int)(plane * 4), 0x00020000);
+                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(lch_u32x4, v), ws, ((m0 + r) * 2 * H + d * H + j0 + j4) * 4, 0, 16 /* sc1 */);
+            }
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        }
+        __syncthreads();
+        if (t == 0) __hip_atomic_store(flags + mem, (unsigned)(s + 1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+}
+
+// asked once per device (the first call is eager: the session's warm-up runs before it captures)
+static int lstm_chain_capacity_now() {
+    static std::mutex mu;
+    static int cap[64];
+    static bool known[64] = {};
+    int dev = 0, cus = 0, n = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return -1;
+    std::lock_guard<std::mutex> lk(mu);
+    if (!known[dev]) {
+        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return -1;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, reinterpret_cast<const void*>(lstm_fwd_chain_kernel), 256, 0) != hipSuccess) return -1;
+        cap[dev] = n * cus;
+        known[dev] = true;
+    }
+    return cap[dev];
+}
+
+// gi (T, Bt, 8H) incl. b_ih, whh* (4H, H), bhh* (4H), out (T, Bt, 2H), sync: 1024 words of workspace (zeroed here; word LCH_ERR is
+// the launch's error word).  Returns 1 for geometries it does not take (H != 256, a grid of more than 256 work-groups or more than
+// the device holds at once): the caller runs the per-step kernels instead.
+TATT_API int tatt_lstm_fwd_chain(const float* gi, const float* whh_f, const float* whh_r, const float* bhh_f, const float* bhh_r,
+                                 float* out, unsigned* sync, int T, int Bt, int H, hipStream_t st) {
+    if (H != LCH_H || Bt <= 0 || T <= 0) return 1;
+    const int nrb = cdiv(Bt, 16), grid = nrb * (H / 16) * 2;
+    if (grid > 256 || (2 * nrb - 1) * 64 + 16 > LCH_ERR) return 1;     // flags[group * 64 + member] stay below the error word
+    if (grid > lstm_chain_capacity_now()) return 1;
+    if (hipMemsetAsync(sync, 0, 1024 * sizeof(unsigned), st) != hipSuccess) return 3;
+    LstmChainP p = {gi, {whh_f, whh_r}, {bhh_f, bhh_r}, out, sync, tatt_sticky_ptr(), T, Bt};
+    hipLaunchKernelGGL(lstm_fwd_chain_kernel, dim3(nrb, H / 16, 2), dim3(256), 0, st, p);
+    return LAUNCH_CHECK();
+}
+
+// out[0]: work-groups of lstm_fwd_chain_kernel the CURRENT device holds at once (occupancy per CU x CUs the process sees).
+TATT_API int tatt_lstm_chain_capacity(int* out) {
+    const int n = lstm_chain_capacity_now();
+    if (n < 0) return 1;
+    out[0] = n;
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------------
+// Eval BatchNorm folded into the preceding convolution: per output channel o, s = gamma_o / sqrt(var_o + eps),
+//   w'[o, :] = w[o, :] * s,   b'_o = (b_o - mean_o) * s + beta_o     (a missing conv bias counts as 0)
+// w, w_out (Cout, K) contiguous.  One work-group per output channel.
+// ------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void bn_fold_kernel(const float* __restrict__ w, const float* __restrict__ bias,
+                                                      const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                      const float* __restrict__ mean, const float* __restrict__ var, float eps,
+                                                      float* __restrict__ w_out, float* __restrict__ b_out, int K) {
+    const int o = blockIdx.x;
+    const float s = gamma[o] / sqrtf(var[o] + eps);
+    const float* src = w + (long)o * K;
+    float* dst = w_out + (long)o * K;
+    for (int k = threadIdx.x; k < K; k += blockDim.x) dst[k] = src[k] * s;
+    if (threadIdx.x == 0) b_out[o] = ((bias ? bias[o] : 0.f) - mean[o]) * s + beta[o];
+}
+TATT_API int tatt_bn_fold(const float* w, const float* bias, const float* gamma, const float* beta, const float* mean,
+                          const float* var, float eps, float* w_out, float* b_out, int Cout, int K, hipStream_t st) {
+    if (Cout <= 0 || K <= 0) return 1;
+    hipLaunchKernelGGL(bn_fold_kernel, dim3(Cout), dim3(256), 0, st, w, bias, gamma, beta, mean, var, eps, w_out, b_out, K);
+    return LAUNCH_CHECK();
+}
+
+// ------------------------------------------------------------------------------------------------
+// Greedy CTC decoding compared with encoded labels (the reference's get_string_crnn + str_filt + string equality, as
+// io.ctc_greedy_decode does it): per image the arg-max class of every step (ties to the lowest index, as torch.argmax), repeats
+// merged and blank 0 dropped, then the classes the keep mask excludes dropped; the result is compared with label[b][0 .. len_b)
+// (class indices, len_b < 0: a label that cannot match).  One wave per image, lane = class (C <= 64).
+// logits (T, B, C) by element strides; keep (C) int; label (B, T) int; label_len (B) int.
+// Outputs (each may be NULL): correct (B) 0/1; counter: += number of correct images (one vector atomic per image);
+// dec (B, T) the decoded classes after the keep mask, padded with -1; dec_len (B).
+// ------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(64) void ctc_greedy_match_kernel(const float* __restrict__ logits, long st_t, long st_b, long st_c, int T,
+                                                              int C, const int* __restrict__ keep, const int* __restrict__ label,
+                                                              const int* __restrict__ label_len, int* correct, int* counter,
+                                                              int* dec, int* dec_len) {
+    __shared__ int amax[256];
+    const int bidx = blockIdx.x, lane = threadIdx.x;
+    for (int t = 0; t < T; ++t) {
+        float v = lane < C ? logits[t * st_t + bidx * st_b + lane * st_c] : -INFINITY;
+        int k = lane < C ? lane : 0x7fffffff;
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            const float v2 = __shfl_xor(v, o, 64);
+            const int k2 = __shfl_xor(k, o, 64);
+            // a NaN wins over any number (torch.argmax), ties and NaN against NaN go to the lower class
+            const bool take = k2 != 0x7fffffff && ((v2 != v2) ? (v == v || k2 < k) : (v == v && (v2 > v || (v2 == v && k2 < k))));
+            if (take) { v = v2; k = k2; }
+        }
+        if (lane == 0) amax[t] = k;
+    }
+    __syncthreads();
+    if (lane != 0) return;
+    const int L = label_len[bidx];
+    int n = 0, last = 0;
+    bool ok = L >= 0;
+    for (int t = 0; t < T; ++t) {
+        const int c = amax[t];
+        if (c != last) {
+            if (c != 0 && keep[c]) {
+                if (dec) dec[(long)bidx * T + n] = c;
+                if (ok && (n >= L || label[(long)bidx * T + n] != c)) ok = false;
+                ++n;
+            }
+            last = c;
+        }
+    }
+    if (n != L) ok = false;
+    if (dec)
+        for (int r = n; r < T; ++r) dec[(long)bidx * T + r] = -1;
+    if (dec_len) dec_len[bidx] = n;
+    if (correct) correct[bidx] = ok ? 1 : 0;
+    if (counter && ok) atomicAdd(counter, 1);
+}
+TATT_API int tatt_ctc_greedy_match(const float* logits, long st_t, long st_b, long st_c, int T, int B, int C, const int* keep,
+                                   const int* label, const int* label_len, int* correct, int* counter, int* dec, int* dec_len,
+                                   hipStream_t st) {
+    if (T <= 0 || T > 256 || B <= 0 || C <= 0 || C > 64) return 1;
+    hipLaunchKernelGGL(ctc_greedy_match_kernel, dim3(B), dim3(64), 0, st, logits, st_t, st_b, st_c, T, C, keep, label, label_len,
+                       correct, counter, dec, dec_len);
+    return LAUNCH_CHECK();
+}

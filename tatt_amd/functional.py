@@ -1695,8 +1695,14 @@ def sync_check():
         if code:
             raise RuntimeError("tatt_amd: a launch that synchronises its work-groups in flight gave up waiting on cuda:%d (%s): its "
                                "results -- and everything computed from them since -- are invalid (work-groups not co-resident?)" % (
-                                   idx, " + ".join(n for b, n in ((1, "query-GRU chain"), (2, "STN head")) if code & b)))
+                                   idx, " + ".join(n for b, n in ((1, "query-GRU chain"), (2, "STN head"), (4, "LSTM chain")) if code & b)))
     qgru_chain_check()
+    from . import infer as _infer
+    for r in _infer.LSTM_SYNC:
+        s = r()
+        if s is not None and int(s[1023].item()) != 0:
+            raise RuntimeError("tatt_amd: a one-launch LSTM layer (tatt_lstm_fwd_chain) gave up waiting for its neighbours (work-groups not "
+                               "co-resident?)")
     for r in STN_SYNC:
         s = r()
         if s is not None and int(s[255].item()) != 0:

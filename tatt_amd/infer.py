@@ -1,0 +1,515 @@
+"""Graph-captured inference: the reference's eval / test loop (interfaces/super_resolution.py:1203-1700, `model_inference` for `tatt`:
+CRNN prior on LR -> generator in eval mode -> recogniser on SR / LR / HR, PSNR and SSIM) as ONE replayed hipGraph per batch size.
+
+`InferenceSession` runs an eval-only forward of its own:
+  * eval BatchNorm is folded into the preceding convolution on the device (tatt_bn_fold): residual blocks' conv1 + bn1 (mish in the
+    convolution's epilogue), conv2 + bn2, block 7, the CRNN's conv2 / 4 / 6 + BatchNorm (ReLU epilogue).  The folded filters are
+    tensors the session owns, packed through the ordinary `ops.PACKED` cache;
+  * each CRNN BiLSTM layer is one launch (tatt_lstm_fwd_chain: W_hh resident per work-group, no cell / gate saves) instead of T;
+  * everything runs under `torch.no_grad()`, so no operator keeps anything for a backward (GruBlocks take their save=False path);
+  * greedy CTC decoding and the label comparison run on the device (tatt_ctc_greedy_match): no host wait inside a batch.
+TBSRN generators are captured as they are (their own eval forward, no folding).
+The operators between those (GruBlocks, TP interpreter, convolutions, activations) are the generators' own helpers, i.e. the autograd
+Functions of `functional`, called under `no_grad`: their `needs_input_grad` is all False, so they save nothing and the GruBlocks
+take their save=False path, and inside the replayed graph the Function layer costs no GPU time.
+
+`evaluate_session` is the drop-in for `tatt_amd.io.evaluate` built on it: every accumulator lives on the device, one host sync at
+the end.  Neither changes the modules' state (training flags, parameters, running statistics, `num_batches_tracked`).
+"""
+from __future__ import annotations
+
+import ctypes
+import weakref
+from typing import Iterable, Optional, Sequence
+
+import torch
+
+from . import functional as Fh
+from . import ops
+from ._lib import LIB
+from .ops import ACT_MISH, ACT_RELU, ACT_TANH
+from .io import ALPHABET, str_filt
+
+# A/B hook: False -> the CRNN's LSTM layers run the per-step kernels (tatt_lstm_fwd_step) inside the session as well
+LSTM_CHAIN = True
+LSTM_SYNC = []           # weak references to the sync buffers handed to tatt_lstm_fwd_chain (functional.sync_check reads word 1023)
+LABEL_RING = 4           # pinned host slots the label encoding of consecutive batches rotates through
+CTC_T = 26               # steps of the recogniser's output for its 100-pixel input (parse_crnn_data): W / 4 + 1
+D2A = "-" + ALPHABET     # class c -> character (class 0 is the CTC blank)
+
+
+# ---- host-side label plumbing ---------------------------------------------------------------------------------------------------
+def keep_mask(voc_type: str = "lower") -> list:
+    """37 entries: 1 where `str_filt` keeps the class's character (the blank is never kept)."""
+    return [0] + [1 if str_filt(ch, voc_type) == ch else 0 for ch in ALPHABET]
+
+
+def encode_labels(labels: Sequence[str], voc_type: str = "lower", T: int = CTC_T):
+    """-> (codes: B lists of T class indices padded with -1, lengths: B ints).  A label is filtered with `str_filt` first; one that holds
+    a character outside ALPHABET (upper case under 'upper', punctuation under 'all') or more than T characters can never equal a
+    greedy decoding and gets length -1."""
+    a2d = {ch: i for i, ch in enumerate(D2A)}
+    codes, lens = [], []
+    for lab in labels:
+        s = str_filt(lab, voc_type)
+        ids = [a2d.get(ch, -1) for ch in s]
+        if len(ids) > T or any(i <= 0 for i in ids):
+            codes.append([-1] * T)
+            lens.append(-1)
+        else:
+            codes.append(ids + [-1] * (T - len(ids)))
+            lens.append(len(ids))
+    return codes, lens
+
+
+# ---- device entry points --------------------------------------------------------------------------------------------------------
+def bn_fold(weight, bias, bn, w_out=None, b_out=None):
+    """Eval BatchNorm `bn` folded into the convolution (weight, bias) -> (w_out, b_out), computed by tatt_bn_fold."""
+    ops._check_dev(weight)
+    Cout = weight.shape[0]
+    w_out = torch.empty_like(weight, memory_format=torch.contiguous_format) if w_out is None else w_out
+    b_out = ops.new(weight, Cout) if b_out is None else b_out
+    gamma = bn.weight if bn.affine else torch.ones(Cout, device=weight.device)
+    beta = bn.bias if bn.affine else torch.zeros(Cout, device=weight.device)
+    ops.call("tatt_bn_fold", ops.P(weight.contiguous()), ops.P(bias), ops.P(gamma), ops.P(beta), ops.P(bn.running_mean),
+             ops.P(bn.running_var), float(bn.eps), ops.P(w_out), ops.P(b_out), Cout, weight.numel() // Cout, ops.stream())
+    return w_out, b_out
+
+
+def ctc_greedy_match(logits, keep, label, label_len, counter=None, want_decoded=False):
+    """logits (T, B, C) on the GPU; keep (C,) / label (B, T) / label_len (B,) int32 device tensors -> correct (B,) int32
+    [, decoded (B, T) int32 padded with -1, lengths (B,)].  `counter` (int32 device scalar): += number of correct images."""
+    ops._check_dev(logits)
+    T, B, C = logits.shape
+    correct = torch.empty(B, dtype=torch.int32, device=logits.device)
+    dec = torch.empty(B, T, dtype=torch.int32, device=logits.device) if want_decoded else None
+    dlen = torch.empty(B, dtype=torch.int32, device=logits.device) if want_decoded else None
+    ops.call("tatt_ctc_greedy_match", ops.P(logits), *logits.stride(), T, B, C, ops.P(keep), ops.P(label), ops.P(label_len),
+             ops.P(correct), ops.P(counter), ops.P(dec), ops.P(dlen), ops.stream())
+    return (correct, dec, dlen) if want_decoded else correct
+
+
+def lstm_chain_capacity(device=None) -> int:
+    out = (ctypes.c_int * 1)()
+    with torch.cuda.device(device if device is not None else torch.cuda.current_device()):
+        ops.call("tatt_lstm_chain_capacity", out)
+    return int(out[0])
+
+
+def _lstm_sync(ref):
+    buf = torch.zeros(1024, dtype=torch.int32, device=ref.device)
+    LSTM_SYNC[:] = [r for r in LSTM_SYNC if r() is not None]
+    LSTM_SYNC.append(weakref.ref(buf))
+    return buf
+
+
+def lstm_input_projection(x, rnn):
+    """gi (T * B, 8H) = x W_ih^T + b_ih of both directions ([forward | reverse] x gates), the operand of the recurrence kernels."""
+    T, B, I = x.shape
+    H = rnn.weight_hh_l0.shape[1]
+    x2 = Fh._c(x).reshape(T * B, I)
+    gi = ops.new(x, T * B, 8 * H)
+    ops.linear_fwd(x2, rnn.weight_ih_l0, rnn.bias_ih_l0, out=gi[:, :4 * H])
+    ops.linear_fwd(x2, rnn.weight_ih_l0_reverse, rnn.bias_ih_l0_reverse, out=gi[:, 4 * H:])
+    return gi
+
+
+def bilstm_eval(x, rnn, sync=None, chain=None):
+    """nn.LSTM(I, H, bidirectional=True) holder on a time-major (T, B, I) sequence, forward only -> (T, B, 2H).  The input projection
+    is the GEMM BiLSTMFn uses; the recurrence is ONE tatt_lstm_fwd_chain launch where it takes the geometry, else the per-step kernels
+    (with scratch for what they save).  `sync`: the chain's 1024-word workspace (allocated here when None)."""
+    chain = LSTM_CHAIN if chain is None else chain
+    T, B, I = x.shape
+    H = rnn.weight_hh_l0.shape[1]
+    gi = lstm_input_projection(x, rnn)
+    out = ops.new(x, T, B, 2 * H)
+    whh_f, whh_r, bhh_f, bhh_r = rnn.weight_hh_l0, rnn.weight_hh_l0_reverse, rnn.bias_hh_l0, rnn.bias_hh_l0_reverse
+    if chain:
+        if sync is None:
+            sync = _lstm_sync(x)
+        rc = getattr(LIB, "tatt_lstm_fwd_chain")(ops.P(gi), ops.P(whh_f), ops.P(whh_r), ops.P(bhh_f), ops.P(bhh_r), ops.P(out),
+                                                 ops.P(sync), T, B, H, ops.stream())
+        if rc == 0:
+            return out
+        if rc != 1:
+            raise RuntimeError("tatt_lstm_fwd_chain failed with code %d" % rc)
+    cseq, gsave = ops.new(x, 2, T, B, H), ops.new(x, 2, T, B, 4, H)
+    for s in range(T):
+        ops.call("tatt_lstm_fwd_step", ops.P(gi), ops.P(whh_f), ops.P(whh_r), ops.P(bhh_f), ops.P(bhh_r), ops.P(out), ops.P(cseq),
+                 ops.P(gsave), T, B, H, s, ops.stream())
+    return out
+
+
+# ---- the session ------------------------------------------------------------------------------------------------------------------
+class _Fold:
+    """conv (weight, bias) + eval BatchNorm -> a folded filter the session owns (refolded in place when the sources change)."""
+
+    def __init__(self, conv, bn):
+        self.conv, self.bn = conv, bn
+        w = conv.weight
+        self.w = torch.empty(w.shape, device=w.device, dtype=torch.float32)
+        self.b = ops.new(w, w.shape[0])
+        self.run()
+
+    def run(self):
+        bn_fold(self.conv.weight, self.conv.bias, self.bn, self.w, self.b)
+
+
+def _check_module(m, what):
+    if m is None:
+        return
+    p = next(m.parameters(), None)
+    if p is None or not p.is_cuda:
+        raise RuntimeError("tatt_amd.infer: the %s must live on an AMD GPU (found %s); the product path has no CPU fallback (the CPU "
+                           "restatement lives in oracle/ and is test infrastructure)." % (what, "no parameters" if p is None else p.device))
+
+
+def _crnn_folds(crnn):
+    return {i: _Fold(getattr(crnn.cnn, "conv%d" % i), getattr(crnn.cnn, "batchnorm%d" % i))
+            for i in range(7) if hasattr(crnn.cnn, "batchnorm%d" % i)}
+
+
+class InferenceSession:
+    """One eval pass -- [prior CRNN on LR ->] generator [-> PSNR / SSIM against HR] [-> recogniser + greedy CTC match on the images
+    named in `accuracy_on`] -- captured as ONE hipGraph for a fixed batch size and replayed by `run`.
+
+    generator: TSRN / TSRN_TL_TRANS (folded eval forward of the session's own) or TBSRN (its own eval forward, captured as is);
+    prior: optional CRNN applied as text_prior(prior(parse_crnn_data(lr))) (the reference's model_inference for `tatt`);
+    recognizer: optional CRNN whose greedy decodings of the images in `accuracy_on` ("sr", "lr", "hr") are compared with the labels.
+
+    Weights contract: every `run` compares the version counters of all parameters and buffers of the three modules (host side, no
+    sync); after a change torch sees (load_state_dict, a `.data` copy, an optimiser step) the folded filters and the packed layouts are
+    rebuilt eagerly in the same buffers before the replay.  Writes torch cannot see (raw pointers) need `refresh()`.  A parameter that
+    moved to another address means a new capture, done automatically.
+    The arithmetic (`tatt_amd.set_arithmetic`) is the one in force at capture time: changing it later needs a new session."""
+
+    def __init__(self, generator, prior=None, recognizer=None, batch_size: int = None, lr_size=(16, 64), accuracy_on=("sr",),
+                 voc_type: str = "lower"):
+        from .tsrn import TSRN, TSRN_TL_TRANS
+        from .tbsrn import TBSRN
+        _check_module(generator, "generator")
+        _check_module(prior, "prior CRNN")
+        _check_module(recognizer, "recogniser CRNN")
+        if not isinstance(generator, (TSRN, TSRN_TL_TRANS, TBSRN)):
+            raise TypeError("InferenceSession takes a TSRN, TSRN_TL_TRANS or TBSRN generator, got %s" % type(generator).__name__)
+        if not (isinstance(batch_size, int) and batch_size > 0):
+            raise ValueError("batch_size must be a positive int")
+        bad = set(accuracy_on) - {"sr", "lr", "hr"}
+        if bad:
+            raise ValueError("accuracy_on takes 'sr', 'lr', 'hr'; got %s" % sorted(bad))
+        self.gen, self.prior, self.rec = generator, prior, recognizer
+        self.B, self.lr_size, self.accuracy_on, self.voc_type = batch_size, tuple(lr_size), tuple(accuracy_on), voc_type
+        self.device = next(generator.parameters()).device
+        self.is_tatt = isinstance(generator, TSRN_TL_TRANS)
+        self.fold_gen = isinstance(generator, (TSRN, TSRN_TL_TRANS))
+        Fh.sticky_word(self.device)                               # (outside any capture)
+        with torch.no_grad():
+            self._folds = {}
+            if self.fold_gen:
+                k = generator.srb_nums
+                for i in range(k):
+                    blk = getattr(generator, "block%d" % (i + 2))
+                    self._folds["srb%d" % i] = (_Fold(blk.conv1, blk.bn1), _Fold(blk.conv2, blk.bn2))
+                b7 = getattr(generator, "block%d" % (k + 2))
+                self._folds["b7"] = _Fold(b7[0], b7[1])
+            self._crnn_folds = {id(m): _crnn_folds(m) for m in (prior, recognizer) if m is not None}
+        self._keep = torch.tensor(keep_mask(voc_type), dtype=torch.int32, device=self.device)
+        self.psnr_sum = torch.zeros((), device=self.device)
+        self.ssim_sum = torch.zeros((), device=self.device)
+        self.correct = torch.zeros(3, dtype=torch.int32, device=self.device)      # sr, lr, hr
+        self.graph = None
+        self._syncs, self._sync_i = [], 0
+        self._sources = [t for m in (generator, prior, recognizer) if m is not None
+                         for t in list(m.parameters()) + list(m.buffers())]
+        self._seen = self._snapshot()
+
+    # -- weights contract ------------------------------------------------------------------------------------------------------------
+    def _snapshot(self):
+        return tuple(t._version for t in self._sources), tuple(t.data_ptr() for t in self._sources)
+
+    def _all_folds(self):
+        out = [f for pair in self._folds.values() for f in (pair if isinstance(pair, tuple) else (pair,))]
+        return out + [f for d in self._crnn_folds.values() for f in d.values()]
+
+    def _repack(self, force):
+        """Packed layouts the graph reads: of the folded filters (always rebuilt: their version counters never move) and of the modules'
+        own filters (rebuilt when their version changed, or all of them with `force`).  Same buffers, so the captured pointers hold."""
+        owned = [f.w for f in self._all_folds()]
+        params = [p for m in (self.gen, self.prior, self.rec) if m is not None for p in m.parameters() if p.dim() == 4]
+        for w, always in [(w, True) for w in owned] + [(p, force) for p in params]:
+            h = getattr(w, "_tatt_packed", None)
+            if h is None or h.key != (w.data_ptr(), tuple(w.shape), str(w.device)):
+                continue
+            for mode, (buf, ver) in list(h.bufs.items()):
+                if always or ver != w._version:
+                    Cout, Cin, KH, KW = w.shape
+                    ops.call("tatt_repack_conv_weight", ops.P(w), ops.P(buf), Cout, Cin, KH, KW, mode, ops.stream())
+                    h.bufs[mode] = (buf, w._version)
+
+    def refresh(self, force: bool = True):
+        """Re-fold and re-pack now (eager launches into the buffers the graph reads).  Call it after writing weights through raw
+        pointers; `run` does it by itself for changes torch sees."""
+        with torch.no_grad():
+            for f in self._all_folds():
+                f.run()
+            self._repack(force)
+        # versions only: a tensor that moved since the capture still makes the next run re-capture
+        self._seen = (self._snapshot()[0], self._seen[1])
+
+    def _check_weights(self):
+        snap = self._snapshot()
+        if snap == self._seen:
+            return
+        if snap[1] != self._seen[1]:                              # storage moved: the captured pointers are stale
+            with torch.no_grad():
+                for f in self._all_folds():
+                    f.run()
+            self.graph = None
+            self._seen = snap
+            return
+        self.refresh(force=False)
+
+    # -- the eval forward ------------------------------------------------------------------------------------------------------------
+    def _sync(self, ref):
+        if self._sync_i == len(self._syncs):
+            self._syncs.append(_lstm_sync(ref))
+        s = self._syncs[self._sync_i]
+        self._sync_i += 1
+        return s
+
+    def _crnn(self, crnn, img):
+        """CRNN.forward (crnn.py) with BatchNorm folded and the chained LSTM layers: img (B, 1, 32, W) -> logits (W/4 + 1, B, 37)."""
+        from .crnn import CRNN
+        folds = self._crnn_folds[id(crnn)]
+        h = img.permute(0, 2, 3, 1)
+        for i in range(7):
+            conv = getattr(crnn.cnn, "conv%d" % i)
+            w, b = (folds[i].w, folds[i].b) if i in folds else (conv.weight, conv.bias)
+            if conv.kernel_size == (3, 3):
+                h = Fh.conv2d(h, w, b, ACT_RELU, any_width=True)
+            else:
+                h = Fh.ActFn.apply(Fh.Conv2x2ValidFn.apply(Fh._c(h), w, b), ACT_RELU)
+            if i in CRNN._POOLS:
+                h = Fh.max_pool(h, *CRNN._POOLS[i])
+        B, Hh, Wd, C = h.shape
+        seq = Fh.Permute4dFn.apply(h, (2, 1, 0, 3)).reshape(Wd, B, C)
+        for blk in crnn.rnn:
+            seq = Fh.linear(bilstm_eval(seq, blk.rnn, self._sync(seq)), blk.embedding.weight, blk.embedding.bias)
+        return seq
+
+    def _generator(self, x, tp):
+        """TSRN / TSRN_TL_TRANS eval forward (tsrn._GeneratorBase._trunk_forward with training False) on folded BatchNorms."""
+        from .tsrn import _gru_block, _nchw, _query_pos, _tp_interpreter
+        m = self.gen
+        k = m.srb_nums
+        qpos = _query_pos(m.infoGen, x.shape[0], x.shape[2], x.shape[3]) if self.is_tatt else None
+        if k > 0:
+            Fh.gru_precompose([g for i in range(k) for g in (getattr(m, "block%d" % (i + 2)).gru1, getattr(m, "block%d" % (i + 2)).gru2)])
+        xin = x.permute(0, 2, 3, 1)
+        c1 = m.block1[0]
+        b1 = Fh.prelu(Fh.conv2d(xin, c1.weight, c1.bias), m.block1[1].weight)
+        tp_map = pr_weights = None
+        if self.is_tatt:
+            tp_map, pr_weights = _tp_interpreter(b1, tp.float(), m.infoGen, False, qpos, None)
+        h = b1
+        for i in range(k):
+            blk = getattr(m, "block%d" % (i + 2))
+            f1, f2 = self._folds["srb%d" % i]
+            r = Fh.conv2d(h, f1.w, f1.b, ACT_MISH)                          # conv1 + bn1 + mish
+            r = Fh.conv2d(r, f2.w, f2.b)                                    # conv2 + bn2
+            r = _gru_block(r, blk.gru1, True, x_cat=tp_map)
+            h = _gru_block(Fh.add(h, r), blk.gru2, False)
+        f7 = self._folds["b7"]
+        h = Fh.conv2d(h, f7.w, f7.b)
+        b8 = getattr(m, "block%d" % (k + 3))
+        u = Fh.add(b1, h)
+        for up in list(b8)[:-1]:
+            u = Fh.PixelShuffleActFn.apply(Fh.conv2d(u, up.conv.weight, up.conv.bias), ACT_MISH)
+        last = b8[len(b8) - 1]
+        sr = Fh.ActFn.apply(Fh.conv2d(u, last.weight, last.bias), ACT_TANH)
+        Fh.gru_precompose_done()
+        return _nchw(sr), pr_weights
+
+    def _forward(self):
+        from .crnn import parse_crnn_data, text_prior
+        self._sync_i = 0
+        lr, hr, tp = self._lr, self._hr, self._tp
+        prior = None
+        if self.prior is not None:
+            prior = text_prior(self._crnn(self.prior, parse_crnn_data(lr)))
+            tp = prior
+        if self.fold_gen:
+            sr, pr_weights = self._generator(lr, tp)
+        else:
+            sr, pr_weights = self.gen(lr), None
+        if hr is not None:
+            from .losses import SSIM
+            from .train import calculate_psnr
+            self.psnr_sum += calculate_psnr(sr[:, :3], hr[:, :3])
+            self.ssim_sum += SSIM()(sr[:, :3], hr[:, :3])
+        if self.rec is not None and self._labels is not None:
+            from .crnn import parse_crnn_data
+            imgs = {"sr": sr, "lr": lr, "hr": hr}
+            self._logits = {}
+            for name in self.accuracy_on:
+                if imgs[name] is None:
+                    continue
+                logits = self._crnn(self.rec, parse_crnn_data(imgs[name][:, :3].contiguous()))
+                if logits.shape[0] != CTC_T:
+                    raise RuntimeError("recogniser output has %d steps, the label buffers %d" % (logits.shape[0], CTC_T))
+                self._logits[name] = logits
+                ctc_greedy_match(logits, self._keep, self._labels[0], self._labels[1], self.correct[("sr", "lr", "hr").index(name):])
+        return sr, pr_weights, prior
+
+    # -- capture and replay ----------------------------------------------------------------------------------------------------------
+    def _stage_inputs(self, lr, hr, labels, text_prior):
+        self._lr.copy_(lr)
+        if hr is not None:
+            self._hr.copy_(hr)
+        if text_prior is not None:
+            self._tp.copy_(text_prior)
+        if labels is not None and self._labels is not None:
+            # encoded on the host into the next pinned staging slot and copied asynchronously: no host wait on the GPU per batch.  A slot
+            # is rewritten only after its previous copy has been consumed (its event; LABEL_RING slots keep the host that far ahead)
+            codes, lens = encode_labels(labels, self.voc_type)
+            k = self._ring_i % LABEL_RING
+            self._ring_i += 1
+            host, ev = self._lab_host[k], self._lab_events[k]
+            if ev is not None:
+                ev.synchronize()
+            n = self.B * CTC_T
+            host[:n].copy_(torch.tensor(codes, dtype=torch.int32).reshape(-1))
+            host[n:].copy_(torch.tensor(lens, dtype=torch.int32))
+            self._lab_dev.copy_(host, non_blocking=True)
+            ev = self._lab_events[k] = ev if ev is not None else torch.cuda.Event()
+            ev.record()
+
+    def _build(self, lr, hr, labels, text_prior):
+        dev = self.device
+        self._lr = torch.empty_like(lr, memory_format=torch.contiguous_format)
+        self._hr = None if hr is None else torch.empty_like(hr, memory_format=torch.contiguous_format)
+        self._tp = None
+        if self.is_tatt and self.prior is None:
+            self._tp = torch.zeros(1, 37, 1, 26, device=dev) if text_prior is None else torch.empty_like(text_prior)
+        self._labels = None
+        if labels is not None and self.rec is not None:
+            n = self.B * CTC_T
+            self._lab_dev = torch.full((n + self.B,), -1, dtype=torch.int32, device=dev)        # codes (B, T) | lengths (B)
+            self._labels = (self._lab_dev[:n].view(self.B, CTC_T), self._lab_dev[n:])
+            self._lab_host = [torch.empty(n + self.B, dtype=torch.int32, pin_memory=True) for _ in range(LABEL_RING)]
+            self._lab_events, self._ring_i = [None] * LABEL_RING, 0
+        self._has = (hr is not None, labels is not None, text_prior is not None)
+        self._stage_inputs(lr, hr, labels, text_prior)
+        acc = (self.psnr_sum.clone(), self.ssim_sum.clone(), self.correct.clone())
+        self._forward()                                          # eager warm-up: workspaces, packed layouts, sync buffers
+        self.psnr_sum.copy_(acc[0]); self.ssim_sum.copy_(acc[1]); self.correct.copy_(acc[2])
+        torch.cuda.synchronize(dev)
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g):
+            self._out = self._forward()
+        self.graph = g
+
+    def run(self, lr, hr=None, labels: Optional[Sequence[str]] = None, text_prior=None):
+        """One eval pass on a batch of `batch_size` LR images (B, C, h, w) [with HR images for PSNR / SSIM, label strings for the
+        accuracies, a text prior (B, 37, 1, 26) for a TATT generator without a prior CRNN].  The first call runs eagerly once and
+        captures; later calls copy the inputs into the session's static buffers and replay the graph.
+        Returns (sr, pr_weights, prior) -- None where the configuration has none.  The tensors are the graph's static outputs:
+        the NEXT run overwrites them (clone what must survive), as with `Trainer.step`."""
+        from .tsrn import _require_gpu
+        _require_gpu(lr)
+        if hr is not None:
+            _require_gpu(hr)
+        if lr.dim() != 4 or lr.shape[0] != self.B or tuple(lr.shape[2:]) != self.lr_size:
+            raise ValueError("session built for (%d, C, %d, %d) LR batches, got %s" % ((self.B,) + self.lr_size + (tuple(lr.shape),)))
+        if labels is not None and len(labels) != self.B:
+            raise ValueError("%d labels for a batch of %d" % (len(labels), self.B))
+        if text_prior is not None and self.prior is not None:
+            raise ValueError("the session computes its text prior with its prior CRNN")
+        saved = [(sub, sub.training) for sub in self.gen.modules()] if not self.fold_gen and self.graph is None else []
+        fork = (Fh.FWD_FORK.enabled, Fh.FWD_FORK_B.enabled)
+        Fh.FWD_FORK.enabled = Fh.FWD_FORK_B.enabled = False      # one stream: no parallel branches in the captured graph
+        try:
+            self._check_weights()
+            with torch.no_grad():
+                if self.graph is None:
+                    if not self.fold_gen:
+                        self.gen.eval()                          # (captured as is: its own eval forward)
+                    self._build(lr, hr, labels, text_prior)
+                else:
+                    has = (hr is not None, labels is not None, text_prior is not None)
+                    if has != self._has:
+                        raise ValueError("run() must get the same kinds of inputs (hr, labels, text_prior) as the call that captured")
+                    self._stage_inputs(lr, hr, labels, text_prior)
+                self.graph.replay()
+        finally:
+            Fh.FWD_FORK.enabled, Fh.FWD_FORK_B.enabled = fork
+            for sub, tr in saved:                                # every submodule's own flag, as it was
+                sub.training = tr
+        return self._out
+
+    def reset_metrics(self):
+        self.psnr_sum.zero_()
+        self.ssim_sum.zero_()
+        self.correct.zero_()
+
+
+class PendingEvaluation:
+    """What `evaluate_session_async` started: the device-side totals of its sessions.  `result()` is the one host sync."""
+
+    def __init__(self, totals, n, n_img):
+        self._totals, self.n_batches, self.n_images = totals, n, n_img
+
+    def result(self):
+        if self._totals is None:
+            return {"psnr": 0.0, "ssim": 0.0, "n_batches": 0}
+        tot = self._totals.cpu()                                  # the one host sync
+        n, n_img = self.n_batches, self.n_images
+        corr = [int(v) for v in tot[2:].tolist()]
+        res = {"psnr": float(tot[0]) / n, "ssim": float(tot[1]) / n, "n_batches": n}
+        if n_img:
+            res.update(accuracy=round(corr[0] / n_img, 4), accuracy_lr=round(corr[1] / n_img, 4), accuracy_hr=round(corr[2] / n_img, 4),
+                       n_images=n_img)
+        return res
+
+
+def evaluate_session_async(generator, batches: Iterable, prior=None, recognizer=None, voc_type: str = "lower",
+                           sessions: dict = None) -> PendingEvaluation:
+    """`evaluate_session` without its final host sync: every batch is staged and replayed without the host waiting on the GPU (the
+    label encodings travel through pinned staging buffers); `.result()` of the returned object reads the totals."""
+    sessions = {} if sessions is None else sessions
+    used, n, n_img = [], 0, 0
+    for batch in batches:
+        lr, hr = batch[0], batch[1]
+        tp = batch[2] if len(batch) > 2 and batch[2] is not None and prior is None else None
+        labels = batch[3] if len(batch) > 3 and recognizer is not None else None
+        key = (lr.shape[0], tuple(lr.shape[2:]), tp is not None, labels is not None)
+        s = sessions.get(key)
+        built = s is None
+        if built:
+            s = sessions[key] = InferenceSession(generator, prior, recognizer, batch_size=lr.shape[0], lr_size=tuple(lr.shape[2:]),
+                                                 accuracy_on=("sr", "lr", "hr"), voc_type=voc_type)
+        if not any(s is u for u in used):
+            if not built:
+                # a session kept from an earlier call: the weights and running statistics may have been written since through raw
+                # pointers (the Trainer's Adam and BatchNorm kernels), which no version counter shows -- re-fold and re-pack first
+                s.refresh()
+            s.reset_metrics()
+            used.append(s)
+        s.run(lr, hr, labels, tp)
+        n += 1
+        if labels is not None:
+            n_img += len(labels)
+    totals = None
+    if used:
+        totals = torch.stack([torch.cat([s.psnr_sum.reshape(1).double(), s.ssim_sum.reshape(1).double(), s.correct.double()])
+                              for s in used]).sum(0)
+    return PendingEvaluation(totals, n, n_img)
+
+
+def evaluate_session(generator, batches: Iterable, prior=None, recognizer=None, voc_type: str = "lower", sessions: dict = None):
+    """Drop-in for `tatt_amd.io.evaluate` on graph-captured sessions: batches of (images_lr, images_hr[, text_prior[, label_strs]]);
+    with a `prior` CRNN the text prior is computed from LR inside the graph (a batch's own prior is then ignored).  One session per
+    batch size (a smaller last batch gets its own, no padding), kept in `sessions` when a dict is passed (reuse across calls: a kept
+    session re-folds and re-packs from the current weights at the start of each call).  PSNR / SSIM sums and the correct-image counters
+    stay on the device and no batch makes the host wait; one host sync at the end.  Returns the dict of io.evaluate."""
+    return evaluate_session_async(generator, batches, prior, recognizer, voc_type, sessions).result()
