@@ -102,7 +102,8 @@ int tatt_reduce_defer(int on, hipStream_t st);
 int tatt_reduce_flush(hipStream_t st);
 
 /* Specialised 3x3 convolution, Cin/Cout/W multiples of 64, NHWC contiguous: the SRB / block7 / up-sampler convs
- * (model/tsrn.py:877,885,612,1043), forward and data gradient.  y = act(conv + bias) + beta*y.  Filter packed [9][Cout][Cin]
+ * (model/tsrn.py:877,885,612,1043), forward and data gradient.  y = act(conv + bias + beta*y) -- as for every 3x3 entry below: the
+ * activation acts on the sum, so a contraction chunked over calls (beta = 1) takes its activation on the last chunk.  Filter packed [9][Cout][Cin]
  * (repack mode 2; mode 3 for the data gradient); the filter slice of each tap is staged through LDS, both MFMA operands are
  * read with 16-byte LDS loads along the contraction axis.  Used when Cin != 64. */
 int tatt_conv3_c64_fwd_t(const float* x, const float* wt, const float* bias, float* y, int B, int H, int W, int Cin,
@@ -125,7 +126,8 @@ int tatt_conv3_c64_fwd_ws16_bn(const float* x, const float* wl, const float* bia
  * a*b ~ hi hi + hi lo + lo hi accumulated in fp32 (the dropped lo*lo term is 2^-16 relative; measured effect on the network:
  * profiles/r03_split_bf16_probe.txt).  x holds cin_total >= 64 channels per pixel; the 64-channel slice starting at ci0 is
  * contracted with the matching chunk of a mode-10 / mode-11 (or 14 / 15: tatt_conv3_sb_packing) packed filter (chunk c starts c*Cout*576 words in); wider inputs are
- * chunked by the caller with beta = 1.  BatchNorm folding arguments as tatt_conv3_c64_fwd_ws16_bn. */
+ * chunked by the caller with beta = 1 and act on the last chunk: y = act(conv + bias + beta*y) on every route.  BatchNorm folding
+ * arguments as tatt_conv3_c64_fwd_ws16_bn. */
 int tatt_conv3_c64_fwd_sb(const float* x, int cin_total, int ci0, const float* wl, const float* bias, float* y, int B, int H,
                           int W, int Cout, int act, float beta, const float* in_scale, const float* in_shift, int in_act,
                           double* stats, hipStream_t st);
@@ -147,9 +149,12 @@ int tatt_conv3_c64_dgrad_bn_sb(const float* x, const float* x2, const float* in_
  * H % 4 == 0, any W (the last tile column of a ragged map is cut), act none / ReLU, no tanh; generation 3 H % 4 == 0, W % 16 == 0, no
  * output activation; everything else runs generation 1 (W % 64 == 0).  tatt_conv3_sb_packing:
  * the tatt_repack_conv_weight mode of the FORWARD filter for a call with these arguments -- 10 (generation 1) or 14 (generations
- * 3 / 4); the data-gradient packing is that + 1. */
+ * 3 / 4); the data-gradient packing is that + 1.  tatt_conv3_sb_route: the generation a call with these arguments runs, 0 when none
+ * takes it (generation 1 and W % 64 != 0: the entries return 1).  Generations 3 / 4 address the maps with 32-bit offsets: from
+ * B*H*W*max(cin_total, Cout)*4 >= 2^31 - 1 bytes on, generation 1 runs. */
 int tatt_conv3_sb_generation(int gen);
 int tatt_conv3_sb_packing(int B, int H, int W, int cin_total, int Cout, int act, int ep_act);
+int tatt_conv3_sb_route(int B, int H, int W, int cin_total, int Cout, int act, int ep_act);
 /* weight-gradient partials part[G][9*Cin][Cout] (G persistent work-groups, G <= B*H*W/64) and, if pdb != NULL, bias-gradient
  * partials pdb[G][Cout] (the column sums of dy the kernel streams anyway; nn.Conv2d's bias gradient); finish with
  * tatt_splitk_reduce(part, dw_oihw, 9*Cin, Cout, G, Cin, 9, beta, db, Cout) where pdb = part + G*9*Cin*Cout */
@@ -161,8 +166,11 @@ int tatt_conv3_c64_wgrad_partial_sb(const float* x, const float* dy, float* part
                                     int Cin, int Cout, int G, hipStream_t st);
 /* Test / A-B hook: 2 (default) = 4 x 16-pixel tiles, transposing LDS reads, staging waves beside MFMA waves (round 6; H % 4 == 0,
  * any W: the last tile column of a ragged map is cut; G <= B * (H / 4) * ceil(W / 16)), 1 = the 64-pixel row segments of rounds 3-5
- * (also what H % 4 != 0 runs; W % 64 == 0).  Returns the previous setting. */
+ * (also what H % 4 != 0 runs; W % 64 == 0).  Returns the previous setting.  tatt_conv3_wgrad_sb_route: the generation a call of
+ * tatt_conv3_c64_wgrad_partial_sb with this geometry runs, 0 when none takes it (the entry returns 1); generation 2 addresses the maps
+ * with 32-bit offsets (B*H*W*max(Cin, Cout)*4 < 2^31 - 1 bytes). */
 int tatt_conv3_wgrad_sb_generation(int gen);
+int tatt_conv3_wgrad_sb_route(int B, int H, int W, int Cin, int Cout);
 
 /* 9x9 convolution 64 -> 4 channels (fp32 vector ALU; filter through the scalar cache): the final reconstruction conv
  * (model/tsrn.py:623) and, with the mode-1 packed filter, the data gradient of block1 (model/tsrn.py:597).
@@ -506,9 +514,11 @@ int tatt_tokgemm_sb_ex(const float* X1, const float* X2, int K1, const float* Wp
 /* The epilogues of a position-wise feed-forward w_2(Dropout(relu(w_1 x))) (reference PositionwiseFeedForward, model/tbsrn.py:154-164):
  * Y = Dropout_pdrop(act(X Wp^T + bias)) with the mask tatt_dropout draws for Y's flat index (forward of w_1), or, with `gate`,
  * Y = (X Wp^T) * gate_scale where gate > 0, else 0 (data gradient of w_2 gated by the saved forward output F: F > 0 exactly where the
- * unit was active and kept, gate_scale = 1 / (1 - pdrop)).  One source, one destination; shapes of tatt_tokgemm_sb_ex. */
+ * unit was active and kept, gate_scale = 1 / (1 - pdrop)).  One source, one destination; shapes of tatt_tokgemm_sb_ex, and with
+ * pdrop > 0 or a gate only those tatt_tokgemm_sb_ffn_takes(N, K) answers 1 for (the others return 1). */
 int tatt_tokgemm_sb_ffn(const float* X, const float* Wp, const float* bias, float* Y, int M, int N, int K, int act, float pdrop,
                         const unsigned long long* seed, unsigned site, const float* gate, float gate_scale, hipStream_t st);
+int tatt_tokgemm_sb_ffn_takes(int N, int K);
 /* Y = X Wp^T + bias + addend: addend (M, N) contiguous and left intact, Y must not alias it; (N, K) within 128 x 128.  The sum of a
  * data gradient and the gradient a residual connection carries (TBSRN FeatureEnhancer sub-layers) without an element-wise launch. */
 int tatt_tokgemm_sb_add(const float* X, const float* Wp, const float* bias, const float* addend, float* Y, int M, int N, int K,
@@ -548,8 +558,10 @@ int tatt_sattn_bwd_bits(const float* Q, const float* K, const float* V, const fl
                         float pdrop, const unsigned long long* seed, unsigned site, hipStream_t st);
 /* Test / A-B hook: 2 (default) = the split-bf16 kernels (csrc/sattn2.hip: three v_mfma_f32_32x32x16_bf16 products of hi / lo halves per
  * fp32 product; P % 128 == 0, B h P^2 < 4e9), 1 = the exact-fp32 MFMA kernels (also what other geometries run).  Returns the previous
- * setting. */
+ * setting.  tatt_sattn2_takes: 1 when the split-bf16 kernels run this geometry under the current setting -- the only case in which
+ * tatt_sattn_fwd_bits fills `bits`. */
 int tatt_sattn_generation(int gen);
+int tatt_sattn2_takes(int B, int P, int h);
 
 /* ---- one TP-interpreter transformer layer as ONE kernel (csrc/tplayer.hip) --------------------------------- */
 

@@ -184,9 +184,10 @@ __global__ __launch_bounds__(256, (CK == 64 ? 1 : (CK == 32 ? 2 : 3))) void conv
 #pragma unroll
             for (int reg = 0; reg < 16; ++reg) {
                 const int px = (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5);
-                float v = apply_act(acc[reg] + bj, p.act);
+                float v = acc[reg] + bj;
                 const long o = (rowbase + px) * p.Cout + co;
                 if (p.beta != 0.f) v += p.beta * p.y[o];
+                v = apply_act(v, p.act);
                 p.y[o] = v;
                 acc[reg] = 0.f;
             }
@@ -342,8 +343,9 @@ __global__ __launch_bounds__(512, 1) void conv3_c64_ws16_kernel(Conv3P p) {
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     float* dst = p.y + (rowbase + 16 * m + r) * p.Cout + co0 + (lane & 15);
-                    float v = apply_act(acc[m][r] + bj, p.act);
+                    float v = acc[m][r] + bj;
                     if (p.beta != 0.f) v += p.beta * *dst;
+                    v = apply_act(v, p.act);
                     *dst = v;
                     st_s += v; st_q += v * v;
                 }
@@ -564,8 +566,9 @@ __global__ __launch_bounds__(512, 1) void conv3_c64_sb_kernel(Conv3SB q) {
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     float* dst = p.y + (rowbase + 16 * m + r) * p.Cout + co0 + (lane & 15);
-                    float v = apply_act((accM[m][r] + accC[m][r]) + bj, p.act);
-                    if (p.beta != 0.f) v += p.beta * *dst;
+                    float v = (accM[m][r] + accC[m][r]) + bj;
+                    if (p.beta != 0.f) v += p.beta * *dst;  // (act after beta: a chunked contraction's activation acts on the whole sum)
+                    v = apply_act(v, p.act);
                     if (EPBN) {                              // v = gradient w.r.t. act(bn(ep_x)); Cout == 64
                         const float xh = (q.ep_x[(rowbase + 16 * m + r) * 64 + co0 + (lane & 15)] - ep_mu) * ep_rs;
                         if (q.ep_act != ACT_NONE) v *= act_grad(fmaf(ep_g, xh, ep_b), q.ep_act);
@@ -1234,6 +1237,11 @@ static int conv3_sb_pick(int B, int H, int W, int cin_total, int Cout, int act, 
 TATT_API int tatt_conv3_sb_packing(int B, int H, int W, int cin_total, int Cout, int act, int ep_act) {
     return conv3_sb_pick(B, H, W, cin_total, Cout, act, ep_act) >= 3 ? 14 : 10;
 }
+// the kernel a call with these arguments runs (4 / 3 / 1), 0 = none: the row-tile kernel walks 64-pixel row segments
+TATT_API int tatt_conv3_sb_route(int B, int H, int W, int cin_total, int Cout, int act, int ep_act) {
+    const int pick = conv3_sb_pick(B, H, W, cin_total, Cout, act, ep_act);
+    return pick == 1 && W % C3_PX ? 0 : pick;
+}
 static int conv3_sb_launch(const Conv3SB& q, hipStream_t st) {
     const Conv3P& p = q.c;
     const int pick = conv3_sb_pick(p.B, p.H, p.W, q.cin_total, p.Cout, p.act, q.ep_act);
@@ -1260,7 +1268,7 @@ static int conv3_sb_launch(const Conv3SB& q, hipStream_t st) {
         }
         return LAUNCH_CHECK();
     }
-    if (p.W % C3_PX) return 1;                               // the row-tile kernel walks 64-pixel row segments
+    if (p.W % C3_PX) return 1;                               // the row-tile kernel walks 64-pixel row segments (tatt_conv3_sb_route 0)
     static TattPerDevice attr_once;
     tatt_per_device(attr_once, [&] {
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv3_c64_sb_kernel<false, false>), hipFuncAttributeMaxDynamicSharedMemorySize, SB_LDS);

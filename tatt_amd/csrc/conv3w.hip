@@ -385,13 +385,21 @@ TATT_API int tatt_conv3_wgrad_sb_generation(int gen) {
     if (gen == 1 || gen == 2) conv3_wgrad_sb_generation = gen;
     return old;
 }
+// which kernel a geometry runs: 2 = square tiles, 1 = row segments, 0 = none (the entry returns 1)
+static int conv3_wgrad_sb_pick(int B, int H, int W, int Cin, int Cout) {
+    if (Cin % 64 || Cout % 64) return 0;
+    const long maxb = (long)B * H * W * (Cin > Cout ? Cin : Cout) * 4;       // (32-bit buffer offsets)
+    if (conv3_wgrad_sb_generation == 2 && H % 4 == 0 && maxb < 0x7fffffffL) return 2;
+    return W % CW_PX ? 0 : 1;
+}
+TATT_API int tatt_conv3_wgrad_sb_route(int B, int H, int W, int Cin, int Cout) { return conv3_wgrad_sb_pick(B, H, W, Cin, Cout); }
 
 // same contract as tatt_conv3_c64_wgrad_partial (conv3.hip): partials part[G][9*Cin][Cout] (+ pdb[G][Cout]) for the split-K reducer
 TATT_API int tatt_conv3_c64_wgrad_partial_sb(const float* x, const float* dy, float* part, float* pdb, int B, int H, int W,
                                              int Cin, int Cout, int G, hipStream_t st) {
-    if (Cin % 64 || Cout % 64) return 1;
-    const long maxb = (long)B * H * W * (Cin > Cout ? Cin : Cout) * 4;       // (32-bit buffer offsets)
-    if (conv3_wgrad_sb_generation == 2 && H % 4 == 0 && maxb < 0x7fffffffL) {
+    const int pick = conv3_wgrad_sb_pick(B, H, W, Cin, Cout);
+    if (pick == 0) return 1;
+    if (pick == 2) {
         const int ntile = B * (H / 4) * ((W + 15) / 16);
         Conv3WSP p2 = {x, dy, part, B, H, W, Cin, Cout, ntile, pdb};
         static TattPerDevice attr2_once;
@@ -401,7 +409,6 @@ TATT_API int tatt_conv3_c64_wgrad_partial_sb(const float* x, const float* dy, fl
         hipLaunchKernelGGL(conv3_c64_wgrad_sb2_kernel, dim3(G, (Cin / 64) * (Cout / 64)), dim3(512), W2_LDS, st, p2);
         return LAUNCH_CHECK();
     }
-    if (W % CW_PX) return 1;
     const int nseg = B * H * (W / CW_PX);
     Conv3WSP p = {x, dy, part, B, H, W, Cin, Cout, nseg, pdb};
     static TattPerDevice attr_once;

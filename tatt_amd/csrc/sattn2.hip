@@ -487,6 +487,7 @@ TATT_API int tatt_sattn_generation(int gen) {
 }
 // geometry the split-bf16 kernels take: 128-row work-groups, 32-bit dropout indices
 static bool sattn2_takes(int B, int P, int h) { return sattn_generation == 2 && P % 128 == 0 && (double)B * h * P * P < 4.0e9; }
+TATT_API int tatt_sattn2_takes(int B, int P, int h) { return sattn2_takes(B, P, h); }
 static int sattn2_mode(float pdrop, const unsigned* bits) { return pdrop > 0.f ? (bits ? 2 : 1) : 0; }
 // -1 = not taken (the caller runs the fp32 kernels, which recompute the masks and never touch `bits`)
 int sattn2_fwd(const float* Q, const float* K, const float* V, float* O, float* lse, int B, int P, int h, float scale, float pdrop,

@@ -248,14 +248,24 @@ static int tg_launch_epi(const TokGemmP& p, hipStream_t st) {
     return LAUNCH_CHECK();
 }
 template <int NCB, int KS>
+static constexpr bool tg_has_epi = NCB <= 2 && KS <= 4;     // the dropout / gate epilogue is instantiated for the feed-forward shapes
+template <int NCB, int KS>
 static int tg_launch(const TokGemmP& p, hipStream_t st) {
     if (p.pdrop > 0.f || p.gate) {
-        if constexpr (NCB <= 2 && KS <= 4) return tg_launch_epi<NCB, KS, true>(p, st);      // (the feed-forward shapes)
+        if constexpr (tg_has_epi<NCB, KS>) return tg_launch_epi<NCB, KS, true>(p, st);
         else return 1;
     }
     return tg_launch_epi<NCB, KS, false>(p, st);
 }
-static int tg_dispatch(const TokGemmP& p, int N, int K, hipStream_t st);
+struct TgRun {
+    const TokGemmP& p; hipStream_t st;
+    template <int NCB, int KS> int go() const { return tg_launch<NCB, KS>(p, st); }
+};
+struct TgEpiTakes {
+    template <int NCB, int KS> int go() const { return tg_has_epi<NCB, KS> ? 0 : 1; }
+};
+template <class F> static int tg_shapes(int N, int K, const F& f);
+static int tg_dispatch(const TokGemmP& p, int N, int K, hipStream_t st) { return tg_shapes(N, K, TgRun{p, st}); }
 // Y = [X1 | X2] Wp^T + bias with Wp from tatt_tokgemm_pack; X1 (M, K1), X2 (M, K - K1) (null when K1 == K); the first N1 output columns
 // go to Y1 (M, N1), the rest to Y2 (M, N - N1) (null when N1 == N).  M a multiple of 64; (N, K) in {64,128,192} x {64,128,192}.
 // _ex: act = ACT_RELU applies max(., 0) after the bias; accum != 0 adds the result to what Y holds (the sum of several data gradients
@@ -287,17 +297,19 @@ TATT_API int tatt_tokgemm_sb_add(const float* X, const float* Wp, const float* b
     TokGemmP p = {X, nullptr, K, Wp, bias, Y, nullptr, N, M, ACT_NONE, 0, 0.f, nullptr, 0u, nullptr, 1.f, addend};
     return tg_dispatch(p, N, K, st);
 }
-static int tg_dispatch(const TokGemmP& p, int N, int K, hipStream_t st) {
-    if (N == 192 && K == 128) return tg_launch<3, 4>(p, st);
-    if (N == 192 && K == 64) return tg_launch<3, 2>(p, st);
-    if (N == 128 && K == 192) return tg_launch<2, 6>(p, st);
-    if (N == 128 && K == 128) return tg_launch<2, 4>(p, st);
-    if (N == 128 && K == 64) return tg_launch<2, 2>(p, st);
-    if (N == 64 && K == 192) return tg_launch<1, 6>(p, st);
-    if (N == 64 && K == 64) return tg_launch<1, 2>(p, st);
-    if (N == 64 && K == 128) return tg_launch<1, 4>(p, st);
+// the (N, K) the kernel is instantiated for; anything else: 1
+template <class F> static int tg_shapes(int N, int K, const F& f) {
+    if (N == 192 && K == 128) return f.template go<3, 4>();
+    if (N == 192 && K == 64) return f.template go<3, 2>();
+    if (N == 128 && K == 192) return f.template go<2, 6>();
+    if (N == 128 && K == 128) return f.template go<2, 4>();
+    if (N == 128 && K == 64) return f.template go<2, 2>();
+    if (N == 64 && K == 192) return f.template go<1, 6>();
+    if (N == 64 && K == 64) return f.template go<1, 2>();
+    if (N == 64 && K == 128) return f.template go<1, 4>();
     return 1;
 }
+TATT_API int tatt_tokgemm_sb_ffn_takes(int N, int K) { return tg_shapes(N, K, TgEpiTakes{}) == 0; }
 TATT_API int tatt_tokgemm_sb(const float* X1, const float* X2, int K1, const float* Wp, const float* bias, float* Y1, float* Y2, int N1,
                              int M, int N, int K, hipStream_t st) {
     return tatt_tokgemm_sb_ex(X1, X2, K1, Wp, bias, Y1, Y2, N1, M, N, K, ACT_NONE, 0, st);

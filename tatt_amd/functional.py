@@ -744,12 +744,20 @@ class FeedForwardLnFn(Function):
         return (dx,) + tuple(g) + (dg, db, None, None, None, None)
 
 
+def _ffn_fused_takes(x, w_1, w_2):
+    """FeedForwardFn runs this call: prepacked weights on a token count the GEMMs take, and a hidden width d_ff whose dropout (forward)
+    and gate (backward) epilogues tatt_tokgemm_sb_ffn has: w_1 (d_ff, d_model) and w_2's data gradient (d_ff, w_2 outputs)"""
+    M = x.numel() // x.shape[-1]
+    Nf, K = w_1.weight.shape
+    return (FFN_FUSED and _packed_linear(w_1.weight, M) is not None and _packed_linear(w_2.weight, M) is not None
+            and bool(ops.LIB.tatt_tokgemm_sb_ffn_takes(Nf, K)) and bool(ops.LIB.tatt_tokgemm_sb_ffn_takes(Nf, w_2.weight.shape[0])))
+
+
 def feed_forward(x, w_1, w_2, pdrop, training, site):
     """w_1, w_2: nn.Linear holders; dropout (site) between them in training"""
     x = _c(x)
-    M = x.numel() // x.shape[-1]
     p = float(pdrop) if training else 0.0
-    if _packed_linear(w_1.weight, M) is not None and _packed_linear(w_2.weight, M) is not None and FFN_FUSED:
+    if _ffn_fused_takes(x, w_1, w_2):
         return FeedForwardFn.apply(x, w_1.weight, w_1.bias, w_2.weight, w_2.bias, p, site)
     f = linear(x, w_1.weight, w_1.bias, act=ACT_RELU)
     f = dropout(f, pdrop, training, site)
@@ -759,10 +767,10 @@ def feed_forward(x, w_1, w_2, pdrop, training, site):
 def feed_forward_ln(x, w_1, w_2, gamma, beta, eps, mode, pdrop, training, site):
     """LayerNorm_mode(x + w_2(Dropout(relu(w_1 x)))): one operator when the weights are prepacked, else the operator chain"""
     x = _c(x)
-    M = x.numel() // x.shape[-1]
     p = float(pdrop) if training else 0.0
-    if (FFN_LN_FUSED and FFN_FUSED and _packed_linear(w_1.weight, M) is not None and _packed_linear(w_2.weight, M) is not None
-            and w_2.weight.shape[0] == x.shape[-1] and x.shape[-1] <= 128 and w_1.weight.shape[0] <= 128):
+    # (+ the residual sum of the backward: tatt_tokgemm_sb_add (d_model, d_ff) within 128 x 128)
+    if (FFN_LN_FUSED and _ffn_fused_takes(x, w_1, w_2) and w_2.weight.shape[0] == x.shape[-1] and x.shape[-1] <= 128
+            and w_1.weight.shape[0] <= 128):
         return FeedForwardLnFn.apply(x, w_1.weight, w_1.bias, w_2.weight, w_2.bias, gamma, beta, eps, mode, p, site)
     f = feed_forward(x, w_1, w_2, pdrop, training, site)
     return LayerNormFn.apply(x, f, gamma, beta, eps, mode, 0.0, 0)
@@ -1930,10 +1938,20 @@ class SelfAttnCoreFn(Function):
         return dQ, dK, dV, None, None, None
 
 
-def _sattn_select():
-    want = 2 if SATTN_SB else 1
+def _sattn_select(want=None):
+    """select the self-attention kernels: `want` (a generation a forward recorded), default SATTN_SB's -> the generation selected"""
+    want = want if want is not None else (2 if SATTN_SB else 1)
     if ops.LIB.tatt_sattn_generation(0) != want:
         ops.LIB.tatt_sattn_generation(want)
+    return want
+
+
+def _sattn_forward_route(B, Pn, h, pdrop, device):
+    """-> (generation, keep-bit words or None) of a score-free forward: bits only where the split-bf16 forward runs the geometry
+    (tatt_sattn2_takes) and so fills them; the backward runs the recorded generation with what its forward was given"""
+    gen = _sattn_select()
+    fills = pdrop > 0.0 and SATTN_KEEP_BITS and bool(ops.LIB.tatt_sattn2_takes(B, Pn, h))
+    return gen, (torch.empty(B * h * Pn * (Pn // 32), device=device, dtype=torch.int32) if fills else None)
 
 
 class SelfAttnFlashFn(Function):
@@ -1949,23 +1967,22 @@ class SelfAttnFlashFn(Function):
         scale = 1.0 / math.sqrt(E // h)
         seed = current_seed(Q.device) if pdrop > 0.0 else None
         O, lse = torch.empty_like(Q), ops.new(Q, B, h, Pn)
-        _sattn_select()
-        bits = torch.empty(B * h * Pn * (Pn // 32), device=Q.device, dtype=torch.int32) if (pdrop > 0.0 and SATTN_KEEP_BITS and Pn % 32 == 0) else None
+        gen, bits = _sattn_forward_route(B, Pn, h, pdrop, Q.device)
         ops.call("tatt_sattn_fwd_bits", ops.P(Q), ops.P(K), ops.P(V), ops.P(O), ops.P(lse), ops.P(bits), B, Pn, h, scale, float(pdrop),
                  ops.P(seed), int(site), ops.stream())
         ctx.save_for_backward(Q, K, V, O, lse)
-        ctx.cfg = (h, float(pdrop), int(site), seed, scale, bits)
+        ctx.cfg = (h, float(pdrop), int(site), seed, scale, bits, gen)
         return O
 
     @staticmethod
     def backward(ctx, dO):
         Q, K, V, O, lse = ctx.saved_tensors
-        h, pdrop, site, seed, scale, bits = ctx.cfg
+        h, pdrop, site, seed, scale, bits, gen = ctx.cfg
         B, Pn, E = Q.shape
         dO = _c(dO)
         dQ, dK, dV = torch.empty_like(Q), torch.empty_like(K), torch.empty_like(V)
         ws = ops.new(Q, B, h, Pn)
-        _sattn_select()
+        _sattn_select(gen)                                           # (the forward's kernels, whatever SATTN_SB says now)
         ops.call("tatt_sattn_bwd_bits", ops.P(Q), ops.P(K), ops.P(V), ops.P(O), ops.P(lse), ops.P(dO), ops.P(bits), ops.P(dQ), ops.P(dK),
                  ops.P(dV), ops.P(ws), B, Pn, h, scale, pdrop, ops.P(seed), site, ops.stream())
         return dQ, dK, dV, None, None, None
@@ -1989,15 +2006,14 @@ class AttnLnFn(Function):
         scale = 1.0 / math.sqrt(E // h)
         seed = current_seed(x.device) if pdrop > 0.0 else None
         O, lse = torch.empty_like(q), ops.new(q, B, h, Pn)
-        _sattn_select()
-        bits = torch.empty(B * h * Pn * (Pn // 32), device=x.device, dtype=torch.int32) if (pdrop > 0.0 and SATTN_KEEP_BITS and Pn % 32 == 0) else None
+        gen, bits = _sattn_forward_route(B, Pn, h, pdrop, x.device)
         ops.call("tatt_sattn_fwd_bits", ops.P(q), ops.P(k), ops.P(v), ops.P(O), ops.P(lse), ops.P(bits), B, Pn, h, scale, float(pdrop),
                  ops.P(seed), int(site), ops.stream())
         a = _tokgemm_ex(O.reshape(-1, E), pks[3][0], bo, E, E)
         out, stats = ops.ln_fwd(x2, a, gamma, beta, eps, mode)
         ctx.save_for_backward(x, q, k, v, O, lse, a, stats, wq, wk, wv, wo, gamma)
         ctx.wbk = [pk[1] for pk in pks]
-        ctx.cfg = (h, float(pdrop), int(site), seed, scale, bits, eps, mode)
+        ctx.cfg = (h, float(pdrop), int(site), seed, scale, bits, eps, mode, gen)
         ctx.has_b = [b is not None for b in (bq, bk, bv, bo)]
         ctx.leaves = (wq, bq, wk, bk, wv, bv, wo, bo)
         return out.reshape(x.shape)
@@ -2005,7 +2021,7 @@ class AttnLnFn(Function):
     @staticmethod
     def backward(ctx, dout):
         x, q, k, v, O, lse, a, stats, wq, wk, wv, wo, gamma = ctx.saved_tensors
-        h, pdrop, site, seed, scale, bits, eps, mode = ctx.cfg
+        h, pdrop, site, seed, scale, bits, eps, mode, gen = ctx.cfg
         B, Pn, E = x.shape
         x2, O2 = x.reshape(-1, E), O.reshape(-1, E)
         M = x2.shape[0]
@@ -2013,7 +2029,7 @@ class AttnLnFn(Function):
         dO = _tokgemm_ex(dxa, ctx.wbk[3], None, E, E).reshape(B, Pn, E)
         dq, dk, dv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
         ws = ops.new(q, B, h, Pn)
-        _sattn_select()
+        _sattn_select(gen)                                           # (the forward's kernels, whatever SATTN_SB says now)
         ops.call("tatt_sattn_bwd_bits", ops.P(q), ops.P(k), ops.P(v), ops.P(O), ops.P(lse), ops.P(dO), ops.P(bits), ops.P(dq), ops.P(dk),
                  ops.P(dv), ops.P(ws), B, Pn, h, scale, pdrop, ops.P(seed), site, ops.stream())
         dq2, dk2, dv2 = dq.reshape(-1, E), dk.reshape(-1, E), dv.reshape(-1, E)

@@ -466,21 +466,56 @@ CONV3_SB = True
 CONV3_SB_GENERATION = 4        # test / A-B hook: which split-bf16 3x3 forward / data-gradient kernel runs (tatt_conv3_sb_generation)
 
 
+def _batch_slices(B, takes):
+    """[(b0, b1)] covering range(B) with slices a kernel takes whole: the whole batch if `takes(B)`, else halves, quarters ... (the
+    kernels' limits are map sizes, so a smaller batch is never refused where a larger one was taken); None if not even one image is"""
+    nb = B
+    while nb > 1 and not takes(nb):
+        nb = (nb + 1) // 2
+    if not takes(nb):
+        return None
+    return [(b, min(B, b + nb)) for b in range(0, B, nb)]
+
+
+def _conv3_sb_slices(x_bhwc, cin, cout, act):
+    """batch slices tatt_conv3_c64_fwd_sb runs (tatt_conv3_sb_route != 0): the square-tile kernels address the maps with 32-bit
+    offsets and the row-tile kernel that runs beyond them takes only W % 64 == 0 -- a larger ragged map runs as slices below the limit"""
+    B, H, W, _ = x_bhwc.shape
+    if LIB.tatt_conv3_sb_generation(0) != CONV3_SB_GENERATION:
+        LIB.tatt_conv3_sb_generation(int(CONV3_SB_GENERATION))
+    return _batch_slices(B, lambda nb: LIB.tatt_conv3_sb_route(nb, H, W, cin, cout, int(act), ACT_NONE) != 0)
+
+
+def _conv3_sb_groups(nb, H, W):
+    """work-groups (= statistics partials) of one tatt_conv3_c64_fwd_sb launch over nb images, 64 output channels"""
+    return min(256, nb * H * W // 64)
+
+
 def _conv3_sb(x_bhwc, w_oihw, mode, bias, act=ACT_NONE, in_scale=None, in_shift=None, in_act=ACT_NONE, stats=None):
     """3x3 'same' convolution through tatt_conv3_c64_fwd_sb; mode 10: forward (Cin = w.shape[1]), mode 11: data gradient of w
-    (input channels = w.shape[0], output channels = w.shape[1]).  Contractions wider than 64 channels are chunked (beta = 1)."""
+    (input channels = w.shape[0], output channels = w.shape[1]).  Contractions wider than 64 channels are chunked (beta = 1, the
+    activation on the last chunk); each batch slice of _conv3_sb_slices is one launch per chunk (stats: _conv3_sb_groups partials
+    per slice, one after the other)."""
     B, H, W, cin = x_bhwc.shape
     cout = w_oihw.shape[0] if mode == 10 else w_oihw.shape[1]
     assert cin == (w_oihw.shape[1] if mode == 10 else w_oihw.shape[0])
-    if LIB.tatt_conv3_sb_generation(0) != CONV3_SB_GENERATION:
-        LIB.tatt_conv3_sb_generation(int(CONV3_SB_GENERATION))
-    wl = repack_weight(w_oihw, LIB.tatt_conv3_sb_packing(B, H, W, cin, cout, int(act), ACT_NONE) + (mode - 10))
+    slices = _conv3_sb_slices(x_bhwc, cin, cout, act)
+    if slices is None:
+        raise RuntimeError("tatt_conv3_c64_fwd_sb takes no slice of a (%d, %d, %d, %d) map" % (B, H, W, cin))
+    nb0 = slices[0][1]                                       # (every slice runs the route of the first: the limits are map sizes)
+    wl = repack_weight(w_oihw, LIB.tatt_conv3_sb_packing(nb0, H, W, cin, cout, int(act), ACT_NONE) + (mode - 10))
     y = new(x_bhwc, B, H, W, cout)
     nchunk = cin // 64
-    assert nchunk == 1 or (act in (ACT_NONE, ACT_RELU) and stats is None)
-    for c in range(nchunk):                                  # (an output activation belongs to the last chunk)
-        call("tatt_conv3_c64_fwd_sb", P(x_bhwc), cin, 64 * c, P(wl[c * cout * 576:]), P(bias) if c == 0 else None, P(y), B, H, W, cout,
-             int(act) if c == nchunk - 1 else ACT_NONE, 0.0 if c == 0 else 1.0, P(in_scale), P(in_shift), int(in_act), P(stats), stream())
+    assert nchunk == 1 or stats is None
+    g0 = 0
+    for b0, b1 in slices:
+        xs, ys = x_bhwc[b0:b1], y[b0:b1]
+        st = stats[g0 * 128:] if stats is not None else None
+        for c in range(nchunk):                              # (an output activation belongs to the last chunk: y = act(conv + b + beta y))
+            call("tatt_conv3_c64_fwd_sb", P(xs), cin, 64 * c, P(wl[c * cout * 576:]), P(bias) if c == 0 else None, P(ys), b1 - b0, H, W,
+                 cout, int(act) if c == nchunk - 1 else ACT_NONE, 0.0 if c == 0 else 1.0, P(in_scale), P(in_shift), int(in_act), P(st),
+                 stream())
+        g0 += _conv3_sb_groups(b1 - b0, H, W)
     return y
 
 
@@ -512,8 +547,7 @@ def conv2d_forward(x_bhwc, weight_oihw, bias, act=ACT_NONE, any_width=False):
         return y
     if _conv3_fast_ok(x_bhwc, Cin, Cout, KH, KW, any_width):
         B, H, W, _ = x_bhwc.shape
-        gen4 = CONV3_SB_GENERATION == 4 and H % 4 == 0       # (generation 4: any width, ReLU on the output, chunked contractions)
-        if CONV3_SB and ((gen4 and act in (ACT_NONE, ACT_RELU)) or act == ACT_NONE or (Cin == 64 and W % 64 == 0)):
+        if CONV3_SB and _conv3_sb_slices(x_bhwc, Cin, Cout, act) is not None:     # (what the C side runs: tatt_conv3_sb_route)
             return _conv3_sb(x_bhwc, weight_oihw, 10, bias, act)
         if W % 64 == 0:                                          # (the exact-fp32 kernels walk 64-pixel row segments)
             y = new(x_bhwc, B, H, W, Cout)
@@ -544,10 +578,13 @@ def conv3_bn_forward(x_bhwc, weight_oihw, bias, in_scale=None, in_shift=None, in
     partials of y's per-channel batch statistics ([G][2][64] doubles) -> (y, part, G)."""
     _check_dev(x_bhwc)
     B, H, W, _ = x_bhwc.shape
+    if CONV3_SB:
+        slices = _conv3_sb_slices(x_bhwc, 64, 64, ACT_NONE) or [(0, B)]
+        G = sum(_conv3_sb_groups(b1 - b0, H, W) for b0, b1 in slices)
+        part = new(x_bhwc, G * 128, dtype=torch.float64) if want_stats else None
+        return _conv3_sb(x_bhwc, weight_oihw, 10, bias, ACT_NONE, in_scale, in_shift, in_act, part), part, G
     G = min(256, B * H * W // 64)
     part = new(x_bhwc, G * 128, dtype=torch.float64) if want_stats else None
-    if CONV3_SB:
-        return _conv3_sb(x_bhwc, weight_oihw, 10, bias, ACT_NONE, in_scale, in_shift, in_act, part), part, G
     y = new(x_bhwc, B, H, W, 64)
     call("tatt_conv3_c64_fwd_ws16_bn", P(x_bhwc), P(repack_weight(weight_oihw, 6)), P(bias), P(y), B, H, W, 64, ACT_NONE, 0.0,
          P(in_scale), P(in_shift), int(in_act), P(part), stream())
@@ -576,8 +613,10 @@ def conv2d_dgrad(dy_bhwc, weight_oihw, any_width=False):
         return dx
     if _conv3_fast_ok(dy_bhwc, Cout, Cin, KH, KW, any_width):
         B, H, W, _ = dy_bhwc.shape
-        if CONV3_SB:
+        if CONV3_SB and _conv3_sb_slices(dy_bhwc, Cout, Cin, ACT_NONE) is not None:
             return _conv3_sb(dy_bhwc, weight_oihw, 11, None)
+        if W % 64:                                               # (the exact-fp32 kernels walk 64-pixel row segments)
+            return conv_fwd(dy_bhwc, repack_weight(weight_oihw, 1), None, Cin, KH, KW)
         dx = new(dy_bhwc, B, H, W, Cin)
         if Cout == 64:
             wl = repack_weight(weight_oihw, _WS_DGRAD_MODE)
@@ -597,14 +636,24 @@ def conv_wgrad(x_bhwc, dy_bhwc, Cout, KH, KW, want_db=False, any_width=False):
     dw = new(x_bhwc, Cout, Cin, KH, KW)
     contig = x_bhwc.is_contiguous() and dy_bhwc.is_contiguous()
     if contig and KH == 3 and KW == 3 and Cin % 64 == 0 and Cout % 64 == 0 and (W % 64 == 0 or (CONV3_WGRAD_SB and H % 4 == 0 and ((CONV3_SB_NARROW_MAPS and W % 16 == 0) or any_width))):
-        nseg = B * (H // 4) * ((W + 15) // 16) if W % 64 else B * H * W // 64
+        # batch slices the kernel takes (tatt_conv3_wgrad_sb_route: the square tiles address the maps with 32-bit offsets, the row
+        # segments beyond them take only W % 64 == 0), each with its own partials; one reduction over all of them
+        slices = (_batch_slices(B, lambda nb: LIB.tatt_conv3_wgrad_sb_route(nb, H, W, Cin, Cout) != 0) if CONV3_WGRAD_SB else None) \
+            or [(0, B)]
         nblk = (Cin // 64) * (Cout // 64)
-        G = min(nseg, max(1, (CONV3_WGRAD_GROUPS if nblk == 1 else 256) // nblk))     # (several channel blocks: one group per CU together)
+        groups = []
+        for b0, b1 in slices:
+            nseg = (b1 - b0) * (H // 4) * ((W + 15) // 16) if W % 64 else (b1 - b0) * H * W // 64
+            groups.append(min(nseg, max(1, (CONV3_WGRAD_GROUPS if nblk == 1 else 256) // nblk)))   # (several channel blocks: one group per CU together)
+        G = sum(groups)
         n = G * 9 * Cin * Cout
         part = _split_ws(new(x_bhwc, n + (G * Cout if want_db else 0)))
         db = new(x_bhwc, Cout) if want_db else None
-        call("tatt_conv3_c64_wgrad_partial_sb" if CONV3_WGRAD_SB else "tatt_conv3_c64_wgrad_partial", P(x_bhwc), P(dy_bhwc), P(part),
-             P(part[n:]) if want_db else None, B, H, W, Cin, Cout, G, stream())
+        g0 = 0
+        for (b0, b1), g in zip(slices, groups):
+            call("tatt_conv3_c64_wgrad_partial_sb" if CONV3_WGRAD_SB else "tatt_conv3_c64_wgrad_partial", P(x_bhwc[b0:b1]), P(dy_bhwc[b0:b1]),
+                 P(part[g0 * 9 * Cin * Cout:]), P(part[n + g0 * Cout:]) if want_db else None, b1 - b0, H, W, Cin, Cout, g, stream())
+            g0 += g
         call("tatt_splitk_reduce", P(part), P(dw), 9 * Cin, Cout, G, Cin, 9, 0.0, P(db), Cout, stream())
         return (dw, db) if want_db else dw
     if want_db:
