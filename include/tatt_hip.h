@@ -749,6 +749,23 @@ int tatt_bicubic_luma(const float* img, long sn, long sc, long sh, long sw, floa
  * loss/semantic_loss.py:21-38: the student / teacher prior distillation loss); out[0] scalar; backward w.r.t. pred */
 int tatt_semantic_loss_fwd(const float* pred, const float* gt, long n, float* out, hipStream_t st);
 int tatt_semantic_loss_bwd(const float* pred, const float* gt, const float* gout, long n, float* dpred, hipStream_t st);
+/* ---- CTC label supervision (csrc/ctc.hip; reference torch.nn.CTCLoss(blank=0, reduction='none'), interfaces/super_resolution.py:51,827-851) -- */
+/* ONE launch: nll[b] = -log p(target_b | x[:, b]) and, when grad != NULL, the unit gradient w.r.t. the un-normalised scores,
+ *   grad[t,b,c] = p[t,b,c] - exp(logsumexp_{s: l'_s = c}(alpha_t(s) + beta_t(s)) - lp[t,b,c] + nll[b]),  rows t >= in_len[b] zero
+ * (grad (T,B,C) contiguous; the convention of ATen's backward; with normalized = 0 the row's log-softmax backward g - p sum_c g is applied
+ * as well: zero in exact arithmetic, it takes the row's common fp32 error out).  x (T,B,C) by element strides; normalized = 1: x holds log-probabilities
+ * (the drop-in form), 0: raw logits, the row log-softmax runs inside.  Labels from DEVICE memory: codes (n_codes int32), offs (B) element
+ * offset of each sample's first code, tgt_len (B), in_len (B, or NULL = T for all).  tgt_len < 0: the sample is ignored (nll 0, gradient 0).
+ * A target EQUAL to blank (not a CTC target; the reference's collate emits one for an empty word) gives what torch's CPU operator gives.
+ * Infeasible samples (more targets, with the blanks repeats need, than steps; a code outside [0, C); an offset / length that leaves
+ * codes or x): nll = +inf and a NaN gradient, or 0 and 0 with zero_infinity.  Bitwise reproducible (no atomics, fixed summation order).
+ * Takes T <= 64, C <= 128 (tatt_ctc_loss_takes answers 1); returns 1 otherwise. */
+int tatt_ctc_loss_fwd(const float* x, long st_t, long st_b, long st_c, int normalized, const int* codes, long n_codes,
+                      const int* offs, const int* tgt_len, const int* in_len, int blank, int zero_infinity, float* nll,
+                      float* grad, int T, int B, int C, hipStream_t st);
+/* dx[t,b,c] = grad[t,b,c] * gout[b]; all contiguous */
+int tatt_ctc_loss_bwd(const float* grad, const float* gout, float* dx, int T, int B, int C, hipStream_t st);
+int tatt_ctc_loss_takes(int T, int C);
 /* calculate_psnr (reference utils/ssim_psnr.py:9-15) of two (B,C,H,W) images in [0,1] given by element strides, first 3 channels */
 int tatt_psnr(const float* a, long a_n, long a_c, long a_h, long a_w, const float* b, long b_n, long b_c, long b_h, long b_w,
               float* out, int B, int C, int H, int W, hipStream_t st);

@@ -2293,6 +2293,52 @@ class SemanticLossFn(Function):
         return d, None
 
 
+def _check_i32(name, t, dev, n=None):
+    if not t.is_cuda or t.device != dev or t.dtype != torch.int32 or not t.is_contiguous():
+        raise RuntimeError("CtcLossFn: %s must be a contiguous int32 tensor on %s (got %s on %s): the kernel reads the labels from "
+                           "device memory; there is no CPU fallback in the product path" % (name, dev, t.dtype, t.device))
+    if n is not None and t.numel() != n:
+        raise RuntimeError("CtcLossFn: %s holds %d elements, expected %d" % (name, t.numel(), n))
+
+
+class CtcLossFn(Function):
+    """torch.nn.CTCLoss(reduction='none') (reference interfaces/super_resolution.py:51) with everything about the labels in DEVICE
+    memory: x (T,B,C) any strides -- raw logits (`normalized=False`: the row log-softmax runs inside the kernel) or log-probabilities;
+    codes int32 (any shape, read flat), offs (B) int32 offset of each sample's first code, tgt_len (B) int32 (< 0: ignored sample),
+    in_len (B) int32 or None (= T).  -> nll (B).  The forward launch (tatt_ctc_loss_fwd) also leaves the unit gradient w.r.t. the
+    scores; the backward is one scaling launch (tatt_ctc_loss_bwd).  No host synchronisation, no allocation that depends on label
+    values: the pair can be captured in a hipGraph and sees new labels on replay."""
+
+    @staticmethod
+    def forward(ctx, x, codes, offs, tgt_len, in_len, blank=0, zero_infinity=False, normalized=False):
+        ops._check_dev(x)
+        if x.dim() != 3:
+            raise RuntimeError("CtcLossFn: x must be (T, B, C), got %s" % (tuple(x.shape),))
+        T, B, C = x.shape
+        if not ops.LIB.tatt_ctc_loss_takes(T, C):
+            raise RuntimeError("tatt_ctc_loss_fwd takes T <= 64 and C <= 128 (got T = %d, C = %d); there is no fallback" % (T, C))
+        _check_i32("codes", codes, x.device)
+        _check_i32("offs", offs, x.device, B)
+        _check_i32("tgt_len", tgt_len, x.device, B)
+        if in_len is not None:
+            _check_i32("in_len", in_len, x.device, B)
+        nll = ops.new(x, B)
+        grad = ops.new(x, T, B, C) if ctx.needs_input_grad[0] else None
+        ops.call("tatt_ctc_loss_fwd", ops.P(x), *x.stride(), int(bool(normalized)), ops.P(codes), codes.numel(), ops.P(offs),
+                 ops.P(tgt_len), ops.P(in_len), int(blank), int(bool(zero_infinity)), ops.P(nll), ops.P(grad), T, B, C, ops.stream())
+        ctx.grad = grad
+        return nll
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        grad = ctx.grad
+        T, B, C = grad.shape
+        dx = torch.empty_like(grad)
+        ops.call("tatt_ctc_loss_bwd", ops.P(grad), ops.P(_c(g)), ops.P(dx), T, B, C, ops.stream())
+        return dx, None, None, None, None, None, None, None
+
+
 # --------------------------------------------------------------------------------------------------
 # SURVEY.md 8f-2: SSIM / TRI_SSIM and the rotation augmentation of the shipped recipe
 # --------------------------------------------------------------------------------------------------

@@ -17,6 +17,7 @@ Layout convention of the kernels: feature maps are NHWC-indexed `(B, H, W, C)` t
   attn_core                                 softmax(QK^T)V over the 26-key text prior, 4 heads (model/transformer_v2.py:806-833)
   tps_grid / grid_sample                    TPS control points -> sampling grid -> bilinear sampler (model/tps_spatial_transformer.py:97-112)
   image_loss                                ImageLoss = MSE + 1e-4 gradient-prior L1 (loss/image_loss.py:19-58)
+  ctc_loss                                  nn.CTCLoss(reduction='none') with the labels in device memory (interfaces/super_resolution.py:51)
 """
 from __future__ import annotations
 
@@ -255,5 +256,20 @@ def _(sr, hr, w_mse, w_gp):
     return sr.new_empty(sr.shape[0])
 
 
+@torch.library.custom_op(NS + "::ctc_loss", mutates_args=(), device_types="cuda")
+def ctc_loss(x: Tensor, codes: Tensor, offs: Tensor, tgt_len: Tensor, in_len: Optional[Tensor], blank: int, zero_infinity: bool,
+             normalized: bool) -> Tensor:
+    """per-sample CTC loss (B,) of x (T, B, C) logits (normalized=False) or log-probabilities; int32 device label tensors"""
+    _dev(x, codes, offs, tgt_len, in_len)
+    from . import functional as Fh
+    with torch.no_grad():
+        return Fh.CtcLossFn.apply(x, codes, offs, tgt_len, in_len, blank, zero_infinity, normalized)
+
+
+@ctc_loss.register_fake
+def _(x, codes, offs, tgt_len, in_len, blank, zero_infinity, normalized):
+    return x.new_empty(x.shape[1])
+
+
 OPS = ("conv2d", "conv2d_dgrad", "conv2d_wgrad", "linear", "gru32_fwd", "gru32_bwd", "bn_train", "bn_backward", "layer_norm_residual",
-       "attn_core", "tps_grid", "grid_sample", "image_loss")
+       "attn_core", "tps_grid", "grid_sample", "image_loss", "ctc_loss")

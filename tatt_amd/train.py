@@ -41,6 +41,55 @@ def semantic_loss(pred, gt):
     return Fh.SemanticLossFn.apply(pred, gt.detach())
 
 
+_CTC_ROW_OFFS = {}          # (B, ld, device) -> (B,) int32 [0, ld, 2 ld, ...]: offsets of the rows of a padded (B, ld) code array
+
+
+def _ctc_row_offsets(B, ld, device):
+    k = (B, ld, str(device))
+    offs = _CTC_ROW_OFFS.get(k)
+    if offs is None:
+        offs = torch.arange(B, device=device, dtype=torch.int32) * ld
+        if not torch.cuda.is_current_stream_capturing():         # (memory of a graph's private pool is not kept across graphs)
+            _CTC_ROW_OFFS[k] = offs
+    return offs
+
+
+def _ctc_reduce(nll, lengths, reduction):
+    if reduction == "none":
+        return nll
+    if reduction == "sum":
+        return nll.sum()
+    if reduction == "mean":                                      # torch: each sample divided by its target length (at least 1) first
+        return (nll / lengths.clamp_min(1).to(nll.dtype)).mean()
+    raise ValueError("reduction must be 'none', 'mean' or 'sum', got %r" % (reduction,))
+
+
+def ctc_loss_from_logits(logits, codes, lengths, input_lengths=None, blank=0, reduction="none", zero_infinity=False):
+    """CTC loss of RAW logits (T,B,C): log-softmax, CTC forward and the gradient in one HIP launch (tatt_ctc_loss_fwd), the form the
+    training step uses.  codes (B, ld) int32 padded class indices, lengths (B) int32 (a negative length: the sample is ignored, loss and
+    gradient 0), input_lengths (B) int32 or None (every sample uses all T steps, the reference's `predicted_length`) -- all DEVICE
+    tensors, read when the launch runs: inside a hipGraph a replay sees what the buffers hold then."""
+    ops._check_dev(logits)
+    if codes.dim() != 2 or codes.shape[0] != logits.shape[1]:
+        raise RuntimeError("ctc_loss_from_logits: codes must be (B, ld) with B = %d, got %s" % (logits.shape[1], tuple(codes.shape)))
+    offs = _ctc_row_offsets(codes.shape[0], codes.shape[1], logits.device)
+    nll = Fh.CtcLossFn.apply(logits, codes, offs, lengths, input_lengths, int(blank), bool(zero_infinity), False)
+    return _ctc_reduce(nll, lengths, reduction)
+
+
+def encode_label_batch(label_strs, voc_type="lower"):
+    """Host half of `TextPriorSR.set_labels`: label strings -> (codes (B, 26) int32, lengths (B) int32, tics (B) float32).  The PLAIN
+    word is encoded (`str_filt`-ed, lower-cased under 'lower'; classes 1..36, padded with -1) as `infer.encode_labels` does: a word of
+    more than 26 characters, or with a character outside the alphabet after filtering, gets length -1 (ignored by the loss).  tic = 1
+    iff the filtered word has at least one character (the reference's `weighted_tics`, dataset/dataset.py:2009-2063)."""
+    from .infer import encode_labels
+    from .io import str_filt
+    codes, lens = encode_labels(label_strs, voc_type)
+    tics = [1.0 if len(str_filt(s, voc_type)) > 0 else 0.0 for s in label_strs]
+    return (torch.tensor(codes, dtype=torch.int32).reshape(len(lens), -1), torch.tensor(lens, dtype=torch.int32),
+            torch.tensor(tics, dtype=torch.float32))
+
+
 def calculate_psnr(img1, img2):
     """calculate_psnr of the reference (utils/ssim_psnr.py:9-15): device scalar, images in [0, 1], first 3 channels."""
     ops._check_dev(img1)
@@ -64,10 +113,16 @@ class TextPriorSR(torch.nn.Module):
       * False -- `--arch tsrn_tl` / `tsrn_tl_wmask` (:729-768): `model(images_lr, label_vecs_final)`, gradients of the SR loss reach the
         recogniser through the prior."""
 
-    def __init__(self, sr, tpg, teacher=None, in_width=100, detach_prior=True):
+    def __init__(self, sr, tpg, teacher=None, in_width=100, detach_prior=True, label_weight=0.0, voc_type="lower"):
         super().__init__()
         self.sr, self.tpg, self.in_width = sr, tpg, in_width
         self.detach_prior = bool(detach_prior)
+        self.label_weight, self.voc_type = float(label_weight), voc_type
+        if self.label_weight < 0.0:
+            raise ValueError("label_weight must be >= 0")
+        if self.label_weight > 0.0:                          # (label_weight == 0: no label state at all)
+            self._labels = None                              # (codes (B, 26) int32, lengths (B) int32, tics (B) fp32): persistent device buffers
+            self._student_logits = None
         if teacher is not None:                              # the reference calls aster.eval() and never optimises it
             teacher.eval()
             teacher.requires_grad_(False)
@@ -112,11 +167,51 @@ class TextPriorSR(torch.nn.Module):
             return []
         return list(self._teacher.parameters()) + list(self._teacher.buffers())
 
-    def _probs(self, net, img):
+    def _probs(self, net, img, keep_logits=False):
         from .crnn import parse_crnn_data
         logits = net(parse_crnn_data(img[:, :3], self.in_width))                 # (T, B, 37)
         T, B, C = logits.shape
+        if keep_logits:
+            # the label term reads the student's logits.  Staged backward: the CTC operator continues on a detached copy cut at stage
+            # "tpg" while the softmax keeps the original, so GradCuts.run("tpg") re-enters the engine once with both `probs` and `logits`
+            cuts = getattr(self.sr, "_grad_cuts", None) if self.training else None
+            self._student_logits = cuts.cut("tpg", logits) if cuts else logits
         return Fh.SoftmaxRowsFn.apply(logits.reshape(T * B, C)).reshape(T, B, C)
+
+    # -- label supervision (label_weight > 0) ---------------------------------------------------------------------------------
+    def set_labels(self, label_strs):
+        """The label strings of the NEXT batch, for the CTC term `label_weight * mean_b(nll_b * tic_b)` on the student's logits.  Encoded
+        on the host (`encode_label_batch`), written through a small ring of pinned staging buffers into persistent device buffers with one
+        non-blocking copy on the current stream.  Call it before `Trainer.step`: the launches of a captured step read those buffers, so
+        a replay sees the new labels."""
+        if not self.label_weight > 0.0:
+            raise RuntimeError("TextPriorSR.set_labels: this model was built with label_weight = 0 (no label term)")
+        from .infer import CTC_T, LABEL_RING
+        dev = next(self.tpg.parameters()).device
+        if dev.type != "cuda":
+            raise RuntimeError("tatt_amd kernels need tensors on an AMD GPU (HIP device); got %s. "
+                               "There is no CPU fallback in the product path." % dev)
+        codes, lens, tics = encode_label_batch(label_strs, self.voc_type)
+        B = lens.numel()
+        n = B * CTC_T
+        if self._labels is None or self._labels[1].numel() != B or self._labels[0].device != dev:
+            buf = torch.full((n + 2 * B,), -1, dtype=torch.int32, device=dev)      # codes (B, T) | lengths (B) | tics (B) fp32 bits
+            self._lab_dev = buf
+            self._labels = (buf[:n].view(B, CTC_T), buf[n:n + B], buf[n + B:].view(torch.float32))
+            self._lab_host = [torch.empty(n + 2 * B, dtype=torch.int32, pin_memory=True) for _ in range(LABEL_RING)]
+            self._lab_events, self._ring_i = [None] * LABEL_RING, 0
+        # a slot is rewritten only after its previous copy has been consumed (its event; LABEL_RING slots keep the host that far ahead)
+        k = self._ring_i % LABEL_RING
+        self._ring_i += 1
+        host, ev = self._lab_host[k], self._lab_events[k]
+        if ev is not None:
+            ev.synchronize()
+        host[:n].copy_(codes.reshape(-1))
+        host[n:n + B].copy_(lens)
+        host[n + B:].view(torch.float32).copy_(tics)
+        self._lab_dev.copy_(host, non_blocking=True)
+        ev = self._lab_events[k] = ev if ev is not None else torch.cuda.Event()
+        ev.record()
 
     def forward(self, x, reuse_prior=False):
         if reuse_prior:                  # interfaces/super_resolution.py:911: the first forward's prior, detached; no second student pass
@@ -125,10 +220,14 @@ class TextPriorSR(torch.nn.Module):
         # the student's pass needs only the LR image: with STUDENT_FORK it is a parallel branch (stream of its own) beside the generator's
         # STN head and first convolution, joined where the generator first reads the prior (tsrn._trunk_forward); its backward (stage
         # "tpg") runs on that stream too -- the autograd engine orders it against the streams that feed and follow it.  Off by default.
+        keep = self.label_weight > 0.0 and self.training
+        if keep and (self._labels is None or self._labels[1].numel() != x.shape[0]):
+            raise RuntimeError("TextPriorSR: label_weight > 0 needs set_labels(label_strs) for this batch of %d before forward()%s" % (
+                x.shape[0], "" if self._labels is None else " (the label buffers hold %d)" % self._labels[1].numel()))
         if STUDENT_FORK:
-            probs = Fh.FWD_FORK_B.run(x, lambda: self._probs(self.tpg, x))
+            probs = Fh.FWD_FORK_B.run(x, lambda: self._probs(self.tpg, x, keep))
         else:
-            probs = self._probs(self.tpg, x)
+            probs = self._probs(self.tpg, x, keep)
         cuts = getattr(self.sr, "_grad_cuts", None) if self.training else None
         # staged backward: every consumer of the prior continues on its own detached copy; stage "tpg" adds their gradients up
         self._student_probs = cuts.cut("tpg", probs) if cuts else probs
@@ -160,7 +259,14 @@ class TextPriorSR(torch.nn.Module):
         self._gt_ahead = (st, gt)
 
     def extra_loss(self, hr):
-        """Distillation term; None without a teacher.  Call after forward()."""
+        """Distillation term (with a teacher) plus the label term (label_weight > 0); None with neither.  Call after forward()."""
+        loss = self._distill_loss(hr)
+        if self.label_weight > 0.0:
+            term = self._label_loss()
+            loss = term if loss is None else loss + term
+        return loss
+
+    def _distill_loss(self, hr):
         if self._teacher is None:
             return None
         assert not self._teacher.training, "the teacher recogniser must stay in eval mode (reference: aster.eval())"
@@ -174,6 +280,16 @@ class TextPriorSR(torch.nn.Module):
         loss = semantic_loss(self._student_probs, gt) * 100.0
         self._student_probs = None
         return loss
+
+    def _label_loss(self):
+        """`label_weight * mean_b(nll_b * tic_b)` (reference interfaces/super_resolution.py:849-851) on the student's LR logits.
+        Infeasible words (more characters, with the blanks doubled letters need, than the 26 steps) count 0 (zero_infinity); words that
+        cannot be encoded are ignored."""
+        logits, self._student_logits = self._student_logits, None
+        assert logits is not None, "extra_loss needs a training-mode forward first"
+        codes, lens, tics = self._labels
+        nll = ctc_loss_from_logits(logits, codes, lens, zero_infinity=True)
+        return (nll * tics).mean() * self.label_weight
 
 
 STUDENT_FORK = False        # True: the student's pass as a parallel branch of the forward (FWD_FORK_B).  Measured, round 6, same call,

@@ -490,3 +490,23 @@ for sbm in (False, True):
             ops.CONV9_SB = old
     timeit("conv9_out_wgrad_%s" % ("sb" if sbm else "fp32"), _wo, f9)
     timeit("conv9_block1_wgrad_%s" % ("sb" if sbm else "fp32"), _wb, f9 / 4)
+
+# ---- CTC loss (csrc/ctc.hip): the forward launch (nll + unit gradient) and forward + the scaling launch, as hipGraph replays ----
+_cT, _cC = 26, 37
+for _cB in (1, 48, 128):
+    _cx = R(_cT, _cB, _cC) * 3.0
+    _ccodes = torch.randint(1, _cC, (_cB, _cT), device=dev, dtype=torch.int32)
+    _clen = torch.randint(0, 14, (_cB,), device=dev, dtype=torch.int32)
+    _coffs = torch.arange(_cB, device=dev, dtype=torch.int32) * _cT
+    _cnll, _cg, _cdx, _cgo = torch.empty(_cB, device=dev), torch.empty_like(_cx), torch.empty_like(_cx), R(_cB)
+
+    def _ctc_fwd(x=_cx, codes=_ccodes, ln=_clen, offs=_coffs, nll=_cnll, g=_cg, Bc=_cB):
+        ops.call("tatt_ctc_loss_fwd", ops.P(x), *x.stride(), 0, ops.P(codes), codes.numel(), ops.P(offs), ops.P(ln), None, 0, 1,
+                 ops.P(nll), ops.P(g), _cT, Bc, _cC, ops.stream())
+
+    def _ctc_fwd_bwd(g=_cg, go=_cgo, dx=_cdx, Bc=_cB, fwd=_ctc_fwd):
+        fwd()
+        ops.call("tatt_ctc_loss_bwd", ops.P(g), ops.P(go), ops.P(dx), _cT, Bc, _cC, ops.stream())
+
+    timeit_graph("ctc_fwd_B%d_graph" % _cB, _ctc_fwd)
+    timeit_graph("ctc_fwd_bwd_B%d_graph" % _cB, _ctc_fwd_bwd)
