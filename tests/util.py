@@ -89,6 +89,41 @@ def compare_param_grads(named_params, oracle_grads, rtol, rtol_stn=None):
     return worst
 
 
+def compare_first_step_moments(tr, named_params, want_grads, rtol, rtol_stn=None, skip=(), limit_of=None):
+    """After ONE optimiser step from zero moments, per parameter: tr.flat_m = (1 - b1) g and tr.flat_v = (1 - b2) g^2 with g =
+    `want_grads[key]`, the oracle's gradient as it reaches Adam (times the clip coefficient where the group is clipped).  The
+    weights after a first step move by about lr whatever the coefficient; the moments carry it (a wrong one is a 100 % error in m).
+    Measure and limits of compare_param_grads; keys in `skip` and structural zeros are not compared, a parameter without a gradient
+    keeps zero moments.  limit_of(key): limits of its own for a model compare_param_grads has none for.
+    -> (worst "m:key" / "v:key", worst relative error)."""
+    b1, b2 = tr.betas
+    worst = ("", 0.0)
+    for name, flat, f in (("m", tr.flat_m, lambda g: (1.0 - b1) * g), ("v", tr.flat_v, lambda g: (1.0 - b2) * g * g)):
+        flat = flat.detach().cpu()
+        scale = max(float(f(g.float()).abs().max()) for g in want_grads.values() if g is not None)
+        for k, p in named_params:
+            off, n = tr.flat.offsets[id(p)]
+            got = flat[off:off + n].view_as(p)
+            og = want_grads.get(k)
+            if og is None:
+                assert float(got.abs().max()) == 0.0, (name, k)
+                continue
+            if STRUCTURAL_ZERO_GRAD.match(k) or k in skip:
+                continue
+            want = f(og.detach().float())
+            r = float((got - want).norm() / (want.norm() + 1e-7 * scale * want.numel() ** 0.5))
+            lim = rtol_stn if (rtol_stn is not None and k.startswith("stn_head")) else rtol
+            if og.numel() == 1 and rtol_stn is not None:
+                lim = 5e-2       # (as in compare_param_grads)
+            if limit_of is not None:
+                lim = limit_of(k)
+            print("first-step moment %s %-60s rel %.3e (limit %.0e)" % (name, k, r, lim))
+            assert r < lim, (name, k, r, lim)
+            if r > worst[1]:
+                worst = (name + ":" + k, r)
+    return worst
+
+
 class TorchStepKernels:
     """TEST INFRASTRUCTURE: torch stand-ins for tatt_l2norm / tatt_adam_step (same argument meaning), injected into
     tatt_amd.train.Trainer by the CPU (gloo) tests of its data-parallel orchestration.  Formulas = oracle.clip_grad_norm /
@@ -99,6 +134,9 @@ class TorchStepKernels:
 
     def adam(self, p, g, m, v, lr, b1, b2, eps, gnorm, max_norm, gscale, step):
         from oracle import tatt_oracle as O
+        # the kernel receives lr / betas / eps as C floats and forms 1 - beta from the rounded value: float32(0.999) is 1.3e-5 of
+        # (1 - beta2) away from 0.999, two hundred fp32 round-offs of v
+        lr, b1, b2, eps = (float(np.float32(x)) for x in (lr, b1, b2, eps))
         coef = gscale
         if max_norm > 0.0:
             coef = coef * min(1.0, max_norm / (float(gnorm) * gscale + 1e-6))
