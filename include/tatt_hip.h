@@ -766,6 +766,21 @@ int tatt_ctc_loss_fwd(const float* x, long st_t, long st_b, long st_c, int norma
 /* dx[t,b,c] = grad[t,b,c] * gout[b]; all contiguous */
 int tatt_ctc_loss_bwd(const float* grad, const float* gout, float* dx, int T, int B, int C, hipStream_t st);
 int tatt_ctc_loss_takes(int T, int C);
+/* ---- batch collation (csrc/collate.hip; reference resizeNormalize + alignCollate_realWTLAMask, dataset/dataset.py:1266-1319,1980-2003) -- */
+/* ONE launch, one work-group per item: PIL's bicubic resize (Image.resize(.., BICUBIC) of an RGB uint8 image, both passes in 22-bit fixed
+ * point), ToTensor (float(v) / 255, planes C,H,W) and, with the mask flag, the fourth plane `1 where gray <= mean gray` -- bit for bit
+ * what Pillow and torch give on the host.  packed (packed_bytes): the interleaved RGB sources; desc (n_items, 8) int32 in DEVICE memory:
+ *   [0] byte offset of the source in packed  [1] H_src  [2] W_src  [3] OH  [4] OW  [5] mask flag  [6] float offset of the item's
+ *   (3 + mask, OH, OW) planes in out  [7] 0
+ * A pass whose source and target size agree is skipped, as in Pillow.  desc_host: the same rows in HOST memory, read before the launch
+ * only to refuse what the kernel does not take: 2 for a geometry beyond tatt_collate_limits, 3 for a source or planes that leave
+ * packed / out (out_floats), 1 for bad arguments; there is no fallback in here.  The kernel itself reads only device memory (the launch
+ * can be captured) and re-checks every row: a row it would have refused gets NaN planes, or nothing when they lie outside out. */
+int tatt_collate_images(const unsigned char* packed, long packed_bytes, const int* desc, const int* desc_host, int n_items,
+                        float* out, long out_floats, hipStream_t st);
+/* out[0..4]: most source rows, most source columns, most bytes of the horizontal pass's result (H_src * OW * 3, counted when
+ * W_src != OW), largest OH, largest OW */
+int tatt_collate_limits(int* out);
 /* calculate_psnr (reference utils/ssim_psnr.py:9-15) of two (B,C,H,W) images in [0,1] given by element strides, first 3 channels */
 int tatt_psnr(const float* a, long a_n, long a_c, long a_h, long a_w, const float* b, long b_n, long b_c, long b_h, long b_w,
               float* out, int B, int C, int H, int W, hipStream_t st);

@@ -17,6 +17,8 @@
   transform calls of :1987-2003): PIL bicubic resize to the HR / LR size, uint8 -> float / 255 in CHW, and the binarised mask channel
   (gray < mean -> 1) as the fourth plane -- the (B, 4, H, W) tensors the generator reads.  Pinned by `tests/golden/collate.npz`,
   generated from the reference's own collate (tools/gen_golden_collate.py).
+* `DeviceCollator` is `collate_pil_batch` with the image stacks built on the GPU: one packing pass over raw bytes, one copy, one HIP
+  launch (csrc/collate.hip) whose result is bit for bit the host path's; `collate_plan` is its host half.
 * `LmdbRecords` reads the reference's lmdb record layout (`lmdbDataset_real`, dataset/dataset.py:565-686): keys `num-samples`,
   `label-%09d`, `image_hr-%09d`, `image_lr-%09d` (1-based), image bytes decoded by PIL to RGB, the label filtered by `str_filt`.
   It takes any object with the lmdb transaction's `get(key)`; `open_lmdb` wraps a real environment when the `lmdb` package is there
@@ -309,3 +311,158 @@ def evaluate(model: torch.nn.Module, batches: Iterable, prior_fn=None, recognize
         res.update(accuracy=round(correct["sr"] / n_img, 4), accuracy_lr=round(correct["lr"] / n_img, 4),
                    accuracy_hr=round(correct["hr"] / n_img, 4), n_images=n_img)
     return res
+
+
+# ---- batch collation on the device (csrc/collate.hip) -----------------------------------------------------------------------------
+COLLATE_DESC = 8          # ints per descriptor row of tatt_collate_images (include/tatt_hip.h)
+_COLLATE_ALIGN = 16
+
+
+def collate_limits():
+    """tatt_collate_limits: {'rows', 'cols', 'inter_bytes', 'oh', 'ow'} -- the sources the device resampler takes (larger ones are resized
+    by PIL on the host and only converted on the device) and the largest target size.  A host-only entry: needs no GPU."""
+    import ctypes
+    from ._lib import LIB
+    out = (ctypes.c_int * 5)()
+    if LIB.tatt_collate_limits(out) != 0:
+        raise RuntimeError("tatt_collate_limits failed")
+    return dict(zip(("rows", "cols", "inter_bytes", "oh", "ow"), (int(v) for v in out)))
+
+
+def collate_plan(images, sizes, mask: bool = True, limits=None):
+    """Host half of `DeviceCollator`, without a device: images: RGB PIL images, sizes: their (width, height) targets.
+    -> (arrays, desc, nbytes, out_floats): arrays[i] the (H, W, 3) uint8 pixels of item i (`np.asarray(img)`; an image beyond `limits` is
+    replaced by its PIL-resized version, which the device then only converts: exact by construction), desc (n, COLLATE_DESC) int32 rows
+    [source byte offset (16-byte aligned, counted from the end of the descriptor table's block), H_src, W_src, OH, OW, mask, float offset
+    of the item's planes, 0] with the planes of the items one after the other, nbytes the packed size of the sources, out_floats the size
+    of the output."""
+    import numpy as np
+    from PIL import Image
+    lim = limits if limits is not None else collate_limits()
+    n = len(images)
+    desc = np.zeros((n, COLLATE_DESC), np.int32)
+    arrays, off, out_off, planes = [], 0, 0, 3 + int(bool(mask))
+    for i, (img, (ow, oh)) in enumerate(zip(images, sizes)):
+        if getattr(img, "mode", None) != "RGB":
+            raise ValueError("DeviceCollator takes RGB PIL images (Image.open(..).convert('RGB')); item %d is %r" % (
+                i, getattr(img, "mode", type(img).__name__)))
+        if not (1 <= oh <= lim["oh"] and 1 <= ow <= lim["ow"]):
+            raise ValueError("tatt_collate_images takes targets up to %d x %d (got %d x %d)" % (lim["oh"], lim["ow"], oh, ow))
+        ws, hs = img.size
+        if hs > lim["rows"] or ws > lim["cols"] or (ws != ow and hs * ow * 3 > lim["inter_bytes"]):
+            img = img.resize((ow, oh), Image.BICUBIC)
+            ws, hs = ow, oh
+        a = np.asarray(img)
+        arrays.append(a)
+        desc[i] = (off, hs, ws, oh, ow, int(bool(mask)), out_off, 0)
+        off += -(-a.size // _COLLATE_ALIGN) * _COLLATE_ALIGN
+        out_off += planes * oh * ow
+        if off >= 2 ** 31 or out_off >= 2 ** 31:
+            raise ValueError("DeviceCollator: the batch does not fit 32-bit offsets")
+    return arrays, desc, off, out_off
+
+
+def collate_fill(flat, arrays, desc, vecs):
+    """Write one staging slot: flat: a writable 1-D uint8 array (the pinned slot, or any buffer) -> (head, pix, used).  Layout, each
+    block 16-byte aligned: descriptor table (desc rows as int32) at 0 | label_vecs as float32 at `head` | the pixels of item i at
+    `pix + desc[i, 0]`; `used` bytes in all (`collate_fill(None, ...)` only computes the three offsets)."""
+    import numpy as np
+    nvec = int(np.prod(vecs.shape))
+    head = -(-desc.nbytes // _COLLATE_ALIGN) * _COLLATE_ALIGN
+    pix = head + -(-nvec * 4 // _COLLATE_ALIGN) * _COLLATE_ALIGN
+    used = pix + (int(desc[-1, 0]) + -(-arrays[-1].size // _COLLATE_ALIGN) * _COLLATE_ALIGN if len(arrays) else 0)
+    if flat is not None:
+        flat[:desc.nbytes].view(np.int32)[:] = desc.reshape(-1)
+        flat[head:head + nvec * 4].view(np.float32)[:] = np.asarray(vecs, dtype=np.float32).reshape(-1)
+        for a, row in zip(arrays, desc):
+            o = pix + int(row[0])
+            flat[o:o + a.size] = a.reshape(-1)
+    return head, pix, used
+
+
+class DeviceCollator:
+    """`collate_pil_batch` with the image stacks built on the GPU: collate(samples) takes what `collate_pil_batch` takes ((img_HR, img_lr,
+    img_HRy, img_lry, label_str) with RGB PIL images) and returns the same 9-tuple with `images_HR` / `images_lr` BIT FOR BIT equal to the
+    host path's, on `device`.  `want_yuv=False` (the TATT recipes never read those members): `images_HRy` / `images_lry` are None; True:
+    they go through the same launch as two more items per sample.  Labels go through `collate_labels`.
+    The host does one packing pass over raw bytes (`collate_plan`) into a slot of a ring of pinned staging buffers -- descriptor table and
+    pixels together -- and enqueues ONE non-blocking copy to a persistent device buffer and ONE launch (tatt_collate_images: resize +
+    ToTensor + mask for every image) on the current stream; it never waits for the device.  A slot is rewritten only after the event
+    recorded behind its previous copy (the discipline of `TextPriorSR.set_labels`); a batch that outgrows the slots re-allocates them after
+    waiting for those events.  The image stacks are views of one freshly allocated tensor per call.  Decoding stays with the caller."""
+
+    def __init__(self, imgH: int = 32, imgW: int = 128, down_sample_scale: int = 2, mask: bool = True, device="cuda",
+                 want_yuv: bool = False, ring: int = 3, alphabet: str = ALPHABET):
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise RuntimeError("tatt_amd kernels need tensors on an AMD GPU (HIP device); got %s. "
+                               "There is no CPU fallback in the product path (collate_pil_batch is the host path)." % self.device)
+        if ring < 1:
+            raise ValueError("DeviceCollator: ring must be at least 1")
+        self.hr_size, self.lr_size = (imgW, imgH), (imgW // down_sample_scale, imgH // down_sample_scale)
+        self.mask, self.want_yuv, self.ring, self.alphabet = bool(mask), bool(want_yuv), int(ring), alphabet
+        self._limits = None
+        self._host, self._events, self._dev_buf, self._i, self._last = [], [], None, 0, None
+
+    def plan(self, samples):
+        """-> (collate_plan(...) of the batch's items, label strings, members): items ordered HR x B, lr x B[, HRy x B, lry x B]"""
+        hr, lr, hry, lry, labels = zip(*samples)
+        members = [(hr, self.hr_size), (lr, self.lr_size)] + ([(hry, self.hr_size), (lry, self.lr_size)] if self.want_yuv else [])
+        if self._limits is None:
+            self._limits = collate_limits()
+        images = [im for ims, _ in members for im in ims]
+        sizes = [size for ims, size in members for _ in ims]
+        return collate_plan(images, sizes, self.mask, self._limits), labels, members
+
+    def _slot(self, need):
+        """the next staging slot (a pinned uint8 tensor of at least `need` bytes), free to be written"""
+        if not self._host or self._host[0].numel() < need:
+            for ev in self._events + ([self._last[1]] if self._last is not None else []):
+                if ev is not None:
+                    ev.synchronize()
+            cap = -(-need * 3 // 2 // 4096) * 4096
+            self._host = [torch.empty(cap, dtype=torch.uint8, pin_memory=True) for _ in range(self.ring)]
+            self._events = [None] * self.ring
+            self._dev_buf = torch.empty(cap, dtype=torch.uint8, device=self.device)
+        k = self._i % self.ring
+        self._i += 1
+        if self._events[k] is not None:
+            self._events[k].synchronize()
+        return k, self._host[k]
+
+    def __call__(self, samples):
+        import ctypes
+        from . import ops
+        samples = list(samples)
+        (arrays, desc, nbytes, out_floats), labels, members = self.plan(samples)
+        B, n = len(samples), len(arrays)
+        vecs, masks, tics = collate_labels(labels, self.alphabet)
+        vecs_np = vecs.numpy()
+        head, pix, used = collate_fill(None, arrays, desc, vecs_np)
+        with torch.cuda.device(self.device):
+            stream = torch.cuda.current_stream()
+            moved = self._last is not None and self._last[0] != stream
+            if moved:
+                stream.wait_event(self._last[1])             # the one device buffer: the previous call's launch still reads it
+            k, host = self._slot(used)
+            if moved:
+                self._dev_buf.record_stream(stream)
+            collate_fill(host.numpy(), arrays, desc, vecs_np)
+            self._dev_buf[:used].copy_(host[:used], non_blocking=True)
+            ev = self._events[k] = self._events[k] if self._events[k] is not None else torch.cuda.Event()
+            ev.record(stream)
+            out = torch.empty(out_floats + vecs.numel(), dtype=torch.float32, device=self.device)
+            base = self._dev_buf.data_ptr()
+            ops.call("tatt_collate_images", ctypes.c_void_p(base + pix), nbytes, ctypes.c_void_p(base),
+                     ctypes.c_void_p(host.data_ptr()), n, ops.P(out), out_floats, ops.stream())
+            vecs_dev = out[out_floats:].view(vecs.shape)     # (device-to-device, behind the one host-to-device copy)
+            vecs_dev.copy_(self._dev_buf[head:head + vecs.numel() * 4].view(torch.float32).view(vecs.shape), non_blocking=True)
+            done = self._last[1] if self._last is not None else torch.cuda.Event()
+            done.record(stream)
+            self._last = (stream, done)
+        C, stacks, o = 3 + int(self.mask), [], 0
+        for _, (w, h) in members:
+            stacks.append(out[o:o + B * C * h * w].view(B, C, h, w))
+            o += B * C * h * w
+        return (stacks[0], None, stacks[1], stacks[2] if self.want_yuv else None, stacks[3] if self.want_yuv else None, tuple(labels),
+                vecs_dev, masks, tics)
