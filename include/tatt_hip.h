@@ -781,6 +781,27 @@ int tatt_collate_images(const unsigned char* packed, long packed_bytes, const in
 /* out[0..4]: most source rows, most source columns, most bytes of the horizontal pass's result (H_src * OW * 3, counted when
  * W_src != OW), largest OH, largest OW */
 int tatt_collate_limits(int* out);
+/* ---- image export (csrc/export.hip; reference eval loop interfaces/super_resolution.py:1572-1622: `.data.cpu().numpy() * 255`, clip,
+ * astype(uint8), cubic resize, lr_sr_hr panel; tripple_display / test_display interfaces/base.py:565-618: ToPILImage -> Resize(.., BICUBIC)
+ * -> ToTensor, make_grid(nrow=1), save_image) -- */
+/* ONE launch, one work-group per item: quantise three channels of an fp32 image to uint8 and resize them as PIL does
+ * (Image.fromarray(q).resize((OW, OH), BICUBIC), both passes in 22-bit fixed point) into interleaved RGB bytes -- bit for bit what numpy
+ * and Pillow give on the host.  src: a (B, C, H, W) fp32 batch by element strides (channels-last SR tensors are read as they are);
+ * desc (n_items, 8) int32 in DEVICE memory:
+ *   [0] image index b  [1] first channel c0 (the item is channels c0 .. c0 + 2)  [2] OH  [3] OW  [4] quantisation rule
+ *   [5] byte offset of the item's first pixel in out  [6] row pitch in bytes, >= 3 OW  [7] 0
+ * Rule 0 ("floor", the eval loop): t = x * 255.0f (one fp32 multiply), clipped to [0, 255], truncated.  Rule 1 ("round",
+ * torchvision.utils.save_image): t + 0.5f (one fp32 add), clipped, truncated.  NaN gives 0 under both rules, +-inf clips.
+ * A pass whose source and target size agree is skipped, as in Pillow.  Offset and pitch let several launches lay their items into one
+ * canvas (the lr_sr_hr panel).  desc_host: the same rows in HOST memory, read before the launch only to refuse what the kernel does not
+ * take: 2 for a geometry beyond tatt_export_limits, 3 for an item whose channels, source or destination bytes leave src / out
+ * (out_bytes), 1 for bad arguments (a rule other than 0 / 1 among them); there is no fallback in here.  The kernel itself reads only
+ * device memory (the launch can be captured) and re-checks every row: it writes nothing for a row it refuses. */
+int tatt_export_images(const float* src, long st_n, long st_c, long st_h, long st_w, int B, int C, int H, int W,
+                       const int* desc, const int* desc_host, int n_items, unsigned char* out, long out_bytes, hipStream_t st);
+/* out[0..4]: largest H, largest W, largest OH, largest OW, most bytes of the horizontal pass's result (H * OW * 3, counted when
+ * W != OW).  Host only: needs no GPU. */
+int tatt_export_limits(int* out);
 /* calculate_psnr (reference utils/ssim_psnr.py:9-15) of two (B,C,H,W) images in [0,1] given by element strides, first 3 channels */
 int tatt_psnr(const float* a, long a_n, long a_c, long a_h, long a_w, const float* b, long b_n, long b_c, long b_h, long b_w,
               float* out, int B, int C, int H, int W, hipStream_t st);

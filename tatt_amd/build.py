@@ -5,6 +5,7 @@ import fcntl
 import hashlib
 import json
 import os
+import re
 import subprocess
 import sys
 from concurrent.futures import ThreadPoolExecutor
@@ -13,20 +14,35 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIBDIR, "libtatt_hip.so")
-SOURCES = ["gemm.hip", "conv3.hip", "conv3w.hip", "conv9.hip", "norm.hip", "elementwise.hip", "gru.hip", "attn.hip", "sattn.hip", "sattn2.hip", "tplayer.hip", "tplayer2.hip", "tokgemm.hip", "tokwgrad.hip", "gruwgrad.hip", "tps.hip", "loss.hip", "lstm.hip", "ssim.hip", "stnhead.hip", "infer.hip", "ctc.hip", "collate.hip"]
+SOURCES = ["gemm.hip", "conv3.hip", "conv3w.hip", "conv9.hip", "norm.hip", "elementwise.hip", "gru.hip", "attn.hip", "sattn.hip", "sattn2.hip", "tplayer.hip", "tplayer2.hip", "tokgemm.hip", "tokwgrad.hip", "gruwgrad.hip", "tps.hip", "loss.hip", "lstm.hip", "ssim.hip", "stnhead.hip", "infer.hip", "ctc.hip", "collate.hip", "export.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden", "-ffp-contract=fast"]
 # per-source additions.  conv3.hip: the staging waves of the 3x3 kernels run beside MFMA waves on the same SIMD, and packed fp32 VALU forms
 # (what SLP vectorisation makes of adjacent scalar adds / fmas) take issue time from the matrix pipe (profiles/r06_conv3_sb4_roles.txt)
 # collate.hip: its coefficient tables must equal Pillow's double arithmetic bit for bit; a contracted multiply-add changes them (the last flag wins)
+# export.hip: the same tables (csrc/pil_resample.h), and its quantisation is one fp32 multiply then one fp32 add, never a fused multiply-add
 EXTRA_FLAGS = {"conv3.hip": ["-fno-slp-vectorize"], "conv3w.hip": ["-fno-slp-vectorize"], "sattn2.hip": ["-fno-slp-vectorize"],
-               "collate.hip": ["-ffp-contract=off"]}
+               "collate.hip": ["-ffp-contract=off"], "export.hip": ["-ffp-contract=off"]}
+_INCLUDE = re.compile(rb'^[ \t]*#[ \t]*include[ \t]+"([^"]+)"', re.M)
 
 
 def _digest(paths, extra=()) -> str:
+    """content hash of the files and the flags; a source or header also brings in the headers of its own directory that it includes
+    with quotes (csrc/pil_resample.h, shared by collate.hip and export.hip), each once, so that editing one rebuilds its users"""
     h = hashlib.sha256(" ".join(FLAGS + list(extra)).encode())
-    for p in paths:
+    todo, seen = list(paths), set()
+    while todo:
+        p = todo.pop(0)
+        if p in seen:
+            continue
+        seen.add(p)
         with open(p, "rb") as f:
-            h.update(f.read())
+            data = f.read()
+        h.update(data)
+        if p.endswith((".hip", ".h")):
+            for name in _INCLUDE.findall(data):
+                q = os.path.join(os.path.dirname(p), name.decode())
+                if os.path.exists(q):
+                    todo.append(q)
     return h.hexdigest()
 
 

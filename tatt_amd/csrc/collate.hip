@@ -21,7 +21,7 @@
 // LDS per item: tables ((4 W_src + 3 OW) + (4 H_src + 3 OH) ints at most, bounds 2 (OW + OH) ints), L (OH * OW bytes), the
 // intermediate (H_src * OW * 3 bytes): 138.3 KB at the limits below, of the CU's 160 KB.
 #include "common.h"
-#include <math.h>
+#include "pil_resample.h"         // col_ksize, col_bicubic, col_coeffs, col_clip8 (shared with export.hip)
 
 #define COL_THREADS 256
 #define COL_DESC 8                     // ints per descriptor row: src byte offset, H_src, W_src, OH, OW, mask flag, out float offset, 0
@@ -31,15 +31,8 @@
 #define COL_MAX_OH 64
 #define COL_MAX_OW 256
 #define COL_LDS 147456                 // dynamic LDS of every launch (the largest item: 141,568 bytes + alignment)
-#define COL_PB 22                      // Pillow's PRECISION_BITS
 
 struct ColLayout { int ksh, ksv, kh, bh, kv, bv, lum, inter, total; };
-
-static __host__ __device__ inline int col_ksize(int in, int out) {
-    double fs = (double)in / out;
-    if (fs < 1.0) fs = 1.0;
-    return (int)ceil(2.0 * fs) * 2 + 1;
-}
 
 static __host__ __device__ inline bool col_takes(int hs, int ws, int oh, int ow) {
     if (hs < 1 || ws < 1 || oh < 1 || ow < 1 || oh > COL_MAX_OH || ow > COL_MAX_OW) return false;
@@ -62,41 +55,6 @@ static __host__ __device__ inline ColLayout col_layout(int hs, int ws, int oh, i
     g.inter = take(g.ksh ? hs * ow * 3 : 0);
     g.total = o;
     return g;
-}
-
-__device__ __forceinline__ double col_bicubic(double x) {          // Pillow's bicubic_filter, a = -0.5
-    const double a = -0.5;
-    if (x < 0.0) x = -x;
-    if (x < 1.0) return ((a + 2.0) * x - (a + 3.0)) * x * x + 1;
-    if (x < 2.0) return (((x - 5) * x + 8) * x - 4) * a;
-    return 0.0;
-}
-
-// row `xx` of the coefficient table of a pass from `in` to `out` samples: kk[xx][0 .. n) and bounds[xx] = (first source sample, n)
-__device__ __forceinline__ void col_coeffs(int xx, int in, int out, int ksize, int* kk, int* bounds) {
-    const double scale = (double)in / out;
-    const double fs = scale < 1.0 ? 1.0 : scale;
-    const double support = 2.0 * fs, center = (xx + 0.5) * scale, ss = 1.0 / fs;
-    int xmin = (int)(center - support + 0.5);
-    if (xmin < 0) xmin = 0;
-    int xmax = (int)(center + support + 0.5);
-    if (xmax > in) xmax = in;
-    xmax -= xmin;                                                   // (<= ksize: Pillow sizes its own table by the same bound)
-    double ww = 0.0;
-    for (int x = 0; x < xmax; ++x) ww += col_bicubic((x + xmin - center + 0.5) * ss);
-    int* k = kk + xx * ksize;
-    for (int x = 0; x < xmax; ++x) {
-        double w = col_bicubic((x + xmin - center + 0.5) * ss);
-        if (ww != 0.0) w /= ww;
-        k[x] = w < 0 ? (int)(-0.5 + w * (1 << COL_PB)) : (int)(0.5 + w * (1 << COL_PB));
-    }
-    bounds[2 * xx] = xmin;
-    bounds[2 * xx + 1] = xmax;
-}
-
-__device__ __forceinline__ int col_clip8(int acc) {
-    const int v = acc >> COL_PB;                                    // arithmetic shift
-    return v < 0 ? 0 : (v > 255 ? 255 : v);
 }
 
 // phase 2 over the item's OH * OW pixels from s1 = uint8 [rows][OW][3] (the source itself or the horizontal pass's result); returns

@@ -15,6 +15,9 @@ take their save=False path, and inside the replayed graph the Function layer cos
 
 `evaluate_session` is the drop-in for `tatt_amd.io.evaluate` built on it: every accumulator lives on the device, one host sync at
 the end.  Neither changes the modules' state (training flags, parameters, running statistics, `num_batches_tracked`).
+
+`SuperResolver` is the reference's `demo()` (interfaces/super_resolution.py:1788-1876) with an output: PIL crops in, PIL images out, through
+`io.DeviceCollator.stack` -> a session -> `io.DeviceExporter` per batch; the host waits only when the result is read.
 """
 from __future__ import annotations
 
@@ -473,10 +476,18 @@ class PendingEvaluation:
 
 
 def evaluate_session_async(generator, batches: Iterable, prior=None, recognizer=None, voc_type: str = "lower",
-                           sessions: dict = None) -> PendingEvaluation:
+                           sessions: dict = None, export=None) -> PendingEvaluation:
     """`evaluate_session` without its final host sync: every batch is staged and replayed without the host waiting on the GPU (the
-    label encodings travel through pinned staging buffers); `.result()` of the returned object reads the totals."""
+    label encodings travel through pinned staging buffers); `.result()` of the returned object reads the totals.
+    `export(batch_index, pending_panels)`: when given, the lr_sr_hr panels of every batch (the eval loop's canvas,
+    `DeviceExporter.panels(lr, sr, hr, gap=5)`, reference interfaces/super_resolution.py:1572-1622) are enqueued behind the batch's
+    replay and the callback gets the `PendingExport`; reading it (`.result()`) is the callback's only wait, and it may keep it for
+    later.  The metrics do not depend on it."""
     sessions = {} if sessions is None else sessions
+    exporter = None
+    if export is not None:
+        from .io import DeviceExporter
+        exporter = DeviceExporter(device=next(generator.parameters()).device, rule="floor")
     used, n, n_img = [], 0, 0
     for batch in batches:
         lr, hr = batch[0], batch[1]
@@ -495,7 +506,9 @@ def evaluate_session_async(generator, batches: Iterable, prior=None, recognizer=
                 s.refresh()
             s.reset_metrics()
             used.append(s)
-        s.run(lr, hr, labels, tp)
+        out = s.run(lr, hr, labels, tp)
+        if exporter is not None:
+            export(n, exporter.panels(lr, out[0], hr, gap=5))          # (reads the static SR output before the next replay: same stream)
         n += 1
         if labels is not None:
             n_img += len(labels)
@@ -506,10 +519,113 @@ def evaluate_session_async(generator, batches: Iterable, prior=None, recognizer=
     return PendingEvaluation(totals, n, n_img)
 
 
-def evaluate_session(generator, batches: Iterable, prior=None, recognizer=None, voc_type: str = "lower", sessions: dict = None):
+def evaluate_session(generator, batches: Iterable, prior=None, recognizer=None, voc_type: str = "lower", sessions: dict = None,
+                     export=None):
     """Drop-in for `tatt_amd.io.evaluate` on graph-captured sessions: batches of (images_lr, images_hr[, text_prior[, label_strs]]);
     with a `prior` CRNN the text prior is computed from LR inside the graph (a batch's own prior is then ignored).  One session per
     batch size (a smaller last batch gets its own, no padding), kept in `sessions` when a dict is passed (reuse across calls: a kept
     session re-folds and re-packs from the current weights at the start of each call).  PSNR / SSIM sums and the correct-image counters
-    stay on the device and no batch makes the host wait; one host sync at the end.  Returns the dict of io.evaluate."""
-    return evaluate_session_async(generator, batches, prior, recognizer, voc_type, sessions).result()
+    stay on the device and no batch makes the host wait; one host sync at the end.  Returns the dict of io.evaluate.
+    `export`: see `evaluate_session_async`."""
+    return evaluate_session_async(generator, batches, prior, recognizer, voc_type, sessions, export).result()
+
+
+# ---- PIL crops in, PIL images out ---------------------------------------------------------------------------------------------------
+class PendingUpscale:
+    """What `SuperResolver.__call__` started.  `result()` is the only host wait: -> the SR images as RGB PIL images, in input order
+    (with a recogniser: (images, texts)).  `sr`: with keep_sr, a clone of every batch's SR tensor."""
+
+    def __init__(self, parts, with_text, sr):
+        self._parts, self._with_text, self.sr = parts, with_text, sr
+
+    def result(self):
+        images, texts = [], []
+        for pending, dec, ev in self._parts:
+            images.extend(pending.result())
+            if dec is not None:
+                ev.synchronize()
+                for row in dec.tolist():                               # (T codes padded with -1 | length)
+                    texts.append("".join(D2A[c] for c in row[:row[-1]]))
+        return (images, texts) if self._with_text else images
+
+
+class SuperResolver:
+    """The reference's `demo()` (interfaces/super_resolution.py:1788-1876: every file resized to the LR size, the model run at B = 1, no
+    image produced) as it should have been: RGB PIL crops of any size in, RGB PIL images out.
+
+        up = SuperResolver(generator, prior=None, recognizer=None, batch_size=48, lr_size=(16, 64), mask=True, rule="floor")
+        images = up(pil_images, out_sizes=None).result()          # with a recogniser: (images, texts)
+
+    The list is cut into batches of `batch_size` (a smaller last batch gets its own session, as in `evaluate_session`; no padding); per
+    batch `DeviceCollator.stack` (PIL's resize to lr_size = (height, width) + ToTensor + mask plane in one launch) ->
+    `InferenceSession.run` (one replayed hipGraph) -> `DeviceExporter` (quantise + resize in one launch, one copy back).  out_sizes: None =
+    the model's HR size, or one (width, height) per image (e.g. twice each crop's own size).  Nothing waits for the device before
+    `PendingUpscale.result()` (but the first batch of each size, which captures its session).  With `recognizer` (a CRNN) the greedy CTC strings of the SR images come back as well: an eager recogniser
+    pass over the SR tensor after the replay, tatt_ctc_greedy_match for the decoding, the codes through a second non-blocking copy.
+    A TSRN_TL_TRANS generator without a `prior` CRNN runs on the session's zero text prior.  keep_sr=True keeps a clone of each batch's
+    SR tensor on the PendingUpscale (`.sr`)."""
+
+    def __init__(self, generator, prior=None, recognizer=None, batch_size: int = 48, lr_size=(16, 64), mask: bool = True,
+                 rule: str = "floor", keep_sr: bool = False):
+        from .io import DeviceCollator, DeviceExporter
+        _check_module(generator, "generator")
+        _check_module(prior, "prior CRNN")
+        _check_module(recognizer, "recogniser CRNN")
+        if not (isinstance(batch_size, int) and batch_size > 0):
+            raise ValueError("batch_size must be a positive int")
+        self.gen, self.prior, self.rec = generator, prior, recognizer
+        self.B, self.lr_size, self.keep_sr = batch_size, tuple(lr_size), bool(keep_sr)
+        self.device = next(generator.parameters()).device
+        self.collator = DeviceCollator(imgH=self.lr_size[0], imgW=self.lr_size[1], down_sample_scale=1, mask=mask, device=self.device)
+        self.exporter = DeviceExporter(device=self.device, rule=rule)
+        self.sessions = {}
+        self._ctc = {}                                               # batch size -> (keep, label, label_len) the decoding ignores
+
+    def _texts(self, sr):
+        """-> (pinned (n, T + 1) int32: decoded classes | length, its event)"""
+        from .crnn import parse_crnn_data
+        was = self.rec.training
+        self.rec.eval()
+        try:
+            with torch.no_grad():
+                logits = self.rec(parse_crnn_data(sr[:, :3].contiguous()))
+        finally:
+            self.rec.train(was)
+        T, n, C = logits.shape
+        if (n, T) not in self._ctc:
+            self._ctc[(n, T)] = (torch.ones(C, dtype=torch.int32, device=self.device),
+                                 torch.zeros(n, T, dtype=torch.int32, device=self.device),
+                                 torch.full((n,), -1, dtype=torch.int32, device=self.device))
+        _, dec, dlen = ctc_greedy_match(logits, *self._ctc[(n, T)], want_decoded=True)
+        host = torch.empty(n, T + 1, dtype=torch.int32, pin_memory=True)
+        host[:, :T].copy_(dec, non_blocking=True)
+        host[:, T].copy_(dlen, non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record()
+        return host, ev
+
+    def __call__(self, images, out_sizes=None) -> PendingUpscale:
+        images = list(images)
+        if out_sizes is not None:
+            out_sizes = [tuple(s) for s in out_sizes]
+            if len(out_sizes) != len(images):
+                raise ValueError("%d out_sizes for %d images" % (len(out_sizes), len(images)))
+        h, w = self.lr_size
+        parts, kept, fresh = [], [], set()
+        with torch.cuda.device(self.device):
+            for i in range(0, len(images), self.B):
+                chunk = images[i:i + self.B]
+                n = len(chunk)
+                lr = self.collator.stack(chunk, (w, h))
+                s = self.sessions.get(n)
+                if s is None:
+                    s = self.sessions[n] = InferenceSession(self.gen, self.prior, None, batch_size=n, lr_size=self.lr_size)
+                elif n not in fresh:
+                    s.refresh()                                      # weights written through raw pointers since the last call
+                fresh.add(n)
+                sr = s.run(lr)[0]
+                parts.append((self.exporter(sr, None if out_sizes is None else out_sizes[i:i + n]),) +
+                             (self._texts(sr) if self.rec is not None else (None, None)))
+                if self.keep_sr:
+                    kept.append(sr.clone())
+        return PendingUpscale(parts, self.rec is not None, kept if self.keep_sr else None)

@@ -19,6 +19,10 @@
   generated from the reference's own collate (tools/gen_golden_collate.py).
 * `DeviceCollator` is `collate_pil_batch` with the image stacks built on the GPU: one packing pass over raw bytes, one copy, one HIP
   launch (csrc/collate.hip) whose result is bit for bit the host path's; `collate_plan` is its host half.
+* `export_pil_batch` is the way back, the reference's per-image export of an image tensor (interfaces/super_resolution.py:1572-1591:
+  `.cpu().numpy() * 255`, clip, `astype(np.uint8)`, resize; interfaces/base.py:565-618 for the `save_image` rounding) on the host;
+  `DeviceExporter` is the same with the pixels made on the GPU: one HIP launch (csrc/export.hip), one copy back of uint8, byte for byte the
+  host path's; `export_plan` / `panel_layout` are its host half.
 * `LmdbRecords` reads the reference's lmdb record layout (`lmdbDataset_real`, dataset/dataset.py:565-686): keys `num-samples`,
   `label-%09d`, `image_hr-%09d`, `image_lr-%09d` (1-based), image bytes decoded by PIL to RGB, the label filtered by `str_filt`.
   It takes any object with the lmdb transaction's `get(key)`; `open_lmdb` wraps a real environment when the `lmdb` package is there
@@ -466,3 +470,342 @@ class DeviceCollator:
             o += B * C * h * w
         return (stacks[0], None, stacks[1], stacks[2] if self.want_yuv else None, stacks[3] if self.want_yuv else None, tuple(labels),
                 vecs_dev, masks, tics)
+
+    def stack(self, images, size):
+        """RGB PIL images, size = (width, height) -> ONE (n, 3 + mask, height, width) stack on the device, bit for bit
+        `torch.stack([resize_normalize(im, size, mask) for im in images])`: the plan / fill / launch of `__call__` without the sample
+        tuples and the labels (what `tatt_amd.infer.SuperResolver` feeds its sessions with).  Never waits for the device."""
+        import ctypes
+        import numpy as np
+        from . import ops
+        images = list(images)
+        if self._limits is None:
+            self._limits = collate_limits()
+        arrays, desc, nbytes, out_floats = collate_plan(images, [tuple(size)] * len(images), self.mask, self._limits)
+        none = np.zeros(0, np.float32)
+        _, pix, used = collate_fill(None, arrays, desc, none)
+        with torch.cuda.device(self.device):
+            stream = torch.cuda.current_stream()
+            moved = self._last is not None and self._last[0] != stream
+            if moved:
+                stream.wait_event(self._last[1])
+            k, host = self._slot(used)
+            if moved:
+                self._dev_buf.record_stream(stream)
+            collate_fill(host.numpy(), arrays, desc, none)
+            self._dev_buf[:used].copy_(host[:used], non_blocking=True)
+            ev = self._events[k] = self._events[k] if self._events[k] is not None else torch.cuda.Event()
+            ev.record(stream)
+            out = torch.empty(out_floats, dtype=torch.float32, device=self.device)
+            base = self._dev_buf.data_ptr()
+            ops.call("tatt_collate_images", ctypes.c_void_p(base + pix), nbytes, ctypes.c_void_p(base),
+                     ctypes.c_void_p(host.data_ptr()), len(arrays), ops.P(out), out_floats, ops.stream())
+            done = self._last[1] if self._last is not None else torch.cuda.Event()
+            done.record(stream)
+            self._last = (stream, done)
+        return out.view(len(images), 3 + int(self.mask), size[1], size[0])
+
+
+# ---- image export on the device (csrc/export.hip) -----------------------------------------------------------------------------------
+EXPORT_DESC = 8           # ints per descriptor row of tatt_export_images (include/tatt_hip.h)
+EXPORT_RULES = {"floor": 0, "round": 1}
+_EXPORT_ALIGN = 16
+
+
+def _rule_code(rule):
+    if rule not in EXPORT_RULES:
+        raise ValueError("export rule must be 'floor' (the eval loop's astype(uint8)) or 'round' (save_image); got %r" % (rule,))
+    return EXPORT_RULES[rule]
+
+
+def export_limits():
+    """tatt_export_limits: {'h', 'w', 'oh', 'ow', 'inter_bytes'} -- the largest source and target the device resampler takes and the most
+    bytes of its horizontal pass (H * OW * 3).  An export at the native size has no limit.  A host-only entry: needs no GPU."""
+    import ctypes
+    from ._lib import LIB
+    out = (ctypes.c_int * 5)()
+    if LIB.tatt_export_limits(out) != 0:
+        raise RuntimeError("tatt_export_limits failed")
+    return dict(zip(("h", "w", "oh", "ow", "inter_bytes"), (int(v) for v in out)))
+
+
+def quantize_u8(a, rule: str = "floor"):
+    """float array -> uint8 as the reference quantises an image in [0, 1]: t = a * 255 in float32; 'floor': the eval loop
+    (interfaces/super_resolution.py:1574-1587: clip to [0, 255], astype(np.uint8)); 'round': torchvision.utils.save_image
+    (mul(255).add_(0.5).clamp_(0, 255).to(uint8); interfaces/base.py:590,618).  NaN becomes 0 (the reference leaves it undefined; the
+    kernel, this function and tests/export_ref.py agree on 0); +-inf clips."""
+    import numpy as np
+    code = _rule_code(rule)
+    with np.errstate(invalid="ignore", over="ignore"):
+        t = np.asarray(a, dtype=np.float32) * 255
+        if code:
+            t = t + np.float32(0.5)
+        t = np.where(np.isnan(t), np.float32(0), t)
+        return np.clip(t, 0, 255).astype(np.uint8)
+
+
+def _export_sizes(n, H, W, sizes):
+    """None -> the native size for every item; one (w, h) -> that size for every item; else one (w, h) per item"""
+    if sizes is None:
+        return [(W, H)] * n
+    sizes = list(sizes)
+    if len(sizes) == 2 and all(isinstance(v, int) for v in sizes):
+        return [tuple(sizes)] * n
+    if len(sizes) != n:
+        raise ValueError("%d sizes for %d images" % (len(sizes), n))
+    out = [(int(w), int(h)) for w, h in sizes]
+    if any(w < 1 or h < 1 for w, h in out):
+        raise ValueError("export sizes must be positive (width, height) pairs")
+    return out
+
+
+def export_pil_batch(images, sizes=None, rule: str = "floor", c0: int = 0):
+    """The host path of image export and the yardstick of `DeviceExporter`: images: a (B, C, H, W) tensor on any device -> B RGB PIL
+    images of channels c0 .. c0 + 2.  Per image what the reference does (interfaces/super_resolution.py:1572-1591): `.cpu().numpy() * 255`,
+    transpose, the quantisation rule (`quantize_u8`), `Image.fromarray`, and `resize(size, Image.BICUBIC)` where sizes[i] = (width, height)
+    differs from the image's own size (None: no resize).  The reference resizes with cv2.INTER_CUBIC in the eval loop and with PIL in
+    tripple_display; cv2 is not in this image, so this is Pillow's resize and the cv2 variant is NOT pinned (cf. `rgb_to_yuv_u8`)."""
+    import numpy as np
+    from PIL import Image
+    B, C, H, W = images.shape
+    sizes = _export_sizes(B, H, W, sizes)
+    out = []
+    for b in range(B):
+        q = quantize_u8(np.transpose(images[b, c0:c0 + 3].detach().cpu().numpy(), (1, 2, 0)), rule)
+        img = Image.fromarray(np.ascontiguousarray(q), "RGB")
+        out.append(img if sizes[b] == (W, H) else img.resize(sizes[b], Image.BICUBIC))
+    return out
+
+
+def _export_takes(H, W, oh, ow, lim):
+    if (oh, ow) == (H, W):
+        return True
+    if H > lim["h"] or W > lim["w"] or oh > lim["oh"] or ow > lim["ow"]:
+        return False
+    return W == ow or H * ow * 3 <= lim["inter_bytes"]
+
+
+def export_plan(B, H, W, sizes, rule: str = "floor", limits=None, pitch=None, origin=None, c0: int = 0):
+    """Host half of `DeviceExporter`, without a device: one item per image b of a (B, C, H, W) batch, sizes[b] = (width, height) its
+    target.  -> (desc, resize, nbytes): desc (B, EXPORT_DESC) int32 rows [b, c0, OH, OW, rule, byte offset, row pitch, 0]; resize[b] is
+    None, or (width, height) for a target beyond `limits`: that item is planned at the NATIVE size and PIL resizes it on the host after
+    the copy -- exact by construction (quantisation happens before the resize on both paths), the mirror of `collate_plan`'s fallback;
+    nbytes: bytes of the output the rows address.
+    pitch / origin None: the items lie one after the other, rows packed (pitch 3 * OW), every item's offset 16-byte aligned.  Given (one
+    int per item): the caller's canvas layout -- item b's first pixel at origin[b], its rows pitch[b] bytes apart (>= 3 * OW)."""
+    import numpy as np
+    lim = limits if limits is not None else export_limits()
+    code = _rule_code(rule)
+    sizes = _export_sizes(B, H, W, sizes)
+    if (pitch is None) != (origin is None):
+        raise ValueError("export_plan: pitch and origin come together")
+    desc = np.zeros((B, EXPORT_DESC), np.int32)
+    resize, off, end = [], 0, 0
+    for b, (ow, oh) in enumerate(sizes):
+        if _export_takes(H, W, oh, ow, lim):
+            resize.append(None)
+        else:
+            resize.append((ow, oh))
+            ow, oh = W, H
+        p = 3 * ow if pitch is None else int(pitch[b])
+        o = off if origin is None else int(origin[b])
+        if p < 3 * ow or o < 0:
+            raise ValueError("export_plan: item %d: pitch %d below 3 * %d or a negative origin" % (b, p, ow))
+        desc[b] = (b, c0, oh, ow, code, o, p, 0)
+        last = o + (oh - 1) * p + 3 * ow
+        end = max(end, last)
+        off = -(-last // _EXPORT_ALIGN) * _EXPORT_ALIGN
+        if end >= 2 ** 31:
+            raise ValueError("DeviceExporter: the batch does not fit 32-bit offsets")
+    return desc, resize, end
+
+
+def panel_layout(B, H, W, gap: int = 0):
+    """The lr_sr_hr canvas of every sample: (height, origins) with origins[m][b] the byte offset of member m (0 LR resized to the HR size,
+    1 SR, 2 HR; each H x W) of sample b; canvas b starts at b * stride (16-byte aligned), its rows 3 * W bytes apart.  gap = 0:
+    make_grid(nrow=1, padding=0) of tripple_display (interfaces/base.py:580): 3 H rows.  gap > 0: the eval loop's canvas
+    (interfaces/super_resolution.py:1611-1614, gap = 5): members `gap` zero rows apart and 2 * gap zero rows at the bottom, 3 H + 4 gap
+    rows (its `+ 20`).  -> (height, stride, origins)"""
+    height = 3 * H + 4 * gap
+    stride = -(-height * 3 * W // _EXPORT_ALIGN) * _EXPORT_ALIGN
+    origins = [[b * stride + m * (H + gap) * 3 * W for b in range(B)] for m in range(3)]
+    return height, stride, origins
+
+
+class _ExportSlot:
+    """one pinned staging buffer of the exporter's ring: [descriptor rows | pixels]"""
+
+    def __init__(self):
+        self.host, self.held, self.event = None, False, None
+
+
+class PendingExport:
+    """What `DeviceExporter.__call__` / `.panels` started.  It owns one pinned slot of the exporter until `result()` / `arrays()` (which
+    wait for its event only, copy the pixels out and release the slot) or `release()` (gives the slot back unread)."""
+
+    def __init__(self, slot, event, pix, views):
+        self._slot, self._event, self._pix, self._views, self._arrays = slot, event, pix, views, None
+
+    def arrays(self):
+        """-> the (OH, OW, 3) uint8 arrays (copies: the slot is free afterwards)"""
+        import numpy as np
+        from PIL import Image
+        if self._arrays is None:
+            if self._slot is None:
+                raise RuntimeError("PendingExport: released before it was read")
+            self._event.synchronize()
+            flat = self._slot.host.numpy()
+            out = []
+            for off, oh, ow, pitch, resize in self._views:
+                a = np.lib.stride_tricks.as_strided(flat[self._pix + off:], (oh, ow, 3), (pitch, 3, 1)).copy()
+                if resize is not None:                                  # the host fallback of export_plan
+                    a = np.asarray(Image.fromarray(a, "RGB").resize(resize, Image.BICUBIC))
+                out.append(a)
+            self._arrays = out
+            self._slot.event = None                                   # complete: nothing left to wait for
+            self.release()
+        return self._arrays
+
+    def result(self):
+        """-> the RGB PIL images"""
+        from PIL import Image
+        return [Image.fromarray(a, "RGB") for a in self.arrays()]
+
+    def release(self):
+        if self._slot is not None:
+            self._slot.held = False
+            self._slot = None
+
+
+class DeviceExporter:
+    """`export_pil_batch` with the pixels made on the GPU: exporter(images, sizes) takes a (B, C, H, W) fp32 tensor on the device (any
+    strides: the channels-last SR tensors are read as they are) and returns a `PendingExport` whose `result()` is BYTE FOR BYTE the host
+    path's list of PIL images.  Per call, on the current stream: the descriptor rows go host-to-device from a pinned slot (non-blocking),
+    ONE launch (tatt_export_images: quantise + PIL's bicubic resize for every image, one work-group each) fills a persistent device
+    buffer, ONE non-blocking device-to-host copy brings all pixels into the pinned slot, an event is recorded.  The call never waits for
+    the device; only `PendingExport.result()` / `.arrays()` do, and only for that event.
+    A slot belongs to its PendingExport until that is read or `release()`d; when every slot is held the exporter adds one -- it never
+    overwrites unread pixels and never blocks on the caller.  (A slot released unread is waited for before its next use.)
+    The source may be a graph session's static output (`InferenceSession.run`): the launch is enqueued on the stream the next replay
+    runs on, hence ordered before it -- export first, then run the next batch, no clone needed.
+    Targets beyond `export_limits()` are exported at the native size and resized by PIL in `result()` (`export_plan`)."""
+
+    def __init__(self, device="cuda", rule: str = "floor", ring: int = 3):
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise RuntimeError("tatt_amd kernels need tensors on an AMD GPU (HIP device); got %s. "
+                               "There is no CPU fallback in the product path (export_pil_batch is the host path)." % self.device)
+        if ring < 1:
+            raise ValueError("DeviceExporter: ring must be at least 1")
+        _rule_code(rule)
+        self.rule, self.ring = rule, int(ring)
+        self._limits = None
+        self._slots, self._i = [_ExportSlot() for _ in range(self.ring)], 0
+        self._dev_buf, self._last = None, None
+        self._alloc = lambda n: torch.empty(n, dtype=torch.uint8, pin_memory=True)
+
+    def _check(self, images, c0):
+        if not isinstance(images, torch.Tensor) or images.dim() != 4 or images.dtype != torch.float32 or c0 < 0 or \
+                images.shape[1] < c0 + 3 or images.numel() == 0:
+            raise ValueError("DeviceExporter takes a 4-D fp32 tensor (B, C, H, W) with at least 3 channels from c0 = %d; got %s" % (
+                c0, "%s %s" % (tuple(images.shape), images.dtype) if isinstance(images, torch.Tensor) else type(images).__name__))
+        if images.device.type != "cuda":
+            raise RuntimeError("tatt_amd kernels need tensors on an AMD GPU (HIP device); got %s. "
+                               "There is no CPU fallback in the product path (export_pil_batch is the host path)." % images.device)
+
+    def _slot(self, need):
+        """a free slot of at least `need` bytes, now held: the next one in ring order that no PendingExport holds, else a new one"""
+        n = len(self._slots)
+        slot = next((self._slots[(self._i + j) % n] for j in range(n) if not self._slots[(self._i + j) % n].held), None)
+        if slot is None:
+            slot = _ExportSlot()
+            self._slots.append(slot)
+            self._i = 0
+        else:
+            self._i = (self._slots.index(slot) + 1) % n
+        if slot.event is not None:                                     # released unread: its copy may still be in flight
+            slot.event.synchronize()
+            slot.event = None
+        if slot.host is None or slot.host.numel() < need:
+            slot.host = self._alloc(-(-need * 3 // 2 // 4096) * 4096)
+        slot.held = True
+        return slot
+
+    def _enqueue(self, jobs, nbytes, views, zero=False):
+        """jobs: [(tensor, desc rows)], all rows addressing one output of nbytes bytes -> PendingExport"""
+        import ctypes
+        import numpy as np
+        from . import ops
+        rows = sum(len(d) for _, d in jobs)
+        pix = -(-rows * EXPORT_DESC * 4 // _EXPORT_ALIGN) * _EXPORT_ALIGN
+        cap = -(-nbytes // _EXPORT_ALIGN) * _EXPORT_ALIGN
+        with torch.cuda.device(self.device):
+            stream = torch.cuda.current_stream()
+            moved = self._last is not None and self._last[0] != stream
+            if moved:
+                stream.wait_event(self._last[1])                      # the one device buffer: the previous call's copy still reads it
+            slot = self._slot(pix + cap)
+            if self._dev_buf is None or self._dev_buf.numel() < pix + cap:
+                self._dev_buf = torch.empty(slot.host.numel(), dtype=torch.uint8, device=self.device)
+            elif moved:
+                self._dev_buf.record_stream(stream)
+            host = slot.host.numpy()
+            host[:rows * EXPORT_DESC * 4].view(np.int32)[:] = np.concatenate([d.reshape(-1) for _, d in jobs])
+            self._dev_buf[:pix].copy_(slot.host[:pix], non_blocking=True)
+            if zero:
+                self._dev_buf[pix:pix + cap].zero_()
+            base, hbase, r0 = self._dev_buf.data_ptr(), slot.host.data_ptr(), 0
+            try:
+                for t, d in jobs:
+                    B, C, H, W = t.shape
+                    ops.call("tatt_export_images", ops.P(t), *t.stride(), B, C, H, W, ctypes.c_void_p(base + r0 * EXPORT_DESC * 4),
+                             ctypes.c_void_p(hbase + r0 * EXPORT_DESC * 4), len(d), ctypes.c_void_p(base + pix), nbytes, ops.stream())
+                    r0 += len(d)
+            except Exception:
+                slot.held = False
+                raise
+            slot.host[pix:pix + cap].copy_(self._dev_buf[pix:pix + cap], non_blocking=True)
+            ev = torch.cuda.Event()
+            ev.record(stream)
+            slot.event = ev
+            self._last = (stream, ev)
+        return PendingExport(slot, ev, pix, views)
+
+    def __call__(self, images, sizes=None, c0: int = 0) -> PendingExport:
+        self._check(images, c0)
+        if self._limits is None:
+            self._limits = export_limits()
+        B, _, H, W = images.shape
+        desc, resize, nbytes = export_plan(B, H, W, sizes, self.rule, self._limits, c0=c0)
+        views = [(int(d[5]), int(d[2]), int(d[3]), int(d[6]), r) for d, r in zip(desc, resize)]
+        return self._enqueue([(images, desc)], nbytes, views)
+
+    def panels(self, lr, sr, hr, gap: int = 0, lr_rule: Optional[str] = None) -> PendingExport:
+        """The lr_sr_hr panel of every sample (`panel_layout`): the LR image resized to the HR size on top, SR and HR below it, as one
+        (3 H + 4 gap, W, 3) canvas per sample -- three launches (LR, SR, HR stacks) into one buffer, one copy back.  gap = 0 is
+        make_grid(nrow=1, padding=0) of tripple_display / test_display (interfaces/base.py:565-618; there the LR image goes through
+        ToPILImage, i.e. `lr_rule="floor"`, and the grid through save_image, i.e. an exporter with rule="round"); gap = 5 the eval loop's
+        canvas with zero rows between (interfaces/super_resolution.py:1611-1614, rule="floor").  `lr_rule` defaults to the exporter's.
+        The LR resize is Pillow's; the eval loop's cv2.resize(.., INTER_CUBIC) cannot be pinned (cv2 is not in this image), so against the
+        eval loop the LR member is NOT pinned to the reference (cf. `rgb_to_yuv_u8`).  The HR size must lie within `export_limits()`."""
+        for t in (lr, sr, hr):
+            self._check(t, 0)
+        if self._limits is None:
+            self._limits = export_limits()
+        B, _, H, W = hr.shape
+        if tuple(sr.shape[2:]) != (H, W) or sr.shape[0] != B or lr.shape[0] != B:
+            raise ValueError("panels: sr %s and hr %s must agree in batch and size, lr %s in batch" % (
+                tuple(sr.shape), tuple(hr.shape), tuple(lr.shape)))
+        if gap < 0:
+            raise ValueError("panels: gap must not be negative")
+        height, stride, origins = panel_layout(B, H, W, gap)
+        jobs, nbytes = [], 0
+        for m, (t, rule) in enumerate(((lr, lr_rule or self.rule), (sr, self.rule), (hr, self.rule))):
+            desc, resize, end = export_plan(B, t.shape[2], t.shape[3], (W, H), rule, self._limits, pitch=[3 * W] * B, origin=origins[m])
+            if any(r is not None for r in resize):
+                raise ValueError("panels: resizing %d x %d to %d x %d is beyond export_limits()" % (t.shape[2], t.shape[3], H, W))
+            jobs.append((t, desc))
+            nbytes = max(nbytes, end)
+        nbytes = max(nbytes, (B - 1) * stride + height * 3 * W)
+        views = [(b * stride, height, W, 3 * W, None) for b in range(B)]
+        return self._enqueue(jobs, nbytes, views, zero=gap > 0)
