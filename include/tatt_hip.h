@@ -740,10 +740,27 @@ int tatt_bn_fold(const float* w, const float* bias, const float* gamma, const fl
 int tatt_ctc_greedy_match(const float* logits, long st_t, long st_b, long st_c, int T, int B, int C, const int* keep,
                           const int* label, const int* label_len, int* correct, int* counter, int* dec, int* dec_len,
                           hipStream_t st);
+/* tatt_ctc_greedy_match plus the Levenshtein distance (unit costs) between the decoding (n <= T classes) and the label, one wave per
+ * image: the eval loop's editdistance.eval(pred, label) (interfaces/super_resolution.py:1531-1556).  label (B,64) int: classes of the
+ * alphabet, ONE code >= 64 for every other kept character (it equals no decoded class), padding -1; label_len (B): m <= 64, or < 0
+ * for a label the 64-character cap excludes.  correct / counter / dec / dec_len as in the match kernel (correct <=> dist == 0); dist (B),
+ * -1 for an excluded label; dec rows are st_dec ints apart, the elements of correct, dec_len and dist st_img ints apart (columns of one
+ * record tensor); hist (65): hist[max(n, m)] += dist, index 0 never written; scored / skipped: += 1 per image.  Integer atomics: the
+ * totals do not depend on the order.  mean of dist / (max(n, m) + 1e-10) = sum_M hist[M] / (M + 1e-10) / scored.  Each output may be
+ * NULL.  Returns 1 for T > 256, C > 64, B <= 0, and for T > 64 with a histogram. */
+int tatt_ctc_greedy_score(const float* logits, long st_t, long st_b, long st_c, int T, int B, int C, const int* keep,
+                          const int* label, const int* label_len, int* correct, int* counter, int* dec, int* dec_len,
+                          int* dist, long st_dec, long st_img, int* hist, int* scored, int* skipped, hipStream_t st);
 /* out (B,OH,OW) = 0.299 R + 0.587 G + 0.114 B of F.interpolate(img[:, :3], (OH,OW), mode='bicubic') (interfaces/base.py:797-815);
  * img (B,C>=3,H,W) by element strides */
 int tatt_bicubic_luma(const float* img, long sn, long sc, long sh, long sw, float* out, int B, int H, int W, int OH,
                       int OW, hipStream_t st);
+/* out = F.interpolate(img, (OH,OW), mode='bicubic') of an fp32 batch, forward only (the eval loop's LR baseline,
+ * interfaces/super_resolution.py:1417-1418), in the arithmetic of tatt_bicubic_luma: fp32 scale in / out, source = (o + 0.5) scale - 0.5,
+ * A = -0.75, border taps clamped, horizontal sums first.  img (B,C,H,W) and out (B,C,OH,OW) by element strides (channels-last tensors
+ * and channel slices are read / written as they are).  Returns 1 for a non-positive size. */
+int tatt_bicubic_resize(const float* img, long sn, long sc, long sh, long sw, float* out, long on, long oc, long oh_s,
+                        long ow_s, int B, int C, int H, int W, int OH, int OW, hipStream_t st);
 
 /* SemanticLoss(pred, gt) = mean|gt - pred| + mean (gt+1e-20)(log(gt+1e-20) - log(pred+1e-20)) over n elements (reference
  * loss/semantic_loss.py:21-38: the student / teacher prior distillation loss); out[0] scalar; backward w.r.t. pred */

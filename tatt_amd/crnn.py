@@ -113,6 +113,28 @@ def parse_crnn_data(img, in_width=100):
     return LumaResizeFn.apply(img.detach(), 32, in_width)
 
 
+def bicubic_resize(img, size, out=None):
+    """F.interpolate(img, size, mode="bicubic") of an fp32 (B, C, H, W) batch on the GPU, forward only (tatt_bicubic_resize: the
+    arithmetic of parse_crnn_data's resize without the luminance) -> (B, C, OH, OW).  The input is read by its strides: channels-last
+    tensors and channel slices such as lr[:, :3] need no copy.  `out`: an fp32 (B, C, OH, OW) tensor of any strides to write into.
+    The eval loop's bicubic LR baseline (reference interfaces/super_resolution.py:1417-1418)."""
+    ops._check_dev(img)
+    if img.requires_grad:
+        raise RuntimeError("bicubic_resize is forward only: its input must not require grad (detach it)")
+    if img.dim() != 4:
+        raise ValueError("bicubic_resize takes a (B, C, H, W) batch, got %s" % (tuple(img.shape),))
+    B, C, H, W = img.shape
+    oh, ow = (int(v) for v in size)
+    if out is None:
+        out = ops.new(img, B, C, oh, ow)
+    else:
+        ops._check_dev(out)
+        if tuple(out.shape) != (B, C, oh, ow):
+            raise ValueError("out must be %s, got %s" % ((B, C, oh, ow), tuple(out.shape)))
+    ops.call("tatt_bicubic_resize", ops.P(img), *img.stride(), ops.P(out), *out.stride(), B, C, H, W, oh, ow, ops.stream())
+    return out
+
+
 def text_prior(logits):
     """(T, B, 37) logits -> (B, 37, 1, T) softmax prior for `TSRN_TL_TRANS.forward(x, text_emb)` (reference
     interfaces/super_resolution.py:796-799).  Softmax over 37 classes of 26 x B rows: the fused row-softmax kernel."""

@@ -208,11 +208,11 @@ TATT_API int tatt_bn_fold(const float* w, const float* bias, const float* gamma,
 // Outputs (each may be NULL): correct (B) 0/1; counter: += number of correct images (one vector atomic per image);
 // dec (B, T) the decoded classes after the keep mask, padded with -1; dec_len (B).
 // ------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(64) void ctc_greedy_match_kernel(const float* __restrict__ logits, long st_t, long st_b, long st_c, int T,
-                                                              int C, const int* __restrict__ keep, const int* __restrict__ label,
-                                                              const int* __restrict__ label_len, int* correct, int* counter,
-                                                              int* dec, int* dec_len) {
-    __shared__ int amax[256];
+// The decoding both kernels share: arg-max of every step over the wave, then lane 0 merges repeats, drops the blank and the classes the
+// keep mask excludes, compacting in place (seq[n] is written only after seq[t >= n] was read).  seq: >= T ints of LDS, n_out: one.
+// Returns the decoded length n; seq[0 .. n) holds the classes, visible to every lane.
+__device__ __forceinline__ int ctc_greedy_decode(const float* __restrict__ logits, long st_t, long st_b, long st_c, int T, int C,
+                                                 const int* __restrict__ keep, int* seq, int* n_out) {
     const int bidx = blockIdx.x, lane = threadIdx.x;
     for (int t = 0; t < T; ++t) {
         float v = lane < C ? logits[t * st_t + bidx * st_b + lane * st_c] : -INFINITY;
@@ -225,25 +225,39 @@ __global__ __launch_bounds__(64) void ctc_greedy_match_kernel(const float* __res
             const bool take = k2 != 0x7fffffff && ((v2 != v2) ? (v == v || k2 < k) : (v == v && (v2 > v || (v2 == v && k2 < k))));
             if (take) { v = v2; k = k2; }
         }
-        if (lane == 0) amax[t] = k;
+        if (lane == 0) seq[t] = k;
     }
     __syncthreads();
-    if (lane != 0) return;
-    const int L = label_len[bidx];
-    int n = 0, last = 0;
-    bool ok = L >= 0;
-    for (int t = 0; t < T; ++t) {
-        const int c = amax[t];
-        if (c != last) {
-            if (c != 0 && keep[c]) {
-                if (dec) dec[(long)bidx * T + n] = c;
-                if (ok && (n >= L || label[(long)bidx * T + n] != c)) ok = false;
-                ++n;
+    if (lane == 0) {
+        int n = 0, last = 0;
+        for (int t = 0; t < T; ++t) {
+            const int c = seq[t];
+            if (c != last) {
+                if (c != 0 && keep[c]) seq[n++] = c;
+                last = c;
             }
-            last = c;
         }
+        *n_out = n;
     }
-    if (n != L) ok = false;
+    __syncthreads();
+    return *n_out;
+}
+
+__global__ __launch_bounds__(64) void ctc_greedy_match_kernel(const float* __restrict__ logits, long st_t, long st_b, long st_c, int T,
+                                                              int C, const int* __restrict__ keep, const int* __restrict__ label,
+                                                              const int* __restrict__ label_len, int* correct, int* counter,
+                                                              int* dec, int* dec_len) {
+    __shared__ int seq[256];
+    __shared__ int n_sh;
+    const int bidx = blockIdx.x;
+    const int n = ctc_greedy_decode(logits, st_t, st_b, st_c, T, C, keep, seq, &n_sh);
+    if (threadIdx.x != 0) return;
+    const int L = label_len[bidx];
+    bool ok = n == L;
+    for (int r = 0; r < n; ++r) {
+        if (dec) dec[(long)bidx * T + r] = seq[r];
+        if (ok && label[(long)bidx * T + r] != seq[r]) ok = false;
+    }
     if (dec)
         for (int r = n; r < T; ++r) dec[(long)bidx * T + r] = -1;
     if (dec_len) dec_len[bidx] = n;
@@ -256,5 +270,72 @@ TATT_API int tatt_ctc_greedy_match(const float* logits, long st_t, long st_b, lo
     if (T <= 0 || T > 256 || B <= 0 || C <= 0 || C > 64) return 1;
     hipLaunchKernelGGL(ctc_greedy_match_kernel, dim3(B), dim3(64), 0, st, logits, st_t, st_b, st_c, T, C, keep, label, label_len,
                        correct, counter, dec, dec_len);
+    return LAUNCH_CHECK();
+}
+
+// ------------------------------------------------------------------------------------------------
+// The match kernel plus the edit distance (the eval loop's editdistance.eval(pred, label), reference
+// interfaces/super_resolution.py:1531-1556): the same decoding, then the Levenshtein distance with unit costs between the decoded
+// classes p_1..p_n (n <= T) and the label codes l_1..l_m (m <= 64).  One wave per image; lane j-1 holds column j of the DP row:
+//   tmp[j]  = min(D[i-1][j] + 1, D[i-1][j-1] + (p_i != l_j))              (deletion, substitution / match)
+//   D[i][j] = min(i + j, j + min_{1 <= k <= j}(tmp[k] - k))               (the insertions, as a prefix minimum: 6 shuffle steps)
+// Columns beyond m hold the padding -1, which equals no class, and never feed a lower column.
+// label (B, 64) int: classes 1 .. C-1, any code >= 64 for a character outside the alphabet (it equals no decoded class), padding -1;
+// label_len (B): m, or < 0 (or > 64) for a label the cap excludes: dist -1, not correct, counted in skipped.
+// Outputs (each may be NULL): correct / counter / dec / dec_len as in the match kernel (correct <=> dist == 0), dec rows st_dec ints
+// apart and the elements of correct, dec_len and dist st_img ints apart (so that they can be columns of one record tensor);
+// dist (B); hist (65) int: hist[max(n, m)] += dist (index 0 is never written); scored, skipped: += 1.
+// ------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(64) void ctc_greedy_score_kernel(const float* __restrict__ logits, long st_t, long st_b, long st_c, int T,
+                                                              int C, const int* __restrict__ keep, const int* __restrict__ label,
+                                                              const int* __restrict__ label_len, int* correct, int* counter,
+                                                              int* dec, int* dec_len, int* dist, long st_dec, long st_img,
+                                                              int* hist, int* scored, int* skipped) {
+    __shared__ int seq[256];
+    __shared__ int n_sh;
+    const int bidx = blockIdx.x, lane = threadIdx.x;
+    const int n = ctc_greedy_decode(logits, st_t, st_b, st_c, T, C, keep, seq, &n_sh);
+    if (dec)
+        for (int r = lane; r < T; r += 64) dec[bidx * st_dec + r] = r < n ? seq[r] : -1;
+    const int m = label_len[bidx];
+    int d = -1;
+    if (m >= 0 && m <= 64) {                                     // (uniform over the wave)
+        const int lj = label[(long)bidx * 64 + lane], j = lane + 1;
+        int row = j;                                             // D[0][j]
+        for (int i = 1; i <= n; ++i) {
+            const int p = seq[i - 1];
+            int diag = __shfl_up(row, 1, 64);
+            if (lane == 0) diag = i - 1;                         // D[i-1][0]
+            int s = min(row + 1, diag + (p != lj ? 1 : 0)) - j;
+#pragma unroll
+            for (int o = 1; o < 64; o <<= 1) {
+                const int s2 = __shfl_up(s, o, 64);
+                if (lane >= o) s = min(s, s2);
+            }
+            row = min(i + j, j + s);
+        }
+        d = __shfl(row, m > 0 ? m - 1 : 0, 64);
+        if (m == 0) d = n;
+    }
+    if (lane != 0) return;
+    if (dec_len) dec_len[bidx * st_img] = n;
+    if (dist) dist[bidx * st_img] = d;
+    if (correct) correct[bidx * st_img] = d == 0 ? 1 : 0;
+    if (counter && d == 0) atomicAdd(counter, 1);
+    if (d < 0) {
+        if (skipped) atomicAdd(skipped, 1);
+        return;
+    }
+    if (scored) atomicAdd(scored, 1);
+    const int M = max(n, m);
+    if (hist && d > 0 && M <= 64) atomicAdd(hist + M, d);
+}
+TATT_API int tatt_ctc_greedy_score(const float* logits, long st_t, long st_b, long st_c, int T, int B, int C, const int* keep,
+                                   const int* label, const int* label_len, int* correct, int* counter, int* dec, int* dec_len,
+                                   int* dist, long st_dec, long st_img, int* hist, int* scored, int* skipped, hipStream_t st) {
+    if (T <= 0 || T > 256 || B <= 0 || C <= 0 || C > 64) return 1;
+    if (hist && T > 64) return 1;                                // max(n, m) must index the 65 bins
+    hipLaunchKernelGGL(ctc_greedy_score_kernel, dim3(B), dim3(64), 0, st, logits, st_t, st_b, st_c, T, C, keep, label, label_len,
+                       correct, counter, dec, dec_len, dist, st_dec, st_img, hist, scored, skipped);
     return LAUNCH_CHECK();
 }

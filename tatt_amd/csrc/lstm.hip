@@ -209,3 +209,55 @@ TATT_API int tatt_bicubic_luma(const float* img, long sn, long sc, long sh, long
     hipLaunchKernelGGL(bicubic_luma_kernel, dim3(cdiv(total, 256)), dim3(256), 0, st, img, sn, sc, sh, sw, out, B, H, W, OH, OW);
     return LAUNCH_CHECK();
 }
+
+// ---- plain bicubic resize, F.interpolate(x, (OH, OW), mode='bicubic') of an fp32 batch, forward only (the eval loop's LR baseline,
+// reference interfaces/super_resolution.py:1417-1418): the arithmetic of bicubic_luma_kernel without the luminance.  img (B, C, H, W)
+// and out (B, C, OH, OW) by element strides; one thread per output element, consecutive threads along the output's fastest axis
+// (c_fast: the channel axis of a channels-last output, else the width). ----
+// one plane's value at a source position, as bicubic_luma_kernel sums it: the four horizontal sums first, then the vertical one
+// (iy, ix: floor of the source position)
+__device__ __forceinline__ float bicubic_plane(const float* __restrict__ pl, long sh, long sw, int iy, int ix, const float wy[4],
+                                               const float wx[4], int H, int W) {
+    float v = 0.f;
+    for (int a = 0; a < 4; ++a) {
+        const int yy = min(max(iy - 1 + a, 0), H - 1);
+        float rowv = 0.f;
+        for (int b = 0; b < 4; ++b) {
+            const int xx = min(max(ix - 1 + b, 0), W - 1);
+            rowv += wx[b] * pl[yy * sh + xx * sw];
+        }
+        v += wy[a] * rowv;
+    }
+    return v;
+}
+__global__ void bicubic_resize_kernel(const float* __restrict__ img, long sn, long sc, long sh, long sw, float* __restrict__ out,
+                                      long on, long oc, long oh_s, long ow_s, int B, int C, int H, int W, int OH, int OW, int c_fast) {
+    const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= (long)B * C * OH * OW) return;
+    int c, oh, ow, n;
+    if (c_fast) {
+        c = idx % C; long r = idx / C;
+        ow = r % OW; r /= OW;
+        oh = r % OH; n = r / OH;
+    } else {
+        ow = idx % OW; long r = idx / OW;
+        oh = r % OH; r /= OH;
+        c = r % C; n = r / C;
+    }
+    const float sy = (oh + 0.5f) * ((float)H / OH) - 0.5f, sx = (ow + 0.5f) * ((float)W / OW) - 0.5f;
+    const float fy = floorf(sy), fx = floorf(sx);
+    float wy[4], wx[4];
+    cubic_w(sy - fy, wy);
+    cubic_w(sx - fx, wx);
+    out[n * on + c * oc + oh * oh_s + ow * ow_s] = bicubic_plane(img + n * sn + c * sc, sh, sw, (int)fy, (int)fx, wy, wx, H, W);
+}
+TATT_API int tatt_bicubic_resize(const float* img, long sn, long sc, long sh, long sw, float* out, long on, long oc, long oh_s,
+                                 long ow_s, int B, int C, int H, int W, int OH, int OW, hipStream_t st) {
+    if (B <= 0 || C <= 0 || H <= 0 || W <= 0 || OH <= 0 || OW <= 0) return 1;
+    const long total = (long)B * C * OH * OW;
+    if ((total + 255) / 256 > 0x7fffffffL) return 1;
+    const int c_fast = C > 1 && oc == 1 && ow_s != 1;
+    hipLaunchKernelGGL(bicubic_resize_kernel, dim3(cdiv(total, 256)), dim3(256), 0, st, img, sn, sc, sh, sw, out, on, oc, oh_s, ow_s,
+                       B, C, H, W, OH, OW, c_fast);
+    return LAUNCH_CHECK();
+}

@@ -31,7 +31,7 @@ from . import functional as Fh
 from . import ops
 from ._lib import LIB
 from .ops import ACT_MISH, ACT_RELU, ACT_TANH
-from .io import ALPHABET, str_filt
+from .io import ALPHABET, LABEL_CAP, str_filt
 
 # A/B hook: False -> the CRNN's LSTM layers run the per-step kernels (tatt_lstm_fwd_step) inside the session as well
 LSTM_CHAIN = True
@@ -39,6 +39,9 @@ LSTM_SYNC = []           # weak references to the sync buffers handed to tatt_ls
 LABEL_RING = 4           # pinned host slots the label encoding of consecutive batches rotates through
 CTC_T = 26               # steps of the recogniser's output for its 100-pixel input (parse_crnn_data): W / 4 + 1
 D2A = "-" + ALPHABET     # class c -> character (class 0 is the CTC blank)
+LABEL_FOREIGN = 64       # the one code of every kept label character outside ALPHABET: it equals no class (C <= 64)
+KINDS = ("sr", "lr", "hr")
+HIST = LABEL_CAP + 1     # bins of the edit-distance histogram, indexed by max(len(pred), len(label))
 
 
 # ---- host-side label plumbing ---------------------------------------------------------------------------------------------------
@@ -61,6 +64,25 @@ def encode_labels(labels: Sequence[str], voc_type: str = "lower", T: int = CTC_T
             lens.append(-1)
         else:
             codes.append(ids + [-1] * (T - len(ids)))
+            lens.append(len(ids))
+    return codes, lens
+
+
+def encode_labels_full(labels: Sequence[str], voc_type: str = "lower", cap: int = LABEL_CAP):
+    """The encoding tatt_ctc_greedy_score reads -> (codes: B lists of `cap` ints padded with -1, lengths: B ints).  The characters of
+    `str_filt(label, voc_type)` in ALPHABET map to their classes 1..36, every other kept character (upper case under 'upper',
+    punctuation under 'all') to the ONE code LABEL_FOREIGN: a decoding holds alphabet classes only, so a foreign character mismatches
+    whatever it meets and the edit distance is exact.  A filtered label longer than `cap` gets length -1 (not scored)."""
+    a2d = {ch: i for i, ch in enumerate(D2A)}
+    codes, lens = [], []
+    for lab in labels:
+        s = str_filt(lab, voc_type)
+        if len(s) > cap:
+            codes.append([-1] * cap)
+            lens.append(-1)
+        else:
+            ids = [a2d[ch] if a2d.get(ch, 0) > 0 else LABEL_FOREIGN for ch in s]
+            codes.append(ids + [-1] * (cap - len(ids)))
             lens.append(len(ids))
     return codes, lens
 
@@ -90,6 +112,36 @@ def ctc_greedy_match(logits, keep, label, label_len, counter=None, want_decoded=
     ops.call("tatt_ctc_greedy_match", ops.P(logits), *logits.stride(), T, B, C, ops.P(keep), ops.P(label), ops.P(label_len),
              ops.P(correct), ops.P(counter), ops.P(dec), ops.P(dlen), ops.stream())
     return (correct, dec, dlen) if want_decoded else correct
+
+
+def ctc_greedy_score(logits, keep, label, label_len, counter=None, stats=None, record=None):
+    """`ctc_greedy_match` plus the edit distance, one launch (tatt_ctc_greedy_score).  logits (T, B, C) on the GPU; keep (C,), label
+    (B, LABEL_CAP) and label_len (B,) int32 device tensors from `encode_labels_full` -> record (B, T + 3) int32:
+    decoded classes padded with -1 | decoded length | correct 0/1 | distance (-1 for a label of length -1).
+    `counter`: += correct images; `stats` (HIST + 2,) int32: [max(len(pred), len(label))] += distance | scored += 1 | skipped += 1
+    (see `ned_from_stats`); `record`: the (B, T + 3) int32 tensor to write into."""
+    ops._check_dev(logits)
+    T, B, C = logits.shape
+    if tuple(label.shape) != (B, LABEL_CAP) or not label.is_contiguous():
+        raise ValueError("label must be a contiguous (%d, %d) int32 tensor, got %s" % (B, LABEL_CAP, tuple(label.shape)))
+    if record is None:
+        record = torch.empty(B, T + 3, dtype=torch.int32, device=logits.device)
+    elif tuple(record.shape) != (B, T + 3) or record.dtype != torch.int32 or not record.is_contiguous():
+        raise ValueError("record must be a contiguous (%d, %d) int32 tensor" % (B, T + 3))
+    if stats is not None and (stats.numel() != HIST + 2 or stats.dtype != torch.int32 or not stats.is_contiguous()):
+        raise ValueError("stats must be a contiguous (%d,) int32 tensor" % (HIST + 2))
+    col = lambda k: ops.P(record[:, T + k])
+    hist, scored, skipped = (None,) * 3 if stats is None else (ops.P(stats), ops.P(stats[HIST:]), ops.P(stats[HIST + 1:]))
+    ops.call("tatt_ctc_greedy_score", ops.P(logits), *logits.stride(), T, B, C, ops.P(keep), ops.P(label), ops.P(label_len),
+             col(1), ops.P(counter), ops.P(record), col(0), col(2), T + 3, T + 3, hist, scored, skipped, ops.stream())
+    return record
+
+
+def ned_from_stats(stats) -> float:
+    """Mean of distance / (max(len(pred), len(label)) + 1e-10) over the scored images (reference
+    interfaces/super_resolution.py:1531-1556,1633-1635) from the integers of one `stats` row (host values)."""
+    vals = [int(v) for v in stats]
+    return sum(vals[M] / (M + 1e-10) for M in range(1, HIST)) / (vals[HIST] + 1e-10)
 
 
 def lstm_chain_capacity(device=None) -> int:
@@ -184,10 +236,15 @@ class InferenceSession:
     sync); after a change torch sees (load_state_dict, a `.data` copy, an optimiser step) the folded filters and the packed layouts are
     rebuilt eagerly in the same buffers before the replay.  Writes torch cannot see (raw pointers) need `refresh()`.  A parameter that
     moved to another address means a new capture, done automatically.
-    The arithmetic (`tatt_amd.set_arithmetic`) is the one in force at capture time: changing it later needs a new session."""
+    The arithmetic (`tatt_amd.set_arithmetic`) is the one in force at capture time: changing it later needs a new session.
+
+    full_metrics=True (opt-in; without it the captured graph is what it always was): with `hr`, `psnr_lr_sum` / `ssim_lr_sum` of
+    bicubic_resize(lr[:, :3], hr size) against HR; for every name in `accuracy_on` tatt_ctc_greedy_score runs INSTEAD of the match
+    launch and fills, per image kind, `ned_stats[k]` (edit-distance histogram | scored | skipped, see `ned_from_stats`) and the last
+    batch's `records[k]` (B, T + 3): decoded | length | correct | distance.  Labels are then encoded LABEL_CAP = 64 wide."""
 
     def __init__(self, generator, prior=None, recognizer=None, batch_size: int = None, lr_size=(16, 64), accuracy_on=("sr",),
-                 voc_type: str = "lower"):
+                 voc_type: str = "lower", full_metrics: bool = False):
         from .tsrn import TSRN, TSRN_TL_TRANS
         from .tbsrn import TBSRN
         _check_module(generator, "generator")
@@ -220,6 +277,13 @@ class InferenceSession:
         self.psnr_sum = torch.zeros((), device=self.device)
         self.ssim_sum = torch.zeros((), device=self.device)
         self.correct = torch.zeros(3, dtype=torch.int32, device=self.device)      # sr, lr, hr
+        # full_metrics: the bicubic LR baseline's sums, per image kind the edit-distance histogram | scored | skipped, and (allocated
+        # with the label buffers) the record of the LAST batch, (3, B, T + 3): decoded | length | correct | distance, -1 where not run
+        self.full_metrics = bool(full_metrics)
+        self.psnr_lr_sum = torch.zeros((), device=self.device)
+        self.ssim_lr_sum = torch.zeros((), device=self.device)
+        self.ned_stats = torch.zeros(3, HIST + 2, dtype=torch.int32, device=self.device)
+        self.records = None
         self.graph = None
         self._syncs, self._sync_i = [], 0
         self._sources = [t for m in (generator, prior, recognizer) if m is not None
@@ -350,6 +414,11 @@ class InferenceSession:
             from .train import calculate_psnr
             self.psnr_sum += calculate_psnr(sr[:, :3], hr[:, :3])
             self.ssim_sum += SSIM()(sr[:, :3], hr[:, :3])
+            if self.full_metrics:                                 # the bicubic baseline (reference :1417-1418, :1452)
+                from .crnn import bicubic_resize
+                up = bicubic_resize(lr[:, :3], hr.shape[-2:])
+                self.psnr_lr_sum += calculate_psnr(up, hr[:, :3])
+                self.ssim_lr_sum += SSIM()(up, hr[:, :3])
         if self.rec is not None and self._labels is not None:
             from .crnn import parse_crnn_data
             imgs = {"sr": sr, "lr": lr, "hr": hr}
@@ -361,7 +430,12 @@ class InferenceSession:
                 if logits.shape[0] != CTC_T:
                     raise RuntimeError("recogniser output has %d steps, the label buffers %d" % (logits.shape[0], CTC_T))
                 self._logits[name] = logits
-                ctc_greedy_match(logits, self._keep, self._labels[0], self._labels[1], self.correct[("sr", "lr", "hr").index(name):])
+                k = KINDS.index(name)
+                if self.full_metrics:                             # the score launch INSTEAD of the match launch
+                    ctc_greedy_score(logits, self._keep, self._labels[0], self._labels[1], self.correct[k:], self.ned_stats[k],
+                                     self.records[k])
+                else:
+                    ctc_greedy_match(logits, self._keep, self._labels[0], self._labels[1], self.correct[k:])
         return sr, pr_weights, prior
 
     # -- capture and replay ----------------------------------------------------------------------------------------------------------
@@ -374,13 +448,13 @@ class InferenceSession:
         if labels is not None and self._labels is not None:
             # encoded on the host into the next pinned staging slot and copied asynchronously: no host wait on the GPU per batch.  A slot
             # is rewritten only after its previous copy has been consumed (its event; LABEL_RING slots keep the host that far ahead)
-            codes, lens = encode_labels(labels, self.voc_type)
+            codes, lens = (encode_labels_full if self.full_metrics else encode_labels)(labels, self.voc_type)
             k = self._ring_i % LABEL_RING
             self._ring_i += 1
             host, ev = self._lab_host[k], self._lab_events[k]
             if ev is not None:
                 ev.synchronize()
-            n = self.B * CTC_T
+            n = self.B * self._lab_w
             host[:n].copy_(torch.tensor(codes, dtype=torch.int32).reshape(-1))
             host[n:].copy_(torch.tensor(lens, dtype=torch.int32))
             self._lab_dev.copy_(host, non_blocking=True)
@@ -396,16 +470,21 @@ class InferenceSession:
             self._tp = torch.zeros(1, 37, 1, 26, device=dev) if text_prior is None else torch.empty_like(text_prior)
         self._labels = None
         if labels is not None and self.rec is not None:
-            n = self.B * CTC_T
-            self._lab_dev = torch.full((n + self.B,), -1, dtype=torch.int32, device=dev)        # codes (B, T) | lengths (B)
-            self._labels = (self._lab_dev[:n].view(self.B, CTC_T), self._lab_dev[n:])
+            self._lab_w = LABEL_CAP if self.full_metrics else CTC_T                          # label codes per image
+            n = self.B * self._lab_w
+            self._lab_dev = torch.full((n + self.B,), -1, dtype=torch.int32, device=dev)        # codes (B, width) | lengths (B)
+            self._labels = (self._lab_dev[:n].view(self.B, self._lab_w), self._lab_dev[n:])
+            if self.full_metrics:
+                self.records = torch.full((3, self.B, CTC_T + 3), -1, dtype=torch.int32, device=dev)
             self._lab_host = [torch.empty(n + self.B, dtype=torch.int32, pin_memory=True) for _ in range(LABEL_RING)]
             self._lab_events, self._ring_i = [None] * LABEL_RING, 0
         self._has = (hr is not None, labels is not None, text_prior is not None)
         self._stage_inputs(lr, hr, labels, text_prior)
-        acc = (self.psnr_sum.clone(), self.ssim_sum.clone(), self.correct.clone())
+        accs = (self.psnr_sum, self.ssim_sum, self.correct, self.psnr_lr_sum, self.ssim_lr_sum, self.ned_stats)
+        acc = [t.clone() for t in accs]
         self._forward()                                          # eager warm-up: workspaces, packed layouts, sync buffers
-        self.psnr_sum.copy_(acc[0]); self.ssim_sum.copy_(acc[1]); self.correct.copy_(acc[2])
+        for t, v in zip(accs, acc):
+            t.copy_(v)
         torch.cuda.synchronize(dev)
         g = torch.cuda.CUDAGraph()
         with torch.cuda.graph(g):
@@ -454,51 +533,89 @@ class InferenceSession:
         self.psnr_sum.zero_()
         self.ssim_sum.zero_()
         self.correct.zero_()
+        self.psnr_lr_sum.zero_()
+        self.ssim_lr_sum.zero_()
+        self.ned_stats.zero_()
 
 
 class PendingEvaluation:
-    """What `evaluate_session_async` started: the device-side totals of its sessions.  `result()` is the one host sync."""
+    """What `evaluate_session_async` started: the device-side totals of its sessions.  `result()` is the one host sync; with
+    full_metrics `records()` reads the per-image recognition record afterwards (one more copy)."""
 
-    def __init__(self, totals, n, n_img):
+    def __init__(self, totals, n, n_img, full=None, records=None):
         self._totals, self.n_batches, self.n_images = totals, n, n_img
+        self._full, self._records, self._rows = full, records, None
 
     def result(self):
         if self._totals is None:
             return {"psnr": 0.0, "ssim": 0.0, "n_batches": 0}
-        tot = self._totals.cpu()                                  # the one host sync
+        # the one host sync (with full_metrics the second tensor rides behind it on the same stream)
+        tot, full = self._totals.cpu(), None if self._full is None else self._full.cpu()
         n, n_img = self.n_batches, self.n_images
         corr = [int(v) for v in tot[2:].tolist()]
         res = {"psnr": float(tot[0]) / n, "ssim": float(tot[1]) / n, "n_batches": n}
+        if full is not None:
+            res.update(psnr_lr=float(full[0]) / n, ssim_lr=float(full[1]) / n)
         if n_img:
             res.update(accuracy=round(corr[0] / n_img, 4), accuracy_lr=round(corr[1] / n_img, 4), accuracy_hr=round(corr[2] / n_img, 4),
                        n_images=n_img)
+            if full is not None:
+                stats = full[2:].reshape(3, HIST + 2).round().long().tolist()
+                res.update(ned=ned_from_stats(stats[0]), ned_lr=ned_from_stats(stats[1]), ned_hr=ned_from_stats(stats[2]),
+                           ned_skipped=max(row[HIST + 1] for row in stats))
         return res
+
+    def records(self):
+        """The recognition record behind the reference's `vis` output (interfaces/super_resolution.py:1518-1560), one dict per image
+        in batch order: 'label' (as given), the filtered decodings 'sr' / 'lr' / 'hr', the flags 'sr_correct' / 'lr_correct' /
+        'hr_correct' and the edit distances 'sr_dist' / 'lr_dist' / 'hr_dist' (-1: the filtered label is longer than LABEL_CAP; an
+        image kind that was not recognised gives None for its three entries).  Read it after `result()`; needs full_metrics."""
+        if self._records is None:
+            raise RuntimeError("records() needs evaluate_session_async(..., full_metrics=True) with a recogniser and labels")
+        if self._rows is None:
+            recs, labels = self._records
+            host = torch.cat(recs, 1).cpu().tolist() if recs else [[], [], []]         # (3, images, T + 3)
+            rows = []
+            for i, lab in enumerate(labels):
+                row = {"label": lab}
+                for k, name in enumerate(KINDS):
+                    r = host[k][i]
+                    n = r[-3]
+                    ran = n >= 0
+                    row[name] = "".join(D2A[c] for c in r[:n]) if ran else None
+                    row[name + "_correct"] = bool(r[-2]) if ran else None
+                    row[name + "_dist"] = r[-1] if ran else None
+                rows.append(row)
+            self._rows = rows
+        return self._rows
 
 
 def evaluate_session_async(generator, batches: Iterable, prior=None, recognizer=None, voc_type: str = "lower",
-                           sessions: dict = None, export=None) -> PendingEvaluation:
+                           sessions: dict = None, export=None, full_metrics: bool = False) -> PendingEvaluation:
     """`evaluate_session` without its final host sync: every batch is staged and replayed without the host waiting on the GPU (the
     label encodings travel through pinned staging buffers); `.result()` of the returned object reads the totals.
     `export(batch_index, pending_panels)`: when given, the lr_sr_hr panels of every batch (the eval loop's canvas,
     `DeviceExporter.panels(lr, sr, hr, gap=5)`, reference interfaces/super_resolution.py:1572-1622) are enqueued behind the batch's
     replay and the callback gets the `PendingExport`; reading it (`.result()`) is the callback's only wait, and it may keep it for
-    later.  The metrics do not depend on it."""
+    later.  The metrics do not depend on it.
+    `full_metrics`: see `evaluate_session`; each batch's record tensor is cloned on the stream behind its replay (a device copy)."""
     sessions = {} if sessions is None else sessions
     exporter = None
     if export is not None:
         from .io import DeviceExporter
         exporter = DeviceExporter(device=next(generator.parameters()).device, rule="floor")
     used, n, n_img = [], 0, 0
+    recs, rec_labels = [], []
     for batch in batches:
         lr, hr = batch[0], batch[1]
         tp = batch[2] if len(batch) > 2 and batch[2] is not None and prior is None else None
         labels = batch[3] if len(batch) > 3 and recognizer is not None else None
-        key = (lr.shape[0], tuple(lr.shape[2:]), tp is not None, labels is not None)
+        key = (lr.shape[0], tuple(lr.shape[2:]), tp is not None, labels is not None) + ((True,) if full_metrics else ())
         s = sessions.get(key)
         built = s is None
         if built:
             s = sessions[key] = InferenceSession(generator, prior, recognizer, batch_size=lr.shape[0], lr_size=tuple(lr.shape[2:]),
-                                                 accuracy_on=("sr", "lr", "hr"), voc_type=voc_type)
+                                                 accuracy_on=("sr", "lr", "hr"), voc_type=voc_type, full_metrics=full_metrics)
         if not any(s is u for u in used):
             if not built:
                 # a session kept from an earlier call: the weights and running statistics may have been written since through raw
@@ -509,25 +626,35 @@ def evaluate_session_async(generator, batches: Iterable, prior=None, recognizer=
         out = s.run(lr, hr, labels, tp)
         if exporter is not None:
             export(n, exporter.panels(lr, out[0], hr, gap=5))          # (reads the static SR output before the next replay: same stream)
+        if full_metrics and labels is not None:
+            recs.append(s.records.clone())                             # (before the next replay overwrites it: same stream)
+            rec_labels.extend(labels)
         n += 1
         if labels is not None:
             n_img += len(labels)
-    totals = None
+    totals = full = None
     if used:
         totals = torch.stack([torch.cat([s.psnr_sum.reshape(1).double(), s.ssim_sum.reshape(1).double(), s.correct.double()])
                               for s in used]).sum(0)
-    return PendingEvaluation(totals, n, n_img)
+        if full_metrics:
+            full = torch.stack([torch.cat([s.psnr_lr_sum.reshape(1).double(), s.ssim_lr_sum.reshape(1).double(),
+                                           s.ned_stats.reshape(-1).double()]) for s in used]).sum(0)
+    return PendingEvaluation(totals, n, n_img, full, (recs, rec_labels) if full_metrics and recognizer is not None else None)
 
 
 def evaluate_session(generator, batches: Iterable, prior=None, recognizer=None, voc_type: str = "lower", sessions: dict = None,
-                     export=None):
+                     export=None, full_metrics: bool = False):
     """Drop-in for `tatt_amd.io.evaluate` on graph-captured sessions: batches of (images_lr, images_hr[, text_prior[, label_strs]]);
     with a `prior` CRNN the text prior is computed from LR inside the graph (a batch's own prior is then ignored).  One session per
     batch size (a smaller last batch gets its own, no padding), kept in `sessions` when a dict is passed (reuse across calls: a kept
     session re-folds and re-packs from the current weights at the start of each call).  PSNR / SSIM sums and the correct-image counters
     stay on the device and no batch makes the host wait; one host sync at the end.  Returns the dict of io.evaluate.
-    `export`: see `evaluate_session_async`."""
-    return evaluate_session_async(generator, batches, prior, recognizer, voc_type, sessions, export).result()
+    `export`: see `evaluate_session_async`.
+    `full_metrics=True` adds the rest of the reference's report, still without a host wait per batch: 'psnr_lr' / 'ssim_lr' (the
+    bicubic baseline, tatt_bicubic_resize of LR against HR) and, with a recogniser, 'ned' / 'ned_lr' / 'ned_hr' (mean normalised edit
+    distance of the SR / LR / HR decodings, tatt_ctc_greedy_score in place of the match launch) and 'ned_skipped' (images whose
+    filtered label has more than LABEL_CAP = 64 characters: the means leave them out).  Sessions of the two modes are kept apart."""
+    return evaluate_session_async(generator, batches, prior, recognizer, voc_type, sessions, export, full_metrics).result()
 
 
 # ---- PIL crops in, PIL images out ---------------------------------------------------------------------------------------------------

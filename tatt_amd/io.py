@@ -273,23 +273,48 @@ def str_filt(s: str, voc_type: str = "lower") -> str:
     return "".join(ch for ch in s if ch in alpha)
 
 
+def edit_distance(a: str, b: str) -> int:
+    """Levenshtein distance with unit costs between two strings: what the reference's `editdistance.eval` returns
+    (interfaces/super_resolution.py:1531-1556).  Pure Python, the textbook row-by-row DP; it is the specification of
+    tatt_ctc_greedy_score's distance."""
+    if len(a) < len(b):
+        a, b = b, a
+    row = list(range(len(b) + 1))
+    for i, ca in enumerate(a, 1):
+        prev, row[0] = row[0], i
+        for j, cb in enumerate(b, 1):
+            prev, row[j] = row[j], min(row[j] + 1, row[j - 1] + 1, prev + (ca != cb))
+    return row[len(b)]
+
+
+LABEL_CAP = 64            # most characters of a filtered label the edit-distance metrics score (the score kernel's label width)
+
+
 @torch.no_grad()
-def evaluate(model: torch.nn.Module, batches: Iterable, prior_fn=None, recognizer=None, voc_type: str = "lower"):
+def evaluate(model: torch.nn.Module, batches: Iterable, prior_fn=None, recognizer=None, voc_type: str = "lower",
+             full_metrics: bool = False):
     """Metric part of the reference's eval loop: for every (images_lr, images_hr[, text_prior[, label_strs]]) batch run the
     generator in eval mode and accumulate calculate_psnr / SSIM of SR vs HR on the first three channels
     (interfaces/super_resolution.py:1454-1455).  With a `recognizer` (tatt_amd.CRNN, the reference's --test_model CRNN) and label
     strings in the batch, also the recognition accuracies of the SR, LR and HR images (:1374-1396,1527-1558,1662-1664).
-    Returns {'psnr', 'ssim', 'n_batches'[, 'accuracy', 'accuracy_lr', 'accuracy_hr', 'n_images']} (python floats)."""
+    Returns {'psnr', 'ssim', 'n_batches'[, 'accuracy', 'accuracy_lr', 'accuracy_hr', 'n_images']} (python floats).
+    full_metrics=True adds the rest of the reference's report: 'psnr_lr' / 'ssim_lr', the bicubic baseline
+    F.interpolate(images_lr, hr_size, mode="bicubic") against HR (:1417-1418,1452), and with a recogniser 'ned' / 'ned_lr' / 'ned_hr',
+    the mean of edit_distance(pred, label) / (max(len(pred), len(label)) + 1e-10) over the images (:1531-1556,1633-1635; both
+    strings through str_filt), and 'ned_skipped': the images whose filtered label has more than LABEL_CAP characters, which the
+    means leave out (the same rule as the device path, `infer.evaluate_session`)."""
     from .losses import SSIM, calculate_psnr
-    from .crnn import parse_crnn_data
+    from .crnn import bicubic_resize, parse_crnn_data
     was_training = model.training
     model.eval()
     ssim = SSIM()
     psnr_sum = torch.zeros((), device=next(model.parameters()).device)
     ssim_sum = torch.zeros_like(psnr_sum)
+    psnr_lr_sum, ssim_lr_sum = torch.zeros_like(psnr_sum), torch.zeros_like(psnr_sum)
     n = 0
     correct = {"sr": 0, "lr": 0, "hr": 0}
-    n_img = 0
+    ned = {"sr": 0.0, "lr": 0.0, "hr": 0.0}
+    n_img = n_scored = n_skipped = 0
     rec_was_training = recognizer.training if recognizer is not None else False
     if recognizer is not None:
         recognizer.eval()
@@ -301,19 +326,35 @@ def evaluate(model: torch.nn.Module, batches: Iterable, prior_fn=None, recognize
         sr = out[0] if isinstance(out, tuple) else out
         psnr_sum += calculate_psnr(sr[:, :3], hr[:, :3])
         ssim_sum += ssim(sr[:, :3], hr[:, :3])
+        if full_metrics:
+            up = bicubic_resize(lr[:, :3], hr.shape[-2:])
+            psnr_lr_sum += calculate_psnr(up, hr[:, :3])
+            ssim_lr_sum += ssim(up, hr[:, :3])
         n += 1
         if recognizer is not None and labels is not None:
+            want = [str_filt(t, voc_type) for t in labels]
+            scored = [len(t) <= LABEL_CAP for t in want]
             for name, img in (("sr", sr), ("lr", lr), ("hr", hr)):
                 pred = ctc_greedy_decode(recognizer(parse_crnn_data(img[:, :3].contiguous())))
-                correct[name] += sum(str_filt(p, voc_type) == str_filt(t, voc_type) for p, t in zip(pred, labels))
+                pred = [str_filt(p, voc_type) for p in pred]
+                correct[name] += sum(p == t for p, t in zip(pred, want))
+                if full_metrics:
+                    ned[name] += sum(edit_distance(p, t) / (max(len(p), len(t)) + 1e-10) for p, t, ok in zip(pred, want, scored) if ok)
             n_img += len(labels)
+            n_scored += sum(scored)
+            n_skipped += len(scored) - sum(scored)
     model.train(was_training)
     if recognizer is not None:
         recognizer.train(rec_was_training)               # e.g. TextPriorSR.tpg under training: BatchNorm must not stay in eval mode
     res = {"psnr": float(psnr_sum) / max(n, 1), "ssim": float(ssim_sum) / max(n, 1), "n_batches": n}
+    if full_metrics:
+        res.update(psnr_lr=float(psnr_lr_sum) / max(n, 1), ssim_lr=float(ssim_lr_sum) / max(n, 1))
     if n_img:
         res.update(accuracy=round(correct["sr"] / n_img, 4), accuracy_lr=round(correct["lr"] / n_img, 4),
                    accuracy_hr=round(correct["hr"] / n_img, 4), n_images=n_img)
+        if full_metrics:
+            res.update(ned=ned["sr"] / (n_scored + 1e-10), ned_lr=ned["lr"] / (n_scored + 1e-10), ned_hr=ned["hr"] / (n_scored + 1e-10),
+                       ned_skipped=n_skipped)
     return res
 
 

@@ -1,13 +1,16 @@
 """Throughput of the eval / test loop: the eager `tatt_amd.io.evaluate` against the graph-captured `tatt_amd.infer.evaluate_session`,
 and the one-launch LSTM layer against the per-step kernels.  Reports only (one JSON line per case), asserts nothing.
 
-    python tools/bench_infer.py [--steps 20] [--warmup 3] [--repeats 5]
+    python tools/bench_infer.py [--steps 20] [--warmup 3] [--repeats 5] [--full-metrics]
 
 Timing as bench.py: warm-up, device-synchronised, median of repeats.  Cases:
   tatt_crnn_b48  TATT with a CRNN prior and a CRNN recogniser (accuracies of SR / LR / HR), B = 48
   tatt_b1        TATT with the CRNN prior at B = 1 (the reference's demo())
   tsrn_b48       TSRN, PSNR / SSIM only, B = 48
   lstm_b48       one BiLSTM layer of the CRNN (T = 26, H = 256): chain vs per-step launches, same process and data
+--full-metrics runs ONE case instead: tatt_crnn_b48 through `evaluate_session` with and without `full_metrics=True` (bicubic LR
+baseline, edit distances, per-image records), alternating in one process; min / median / max of the repeats and the kernel nodes
+of either graph.
 """
 import argparse
 import json
@@ -75,6 +78,67 @@ def bench_loop(name, dev, tatt, B, use_prior, use_rec, args):
                       "session_img_s": round(n_img / sess, 1), "speedup": round(eager / sess, 2)}), flush=True)
 
 
+def _graph_kernel_nodes(session):
+    """Kernel nodes of the session's graph: its forward captured once more into a graph that keeps its hipGraph_t, whose nodes the
+    HIP runtime lists (hipGraphGetNodes / hipGraphNodeGetType; type 0 is a kernel launch)."""
+    import ctypes
+    from tatt_amd import functional as Fh
+    with open("/proc/self/maps") as f:                                    # the runtime torch already loaded, not a second copy
+        path = next(line.split()[-1] for line in f if "libamdhip64" in line)
+    hip = ctypes.CDLL(path)
+    g = torch.cuda.CUDAGraph(keep_graph=True)
+    fork = (Fh.FWD_FORK.enabled, Fh.FWD_FORK_B.enabled)
+    Fh.FWD_FORK.enabled = Fh.FWD_FORK_B.enabled = False                   # as InferenceSession.run captures
+    try:
+        with torch.no_grad(), torch.cuda.graph(g):
+            session._forward()
+    finally:
+        Fh.FWD_FORK.enabled, Fh.FWD_FORK_B.enabled = fork
+    graph, n = ctypes.c_void_p(g.raw_cuda_graph()), ctypes.c_size_t(0)
+    if hip.hipGraphGetNodes(graph, None, ctypes.byref(n)) != 0:
+        raise RuntimeError("hipGraphGetNodes failed")
+    nodes = (ctypes.c_void_p * n.value)()
+    if hip.hipGraphGetNodes(graph, nodes, ctypes.byref(n)) != 0:
+        raise RuntimeError("hipGraphGetNodes failed")
+    kernels = 0
+    for node in nodes:
+        kind = ctypes.c_int(-1)
+        if hip.hipGraphNodeGetType(ctypes.c_void_p(node), ctypes.byref(kind)) != 0:
+            raise RuntimeError("hipGraphNodeGetType failed")
+        kernels += kind.value == 0
+    return kernels
+
+
+def bench_full_metrics(dev, args, B=48):
+    from tatt_amd.infer import evaluate_session
+    g, c = _models(dev, True)
+    batches = _batches(dev, B, args.steps, True)
+    sessions = {}
+    run = {full: (lambda full=full: evaluate_session(g, batches, prior=c, recognizer=c, sessions=sessions, full_metrics=full))
+           for full in (False, True)}
+    for _ in range(args.warmup):
+        for full in (False, True):
+            run[full]()
+    torch.cuda.synchronize()
+    ts = {False: [], True: []}
+    for _ in range(args.repeats):                                         # alternating: both see the same machine state
+        for full in (False, True):
+            t0 = time.perf_counter()
+            run[full]()                                                   # (ends in the host read of the totals)
+            torch.cuda.synchronize()
+            ts[full].append(1e3 * (time.perf_counter() - t0) / args.steps)
+    launches = {}
+    for key, s in sessions.items():
+        try:
+            launches[s.full_metrics] = _graph_kernel_nodes(s)
+        except Exception as e:                                            # a report, not a check
+            launches[s.full_metrics] = "not measured (%s: %s)" % (type(e).__name__, e)
+    stat = lambda v: {"min": round(min(v), 3), "median": round(statistics.median(v), 3), "max": round(max(v), 3)}
+    print(json.dumps({"case": "tatt_crnn_b48_full_metrics", "B": B, "batches": args.steps, "repeats": args.repeats,
+                      "session_ms_per_batch": stat(ts[False]), "full_metrics_ms_per_batch": stat(ts[True]),
+                      "graph_launches": launches.get(False), "full_metrics_graph_launches": launches.get(True)}), flush=True)
+
+
 def bench_lstm(dev, args, B=48, T=26):
     from tatt_amd.infer import bilstm_eval
     torch.manual_seed(0)
@@ -104,10 +168,16 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--only", default="", help="comma-separated case names")
+    ap.add_argument("--full-metrics", action="store_true", help="time evaluate_session with and without full_metrics=True instead")
     args = ap.parse_args()
     import __graft_entry__
     __graft_entry__.build()
     dev = torch.device("cuda:0")
+    if args.full_metrics:
+        bench_full_metrics(dev, args)
+        import tatt_amd
+        tatt_amd.sync_check()
+        return
     only = set(filter(None, args.only.split(",")))
     cases = [("tatt_crnn_b48", True, 48, True, True), ("tatt_b1", True, 1, True, False), ("tsrn_b48", False, 48, False, False)]
     for name, tatt, B, pr, rec in cases:
