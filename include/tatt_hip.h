@@ -819,6 +819,39 @@ int tatt_export_images(const float* src, long st_n, long st_c, long st_h, long s
 /* out[0..4]: largest H, largest W, largest OH, largest OW, most bytes of the horizontal pass's result (H * OW * 3, counted when
  * W != OW).  Host only: needs no GPU. */
 int tatt_export_limits(int* out);
+/* ---- text lines of any width (csrc/lines.hip; tatt_amd/lines.py is the specification) -- */
+/* ONE launch, one work-group per window: window x0 .. x0 + w - 1 of `line = img.resize((wl, h), BICUBIC)` for an RGB uint8 source,
+ * ToTensor (float(v) / 255, planes C,H,W) and, with the mask flag, the fourth plane `1 where gray <= the WINDOW's mean gray` -- bit for
+ * bit `resize_normalize`-style output of `line.crop((x0, 0, x0 + w, h))`.  The coefficient tables are those of the full line (W_src -> wl,
+ * H_src -> h); only the window's columns are computed.  packed (packed_bytes): the interleaved RGB sources, one per LINE (all windows of a
+ * line name the same offset); desc (n_windows, 12) int32 in DEVICE memory:
+ *   [0] byte offset of the source in packed  [1] H_src  [2] W_src  [3] h  [4] wl  [5] x0  [6] w  [7] mask flag  [8] float offset of the
+ *   window's (3 + mask, h, w) planes in out  [9..11] 0
+ * A pass whose source and target size agree is skipped, as in Pillow.  desc_host: the same rows in HOST memory, read before the launch
+ * only to refuse what the kernel does not take: 2 for a geometry beyond tatt_line_limits (or x0 outside 0 .. wl - w), 3 for a source or
+ * planes that leave packed / out (out_floats), 1 for bad arguments or a reserved word; there is no fallback in here.  The kernel itself
+ * reads only device memory (the launch can be captured) and re-checks every row: a row it would have refused gets NaN planes, or nothing
+ * when they lie outside out. */
+int tatt_line_windows(const unsigned char* packed, long packed_bytes, const int* desc, const int* desc_host, int n_windows,
+                      float* out, long out_floats, hipStream_t st);
+/* ONE launch for all lines: the SR windows src (B, C, H, W) fp32 by element strides (channels-last or contiguous) merged into one
+ * (H, scale * wl, 3) uint8 canvas per line.  desc (n_lines, 8) int32 in DEVICE memory:
+ *   [0] index of the line's first window in src and in starts  [1] its windows  [2] wl  [3] scale (W = scale * w)  [4] quantisation rule
+ *   [5] first channel c0  [6] byte offset of the canvas in out  [7] row pitch in bytes, >= 3 * scale * wl
+ * starts (n_starts) int32 in DEVICE memory: the LR column x_k of every window.  Every window is quantised like tatt_export_images (rule 0:
+ * x * 255.0f clipped and truncated; rule 1: + 0.5f first; NaN -> 0).  Canvas column X takes every window k with
+ * scale * x_k <= X < scale * x_k + W at its local column j = X - scale * x_k with the integer weight min(j + 1, W - j); the pixel is
+ * (2 N + D) / (2 D) for N = sum weight * value, D = sum weight.  desc_host / starts_host: the same in HOST memory, read before the launch
+ * only to refuse: 1 bad arguments or rule, 2 geometry (scale not dividing W, wl beyond tatt_line_limits, more windows than it reports,
+ * starts that do not begin at 0, end flush right, increase and cover every column), 3 windows, channels or destination bytes that leave
+ * src / starts / out (out_bytes).  The kernel reads only device memory and re-checks every row: it writes nothing for a row it refuses. */
+int tatt_line_blend(const float* src, long st_n, long st_c, long st_h, long st_w, int B, int C, int H, int W, const int* desc,
+                    const int* desc_host, int n_lines, const int* starts, const int* starts_host, int n_starts,
+                    unsigned char* out, long out_bytes, hipStream_t st);
+/* out[0..7]: most source rows, most source columns, largest wl, largest window height, largest window width, most bytes of the
+ * horizontal pass's result (H_src * w * 3) and of its coefficient rows (w * ksize * 4), both counted when W_src != wl, most windows of
+ * one line.  Host only: needs no GPU. */
+int tatt_line_limits(int* out);
 /* calculate_psnr (reference utils/ssim_psnr.py:9-15) of two (B,C,H,W) images in [0,1] given by element strides, first 3 channels */
 int tatt_psnr(const float* a, long a_n, long a_c, long a_h, long a_w, const float* b, long b_n, long b_c, long b_h, long b_w,
               float* out, int B, int C, int H, int W, hipStream_t st);

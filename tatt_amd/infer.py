@@ -660,10 +660,12 @@ def evaluate_session(generator, batches: Iterable, prior=None, recognizer=None, 
 # ---- PIL crops in, PIL images out ---------------------------------------------------------------------------------------------------
 class PendingUpscale:
     """What `SuperResolver.__call__` started.  `result()` is the only host wait: -> the SR images as RGB PIL images, in input order
-    (with a recogniser: (images, texts)).  `sr`: with keep_sr, a clone of every batch's SR tensor."""
+    (with a recogniser: (images, texts)).  `sr`: with keep_sr, a clone of every batch's SR tensor; with long_lines the ONE
+    (n_windows, C, H, W) buffer of all SR windows, beside `lr` (the window stack the sessions read) and `lines` (`io.Line` records)."""
 
-    def __init__(self, parts, with_text, sr):
+    def __init__(self, parts, with_text, sr, lr=None, lines=None):
         self._parts, self._with_text, self.sr = parts, with_text, sr
+        self.lr, self.lines = lr, lines                              # long_lines with keep_sr: the window stack and its Line records
 
     def result(self):
         images, texts = [], []
@@ -690,18 +692,34 @@ class SuperResolver:
     `PendingUpscale.result()` (but the first batch of each size, which captures its session).  With `recognizer` (a CRNN) the greedy CTC strings of the SR images come back as well: an eager recogniser
     pass over the SR tensor after the replay, tatt_ctc_greedy_match for the decoding, the codes through a second non-blocking copy.
     A TSRN_TL_TRANS generator without a `prior` CRNN runs on the session's zero text prior.  keep_sr=True keeps a clone of each batch's
-    SR tensor on the PendingUpscale (`.sr`)."""
+    SR tensor on the PendingUpscale (`.sr`).
+
+    long_lines=True (opt-in; without it nothing changes) takes text lines of ANY width: an image is not squeezed into lr_size but
+    resized to the LR height at its own aspect ratio and cut into LR windows `stride` columns apart (`io.line_plan`,
+    `DeviceCollator.windows`: one launch for all windows of the call); the window stack is cut into batches of `batch_size` and run
+    through the sessions exactly as batches are (a batch may mix windows of different lines), each batch's SR copied on the stream into
+    one (n_windows, C, H, W) buffer; `DeviceExporter.lines` merges the windows of every line with tent weights in one launch.  One RGB
+    image of size (scale * wl, H) per input -- an image no wider than the LR window's aspect ratio yields one window and the bytes it
+    gets with long_lines=False; out_sizes: PIL resizes the finished line on the host.  Byte for byte `io.super_resolve_lines_host` on
+    the same SR windows.  A TSRN_TL_TRANS generator without a `prior` runs every window on a zero row of the text prior.  No
+    recogniser with long_lines (ValueError): reading a tiled line is not defined here."""
 
     def __init__(self, generator, prior=None, recognizer=None, batch_size: int = 48, lr_size=(16, 64), mask: bool = True,
-                 rule: str = "floor", keep_sr: bool = False):
+                 rule: str = "floor", keep_sr: bool = False, long_lines: bool = False, stride: int = 32):
         from .io import DeviceCollator, DeviceExporter
         _check_module(generator, "generator")
         _check_module(prior, "prior CRNN")
         _check_module(recognizer, "recogniser CRNN")
         if not (isinstance(batch_size, int) and batch_size > 0):
             raise ValueError("batch_size must be a positive int")
+        if long_lines:
+            from .io import line_plan
+            if recognizer is not None:
+                raise ValueError("SuperResolver: a recogniser cannot read tiled lines (long_lines=True); pass recognizer=None")
+            line_plan((lr_size[1], lr_size[0]), lr_size, stride)      # (raises for a stride outside [w / 2, w])
         self.gen, self.prior, self.rec = generator, prior, recognizer
         self.B, self.lr_size, self.keep_sr = batch_size, tuple(lr_size), bool(keep_sr)
+        self.long_lines, self.stride, self._zero_tp = bool(long_lines), stride, {}
         self.device = next(generator.parameters()).device
         self.collator = DeviceCollator(imgH=self.lr_size[0], imgW=self.lr_size[1], down_sample_scale=1, mask=mask, device=self.device)
         self.exporter = DeviceExporter(device=self.device, rule=rule)
@@ -737,6 +755,8 @@ class SuperResolver:
             out_sizes = [tuple(s) for s in out_sizes]
             if len(out_sizes) != len(images):
                 raise ValueError("%d out_sizes for %d images" % (len(out_sizes), len(images)))
+        if self.long_lines:
+            return self._lines(images, out_sizes)
         h, w = self.lr_size
         parts, kept, fresh = [], [], set()
         with torch.cuda.device(self.device):
@@ -744,15 +764,53 @@ class SuperResolver:
                 chunk = images[i:i + self.B]
                 n = len(chunk)
                 lr = self.collator.stack(chunk, (w, h))
-                s = self.sessions.get(n)
-                if s is None:
-                    s = self.sessions[n] = InferenceSession(self.gen, self.prior, None, batch_size=n, lr_size=self.lr_size)
-                elif n not in fresh:
-                    s.refresh()                                      # weights written through raw pointers since the last call
-                fresh.add(n)
-                sr = s.run(lr)[0]
+                sr = self._session(n, fresh).run(lr)[0]
                 parts.append((self.exporter(sr, None if out_sizes is None else out_sizes[i:i + n]),) +
                              (self._texts(sr) if self.rec is not None else (None, None)))
                 if self.keep_sr:
                     kept.append(sr.clone())
         return PendingUpscale(parts, self.rec is not None, kept if self.keep_sr else None)
+
+    def _session(self, n, fresh):
+        """the session of batch size n, captured on first use; refreshed once per call (`fresh`: the sizes this call has met)"""
+        s = self.sessions.get(n)
+        if s is None:
+            s = self.sessions[n] = InferenceSession(self.gen, self.prior, None, batch_size=n, lr_size=self.lr_size)
+        elif n not in fresh:
+            s.refresh()                                              # weights written through raw pointers since the last call
+        fresh.add(n)
+        return s
+
+    def _zero_prior(self, n):
+        """a TSRN_TL_TRANS generator without a prior CRNN: the zero text prior, one row per window of the batch (the session's own
+        fallback is the reference's single row, which serves a batch of one); None for every other configuration"""
+        from .tsrn import TSRN_TL_TRANS
+        if self.prior is not None or not isinstance(self.gen, TSRN_TL_TRANS):
+            return None
+        if n not in self._zero_tp:
+            self._zero_tp[n] = torch.zeros(n, 37, 1, 26, device=self.device)
+        return self._zero_tp[n]
+
+    def _lines(self, images, out_sizes) -> PendingUpscale:
+        """the long_lines call: windows of all images -> sessions over batches of windows -> one SR buffer -> one blend launch"""
+        h, w = self.lr_size
+        fresh, buf = set(), None
+        if not images:
+            return PendingUpscale([], False, None)
+        with torch.cuda.device(self.device):
+            stack, lines = self.collator.windows(images, self.stride)
+            N = stack.shape[0]
+            for i in range(0, N, self.B):
+                n = min(self.B, N - i)
+                sr = self._session(n, fresh).run(stack[i:i + n], text_prior=self._zero_prior(n))[0]
+                if buf is None:                                      # (in the layout the session leaves: a plain copy per batch)
+                    cl = sr.stride(1) == 1 and not sr.is_contiguous()
+                    buf = torch.empty((N,) + tuple(sr.shape[1:]), dtype=sr.dtype, device=sr.device,
+                                      memory_format=torch.channels_last if cl else torch.contiguous_format)
+                buf[i:i + n].copy_(sr)                               # the session's output is static: the next replay overwrites it
+            H, W = buf.shape[2:]
+            if H % h or W % w or H // h != W // w:
+                raise ValueError("the SR windows %d x %d are no integer multiple of the LR window %d x %d" % (H, W, h, w))
+            pending = self.exporter.lines(buf, lines, H // h, out_sizes=out_sizes)
+        keep = self.keep_sr
+        return PendingUpscale([(pending, None, None)], False, buf if keep else None, stack if keep else None, lines if keep else None)

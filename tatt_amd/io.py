@@ -23,6 +23,9 @@
   `.cpu().numpy() * 255`, clip, `astype(np.uint8)`, resize; interfaces/base.py:565-618 for the `save_image` rounding) on the host;
   `DeviceExporter` is the same with the pixels made on the GPU: one HIP launch (csrc/export.hip), one copy back of uint8, byte for byte the
   host path's; `export_plan` / `panel_layout` are its host half.
+* `line_plan` / `line_windows_host` / `blend_windows_host` / `super_resolve_lines_host` (tatt_amd/lines.py, re-exported here) take a
+  text line of any width through a generator that knows one LR size: windows of the line at its own aspect ratio, merged back with tent
+  weights; `DeviceCollator.windows` and `DeviceExporter.lines` are the same on the GPU (csrc/lines.hip), bit for bit.
 * `LmdbRecords` reads the reference's lmdb record layout (`lmdbDataset_real`, dataset/dataset.py:565-686): keys `num-samples`,
   `label-%09d`, `image_hr-%09d`, `image_lr-%09d` (1-based), image bytes decoded by PIL to RGB, the label filtered by `str_filt`.
   It takes any object with the lmdb transaction's `get(key)`; `open_lmdb` wraps a real environment when the `lmdb` package is there
@@ -446,7 +449,7 @@ class DeviceCollator:
             raise ValueError("DeviceCollator: ring must be at least 1")
         self.hr_size, self.lr_size = (imgW, imgH), (imgW // down_sample_scale, imgH // down_sample_scale)
         self.mask, self.want_yuv, self.ring, self.alphabet = bool(mask), bool(want_yuv), int(ring), alphabet
-        self._limits = None
+        self._limits = self._line_limits = None
         self._host, self._events, self._dev_buf, self._i, self._last = [], [], None, 0, None
 
     def plan(self, samples):
@@ -545,6 +548,44 @@ class DeviceCollator:
             done.record(stream)
             self._last = (stream, done)
         return out.view(len(images), 3 + int(self.mask), size[1], size[0])
+
+    def windows(self, images, stride: int = 32):
+        """RGB PIL images (text lines of any width) -> (stack, lines): ONE (n_windows, 3 + mask, h, w) stack on the device holding the
+        windows of every line at the collator's LR size, lines in input order and windows left to right, bit for bit
+        `torch.cat([line_windows_host(im, (h, w), stride, mask) for im in images])`; lines[i] = Line(wl, starts, first window index), what
+        `DeviceExporter.lines` needs.  One upload per line (not per window), one copy, one launch (tatt_line_windows) through the ring of
+        `stack`.  Never waits for the device."""
+        import ctypes
+        from . import ops
+        from .lines import line_limits, lines_fill, lines_plan
+        images = list(images)
+        if self._line_limits is None:
+            self._line_limits = line_limits()
+        w, h = self.lr_size
+        arrays, desc, lines, nbytes, out_floats = lines_plan(images, (h, w), stride, self.mask, self._line_limits)
+        if not lines:
+            raise ValueError("DeviceCollator.windows: no images")
+        pix, used = lines_fill(None, arrays, desc)
+        with torch.cuda.device(self.device):
+            stream = torch.cuda.current_stream()
+            moved = self._last is not None and self._last[0] != stream
+            if moved:
+                stream.wait_event(self._last[1])
+            k, host = self._slot(used)
+            if moved:
+                self._dev_buf.record_stream(stream)
+            lines_fill(host.numpy(), arrays, desc)
+            self._dev_buf[:used].copy_(host[:used], non_blocking=True)
+            ev = self._events[k] = self._events[k] if self._events[k] is not None else torch.cuda.Event()
+            ev.record(stream)
+            out = torch.empty(out_floats, dtype=torch.float32, device=self.device)
+            base = self._dev_buf.data_ptr()
+            ops.call("tatt_line_windows", ctypes.c_void_p(base + pix), nbytes, ctypes.c_void_p(base), ctypes.c_void_p(host.data_ptr()),
+                     len(desc), ops.P(out), out_floats, ops.stream())
+            done = self._last[1] if self._last is not None else torch.cuda.Event()
+            done.record(stream)
+            self._last = (stream, done)
+        return out.view(len(desc), 3 + int(self.mask), h, w), lines
 
 
 # ---- image export on the device (csrc/export.hip) -----------------------------------------------------------------------------------
@@ -740,7 +781,7 @@ class DeviceExporter:
             raise ValueError("DeviceExporter: ring must be at least 1")
         _rule_code(rule)
         self.rule, self.ring = rule, int(ring)
-        self._limits = None
+        self._limits = self._line_limits = None
         self._slots, self._i = [_ExportSlot() for _ in range(self.ring)], 0
         self._dev_buf, self._last = None, None
         self._alloc = lambda n: torch.empty(n, dtype=torch.uint8, pin_memory=True)
@@ -772,13 +813,15 @@ class DeviceExporter:
         slot.held = True
         return slot
 
-    def _enqueue(self, jobs, nbytes, views, zero=False):
-        """jobs: [(tensor, desc rows)], all rows addressing one output of nbytes bytes -> PendingExport"""
+    def _enqueue(self, jobs, nbytes, views, zero=False, head=None, launch=None):
+        """jobs: [(tensor, desc rows)], all rows addressing one output of nbytes bytes -> PendingExport.  `head` / `launch` (`lines`): the
+        int32 words to stage in front of the pixels instead of the jobs' rows, and launch(device base, host base, pixel offset) instead of
+        the jobs' launches."""
         import ctypes
         import numpy as np
         from . import ops
-        rows = sum(len(d) for _, d in jobs)
-        pix = -(-rows * EXPORT_DESC * 4 // _EXPORT_ALIGN) * _EXPORT_ALIGN
+        head = np.concatenate([d.reshape(-1) for _, d in jobs]) if head is None else head
+        pix = -(-head.size * 4 // _EXPORT_ALIGN) * _EXPORT_ALIGN
         cap = -(-nbytes // _EXPORT_ALIGN) * _EXPORT_ALIGN
         with torch.cuda.device(self.device):
             stream = torch.cuda.current_stream()
@@ -791,12 +834,14 @@ class DeviceExporter:
             elif moved:
                 self._dev_buf.record_stream(stream)
             host = slot.host.numpy()
-            host[:rows * EXPORT_DESC * 4].view(np.int32)[:] = np.concatenate([d.reshape(-1) for _, d in jobs])
+            host[:head.size * 4].view(np.int32)[:] = head
             self._dev_buf[:pix].copy_(slot.host[:pix], non_blocking=True)
             if zero:
                 self._dev_buf[pix:pix + cap].zero_()
             base, hbase, r0 = self._dev_buf.data_ptr(), slot.host.data_ptr(), 0
             try:
+                if launch is not None:
+                    launch(base, hbase, pix)
                 for t, d in jobs:
                     B, C, H, W = t.shape
                     ops.call("tatt_export_images", ops.P(t), *t.stride(), B, C, H, W, ctypes.c_void_p(base + r0 * EXPORT_DESC * 4),
@@ -850,3 +895,41 @@ class DeviceExporter:
         nbytes = max(nbytes, (B - 1) * stride + height * 3 * W)
         views = [(b * stride, height, W, 3 * W, None) for b in range(B)]
         return self._enqueue(jobs, nbytes, views, zero=gap > 0)
+
+    def lines(self, sr_windows, lines, scale: int, c0: int = 0, out_sizes=None) -> PendingExport:
+        """The SR windows of text lines merged into one image per line: sr_windows (n_windows, C, H, W) fp32 on the device (any strides),
+        lines: the Line records of `DeviceCollator.windows`, scale = H // h -> a PendingExport whose `result()` is BYTE FOR BYTE
+        `blend_windows_host(sr_windows[first:first + n], starts, wl, scale, rule, c0)` of every line, an RGB PIL image of size
+        (scale * wl, H) each.  The line rows and window starts go host-to-device from a pinned slot, ONE launch (tatt_line_blend) for all
+        lines, ONE non-blocking copy of all canvases back.  out_sizes[i] = (width, height): PIL resizes the finished line in `result()`
+        (quantisation and blending happen before the resize on both paths)."""
+        import ctypes
+        import numpy as np
+        from . import ops
+        from .lines import blend_plan, line_limits
+        self._check(sr_windows, c0)
+        lines = list(lines)
+        if self._line_limits is None:
+            self._line_limits = line_limits()
+        if out_sizes is not None and len(out_sizes) != len(lines):
+            raise ValueError("%d out_sizes for %d lines" % (len(out_sizes), len(lines)))
+        B, C, H, W = sr_windows.shape
+        desc, starts, nbytes = blend_plan(lines, B, H, W, scale, self.rule, c0, self._line_limits)
+        views = []
+        for i, d in enumerate(desc):
+            size = (scale * int(d[2]), H)
+            want = size if out_sizes is None else (int(out_sizes[i][0]), int(out_sizes[i][1]))
+            views.append((int(d[6]), H, size[0], int(d[7]), None if want == size else want))
+        rows = -(-desc.size // 4) * 4                                   # (the starts table 16-byte aligned behind the rows)
+        head = np.zeros(rows + starts.size, np.int32)
+        head[:desc.size], head[rows:] = desc.reshape(-1), starts
+
+        def launch(base, hbase, pix):
+            ops.call("tatt_line_blend", ops.P(sr_windows), *sr_windows.stride(), B, C, H, W, ctypes.c_void_p(base), ctypes.c_void_p(hbase),
+                     len(desc), ctypes.c_void_p(base + rows * 4), ctypes.c_void_p(hbase + rows * 4), int(starts.size),
+                     ctypes.c_void_p(base + pix), nbytes, ops.stream())
+        return self._enqueue([], nbytes, views, head=head, launch=launch)
+
+
+from .lines import (LINE_MAX_WL, Line, blend_plan, blend_windows_host, line_limits, line_plan, line_windows_host, lines_fill,  # noqa: E402,F401
+                    lines_plan, super_resolve_lines_host)
