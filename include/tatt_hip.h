@@ -852,6 +852,37 @@ int tatt_line_blend(const float* src, long st_n, long st_c, long st_h, long st_w
  * horizontal pass's result (H_src * w * 3) and of its coefficient rows (w * ksize * 4), both counted when W_src != wl, most windows of
  * one line.  Host only: needs no GPU. */
 int tatt_line_limits(int* out);
+/* ---- scene images (csrc/scene.hip; tatt_amd/scene.py is the specification) -- */
+/* tatt_line_windows for sources that are SUB-RECTANGLES (text boxes) of uploaded images: ONE launch, one work-group per window, bit for
+ * bit the windows of `scene.crop(box)`.  desc (n_windows, 16) int32 in DEVICE memory: words [0..8] as tatt_line_windows has them, with
+ * [0] the byte offset of the IMAGE's first pixel in packed and [1] H_src, [2] W_src the BOX's height and width (the coefficient tables
+ * are the box's, not the image's);  [9] the image's row pitch in bytes, >= 3 * ([10] + W_src)  [10] box x0  [11] box y0  [12..15] 0.
+ * A source of its own (the host fallback: a box beyond tatt_line_limits, resized by PIL) has pitch 3 * W_src and origin (0, 0).
+ * Limits and return codes are those of tatt_line_windows (2 beyond tatt_line_limits, 3 for a box or planes that leave packed / out,
+ * a negative origin or a pitch below the box's right edge, 1 for bad arguments or a reserved word); the kernel reads only device memory
+ * and re-checks every row: a row it would have refused gets NaN planes, or nothing when they lie outside out. */
+int tatt_scene_windows(const unsigned char* packed, long packed_bytes, const int* desc, const int* desc_host, int n_windows,
+                       float* out, long out_floats, hipStream_t st);
+/* Pillow's 8-bit bicubic Image.resize, uint8 RGB in device memory to uint8 RGB in device memory, tiled over the output (grid: tile x
+ * item), so sources and targets of any size up to tatt_scene_limits go through; bit for bit Image.resize((OW, OH), BICUBIC): horizontal
+ * pass first, its result rounded to uint8, a pass whose sizes agree skipped.  desc (n_items, 16) int32 in DEVICE memory:
+ *   [0] byte offset of the source's first pixel in src  [1] H_src  [2] W_src  [3] source row pitch in bytes, >= 3 W_src
+ *   [4] byte offset of the target's first pixel in dst  [5] OH  [6] OW  [7] target row pitch in bytes, >= 3 OW
+ *   [8] feather F >= 0  [9..15] 0
+ * F = 0 stores the resized pixels.  F > 0 blends them into what dst holds: a pixel at distance d = min(i, OH - 1 - i, j, OW - 1 - j)
+ * from the nearest side of the target rectangle takes a = min(d + 1, F + 1), D = F + 1 and becomes
+ * (2 (a new + (D - a) old) + D) / (2 D) in integers.  src and dst may be one buffer; the target rectangles of one launch must be
+ * disjoint and must not overlap a source (the caller's layers see to it).  Every per-axis factor OUT / IN from 1 / 16 up is taken.
+ * desc_host: the same rows in HOST memory, read before the launch only to refuse: 1 bad arguments, a reserved word or a negative
+ * feather, 2 a geometry beyond tatt_scene_limits (a side, a down-scale beyond 16, the feather, more than 65535 items), 3 a source or
+ * target rectangle that leaves src (src_bytes) / dst (dst_bytes).  The kernel reads only device memory (the launch can be captured)
+ * and re-checks every row: it writes nothing for a row it refuses. */
+int tatt_resize_u8(const unsigned char* src, long src_bytes, const int* desc, const int* desc_host, int n_items,
+                   unsigned char* dst, long dst_bytes, hipStream_t st);
+/* out[0..7]: largest side of a source or target of tatt_resize_u8, most boxes of one scene, tile height, tile width, largest down-scale
+ * factor per axis, largest feather, most intermediate rows of a tile (the tile height is halved until its source rows fit), most items
+ * of one launch.  Host only: needs no GPU. */
+int tatt_scene_limits(int* out);
 /* calculate_psnr (reference utils/ssim_psnr.py:9-15) of two (B,C,H,W) images in [0,1] given by element strides, first 3 channels */
 int tatt_psnr(const float* a, long a_n, long a_c, long a_h, long a_w, const float* b, long b_n, long b_c, long b_h, long b_w,
               float* out, int B, int C, int H, int W, hipStream_t st);

@@ -678,6 +678,18 @@ class PendingUpscale:
         return (images, texts) if self._with_text else images
 
 
+class PendingScene:
+    """What `SuperResolver.scene` started.  `result()` is the only host wait: -> the RGB PIL image of size (scale * Ws, scale * Hs).
+    With keep_sr: `sr` the ONE (n_windows, C, H, W) buffer of all SR windows (None without boxes), `lr` the window stack the sessions
+    read, `lines` its `io.Line` records (one per box), `boxes` the checked boxes and `layers` their paste layers (`io.scene_layers`)."""
+
+    def __init__(self, pending, sr=None, lr=None, lines=None, boxes=None, layers=None):
+        self._pending, self.sr, self.lr, self.lines, self.boxes, self.layers = pending, sr, lr, lines, boxes, layers
+
+    def result(self):
+        return self._pending.result()[0]
+
+
 class SuperResolver:
     """The reference's `demo()` (interfaces/super_resolution.py:1788-1876: every file resized to the LR size, the model run at B = 1, no
     image produced) as it should have been: RGB PIL crops of any size in, RGB PIL images out.
@@ -702,7 +714,10 @@ class SuperResolver:
     image of size (scale * wl, H) per input -- an image no wider than the LR window's aspect ratio yields one window and the bytes it
     gets with long_lines=False; out_sizes: PIL resizes the finished line on the host.  Byte for byte `io.super_resolve_lines_host` on
     the same SR windows.  A TSRN_TL_TRANS generator without a `prior` runs every window on a zero row of the text prior.  No
-    recogniser with long_lines (ValueError): reading a tiled line is not defined here."""
+    recogniser with long_lines (ValueError): reading a tiled line is not defined here.
+
+    `scene(image, boxes, feather=0)` (any instance without a recogniser) takes a whole picture and a detector's boxes and returns the
+    up-scaled picture with the text of every box super-resolved and pasted back: see the method."""
 
     def __init__(self, generator, prior=None, recognizer=None, batch_size: int = 48, lr_size=(16, 64), mask: bool = True,
                  rule: str = "floor", keep_sr: bool = False, long_lines: bool = False, stride: int = 32):
@@ -770,6 +785,52 @@ class SuperResolver:
                 if self.keep_sr:
                     kept.append(sr.clone())
         return PendingUpscale(parts, self.rec is not None, kept if self.keep_sr else None)
+
+    def _scale(self):
+        """the generator's up-scaling factor without running it: one PixelShuffle(2) stage per UpsampleBLock"""
+        from .tsrn import UpsampleBLock
+        return 2 ** sum(isinstance(m, UpsampleBLock) for m in self.gen.modules())
+
+    def scene(self, image, boxes, feather: int = 0) -> PendingScene:
+        """A whole picture: image: an RGB PIL image, boxes: integer (x0, y0, x1, y1) rectangles of text in it (`io.scene_check`) ->
+        PendingScene whose `result()` (the only host wait) is the RGB PIL image of size (scale * Ws, scale * Hs): the bicubic up-scale of
+        the picture with every box replaced by its super-resolved text, later boxes over earlier ones; feather = F > 0 fades the outer F
+        pixels of every pasted rectangle into what lies below.  Every box is a text line (long_lines' windows, whatever `long_lines`
+        says; the instance's `stride`): `DeviceCollator.scene_windows` uploads the picture once and cuts all windows in one launch, the
+        windows go through the sessions in batches of `batch_size` exactly as `long_lines` runs them, `DeviceExporter.scene` merges,
+        up-scales and pastes on the device and copies the canvas back once.  Byte for byte `io.super_resolve_scene_host` on the same SR
+        windows.  No boxes: the up-scaled picture, no session runs.  Not with a recogniser (ValueError)."""
+        from .io import line_plan, scene_layers
+        if self.rec is not None:
+            raise ValueError("SuperResolver: a recogniser cannot read tiled lines (scene); pass recognizer=None")
+        if not (isinstance(feather, int) and not isinstance(feather, bool) and feather >= 0):
+            raise ValueError("SuperResolver.scene: feather must be an int >= 0; got %r" % (feather,))
+        h, w = self.lr_size
+        line_plan((w, h), self.lr_size, self.stride)                 # (raises for a stride outside [w / 2, w])
+        fresh, buf, boxes = set(), None, list(boxes)
+        with torch.cuda.device(self.device):
+            stack, lines, scene_dev = self.collator.scene_windows(image, boxes, self.stride)
+            N = stack.shape[0]
+            for i in range(0, N, self.B):
+                n = min(self.B, N - i)
+                sr = self._session(n, fresh).run(stack[i:i + n], text_prior=self._zero_prior(n))[0]
+                if buf is None:                                      # (in the layout the session leaves: a plain copy per batch)
+                    cl = sr.stride(1) == 1 and not sr.is_contiguous()
+                    buf = torch.empty((N,) + tuple(sr.shape[1:]), dtype=sr.dtype, device=sr.device,
+                                      memory_format=torch.channels_last if cl else torch.contiguous_format)
+                buf[i:i + n].copy_(sr)                               # the session's output is static: the next replay overwrites it
+            if buf is not None:
+                H, W = buf.shape[2:]
+                if H % h or W % w or H // h != W // w:
+                    raise ValueError("the SR windows %d x %d are no integer multiple of the LR window %d x %d" % (H, W, h, w))
+                scale = H // h
+            else:
+                scale = self._scale()
+            boxes = [tuple(int(v) for v in b) for b in boxes]        # (checked by scene_windows)
+            pending = self.exporter.scene(scene_dev, buf, lines, boxes, scale, feather)
+        if not self.keep_sr:
+            return PendingScene(pending)
+        return PendingScene(pending, buf, stack, lines, boxes, scene_layers(boxes))
 
     def _session(self, n, fresh):
         """the session of batch size n, captured on first use; refreshed once per call (`fresh`: the sizes this call has met)"""

@@ -587,6 +587,47 @@ class DeviceCollator:
             self._last = (stream, done)
         return out.view(len(desc), 3 + int(self.mask), h, w), lines
 
+    def scene_windows(self, scene, boxes, stride: int = 32):
+        """RGB PIL image and integer boxes (x0, y0, x1, y1) (`scene_check`) -> (stack, lines, scene_dev): ONE (n_windows, 3 + mask, h, w)
+        stack on the device with the windows of every box, bit for bit `scene_windows_host(scene, boxes, (h, w), stride, mask)`, its Line
+        records, and the scene's (Hs, Ws, 3) uint8 pixels on the device (a view of the collator's device buffer: valid, in stream order,
+        until the collator's next call -- what `DeviceExporter.scene` up-scales for the background).  The scene is uploaded ONCE, with the
+        descriptor table and the host-resized fallback sources (`scene_plan`), from a pinned slot with one copy; one launch
+        (tatt_scene_windows) reads every window out of its box's rectangle.  No boxes: the upload alone, an empty stack.  Never waits
+        for the device."""
+        import ctypes
+        from . import ops
+        from .lines import line_limits
+        from .scene import scene_fill, scene_plan
+        if self._line_limits is None:
+            self._line_limits = line_limits()
+        w, h = self.lr_size
+        plan = scene_plan(scene, boxes, (h, w), stride, self.mask, self._line_limits)
+        pix, used = scene_fill(None, plan)
+        Hs, Ws = plan.arrays[0].shape[:2]
+        with torch.cuda.device(self.device):
+            stream = torch.cuda.current_stream()
+            moved = self._last is not None and self._last[0] != stream
+            if moved:
+                stream.wait_event(self._last[1])
+            k, host = self._slot(used)
+            if moved:
+                self._dev_buf.record_stream(stream)
+            scene_fill(host.numpy(), plan)
+            self._dev_buf[:used].copy_(host[:used], non_blocking=True)
+            ev = self._events[k] = self._events[k] if self._events[k] is not None else torch.cuda.Event()
+            ev.record(stream)
+            out = torch.empty(plan.out_floats, dtype=torch.float32, device=self.device)
+            base = self._dev_buf.data_ptr()
+            if len(plan.desc):
+                ops.call("tatt_scene_windows", ctypes.c_void_p(base + pix), plan.nbytes, ctypes.c_void_p(base),
+                         ctypes.c_void_p(host.data_ptr()), len(plan.desc), ops.P(out), plan.out_floats, ops.stream())
+            done = self._last[1] if self._last is not None else torch.cuda.Event()
+            done.record(stream)
+            self._last = (stream, done)
+        scene_dev = self._dev_buf[pix:pix + Hs * Ws * 3].view(Hs, Ws, 3)
+        return out.view(len(plan.desc), 3 + int(self.mask), h, w), plan.lines, scene_dev
+
 
 # ---- image export on the device (csrc/export.hip) -----------------------------------------------------------------------------------
 EXPORT_DESC = 8           # ints per descriptor row of tatt_export_images (include/tatt_hip.h)
@@ -930,6 +971,61 @@ class DeviceExporter:
                      ctypes.c_void_p(base + pix), nbytes, ops.stream())
         return self._enqueue([], nbytes, views, head=head, launch=launch)
 
+    def scene(self, scene_dev, sr_windows, lines, boxes, scale: int, feather: int = 0, c0: int = 0) -> PendingExport:
+        """The finished scene: scene_dev: the (Hs, Ws, 3) uint8 scene on the device (`DeviceCollator.scene_windows`), sr_windows
+        (n_windows, C, H, W) fp32 on the device: the SR windows of all boxes (None without boxes), lines: their Line records, one per box
+        -> a PendingExport whose `result()` is one RGB PIL image of size (scale * Ws, scale * Hs), BYTE FOR BYTE
+        `scene_compose_host(scene, boxes, [blend_windows_host(..) per box], scale, feather)`.  On the current stream: the rows of all
+        launches go host-to-device from a pinned slot, ONE tatt_line_blend launch merges the windows of every box into uint8 line
+        canvases that stay on the device, ONE tatt_resize_u8 launch up-scales the scene into the canvas, ONE tatt_resize_u8 launch per
+        layer (`scene_layers`: boxes that do not intersect share a launch) resizes the line canvases into their rectangles, feathered
+        against what the canvas holds, and ONE non-blocking copy brings the buffer into the pinned slot.  Never waits for the device."""
+        import ctypes
+        import numpy as np
+        from . import ops
+        from .lines import BLEND_DESC, blend_plan, line_limits
+        from .scene import RESIZE_DESC, paste_plan, scene_limits
+        if not (isinstance(scene_dev, torch.Tensor) and scene_dev.dim() == 3 and scene_dev.shape[2] == 3 and
+                scene_dev.dtype == torch.uint8 and scene_dev.is_contiguous() and scene_dev.device.type == "cuda"):
+            raise ValueError("DeviceExporter.scene takes the contiguous (Hs, Ws, 3) uint8 scene on the device")
+        lines, boxes = list(lines), list(boxes)
+        if self._line_limits is None:
+            self._line_limits = line_limits()
+        if getattr(self, "_scene_limits", None) is None:
+            self._scene_limits = scene_limits()
+        Hs, Ws = int(scene_dev.shape[0]), int(scene_dev.shape[1])
+        if lines:
+            self._check(sr_windows, c0)
+            B, C, H, W = sr_windows.shape
+            bdesc, starts, bbytes = blend_plan(lines, B, H, W, scale, self.rule, c0, self._line_limits)
+        else:
+            B = C = H = W = 0
+            bdesc, starts, bbytes = np.zeros((0, BLEND_DESC), np.int32), np.zeros(0, np.int32), 0
+        plan = paste_plan((Ws, Hs), boxes, bdesc, bbytes, scale, H, feather, self._scene_limits)
+        at = lambda n: -(-n // 4) * 4                                  # (every table 16-byte aligned)
+        o_starts = at(bdesc.size)
+        o_rows = o_starts + at(starts.size)
+        head = np.zeros(o_rows + plan.rows.size, np.int32)
+        head[:bdesc.size], head[o_starts:o_starts + starts.size], head[o_rows:] = bdesc.reshape(-1), starts, plan.rows.reshape(-1)
+        views = [(plan.canvas_off, scale * Hs, scale * Ws, plan.pitch, None)]
+        nbytes, src_bytes = plan.nbytes, Hs * Ws * 3
+
+        def launch(base, hbase, pix):
+            out = ctypes.c_void_p(base + pix)
+            if lines:
+                ops.call("tatt_line_blend", ops.P(sr_windows), *sr_windows.stride(), B, C, H, W, ctypes.c_void_p(base),
+                         ctypes.c_void_p(hbase), len(bdesc), ctypes.c_void_p(base + o_starts * 4), ctypes.c_void_p(hbase + o_starts * 4),
+                         int(starts.size), out, max(bbytes, 1), ops.stream())
+            row = lambda r: (ctypes.c_void_p(base + (o_rows + r * RESIZE_DESC) * 4), ctypes.c_void_p(hbase + (o_rows + r * RESIZE_DESC) * 4))
+            ops.call("tatt_resize_u8", ops.P(scene_dev), src_bytes, *row(0), 1, out, nbytes, ops.stream())
+            r = 1
+            for n in plan.counts:                                      # the line canvases lie in front of the canvas, in the same buffer
+                ops.call("tatt_resize_u8", out, plan.canvas_off, *row(r), n, out, nbytes, ops.stream())
+                r += n
+        return self._enqueue([], nbytes, views, head=head, launch=launch)
+
 
 from .lines import (LINE_MAX_WL, Line, blend_plan, blend_windows_host, line_limits, line_plan, line_windows_host, lines_fill,  # noqa: E402,F401
                     lines_plan, super_resolve_lines_host)
+from .scene import (SCENE_MIN_SIDE, paste_plan, scene_check, scene_compose_host, scene_fill, scene_layers, scene_limits,  # noqa: E402,F401
+                    scene_plan, scene_windows_host, super_resolve_scene_host)
