@@ -883,6 +883,29 @@ int tatt_resize_u8(const unsigned char* src, long src_bytes, const int* desc, co
  * factor per axis, largest feather, most intermediate rows of a tile (the tile height is halved until its source rows fit), most items
  * of one launch.  Host only: needs no GPU. */
 int tatt_scene_limits(int* out);
+/* ---- quadrilateral text boxes (csrc/quads.hip; tatt_amd/quads.py is the specification) -- */
+/* A projective warp of uint8 RGB in device memory to uint8 RGB in device memory, tiled over the output (grid: tile x item, one thread per
+ * destination pixel), byte for byte `warp_u8_host`.  desc (n_items, 32) int32 in DEVICE memory:
+ *   [0] byte offset of the source's first pixel in src  [1] H_src  [2] W_src  [3] source row pitch in bytes, >= 3 W_src
+ *   [4] byte offset of the target's first pixel in dst  [5] OH  [6] OW  [7] target row pitch in bytes, >= 3 OW
+ *   [8] feather F >= 0  [9] mode: 0 rectify, 1 paste  [10..27] the nine entries of the integer matrix m, row-major, each a 64-bit two's
+ *   complement value as (low word, high word)  [28..31] 0
+ * Destination pixel (i, j): with J = 2 j + 1, I = 2 i + 1: X = m00 J + m01 I + m02, Y = m10 J + m11 I + m12, Wd = m20 J + m21 I + m22 in
+ * 64-bit integers; gx = floor(256 X / Wd), gy = floor(256 Y / Wd) (true floor division); fx = gx - 128, x0 = fx >> 8, ax = fx & 255 (fy
+ * alike); the pixel is ((256 - ay) ((256 - ax) p[y0][x0] + ax p[y0][x0 + 1]) + ay ((256 - ax) p[y0 + 1][x0] + ax p[y0 + 1][x0 + 1]) +
+ * 32768) >> 16 per channel, every tap index clamped to the source.  Mode 0 writes every destination pixel (zero where Wd <= 0).  Mode 1
+ * paints a pixel iff Wd > 0, 0 <= gx < 256 W_src and 0 <= gy < 256 H_src and leaves every other pixel as it is; with F > 0 a painted pixel
+ * at d = min(xi, W_src - 1 - xi, yi, H_src - 1 - yi), xi = gx >> 8, yi = gy >> 8, takes a = min(d + 1, F + 1), D = F + 1 and becomes
+ * (2 (a new + (D - a) old) + D) / (2 D).  src and dst may be one buffer; the target rectangles of one launch must be disjoint and must
+ * not overlap a source.  desc_host: the same rows in HOST memory, read before the launch only to refuse: 1 bad arguments, a reserved
+ * word, a negative feather or an unknown mode, 2 a geometry beyond tatt_quad_limits (a side, the feather, more than 65535 items), 3 a
+ * source or target rectangle that leaves src (src_bytes) / dst (dst_bytes).  The kernel reads only device memory (the launch can be
+ * captured), re-checks every row (it writes nothing for a row it refuses) and clamps every tap whatever the matrix says. */
+int tatt_warp_u8(const unsigned char* src, long src_bytes, const int* desc, const int* desc_host, int n_items,
+                 unsigned char* dst, long dst_bytes, hipStream_t st);
+/* out[0..5]: tile height, tile width, most items of one launch, largest side of a source or target, largest feather, ints per
+ * descriptor row.  Host only: needs no GPU. */
+int tatt_quad_limits(int* out);
 /* calculate_psnr (reference utils/ssim_psnr.py:9-15) of two (B,C,H,W) images in [0,1] given by element strides, first 3 channels */
 int tatt_psnr(const float* a, long a_n, long a_c, long a_h, long a_w, const float* b, long b_n, long b_c, long b_h, long b_w,
               float* out, int B, int C, int H, int W, hipStream_t st);

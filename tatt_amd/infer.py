@@ -717,7 +717,8 @@ class SuperResolver:
     recogniser with long_lines (ValueError): reading a tiled line is not defined here.
 
     `scene(image, boxes, feather=0)` (any instance without a recogniser) takes a whole picture and a detector's boxes and returns the
-    up-scaled picture with the text of every box super-resolved and pasted back: see the method."""
+    up-scaled picture with the text of every box super-resolved and pasted back: see the method.  `scene_quads(image, quads, feather=0)`
+    is the same for quadrilaterals (four corner points per text instance, rotated or under perspective)."""
 
     def __init__(self, generator, prior=None, recognizer=None, batch_size: int = 48, lr_size=(16, 64), mask: bool = True,
                  rule: str = "floor", keep_sr: bool = False, long_lines: bool = False, stride: int = 32):
@@ -831,6 +832,49 @@ class SuperResolver:
         if not self.keep_sr:
             return PendingScene(pending)
         return PendingScene(pending, buf, stack, lines, boxes, scene_layers(boxes))
+
+    def scene_quads(self, image, quads, feather: int = 0) -> PendingScene:
+        """`scene` for a detector's QUADRILATERALS: image: an RGB PIL image, quads: four integer corner points per text instance,
+        top-left, top-right, bottom-right, bottom-left in reading direction (`io.quad_check`) -> PendingScene whose `result()` (the only
+        host wait) is the RGB PIL image of size (scale * Ws, scale * Hs): the bicubic up-scale of the picture with every quad replaced by
+        its super-resolved text, later quads over earlier ones, only the pixels of the quad painted; feather = F > 0 fades the outer F
+        pixels of every line into what lies below.  `DeviceCollator.quad_windows` uploads the picture once, rectifies every quad into an
+        upright crop and cuts all windows on the device, the windows go through the sessions in batches of `batch_size` exactly as
+        `scene` runs them, `DeviceExporter.scene_quads` merges, up-scales, warps back and pastes on the device and copies the canvas back
+        once.  Byte for byte `io.super_resolve_quads_host` on the same SR windows; axis-aligned quads give the bytes of `scene` on their
+        boxes.  No quads: the up-scaled picture, no session runs.  Not with a recogniser (ValueError).  With keep_sr the PendingScene's
+        `boxes` are the checked quads and `layers` their paste layers (`io.quad_layers`)."""
+        from .io import line_plan, quad_layers
+        if self.rec is not None:
+            raise ValueError("SuperResolver: a recogniser cannot read tiled lines (scene_quads); pass recognizer=None")
+        if not (isinstance(feather, int) and not isinstance(feather, bool) and feather >= 0):
+            raise ValueError("SuperResolver.scene_quads: feather must be an int >= 0; got %r" % (feather,))
+        h, w = self.lr_size
+        line_plan((w, h), self.lr_size, self.stride)                 # (raises for a stride outside [w / 2, w])
+        fresh, buf, quads = set(), None, list(quads)
+        with torch.cuda.device(self.device):
+            stack, lines, scene_dev = self.collator.quad_windows(image, quads, self.stride)
+            N = stack.shape[0]
+            for i in range(0, N, self.B):
+                n = min(self.B, N - i)
+                sr = self._session(n, fresh).run(stack[i:i + n], text_prior=self._zero_prior(n))[0]
+                if buf is None:                                      # (in the layout the session leaves: a plain copy per batch)
+                    cl = sr.stride(1) == 1 and not sr.is_contiguous()
+                    buf = torch.empty((N,) + tuple(sr.shape[1:]), dtype=sr.dtype, device=sr.device,
+                                      memory_format=torch.channels_last if cl else torch.contiguous_format)
+                buf[i:i + n].copy_(sr)                               # the session's output is static: the next replay overwrites it
+            if buf is not None:
+                H, W = buf.shape[2:]
+                if H % h or W % w or H // h != W // w:
+                    raise ValueError("the SR windows %d x %d are no integer multiple of the LR window %d x %d" % (H, W, h, w))
+                scale = H // h
+            else:
+                scale = self._scale()
+            quads = [tuple((int(x), int(y)) for x, y in q) for q in quads]        # (checked by quad_windows)
+            pending = self.exporter.scene_quads(scene_dev, buf, lines, quads, scale, feather)
+        if not self.keep_sr:
+            return PendingScene(pending)
+        return PendingScene(pending, buf, stack, lines, quads, quad_layers(quads))
 
     def _session(self, n, fresh):
         """the session of batch size n, captured on first use; refreshed once per call (`fresh`: the sizes this call has met)"""

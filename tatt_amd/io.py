@@ -26,6 +26,9 @@
 * `line_plan` / `line_windows_host` / `blend_windows_host` / `super_resolve_lines_host` (tatt_amd/lines.py, re-exported here) take a
   text line of any width through a generator that knows one LR size: windows of the line at its own aspect ratio, merged back with tent
   weights; `DeviceCollator.windows` and `DeviceExporter.lines` are the same on the GPU (csrc/lines.hip), bit for bit.
+* `quad_check` / `quad_matrices` / `warp_u8_host` / `quad_compose_host` / `super_resolve_quads_host` (tatt_amd/quads.py, re-exported here)
+  take a detector's QUADRILATERALS instead of boxes: every quad rectified into an upright crop, the finished line warped back into its
+  place; `DeviceCollator.quad_windows` and `DeviceExporter.scene_quads` are the same on the GPU (csrc/quads.hip), byte for byte.
 * `LmdbRecords` reads the reference's lmdb record layout (`lmdbDataset_real`, dataset/dataset.py:565-686): keys `num-samples`,
   `label-%09d`, `image_hr-%09d`, `image_lr-%09d` (1-based), image bytes decoded by PIL to RGB, the label filtered by `str_filt`.
   It takes any object with the lmdb transaction's `get(key)`; `open_lmdb` wraps a real environment when the `lmdb` package is there
@@ -628,6 +631,55 @@ class DeviceCollator:
         scene_dev = self._dev_buf[pix:pix + Hs * Ws * 3].view(Hs, Ws, 3)
         return out.view(len(plan.desc), 3 + int(self.mask), h, w), plan.lines, scene_dev
 
+    def quad_windows(self, scene, quads, stride: int = 32):
+        """RGB PIL image and quadrilateral boxes (four integer corner points each, `quad_check`) -> (stack, lines, scene_dev): ONE
+        (n_windows, 3 + mask, h, w) stack on the device with the windows of every quad's rectified crop, bit for bit
+        `quad_windows_host(scene, quads, (h, w), stride, mask)`, its Line records, and the scene's (Hs, Ws, 3) uint8 pixels on the device
+        (a view of the collator's device buffer, as `scene_windows` returns it).  The scene and all tables go up ONCE from a pinned slot;
+        ONE tatt_warp_u8 launch writes every rectified crop into a region of the device buffer behind the upload, ONE tatt_resize_u8
+        launch resizes the crops beyond `line_limits()` to (wl, h) on the device (none in the common case: no launch), ONE
+        tatt_scene_windows launch reads every window out of its crop (`quad_plan`).  No quads: the upload alone, an empty stack.  Never
+        waits for the device."""
+        import ctypes
+        from . import ops
+        from .lines import line_limits
+        from .quads import quad_fill, quad_limits, quad_plan
+        from .scene import scene_limits
+        if self._line_limits is None:
+            self._line_limits = line_limits()
+        if getattr(self, "_quad_limits", None) is None:
+            self._quad_limits = (scene_limits(), quad_limits())
+        w, h = self.lr_size
+        plan = quad_plan(scene, quads, (h, w), stride, self.mask, self._line_limits, *self._quad_limits)
+        o_warp, o_resize, o_desc, pix, used, total = quad_fill(None, plan)
+        Hs, Ws = plan.arrays[0].shape[:2]
+        with torch.cuda.device(self.device):
+            stream = torch.cuda.current_stream()
+            moved = self._last is not None and self._last[0] != stream
+            if moved:
+                stream.wait_event(self._last[1])
+            k, host = self._slot(total)                              # (the device buffer holds the crops behind the upload)
+            if moved:
+                self._dev_buf.record_stream(stream)
+            quad_fill(host.numpy(), plan)
+            self._dev_buf[:used].copy_(host[:used], non_blocking=True)
+            ev = self._events[k] = self._events[k] if self._events[k] is not None else torch.cuda.Event()
+            ev.record(stream)
+            out = torch.empty(plan.out_floats, dtype=torch.float32, device=self.device)
+            base, hbase = self._dev_buf.data_ptr(), host.data_ptr()
+            buf, at = ctypes.c_void_p(base + pix), lambda o: (ctypes.c_void_p(base + o), ctypes.c_void_p(hbase + o))
+            if len(plan.warp):
+                ops.call("tatt_warp_u8", buf, plan.nbytes, *at(o_warp), len(plan.warp), buf, plan.nbytes, ops.stream())
+            if len(plan.resize):
+                ops.call("tatt_resize_u8", buf, plan.nbytes, *at(o_resize), len(plan.resize), buf, plan.nbytes, ops.stream())
+            if len(plan.desc):
+                ops.call("tatt_scene_windows", buf, plan.nbytes, *at(o_desc), len(plan.desc), ops.P(out), plan.out_floats, ops.stream())
+            done = self._last[1] if self._last is not None else torch.cuda.Event()
+            done.record(stream)
+            self._last = (stream, done)
+        scene_dev = self._dev_buf[pix:pix + Hs * Ws * 3].view(Hs, Ws, 3)
+        return out.view(len(plan.desc), 3 + int(self.mask), h, w), plan.lines, scene_dev
+
 
 # ---- image export on the device (csrc/export.hip) -----------------------------------------------------------------------------------
 EXPORT_DESC = 8           # ints per descriptor row of tatt_export_images (include/tatt_hip.h)
@@ -1024,8 +1076,72 @@ class DeviceExporter:
                 r += n
         return self._enqueue([], nbytes, views, head=head, launch=launch)
 
+    def scene_quads(self, scene_dev, sr_windows, lines, quads, scale: int, feather: int = 0, c0: int = 0) -> PendingExport:
+        """`scene` for quadrilateral boxes: scene_dev: the (Hs, Ws, 3) uint8 scene on the device (`DeviceCollator.quad_windows`),
+        sr_windows (n_windows, C, H, W) fp32 on the device: the SR windows of all quads (None without quads), lines: their Line records,
+        one per quad -> a PendingExport whose `result()` is one RGB PIL image of size (scale * Ws, scale * Hs), BYTE FOR BYTE
+        `quad_compose_host(scene, quads, [blend_windows_host(..) per quad], scale, feather)`.  On the current stream: the rows of all
+        launches go host-to-device from a pinned slot, ONE tatt_line_blend launch merges the windows of every quad into uint8 line
+        canvases, ONE tatt_resize_u8 launch up-scales the scene into the canvas, ONE tatt_resize_u8 launch resizes all lines into their
+        (scale * bh, scale * bw) rectangles (in the output buffer, in front of the canvas), ONE tatt_warp_u8 launch per layer
+        (`quad_layers`: quads whose bounding boxes do not intersect share a launch) warps the rectangles into their quads, feathered
+        against what the canvas holds, and ONE non-blocking copy brings the buffer into the pinned slot.  Never waits for the device."""
+        import ctypes
+        import numpy as np
+        from . import ops
+        from .lines import BLEND_DESC, blend_plan, line_limits
+        from .quads import QUAD_DESC, quad_limits, quad_paste_plan
+        from .scene import RESIZE_DESC, scene_limits
+        if not (isinstance(scene_dev, torch.Tensor) and scene_dev.dim() == 3 and scene_dev.shape[2] == 3 and
+                scene_dev.dtype == torch.uint8 and scene_dev.is_contiguous() and scene_dev.device.type == "cuda"):
+            raise ValueError("DeviceExporter.scene_quads takes the contiguous (Hs, Ws, 3) uint8 scene on the device")
+        lines, quads = list(lines), list(quads)
+        if self._line_limits is None:
+            self._line_limits = line_limits()
+        if getattr(self, "_scene_limits", None) is None:
+            self._scene_limits = scene_limits()
+        if getattr(self, "_quad_limits", None) is None:
+            self._quad_limits = quad_limits()
+        Hs, Ws = int(scene_dev.shape[0]), int(scene_dev.shape[1])
+        if lines:
+            self._check(sr_windows, c0)
+            B, C, H, W = sr_windows.shape
+            bdesc, starts, bbytes = blend_plan(lines, B, H, W, scale, self.rule, c0, self._line_limits)
+        else:
+            B = C = H = W = 0
+            bdesc, starts, bbytes = np.zeros((0, BLEND_DESC), np.int32), np.zeros(0, np.int32), 0
+        plan = quad_paste_plan((Ws, Hs), quads, bdesc, bbytes, scale, H, feather, self._scene_limits, self._quad_limits)
+        at = lambda n: -(-n // 4) * 4                                  # (every table 16-byte aligned)
+        o_starts = at(bdesc.size)
+        o_rows = o_starts + at(starts.size)
+        o_warp = o_rows + at(plan.resize.size)
+        head = np.zeros(o_warp + plan.warp.size, np.int32)
+        head[:bdesc.size], head[o_starts:o_starts + starts.size] = bdesc.reshape(-1), starts
+        head[o_rows:o_rows + plan.resize.size], head[o_warp:] = plan.resize.reshape(-1), plan.warp.reshape(-1)
+        views = [(plan.canvas_off, scale * Hs, scale * Ws, plan.pitch, None)]
+        nbytes, src_bytes, n = plan.nbytes, Hs * Ws * 3, len(quads)
+
+        def launch(base, hbase, pix):
+            out = ctypes.c_void_p(base + pix)
+            if lines:
+                ops.call("tatt_line_blend", ops.P(sr_windows), *sr_windows.stride(), B, C, H, W, ctypes.c_void_p(base),
+                         ctypes.c_void_p(hbase), len(bdesc), ctypes.c_void_p(base + o_starts * 4), ctypes.c_void_p(hbase + o_starts * 4),
+                         int(starts.size), out, max(bbytes, 1), ops.stream())
+            row = lambda o: (ctypes.c_void_p(base + o * 4), ctypes.c_void_p(hbase + o * 4))
+            ops.call("tatt_resize_u8", ops.P(scene_dev), src_bytes, *row(o_rows), 1, out, nbytes, ops.stream())
+            if n:                                                      # the line canvases lie in front of the rectangles, in the same buffer
+                ops.call("tatt_resize_u8", out, max(bbytes, 1), *row(o_rows + RESIZE_DESC), n, out, plan.canvas_off, ops.stream())
+            r = 0
+            for c in plan.counts:                                      # the rectangles lie in front of the canvas
+                ops.call("tatt_warp_u8", out, plan.canvas_off, *row(o_warp + r * QUAD_DESC), c, out, nbytes, ops.stream())
+                r += c
+        return self._enqueue([], nbytes, views, head=head, launch=launch)
+
 
 from .lines import (LINE_MAX_WL, Line, blend_plan, blend_windows_host, line_limits, line_plan, line_windows_host, lines_fill,  # noqa: E402,F401
                     lines_plan, super_resolve_lines_host)
 from .scene import (SCENE_MIN_SIDE, paste_plan, scene_check, scene_compose_host, scene_fill, scene_layers, scene_limits,  # noqa: E402,F401
                     scene_plan, scene_windows_host, super_resolve_scene_host)
+from .quads import (QUAD_MAX_TAPER, QUAD_SHIFT, quad_bbox, quad_check, quad_compose_host, quad_fill, quad_layers,  # noqa: E402,F401
+                    quad_limits, quad_matrices, quad_paste_plan, quad_plan, quad_rectify_host, quad_size, quad_windows_host,
+                    super_resolve_quads_host, warp_inside_host, warp_u8_host)
