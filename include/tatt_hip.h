@@ -906,6 +906,31 @@ int tatt_warp_u8(const unsigned char* src, long src_bytes, const int* desc, cons
 /* out[0..5]: tile height, tile width, most items of one launch, largest side of a source or target, largest feather, ints per
  * descriptor row.  Host only: needs no GPU. */
 int tatt_quad_limits(int* out);
+/* ---- reading super-resolved lines at their own width (csrc/read.hip; tatt_amd/read.py is the specification) -- */
+/* ONE launch for all lines of a call: every uint8 RGB line canvas in src (where tatt_line_blend left it) goes through Pillow's 8-bit
+ * bicubic Image.resize((rw, 32), BICUBIC) (horizontal pass first, its result rounded to uint8, a pass whose sizes agree skipped), then
+ * n = 299 R + 587 G + 114 B and float(n) * float(1 / 255000) -- bit for bit read.line_luma_host -- stored as the fp32 (32, rw) plane
+ * at its float offset in out, tiled over the output (grid: tile x line).  desc (n_lines, 8) int32 in DEVICE memory:
+ *   [0] byte offset of the line's first pixel in src  [1] H  [2] W  [3] row pitch in bytes, >= 3 W  [4] rw  [5] float offset of the
+ *   (32, rw) target in out  [6..7] 0
+ * desc_host: the same rows in HOST memory, read before the launch only to refuse: 1 bad arguments or a reserved word, 2 a geometry
+ * beyond tatt_read_limits (rw, a down-scale beyond 16 per axis, the width, more than 65535 lines), 3 a source rectangle or a target
+ * that leaves src (src_bytes) / out (out_floats).  The kernel reads only device memory and re-checks every row: a row it would have
+ * refused gets a NaN target, or nothing when the target lies outside out. */
+int tatt_line_luma(const unsigned char* src, long src_bytes, const int* desc, const int* desc_host, int n_lines, float* out,
+                   long out_floats, hipStream_t st);
+/* out[0..7]: the target height (32), largest rw, largest down-scale factor per axis, widest line, most lines of one launch, most steps T
+ * and most classes C of tatt_ctc_greedy_read, ints per descriptor row.  Host only: needs no GPU. */
+int tatt_read_limits(int* out);
+/* greedy CTC decoding with confidences of logits (T,B,C) by element strides, T <= 256, C <= 64, one wave per image: per step the
+ * arg-max (ties to the lower class) and its soft-max probability 1 / sum_c exp(x_c - max); repeats merged, blank 0 dropped, every other
+ * class kept.  Image b writes the record row index[b] (rows st_rec 32-bit words apart; an index outside 0 .. n_rows - 1 writes nothing):
+ *   [0, cap) decoded classes padded with -1  [cap, 2 cap) the first step of each decoded class's run, padded with -1
+ *   [2 cap, 3 cap) fp32: the probability at that step, padded with 0  [3 cap] the decoded length
+ *   [3 cap + 1] fp32: the minimum over ALL T steps of the arg-max's probability
+ * Returns 1 for geometries it does not take (T, C, cap < T, st_rec < 3 cap + 2). */
+int tatt_ctc_greedy_read(const float* logits, long st_t, long st_b, long st_c, int T, int B, int C, const int* index, int* record,
+                         int n_rows, int cap, long st_rec, hipStream_t st);
 /* calculate_psnr (reference utils/ssim_psnr.py:9-15) of two (B,C,H,W) images in [0,1] given by element strides, first 3 channels */
 int tatt_psnr(const float* a, long a_n, long a_c, long a_h, long a_w, const float* b, long b_n, long b_c, long b_h, long b_w,
               float* out, int B, int C, int H, int W, hipStream_t st);

@@ -224,6 +224,42 @@ def _crnn_folds(crnn):
             for i in range(7) if hasattr(crnn.cnn, "batchnorm%d" % i)}
 
 
+def crnn_eval(crnn, folds, img, sync):
+    """CRNN.forward (crnn.py) with BatchNorm folded and the chained LSTM layers: img (B, 1, 32, W) -> logits (W/4 + 1, B, 37).
+    folds: `_crnn_folds(crnn)`; sync(ref) -> the 1024-word workspace of the next LSTM layer.  The sessions and `read.LineReader` share it."""
+    from .crnn import CRNN
+    h = img.permute(0, 2, 3, 1)
+    for i in range(7):
+        conv = getattr(crnn.cnn, "conv%d" % i)
+        w, b = (folds[i].w, folds[i].b) if i in folds else (conv.weight, conv.bias)
+        if conv.kernel_size == (3, 3):
+            h = Fh.conv2d(h, w, b, ACT_RELU, any_width=True)
+        else:
+            h = Fh.ActFn.apply(Fh.Conv2x2ValidFn.apply(Fh._c(h), w, b), ACT_RELU)
+        if i in CRNN._POOLS:
+            h = Fh.max_pool(h, *CRNN._POOLS[i])
+    B, Hh, Wd, C = h.shape
+    seq = Fh.Permute4dFn.apply(h, (2, 1, 0, 3)).reshape(Wd, B, C)
+    for blk in crnn.rnn:
+        seq = Fh.linear(bilstm_eval(seq, blk.rnn, sync(seq)), blk.embedding.weight, blk.embedding.bias)
+    return seq
+
+
+def repack_filters(owned, modules, force):
+    """Packed layouts of the folded filters `owned` (always rebuilt: their version counters never move) and of the modules' own filters
+    (rebuilt when their version changed, or all of them with `force`).  Same buffers, so pointers a graph captured hold."""
+    params = [p for m in modules if m is not None for p in m.parameters() if p.dim() == 4]
+    for w, always in [(w, True) for w in owned] + [(p, force) for p in params]:
+        h = getattr(w, "_tatt_packed", None)
+        if h is None or h.key != (w.data_ptr(), tuple(w.shape), str(w.device)):
+            continue
+        for mode, (buf, ver) in list(h.bufs.items()):
+            if always or ver != w._version:
+                Cout, Cin, KH, KW = w.shape
+                ops.call("tatt_repack_conv_weight", ops.P(w), ops.P(buf), Cout, Cin, KH, KW, mode, ops.stream())
+                h.bufs[mode] = (buf, w._version)
+
+
 class InferenceSession:
     """One eval pass -- [prior CRNN on LR ->] generator [-> PSNR / SSIM against HR] [-> recogniser + greedy CTC match on the images
     named in `accuracy_on`] -- captured as ONE hipGraph for a fixed batch size and replayed by `run`.
@@ -301,17 +337,7 @@ class InferenceSession:
     def _repack(self, force):
         """Packed layouts the graph reads: of the folded filters (always rebuilt: their version counters never move) and of the modules'
         own filters (rebuilt when their version changed, or all of them with `force`).  Same buffers, so the captured pointers hold."""
-        owned = [f.w for f in self._all_folds()]
-        params = [p for m in (self.gen, self.prior, self.rec) if m is not None for p in m.parameters() if p.dim() == 4]
-        for w, always in [(w, True) for w in owned] + [(p, force) for p in params]:
-            h = getattr(w, "_tatt_packed", None)
-            if h is None or h.key != (w.data_ptr(), tuple(w.shape), str(w.device)):
-                continue
-            for mode, (buf, ver) in list(h.bufs.items()):
-                if always or ver != w._version:
-                    Cout, Cin, KH, KW = w.shape
-                    ops.call("tatt_repack_conv_weight", ops.P(w), ops.P(buf), Cout, Cin, KH, KW, mode, ops.stream())
-                    h.bufs[mode] = (buf, w._version)
+        repack_filters([f.w for f in self._all_folds()], (self.gen, self.prior, self.rec), force)
 
     def refresh(self, force: bool = True):
         """Re-fold and re-pack now (eager launches into the buffers the graph reads).  Call it after writing weights through raw
@@ -346,23 +372,7 @@ class InferenceSession:
 
     def _crnn(self, crnn, img):
         """CRNN.forward (crnn.py) with BatchNorm folded and the chained LSTM layers: img (B, 1, 32, W) -> logits (W/4 + 1, B, 37)."""
-        from .crnn import CRNN
-        folds = self._crnn_folds[id(crnn)]
-        h = img.permute(0, 2, 3, 1)
-        for i in range(7):
-            conv = getattr(crnn.cnn, "conv%d" % i)
-            w, b = (folds[i].w, folds[i].b) if i in folds else (conv.weight, conv.bias)
-            if conv.kernel_size == (3, 3):
-                h = Fh.conv2d(h, w, b, ACT_RELU, any_width=True)
-            else:
-                h = Fh.ActFn.apply(Fh.Conv2x2ValidFn.apply(Fh._c(h), w, b), ACT_RELU)
-            if i in CRNN._POOLS:
-                h = Fh.max_pool(h, *CRNN._POOLS[i])
-        B, Hh, Wd, C = h.shape
-        seq = Fh.Permute4dFn.apply(h, (2, 1, 0, 3)).reshape(Wd, B, C)
-        for blk in crnn.rnn:
-            seq = Fh.linear(bilstm_eval(seq, blk.rnn, self._sync(seq)), blk.embedding.weight, blk.embedding.bias)
-        return seq
+        return crnn_eval(crnn, self._crnn_folds[id(crnn)], img, self._sync)
 
     def _generator(self, x, tp):
         """TSRN / TSRN_TL_TRANS eval forward (tsrn._GeneratorBase._trunk_forward with training False) on folded BatchNorms."""
@@ -660,12 +670,14 @@ def evaluate_session(generator, batches: Iterable, prior=None, recognizer=None, 
 # ---- PIL crops in, PIL images out ---------------------------------------------------------------------------------------------------
 class PendingUpscale:
     """What `SuperResolver.__call__` started.  `result()` is the only host wait: -> the SR images as RGB PIL images, in input order
-    (with a recogniser: (images, texts)).  `sr`: with keep_sr, a clone of every batch's SR tensor; with long_lines the ONE
-    (n_windows, C, H, W) buffer of all SR windows, beside `lr` (the window stack the sessions read) and `lines` (`io.Line` records)."""
+    (with a recogniser, or with a reader on long_lines: (images, texts)).  `sr`: with keep_sr, a clone of every batch's SR tensor; with
+    long_lines the ONE (n_windows, C, H, W) buffer of all SR windows, beside `lr` (the window stack the sessions read) and `lines`
+    (`io.Line` records).  With a reader `readings()` gives the `read.Reading` record of every line (text, confidences, steps, rw)."""
 
-    def __init__(self, parts, with_text, sr, lr=None, lines=None):
+    def __init__(self, parts, with_text, sr, lr=None, lines=None, reading=None):
         self._parts, self._with_text, self.sr = parts, with_text, sr
         self.lr, self.lines = lr, lines                              # long_lines with keep_sr: the window stack and its Line records
+        self._reading = reading                                      # long_lines with a reader: the PendingReading of the lines
 
     def result(self):
         images, texts = [], []
@@ -675,19 +687,38 @@ class PendingUpscale:
                 ev.synchronize()
                 for row in dec.tolist():                               # (T codes padded with -1 | length)
                     texts.append("".join(D2A[c] for c in row[:row[-1]]))
+        if self._reading is not None:
+            texts = self._reading.texts()
         return (images, texts) if self._with_text else images
+
+    def readings(self):
+        """one `read.Reading` per line, in input order (long_lines on an instance with `reader=`)"""
+        if self._reading is None:
+            raise RuntimeError("readings() needs SuperResolver(..., reader=crnn, long_lines=True)")
+        return self._reading.result()
 
 
 class PendingScene:
     """What `SuperResolver.scene` started.  `result()` is the only host wait: -> the RGB PIL image of size (scale * Ws, scale * Hs).
     With keep_sr: `sr` the ONE (n_windows, C, H, W) buffer of all SR windows (None without boxes), `lr` the window stack the sessions
-    read, `lines` its `io.Line` records (one per box), `boxes` the checked boxes and `layers` their paste layers (`io.scene_layers`)."""
+    read, `lines` its `io.Line` records (one per box), `boxes` the checked boxes and `layers` their paste layers (`io.scene_layers`).
+    On an instance with `reader=`: `texts()` / `readings()`, one string / `read.Reading` per box or quad in input order ([] without
+    boxes), read from the blended lines BEFORE they were pasted (so `feather` does not reach them)."""
 
-    def __init__(self, pending, sr=None, lr=None, lines=None, boxes=None, layers=None):
+    def __init__(self, pending, sr=None, lr=None, lines=None, boxes=None, layers=None, reading=None):
         self._pending, self.sr, self.lr, self.lines, self.boxes, self.layers = pending, sr, lr, lines, boxes, layers
+        self._reading = reading
 
     def result(self):
         return self._pending.result()[0]
+
+    def readings(self):
+        if self._reading is None:
+            raise RuntimeError("readings() / texts() need SuperResolver(..., reader=crnn)")
+        return self._reading.result()
+
+    def texts(self):
+        return [r.text for r in self.readings()]
 
 
 class SuperResolver:
@@ -714,18 +745,28 @@ class SuperResolver:
     image of size (scale * wl, H) per input -- an image no wider than the LR window's aspect ratio yields one window and the bytes it
     gets with long_lines=False; out_sizes: PIL resizes the finished line on the host.  Byte for byte `io.super_resolve_lines_host` on
     the same SR windows.  A TSRN_TL_TRANS generator without a `prior` runs every window on a zero row of the text prior.  No
-    recogniser with long_lines (ValueError): reading a tiled line is not defined here.
+    `recognizer` with long_lines (ValueError): it reads a 32 x 128 crop squeezed to 32 x 100; tiled lines are read by `reader=`.
 
     `scene(image, boxes, feather=0)` (any instance without a recogniser) takes a whole picture and a detector's boxes and returns the
     up-scaled picture with the text of every box super-resolved and pasted back: see the method.  `scene_quads(image, quads, feather=0)`
-    is the same for quadrilaterals (four corner points per text instance, rotated or under perspective)."""
+    is the same for quadrilaterals (four corner points per text instance, rotated or under perspective).
+
+    reader=crnn (opt-in; images and pictures are byte for byte those without it) reads every tiled line at its OWN width
+    (`read.LineReader`, specification `read.read_lines_host`): the blended uint8 line is resized to (32, rw), rw = `read.read_width(wl)`
+    (100 for a one-window line, a multiple of 20, at most 1020: a wider line is read squeezed), lines of one rw share a forward without
+    padding, the greedy CTC decoding reports the soft-max probability of every decision.  Per call +1 tatt_line_luma launch, per
+    bucket chunk one eager CRNN forward and one tatt_ctc_greedy_read launch, +1 copy; nothing waits before `result()`.  With
+    long_lines `result()` is (images, texts) and `PendingUpscale.readings()` the `read.Reading` records; `scene` / `scene_quads` keep
+    `result()` (the picture) and add `PendingScene.texts()` / `.readings()`, one per box in input order.  Lines are read before
+    `out_sizes` and `feather` apply.  A plain call on an instance with `reader=` and no `recognizer=` raises ValueError."""
 
     def __init__(self, generator, prior=None, recognizer=None, batch_size: int = 48, lr_size=(16, 64), mask: bool = True,
-                 rule: str = "floor", keep_sr: bool = False, long_lines: bool = False, stride: int = 32):
+                 rule: str = "floor", keep_sr: bool = False, long_lines: bool = False, stride: int = 32, reader=None):
         from .io import DeviceCollator, DeviceExporter
         _check_module(generator, "generator")
         _check_module(prior, "prior CRNN")
         _check_module(recognizer, "recogniser CRNN")
+        _check_module(reader, "reader CRNN")
         if not (isinstance(batch_size, int) and batch_size > 0):
             raise ValueError("batch_size must be a positive int")
         if long_lines:
@@ -741,6 +782,10 @@ class SuperResolver:
         self.exporter = DeviceExporter(device=self.device, rule=rule)
         self.sessions = {}
         self._ctc = {}                                               # batch size -> (keep, label, label_len) the decoding ignores
+        self.reader = None
+        if reader is not None:
+            from .read import LineReader
+            self.reader = LineReader(reader, batch_size=batch_size, device=self.device, w=self.lr_size[1])
 
     def _texts(self, sr):
         """-> (pinned (n, T + 1) int32: decoded classes | length, its event)"""
@@ -773,6 +818,9 @@ class SuperResolver:
                 raise ValueError("%d out_sizes for %d images" % (len(out_sizes), len(images)))
         if self.long_lines:
             return self._lines(images, out_sizes)
+        if self.reader is not None and self.rec is None:
+            raise ValueError("SuperResolver: reader= reads tiled lines (long_lines=True, scene, scene_quads); a plain call squeezes every "
+                             "crop into the LR size: pass recognizer= for its texts, or build the instance with long_lines=True")
         h, w = self.lr_size
         parts, kept, fresh = [], [], set()
         with torch.cuda.device(self.device):
@@ -829,9 +877,10 @@ class SuperResolver:
                 scale = self._scale()
             boxes = [tuple(int(v) for v in b) for b in boxes]        # (checked by scene_windows)
             pending = self.exporter.scene(scene_dev, buf, lines, boxes, scale, feather)
+            reading = self._read(pending, scale)
         if not self.keep_sr:
-            return PendingScene(pending)
-        return PendingScene(pending, buf, stack, lines, boxes, scene_layers(boxes))
+            return PendingScene(pending, reading=reading)
+        return PendingScene(pending, buf, stack, lines, boxes, scene_layers(boxes), reading)
 
     def scene_quads(self, image, quads, feather: int = 0) -> PendingScene:
         """`scene` for a detector's QUADRILATERALS: image: an RGB PIL image, quads: four integer corner points per text instance,
@@ -872,9 +921,17 @@ class SuperResolver:
                 scale = self._scale()
             quads = [tuple((int(x), int(y)) for x, y in q) for q in quads]        # (checked by quad_windows)
             pending = self.exporter.scene_quads(scene_dev, buf, lines, quads, scale, feather)
+            reading = self._read(pending, scale)
         if not self.keep_sr:
-            return PendingScene(pending)
-        return PendingScene(pending, buf, stack, lines, quads, quad_layers(quads))
+            return PendingScene(pending, reading=reading)
+        return PendingScene(pending, buf, stack, lines, quads, quad_layers(quads), reading)
+
+    def _read(self, pending, scale):
+        """with a reader: its launches on the blended lines of `pending` (a PendingExport of lines / scene / scene_quads), enqueued right
+        behind the exporter's on the same stream -- the lines stay where they are until the exporter's next call"""
+        if self.reader is None:
+            return None
+        return self.reader.read(*pending.line_canvases, scale)
 
     def _session(self, n, fresh):
         """the session of batch size n, captured on first use; refreshed once per call (`fresh`: the sizes this call has met)"""
@@ -900,8 +957,9 @@ class SuperResolver:
         """the long_lines call: windows of all images -> sessions over batches of windows -> one SR buffer -> one blend launch"""
         h, w = self.lr_size
         fresh, buf = set(), None
+        with_text = self.reader is not None
         if not images:
-            return PendingUpscale([], False, None)
+            return PendingUpscale([], with_text, None, reading=self.reader.read(None, [], 1) if with_text else None)
         with torch.cuda.device(self.device):
             stack, lines = self.collator.windows(images, self.stride)
             N = stack.shape[0]
@@ -917,5 +975,7 @@ class SuperResolver:
             if H % h or W % w or H // h != W // w:
                 raise ValueError("the SR windows %d x %d are no integer multiple of the LR window %d x %d" % (H, W, h, w))
             pending = self.exporter.lines(buf, lines, H // h, out_sizes=out_sizes)
+            reading = self._read(pending, H // h)
         keep = self.keep_sr
-        return PendingUpscale([(pending, None, None)], False, buf if keep else None, stack if keep else None, lines if keep else None)
+        return PendingUpscale([(pending, None, None)], with_text, buf if keep else None, stack if keep else None, lines if keep else None,
+                              reading)

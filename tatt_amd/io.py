@@ -816,10 +816,14 @@ class _ExportSlot:
 
 class PendingExport:
     """What `DeviceExporter.__call__` / `.panels` started.  It owns one pinned slot of the exporter until `result()` / `arrays()` (which
-    wait for its event only, copy the pixels out and release the slot) or `release()` (gives the slot back unread)."""
+    wait for its event only, copy the pixels out and release the slot) or `release()` (gives the slot back unread).
+    `line_canvases` (of `.lines`, `.scene` and `.scene_quads`; None otherwise): (the exporter's uint8 device buffer, [(byte offset, H, W,
+    row pitch)] of every blended line in it, in line order) -- where tatt_line_blend left the lines, valid until the exporter's NEXT
+    call: work enqueued on the same stream before that call reads them safely (`read.LineReader.read`)."""
 
-    def __init__(self, slot, event, pix, views):
+    def __init__(self, slot, event, pix, views, line_canvases=None):
         self._slot, self._event, self._pix, self._views, self._arrays = slot, event, pix, views, None
+        self.line_canvases = line_canvases
 
     def arrays(self):
         """-> the (OH, OW, 3) uint8 arrays (copies: the slot is free afterwards)"""
@@ -906,10 +910,10 @@ class DeviceExporter:
         slot.held = True
         return slot
 
-    def _enqueue(self, jobs, nbytes, views, zero=False, head=None, launch=None):
+    def _enqueue(self, jobs, nbytes, views, zero=False, head=None, launch=None, canvases=None):
         """jobs: [(tensor, desc rows)], all rows addressing one output of nbytes bytes -> PendingExport.  `head` / `launch` (`lines`): the
         int32 words to stage in front of the pixels instead of the jobs' rows, and launch(device base, host base, pixel offset) instead of
-        the jobs' launches."""
+        the jobs' launches.  `canvases`: [(byte offset from the pixels, H, W, pitch)] of the blended lines, for `line_canvases`."""
         import ctypes
         import numpy as np
         from . import ops
@@ -948,7 +952,8 @@ class DeviceExporter:
             ev.record(stream)
             slot.event = ev
             self._last = (stream, ev)
-        return PendingExport(slot, ev, pix, views)
+            where = None if canvases is None else (self._dev_buf, [(pix + o, h, w, p) for o, h, w, p in canvases])
+        return PendingExport(slot, ev, pix, views, where)
 
     def __call__(self, images, sizes=None, c0: int = 0) -> PendingExport:
         self._check(images, c0)
@@ -1021,7 +1026,8 @@ class DeviceExporter:
             ops.call("tatt_line_blend", ops.P(sr_windows), *sr_windows.stride(), B, C, H, W, ctypes.c_void_p(base), ctypes.c_void_p(hbase),
                      len(desc), ctypes.c_void_p(base + rows * 4), ctypes.c_void_p(hbase + rows * 4), int(starts.size),
                      ctypes.c_void_p(base + pix), nbytes, ops.stream())
-        return self._enqueue([], nbytes, views, head=head, launch=launch)
+        canvases = [(int(d[6]), H, scale * int(d[2]), int(d[7])) for d in desc]
+        return self._enqueue([], nbytes, views, head=head, launch=launch, canvases=canvases)
 
     def scene(self, scene_dev, sr_windows, lines, boxes, scale: int, feather: int = 0, c0: int = 0) -> PendingExport:
         """The finished scene: scene_dev: the (Hs, Ws, 3) uint8 scene on the device (`DeviceCollator.scene_windows`), sr_windows
@@ -1074,7 +1080,8 @@ class DeviceExporter:
             for n in plan.counts:                                      # the line canvases lie in front of the canvas, in the same buffer
                 ops.call("tatt_resize_u8", out, plan.canvas_off, *row(r), n, out, nbytes, ops.stream())
                 r += n
-        return self._enqueue([], nbytes, views, head=head, launch=launch)
+        canvases = [(int(d[6]), H, scale * int(d[2]), int(d[7])) for d in bdesc]
+        return self._enqueue([], nbytes, views, head=head, launch=launch, canvases=canvases)
 
     def scene_quads(self, scene_dev, sr_windows, lines, quads, scale: int, feather: int = 0, c0: int = 0) -> PendingExport:
         """`scene` for quadrilateral boxes: scene_dev: the (Hs, Ws, 3) uint8 scene on the device (`DeviceCollator.quad_windows`),
@@ -1135,7 +1142,8 @@ class DeviceExporter:
             for c in plan.counts:                                      # the rectangles lie in front of the canvas
                 ops.call("tatt_warp_u8", out, plan.canvas_off, *row(o_warp + r * QUAD_DESC), c, out, nbytes, ops.stream())
                 r += c
-        return self._enqueue([], nbytes, views, head=head, launch=launch)
+        canvases = [(int(d[6]), H, scale * int(d[2]), int(d[7])) for d in bdesc]
+        return self._enqueue([], nbytes, views, head=head, launch=launch, canvases=canvases)
 
 
 from .lines import (LINE_MAX_WL, Line, blend_plan, blend_windows_host, line_limits, line_plan, line_windows_host, lines_fill,  # noqa: E402,F401
@@ -1145,3 +1153,5 @@ from .scene import (SCENE_MIN_SIDE, paste_plan, scene_check, scene_compose_host,
 from .quads import (QUAD_MAX_TAPER, QUAD_SHIFT, quad_bbox, quad_check, quad_compose_host, quad_fill, quad_layers,  # noqa: E402,F401
                     quad_limits, quad_matrices, quad_paste_plan, quad_plan, quad_rectify_host, quad_size, quad_windows_host,
                     super_resolve_quads_host, warp_inside_host, warp_u8_host)
+from .read import (READ_MAX, READ_QUANTUM, Reading, ctc_greedy_read_host, line_luma_host, read_limits, read_lines_host,  # noqa: E402,F401
+                   read_plan, read_squeezed, read_width)
