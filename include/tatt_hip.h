@@ -957,6 +957,38 @@ int tatt_affine_sample_fwd(const float* x, long xsn, long xsc, long xsh, long xs
 int tatt_affine_sample_bwd(const float* theta, const float* dout, float* dimg, int B, int C, int H, int W,
                            hipStream_t st);
 
+/* ---- the ASTER recogniser (reference model/recognizer/; csrc/aster.hip) ------------------------------------------------------------ */
+/* y (B,C,Ho,Wo contiguous) = F.interpolate(x, (Ho, Wo), mode="bilinear", align_corners=True) (recognizer_builder.py:77: the STN head
+ * reads the image squeezed to 32 x 64); x[b*xsn + c*xsc + h*xsh + w*xsw] */
+int tatt_resize_bilinear_ac(const float* x, long xsn, long xsc, long xsh, long xsw, float* y, int B, int C, int H, int W,
+                            int Ho, int Wo, hipStream_t st);
+/* tatt_grid_sample_fwd with an output size of its own: src (B, Ho*Wo, 2), out (B,Ho,Wo,C), x (B,C,H,W) by element strides
+ * (the recogniser rectifies its 32 x 128 input into 32 x 100: recognizer_builder.py:20-21,79) */
+int tatt_grid_sample_sized_fwd(const float* x, long xsn, long xsc, long xsh, long xsw, const float* src, float* out, int B,
+                               int C, int H, int W, int Ho, int Wo, hipStream_t st);
+/* y = relu(a + b): the tail of AsterBlock (resnet_aster.py:59-60), where the activation follows the residual sum */
+int tatt_add_relu(const float* a, const float* b, float* y, long n, hipStream_t st);
+/* one nn.GRU step from its projections: gi, gh (R, 3H) in gate order r|z|n, h (R, H) -> hout (R, H) (the decoder's step-by-step route) */
+int tatt_gru_cell(const float* gi, const float* gh, const float* h, float* hout, int R, int H, hipStream_t st);
+/* AttentionRecognitionHead (attention_recognition_head.py), all L steps in ONE launch, one work-group per image, no synchronisation
+ * between work-groups.  x, xproj (B,T,512): encoder features and xEmbed(x); WsT (512,512) = sEmbed.weight^T, bs; wv (512), wb (1): wEmbed;
+ * E2 (C+1, 1536) = tgt_embedding.weight W_ih[:, :512]^T + b_ih; WicT (512,1536) = W_ih[:, 512:]^T; WhhT (512,1536) = W_hh^T, bhh (1536);
+ * fcT (512, C) = fc.weight^T, fcb (C).
+ * mode 0 forced: y_prev from targets (B,L) int (clamped to [0, C]) -> logits (B,L,C);
+ * mode 1 greedy (`sample`): ids (B,L) int, scores (B,L) = the arg-max's softmax value; beyond a row's first EOS ids = eos, scores = 0;
+ * mode 2 beam (`beam_search`, beam = 5, backtracking included; candidates ordered by score descending, then flat index ascending):
+ *        ids = the best sequence per image, scores = 1.
+ * Takes T <= 32, 2 <= C <= 128 (5 <= C for the beam), L <= 100, sDim = attDim = xDim = 512; anything else returns 1. */
+int tatt_attn_decode(const float* x, const float* xproj, const float* WsT, const float* bs, const float* wv, const float* wb,
+                     const float* E2, const float* WicT, const float* WhhT, const float* bhh, const float* fcT,
+                     const float* fcb, const int* targets, float* logits, int* ids, float* scores, int B, int T, int C, int L,
+                     int sDim, int attDim, int xDim, int eos, int mode, int beam, hipStream_t st);
+/* the backtracking of `beam_search` alone (attention_recognition_head.py:127-187; tatt_attn_decode does it itself): stored decisions
+ * sym, pred (slot of the previous step), score, each (L, B, K), K <= 8 -> ids (B, L) of the best sequence per image; ws: B*L*K ints.
+ * Ties: score descending, then index ascending. */
+int tatt_beam_backtrack(const int* sym, const int* pred, const float* score, int* ids, int* ws, int L, int B, int K, int eos,
+                        hipStream_t st);
+
 #ifdef __cplusplus
 }
 #endif

@@ -3,6 +3,7 @@
     from tatt_amd import TSRN, TSRN_TL_TRANS      # drop-ins for the reference's model/tsrn.py classes
     from tatt_amd import TBSRN                    # drop-in for the reference's model/tbsrn.py class
     from tatt_amd import CRNN                     # drop-in for the reference's model/crnn/crnn.py text-prior generator
+    from tatt_amd import ASTER                    # drop-in for the reference's model/recognizer RecognizerBuilder (evaluation only)
 
 Host code is Python on PyTorch-ROCm (device memory, streams, autograd tape, torch.distributed/RCCL);
 all arithmetic of the path runs in hand-written HIP kernels (tatt_amd/csrc -> lib/libtatt_hip.so, C ABI in
@@ -11,9 +12,11 @@ include/tatt_hip.h).  No CPU fallback: see oracle/ for the CPU restatement used 
 from .tsrn import TSRN, TSRN_TL_TRANS  # noqa: F401
 from .tbsrn import TBSRN  # noqa: F401
 from .crnn import CRNN  # noqa: F401
+from .aster import ASTER  # noqa: F401
+from . import aster  # noqa: F401
 from . import torch_ops  # noqa: F401  (registers torch.ops.tatt_hip.*: the operator-registry view of the kernels)
 
-__all__ = ["TSRN", "TSRN_TL_TRANS", "TBSRN", "CRNN", "set_arithmetic", "get_arithmetic", "sync_check"]
+__all__ = ["TSRN", "TSRN_TL_TRANS", "TBSRN", "CRNN", "ASTER", "set_arithmetic", "get_arithmetic", "sync_check"]
 
 
 def set_arithmetic(mode: str) -> None:

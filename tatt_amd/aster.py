@@ -1,0 +1,515 @@
+"""The ASTER recogniser for evaluation (reference model/recognizer/: RecognizerBuilder = STN head + TPS rectification -> ResNet-45 +
+2 x BiLSTM -> attention decoder), the recogniser whose accuracy on the SR images is the headline column of the TATT / TextZoom tables.
+
+`ASTER` is a drop-in for the reference's `RecognizerBuilder` as the reference's eval loop uses it (`Aster_init`,
+interfaces/base.py:837-848): same keyword arguments, same `state_dict` keys and shapes (384 entries), seed for seed the same initial
+weights (sub-modules are constructed and initialised in the reference's order; torch.nn layers are parameter holders only), so a
+checkpoint saved by the reference loads with `load_state_dict(strict=True)`.
+
+EVAL ONLY.  `forward(input_dict)` in eval mode returns {'losses': {}, 'output': {'pred_rec', 'pred_rec_score'}}; the reference
+also runs a teacher-forced pass on dummy targets there and reports its cross entropy as `losses['loss_rec']`
+(recognizer_builder.py:94-96) -- nothing reads it, and it is NOT computed here.  In training mode `forward` raises: the decoder's
+backward and the sequence cross entropy are not part of this package.
+
+All arithmetic runs in HIP kernels (no CPU fallback).  Eval BatchNorm is folded into the preceding convolution / linear layer on the
+device (tatt_bn_fold); the convolutions are the shared implicit-GEMM kernels on strided views (a strided 1 x 1 convolution is a
+stride-1 one on a sub-sampled view); the BiLSTM layers are `infer.bilstm_eval` (one launch per layer); the attention decoder's
+`max_len_labels` steps are ONE launch (tatt_attn_decode, csrc/aster.hip), with `decode_eager` as the step-by-step route on the shared
+operators for geometries that launch refuses (and as the timing yardstick of tools/bench_aster.py).
+
+Early exit: a greedy row stops at its first EOS, and a beam whose five hypotheses have all ended only keeps its bookkeeping going.
+What `get_string_aster` reads -- the ids up to and including a row's first EOS -- equals the reference's; beyond a greedy row's
+first EOS the ids are EOS and the scores 0 (the reference goes on decoding there).  The beam returns every position as the reference
+does, and scores of 1.
+"""
+from __future__ import annotations
+
+import string
+
+import numpy as np
+import torch
+from torch import nn
+
+from . import functional as Fh
+from . import ops
+from ._lib import LIB
+from .ops import ACT_NONE, ACT_RELU, ACT_TANH
+from .tsrn import _Holder, STNHead, TPSSpatialTransformer
+
+TPS_INPUTSIZE = (32, 64)          # recognizer_builder.py:20-24
+TPS_OUTPUTSIZE = (32, 100)
+NUM_CONTROL_POINTS = 20
+TPS_MARGINS = (0.05, 0.05)
+BEAM_WIDTH = 5
+MODES = {"forced": 0, "greedy": 1, "beam": 2}
+
+DECODE_ONE_LAUNCH = True          # test / A-B hook: False -> `ASTER.decode` always takes `decode_eager`
+LAUNCHES = {"one_launch": 0, "eager": 0}      # how often each decoder route ran (tests, tools/bench_aster.py)
+
+
+# ---- the reference's helpers (interfaces/base.py:850-875, utils/labelmaps.py:6-30, utils/metrics.py:15-68) -------------------------
+def get_vocabulary(voc_type, EOS="EOS", PADDING="PADDING", UNKNOWN="UNKNOWN"):
+    voc = {"digit": string.digits, "lower": string.digits + string.ascii_lowercase, "upper": string.digits + string.ascii_letters,
+           "all": string.digits + string.ascii_letters + string.punctuation}
+    if voc_type not in voc:
+        raise KeyError("voc_type must be one of %s" % sorted(voc))
+    return list(voc[voc_type]) + [EOS, PADDING, UNKNOWN]
+
+
+class AsterInfo:
+    def __init__(self, voc_type="all"):
+        self.voc_type = voc_type
+        self.EOS, self.PADDING, self.UNKNOWN = "EOS", "PADDING", "UNKNOWN"
+        self.max_len = 100
+        self.voc = get_vocabulary(voc_type, EOS=self.EOS, PADDING=self.PADDING, UNKNOWN=self.UNKNOWN)
+        self.char2id = dict(zip(self.voc, range(len(self.voc))))
+        self.id2char = dict(zip(range(len(self.voc)), self.voc))
+        self.rec_num_classes = len(self.voc)
+
+
+def parse_aster_data(imgs):
+    """images in [0, 1] -> the recogniser's input range [-1, 1] (the reference also builds dummy targets for its unused loss)."""
+    return imgs * 2 - 1
+
+
+def get_string_aster(ids, info: AsterInfo):
+    """(B, L) class ids (tensor, array or lists) -> B strings: cut at the first EOS, UNKNOWN dropped, alphanumerics only, lower case."""
+    if torch.is_tensor(ids):
+        ids = ids.cpu().numpy()
+    end, unk = info.char2id[info.EOS], info.char2id[info.UNKNOWN]
+    keep = string.digits + string.ascii_letters
+    out = []
+    for row in np.asarray(ids):
+        chars = []
+        for i in row:
+            i = int(i)
+            if i == end:
+                break
+            if i != unk:
+                chars.append(info.id2char[i])
+        out.append("".join(ch for ch in chars if ch in keep).lower())
+    return out
+
+
+# ---- parameter holders (attribute names = the reference's => identical state_dict keys) --------------------------------------------
+class AsterBlock(_Holder):
+    def __init__(self, inplanes, planes, stride=(1, 1), downsample=None):
+        super().__init__()
+        self.conv1 = nn.Conv2d(inplanes, planes, kernel_size=1, stride=stride, bias=False)
+        self.bn1 = nn.BatchNorm2d(planes)
+        self.conv2 = nn.Conv2d(planes, planes, kernel_size=3, stride=1, padding=1, bias=False)
+        self.bn2 = nn.BatchNorm2d(planes)
+        self.downsample = downsample
+        self.stride = tuple(stride)
+
+
+class ResNet_ASTER(_Holder):
+    """reference resnet_aster.py:64-111 with its LSTM (the builder passes the arch string as `with_lstm`, which is truthy)."""
+
+    def __init__(self):
+        super().__init__()
+        self.layer0 = nn.Sequential(nn.Conv2d(3, 32, kernel_size=3, stride=1, padding=1, bias=False), nn.BatchNorm2d(32), nn.ReLU(inplace=True))
+        self.inplanes = 32
+        self.layer1 = self._make_layer(32, 3, (2, 2))
+        self.layer2 = self._make_layer(64, 4, (2, 2))
+        self.layer3 = self._make_layer(128, 6, (2, 1))
+        self.layer4 = self._make_layer(256, 6, (2, 1))
+        self.layer5 = self._make_layer(512, 3, (2, 1))
+        self.rnn = nn.LSTM(512, 256, bidirectional=True, num_layers=2, batch_first=True)
+        self.out_planes = 512
+        for m in self.modules():
+            if isinstance(m, nn.Conv2d):
+                nn.init.kaiming_normal_(m.weight, mode="fan_out", nonlinearity="relu")
+            elif isinstance(m, nn.BatchNorm2d):
+                nn.init.constant_(m.weight, 1)
+                nn.init.constant_(m.bias, 0)
+
+    def _make_layer(self, planes, blocks, stride):
+        downsample = nn.Sequential(nn.Conv2d(self.inplanes, planes, kernel_size=1, stride=stride, bias=False), nn.BatchNorm2d(planes))
+        layers = [AsterBlock(self.inplanes, planes, stride, downsample)]
+        self.inplanes = planes
+        layers += [AsterBlock(planes, planes) for _ in range(1, blocks)]
+        return nn.Sequential(*layers)
+
+
+class AttentionUnit(_Holder):
+    def __init__(self, sDim, xDim, attDim):
+        super().__init__()
+        self.sEmbed = nn.Linear(sDim, attDim)
+        self.xEmbed = nn.Linear(xDim, attDim)
+        self.wEmbed = nn.Linear(attDim, 1)
+
+
+class DecoderUnit(_Holder):
+    def __init__(self, sDim, xDim, yDim, attDim):
+        super().__init__()
+        self.attention_unit = AttentionUnit(sDim, xDim, attDim)
+        self.tgt_embedding = nn.Embedding(yDim + 1, attDim)              # the last row is <BOS>
+        self.gru = nn.GRU(input_size=xDim + attDim, hidden_size=sDim, batch_first=True)
+        self.fc = nn.Linear(sDim, yDim)
+
+
+class AttentionRecognitionHead(_Holder):
+    def __init__(self, num_classes, in_planes, sDim, attDim, max_len_labels):
+        super().__init__()
+        self.num_classes, self.in_planes, self.sDim, self.attDim, self.max_len_labels = num_classes, in_planes, sDim, attDim, max_len_labels
+        self.decoder = DecoderUnit(sDim=sDim, xDim=in_planes, yDim=num_classes, attDim=attDim)
+
+
+class _Layer1View:
+    """layer 1 of the two-layer nn.LSTM under the `_l0` names `infer.bilstm_eval` reads"""
+
+    def __init__(self, rnn):
+        for n in ("weight_ih", "weight_hh", "bias_ih", "bias_hh"):
+            setattr(self, n + "_l0", getattr(rnn, n + "_l1"))
+            setattr(self, n + "_l0_reverse", getattr(rnn, n + "_l1_reverse"))
+
+
+# ---- device entry points -----------------------------------------------------------------------------------------------------------
+def resize_bilinear_ac(x_nchw, size):
+    """F.interpolate(x, size, mode="bilinear", align_corners=True) of a (B, C, H, W) view -> contiguous (B, C, Ho, Wo)"""
+    ops._check_dev(x_nchw)
+    B, C, H, W = x_nchw.shape
+    out = ops.new(x_nchw, B, C, size[0], size[1])
+    ops.call("tatt_resize_bilinear_ac", ops.P(x_nchw), *x_nchw.stride(), ops.P(out), B, C, H, W, size[0], size[1], ops.stream())
+    return out
+
+
+def grid_sample_sized(x_nchw, src, size):
+    """F.grid_sample(x, 2 * clamp(src, 0, 1) - 1) with an output size of its own: x (B, C, H, W) view, src (B, Ho * Wo, 2) -> NHWC
+    (B, Ho, Wo, C)"""
+    ops._check_dev(x_nchw)
+    B, C, H, W = x_nchw.shape
+    assert tuple(src.shape) == (B, size[0] * size[1], 2) and src.is_contiguous()
+    out = ops.new(x_nchw, B, size[0], size[1], C)
+    ops.call("tatt_grid_sample_sized_fwd", ops.P(x_nchw), *x_nchw.stride(), ops.P(src), ops.P(out), B, C, H, W, size[0], size[1],
+             ops.stream())
+    return out
+
+
+def add_relu(a, b):
+    assert a.shape == b.shape and a.is_contiguous() and b.is_contiguous()
+    y = torch.empty_like(a)
+    ops.call("tatt_add_relu", ops.P(a), ops.P(b), ops.P(y), a.numel(), ops.stream())
+    return y
+
+
+def gru_cell(gi, gh, h):
+    R, H = h.shape
+    out = torch.empty_like(h)
+    ops.call("tatt_gru_cell", ops.P(gi), ops.P(gh), ops.P(h), ops.P(out), R, H, ops.stream())
+    return out
+
+
+def decoder_operands(head: AttentionRecognitionHead):
+    """What tatt_attn_decode reads, from the decoder's parameters: the transposed weights and E2 = tgt_embedding W_ih[:, :att]^T + b_ih
+    (step-invariant; one GEMM).  Built once per parameter set by `ASTER`; tests call it directly."""
+    du = head.decoder
+    au, gru = du.attention_unit, du.gru
+    att = head.attDim
+    C1 = du.tgt_embedding.weight.shape[0]
+    G = gru.weight_ih_l0.shape[0]
+    E2 = ops.new(gru.weight_ih_l0, C1, G)
+    W = gru.weight_ih_l0                              # (3 sDim, att + xDim): B(k, j) = W[j, k] for k < att
+    ops.gemm(du.tgt_embedding.weight, att, 1, W, 1, W.shape[1], E2, G, 1, C1, G, att, bias=gru.bias_ih_l0)
+    return {"WsT": au.sEmbed.weight.t().contiguous(), "bs": au.sEmbed.bias, "wv": au.wEmbed.weight.reshape(-1).contiguous(),
+            "wb": au.wEmbed.bias, "E2": E2, "WicT": W[:, att:].t().contiguous(), "WhhT": gru.weight_hh_l0.t().contiguous(),
+            "bhh": gru.bias_hh_l0, "fcT": du.fc.weight.t().contiguous(), "fcb": du.fc.bias}
+
+
+def _check_mode(head, mode, targets, x):
+    if mode not in (0, 1, 2):
+        raise ValueError("mode must be 0 (forced), 1 (greedy) or 2 (beam), got %r" % (mode,))
+    if mode == 0:
+        if targets is None or targets.dim() != 2 or targets.shape[0] != x.shape[0]:
+            raise ValueError("forced decoding needs targets of shape (B, L)")
+        return targets.shape[1]
+    return head.max_len_labels
+
+
+def attn_decode(head: AttentionRecognitionHead, x, mode, eos=0, targets=None, operands=None):
+    """The decoder in ONE launch (tatt_attn_decode): x (B, T, xDim) encoder features -> logits (B, L, C) [mode 0: y_prev from `targets`
+    (B, L)] or (ids (B, L) int32, scores (B, L)) [1: greedy `sample`, 2: `beam_search` with 5 beams].  None when the launch refuses the
+    geometry (the caller takes `decode_eager`)."""
+    ops._check_dev(x)
+    L = _check_mode(head, mode, targets, x)
+    B, T, D = x.shape
+    C = head.num_classes
+    du = head.decoder
+    xc = Fh._c(x)
+    if head.sDim != 512 or head.attDim != 512 or D != 512 or T > 32 or not 2 <= C <= 128 or L > 100 or (mode == 2 and C < 5):
+        return None                                   # (what the entry point itself refuses; asked first so that no operand is built)
+    op = operands if operands is not None else decoder_operands(head)
+    xproj = ops.linear_fwd(xc.reshape(B * T, D), du.attention_unit.xEmbed.weight, du.attention_unit.xEmbed.bias)
+    logits = ids = scores = tg = None
+    if mode == 0:
+        tg = targets.to(device=x.device, dtype=torch.int32).contiguous()
+        logits = ops.new(x, B, L, C)
+    else:
+        ids = torch.empty(B, L, dtype=torch.int32, device=x.device)
+        scores = ops.new(x, B, L)
+    rc = getattr(LIB, "tatt_attn_decode")(ops.P(xc), ops.P(xproj), ops.P(op["WsT"]), ops.P(op["bs"]), ops.P(op["wv"]), ops.P(op["wb"]),
+                                          ops.P(op["E2"]), ops.P(op["WicT"]), ops.P(op["WhhT"]), ops.P(op["bhh"]), ops.P(op["fcT"]),
+                                          ops.P(op["fcb"]), ops.P(tg), ops.P(logits), ops.P(ids), ops.P(scores), B, T, C, L, head.sDim,
+                                          head.attDim, D, int(eos), mode, BEAM_WIDTH, ops.stream())
+    if rc == 1:
+        return None
+    if rc != 0:
+        raise RuntimeError("tatt_attn_decode failed with code %d" % rc)
+    LAUNCHES["one_launch"] += 1
+    return logits if mode == 0 else (ids, scores)
+
+
+def beam_backtrack(sym, pred, score, eos):
+    """The backtracking of the reference's `beam_search` (attention_recognition_head.py:127-187) on stored decisions: sym, pred (L, B, K)
+    ints (pred: the slot of the previous step), score (L, B, K) -> (B, L) ids of the best sequence per image.  Ties: score descending,
+    then index ascending.  Host arrays, every image at once (the one loop runs over the L steps): the host statement of
+    tatt_beam_backtrack, which the step-by-step route runs on the device."""
+    L, B, K = sym.shape
+    sym, pred = np.asarray(sym, dtype=np.int64), np.asarray(pred, dtype=np.int64)
+    rows = np.arange(B)
+    col = rows[:, None]
+    order = np.argsort(-score[L - 1], axis=1, kind="stable")              # stable: equal scores keep ascending index
+    s = np.take_along_axis(score[L - 1], order, 1).copy()
+    tp = order
+    found = np.zeros(B, dtype=np.int64)
+    is_eos = sym == eos
+    any_eos = is_eos.any((1, 2))                                           # (L,)
+    p = np.empty((L, B, K), dtype=np.int64)
+    for t in range(L - 1, -1, -1):
+        cs = sym[t][col, tp]
+        tp = pred[t][col, tp]
+        if any_eos[t]:
+            # the reference walks a step's EOS slots from the last to the first and gives each the next replacement slot; at most K of
+            # them per image and step, so their slots are distinct and the writes are independent
+            m = is_eos[t]
+            after = np.cumsum(m[:, ::-1], 1)[:, ::-1] - m                 # EOS slots behind this one
+            bi, ji = np.nonzero(m)
+            rk = K - ((found[bi] + after[bi, ji]) % K) - 1
+            tp[bi, rk], cs[bi, rk], s[bi, rk] = pred[t, bi, ji], eos, score[t, bi, ji]
+            found += m.sum(1)
+        p[t] = cs
+    best = np.argsort(-s, axis=1, kind="stable")[:, 0]
+    return np.ascontiguousarray(p[:, rows, best].T).astype(np.int32)
+
+
+def decode_eager(head: AttentionRecognitionHead, x, mode, eos=0, targets=None):
+    """`attn_decode` step by step on the shared operators (about a dozen launches per step; torch does the beam's bookkeeping, one
+    launch its backtracking: tatt_beam_backtrack): the route for geometries the one launch refuses, and the timing yardstick.  Same
+    results, same tie rule, and like the one launch no host synchronisation."""
+    ops._check_dev(x)
+    L = _check_mode(head, mode, targets, x)
+    B, T, D = x.shape
+    C, sD, aD = head.num_classes, head.sDim, head.attDim
+    du = head.decoder
+    au, gru = du.attention_unit, du.gru
+    K = BEAM_WIDTH if mode == 2 else 1
+    R = B * K
+    dev = x.device
+    xc = Fh._c(x)
+    xproj = ops.linear_fwd(xc.reshape(B * T, D), au.xEmbed.weight, au.xEmbed.bias).view(B, T, aD)
+    xr = xc if K == 1 else xc.repeat_interleave(K, 0).contiguous()
+    xp_tr = (xproj if K == 1 else xproj.repeat_interleave(K, 0)).permute(1, 0, 2).contiguous().view(T * R, aD)     # row t * R + r
+    s = torch.zeros(R, sD, device=dev)
+    y = torch.full((R,), C, dtype=torch.long, device=dev)
+    seed = Fh.seed_tensor(dev)
+    if mode == 2:
+        seq = torch.full((B, K), float("-inf"), device=dev)
+        seq[:, 0] = 0.0
+        seq = seq.view(R)
+        pos = (torch.arange(B, device=dev) * K).view(B, 1)
+        st_sym, st_pred, st_score = [], [], []
+    outs, out_ids, out_scores = [], [], []
+    for i in range(L):
+        sproj = ops.linear_fwd(s, au.sEmbed.weight, au.sEmbed.bias)
+        th = ops.act_fwd(ops.add_rowbcast(xp_tr, sproj, R), ACT_TANH)
+        e = ops.new(x, R, T)
+        ops.gemm(th, aD, 1, au.wEmbed.weight, 1, 0, e, T, 1, R, 1, aD, bias=au.wEmbed.bias, Z=T, bsA=R * aD, bsC=1)
+        ops.call("tatt_softmax_rows_fwd", ops.P(e), None, R, T, 0.0, ops.P(seed), 0, ops.stream())
+        ctx = ops.new(x, R, D)
+        ops.gemm(e, T, 1, xr, D, 1, ctx, D, 1, 1, D, T, Z=R, bsA=T, bsB=T * D, bsC=D)
+        yproj = du.tgt_embedding.weight.index_select(0, y)
+        gi = ops.linear_fwd(yproj, gru.weight_ih_l0, gru.bias_ih_l0, x2b=ctx)
+        gh = ops.linear_fwd(s, gru.weight_hh_l0, gru.bias_hh_l0)
+        s = gru_cell(gi, gh, s)
+        logits = ops.linear_fwd(s, du.fc.weight, du.fc.bias)
+        if mode == 0:
+            outs.append(logits)
+            y = targets[:, i].to(dev).long().clamp(0, C)
+        elif mode == 1:
+            score, y = torch.softmax(logits, 1).max(1)
+            out_ids.append(y)
+            out_scores.append(score)
+        else:
+            cand = (seq.view(R, 1) + torch.log_softmax(logits, 1)).view(B, K * C)
+            val, idx = torch.sort(cand, dim=1, descending=True, stable=True)       # score descending, flat index ascending
+            val, idx = val[:, :K], idx[:, :K]
+            y = (idx % C).view(R)
+            local = idx // C
+            s = s.index_select(0, (local + pos).view(R))
+            st_sym.append(y.view(B, K))
+            st_pred.append(local)
+            st_score.append(val)
+            seq = val.reshape(R).masked_fill(y == eos, float("-inf"))
+    LAUNCHES["eager"] += 1
+    if mode == 0:
+        return torch.stack(outs, 1)
+    if mode == 1:
+        ids, scores = torch.stack(out_ids, 1), torch.stack(out_scores, 1)
+        is_eos = ids == eos
+        after = (is_eos.cumsum(1) - is_eos.long()) > 0                    # positions beyond the row's first EOS
+        return ids.masked_fill(after, eos).int(), scores.masked_fill(after, 0.0)
+    sym, pred, score = torch.stack(st_sym).int().contiguous(), torch.stack(st_pred).int().contiguous(), torch.stack(st_score).contiguous()
+    ids = torch.empty(B, L, dtype=torch.int32, device=dev)
+    ws = torch.empty(B, L, K, dtype=torch.int32, device=dev)
+    ops.call("tatt_beam_backtrack", ops.P(sym), ops.P(pred), ops.P(score), ops.P(ids), ops.P(ws), L, B, K, int(eos), ops.stream())
+    return ids, torch.ones(B, L, device=dev)
+
+
+# ---- the recogniser ----------------------------------------------------------------------------------------------------------------
+class ASTER(nn.Module):
+    """Drop-in for the reference's RecognizerBuilder (eval only; see the module docstring)."""
+
+    def __init__(self, arch="ResNet_ASTER", rec_num_classes=97, sDim=512, attDim=512, max_len_labels=100, eos=94, STN_ON=True):
+        super().__init__()
+        if arch != "ResNet_ASTER":
+            raise ValueError("tatt_amd.ASTER builds the reference's 'ResNet_ASTER' encoder only (its one arch), got arch=%r" % (arch,))
+        self.arch, self.rec_num_classes, self.sDim, self.attDim = arch, rec_num_classes, sDim, attDim
+        self.max_len_labels, self.eos, self.STN_ON = max_len_labels, eos, STN_ON
+        self.tps_inputsize = list(TPS_INPUTSIZE)
+        self.encoder = ResNet_ASTER()
+        self.decoder = AttentionRecognitionHead(num_classes=rec_num_classes, in_planes=self.encoder.out_planes, sDim=sDim, attDim=attDim,
+                                                max_len_labels=max_len_labels)
+        if STN_ON:
+            self.tps = TPSSpatialTransformer(output_image_size=TPS_OUTPUTSIZE, num_control_points=NUM_CONTROL_POINTS, margins=TPS_MARGINS)
+            self.stn_head = STNHead(in_planes=3, num_ctrlpoints=NUM_CONTROL_POINTS, activation="none")
+        self._prep = None
+        self.info = None              # optional AsterInfo: the vocabulary `io.evaluate` decodes with (None: the one with rec_num_classes classes)
+
+    # -- derived operands (folded filters, the decoder's transposed weights), rebuilt when a parameter or buffer changed.  A change is seen
+    # through the tensors' addresses and version counters: a write that bumps no counter (through `.data`, or by a kernel of this library)
+    # leaves the derived operands stale -- assign through `load_state_dict` / `copy_` / in-place torch operators.  The check walks all
+    # ~500 tensors, so `read` does it once and hands the result to its stages (`prep=`).
+    def _signature(self):
+        return tuple((t.data_ptr(), t._version) for t in list(self.parameters()) + list(self.buffers()))
+
+    def _prepared(self):
+        sig = self._signature()
+        if self._prep is None or self._prep["sig"] != sig:
+            from .infer import bn_fold
+            folds = {}
+
+            def fold(key, lin, bn):
+                w = lin.weight
+                folds[key] = bn_fold(w, lin.bias, bn)
+
+            fold("l0", self.encoder.layer0[0], self.encoder.layer0[1])
+            for li in range(1, 6):
+                for bi, blk in enumerate(getattr(self.encoder, "layer%d" % li)):
+                    fold((li, bi, 1), blk.conv1, blk.bn1)
+                    fold((li, bi, 2), blk.conv2, blk.bn2)
+                    if blk.downsample is not None:
+                        fold((li, bi, 0), blk.downsample[0], blk.downsample[1])
+            if self.STN_ON:
+                for i in (0, 2, 4, 6, 8, 10):
+                    fold(("stn", i), self.stn_head.stn_convnet[i][0], self.stn_head.stn_convnet[i][1])
+                fold("fc1", self.stn_head.stn_fc1[0], self.stn_head.stn_fc1[1])
+            operands = None
+            if self.sDim == 512 and self.attDim == 512 and 2 <= self.rec_num_classes <= 128:
+                operands = decoder_operands(self.decoder)
+            self._prep = {"sig": sig, "folds": folds, "operands": operands}
+        return self._prep
+
+    # -- the stages
+    def control_points(self, images, prep=None):
+        """images (B, 3, H, W) in [-1, 1] -> the STN head's control points (B, 20, 2) (stn_head.py:86-96 on the image squeezed to 32 x 64)"""
+        folds = (prep or self._prepared())["folds"]
+        h = resize_bilinear_ac(images, TPS_INPUTSIZE).permute(0, 2, 3, 1)
+        for i in (0, 2, 4, 6, 8, 10):
+            w, b = folds[("stn", i)]
+            h = ops.conv2d_forward(h, w, b, ACT_RELU)
+            if i != 10:
+                h = ops.maxpool_fwd(h, 2, 2)
+        B = h.shape[0]
+        h = ops.to_contiguous(h.permute(0, 3, 1, 2)).reshape(B, -1)          # x.view(B, -1) of the NCHW map
+        w, b = folds["fc1"]
+        feat = ops.linear_fwd(h, w, b, act=ACT_RELU)
+        fc2 = self.stn_head.stn_fc2
+        return ops.linear_fwd(ops.axpby(feat, None, 0.1, 0.0), fc2.weight, fc2.bias).reshape(B, NUM_CONTROL_POINTS, 2)
+
+    def rectify(self, images, ctrl=None, prep=None):
+        """-> the rectified image, NHWC (B, 32, 100, 3) (tps_spatial_transformer.py:100-115)"""
+        ctrl = self.control_points(images, prep) if ctrl is None else ctrl
+        src = ops.tps_grid_fwd(Fh._c(ctrl), self.tps.inverse_kernel, self.tps.padding_matrix, self.tps.target_coordinate_repr)
+        return grid_sample_sized(images, src, TPS_OUTPUTSIZE)
+
+    def encode(self, x_nhwc, prep=None):
+        """ResNet-45 + 2 x BiLSTM on an NHWC image view (B, 32, W, 3) -> features (B, W / 4, 512)"""
+        folds = (prep or self._prepared())["folds"]
+        w, b = folds["l0"]
+        h = ops.conv2d_forward(x_nhwc, w, b, ACT_RELU)
+        for li in range(1, 6):
+            for bi, blk in enumerate(getattr(self.encoder, "layer%d" % li)):
+                sh, sw = blk.stride
+                xin = h[:, ::sh, ::sw, :] if (sh, sw) != (1, 1) else h
+                w, b = folds[(li, bi, 1)]
+                o = ops.conv2d_forward(xin, w, b, ACT_RELU)
+                w, b = folds[(li, bi, 2)]
+                o = ops.conv2d_forward(o, w, b, ACT_NONE)
+                if blk.downsample is not None:
+                    w, b = folds[(li, bi, 0)]
+                    res = ops.conv2d_forward(xin, w, b, ACT_NONE)
+                else:
+                    res = h
+                h = add_relu(o, res)
+        B, Hh, Wd, Cc = h.shape
+        if Hh != 1:
+            raise ValueError("tatt_amd.ASTER reads images 32 pixels high (the feature map must be one row high, got %d)" % Hh)
+        seq = Fh._c(h.reshape(B, Wd, Cc).permute(1, 0, 2))                     # time-major for the LSTM kernels
+        rnn = self.encoder.rnn
+        seq = infer_bilstm(seq, rnn)
+        seq = infer_bilstm(seq, _Layer1View(rnn))
+        return Fh._c(seq.permute(1, 0, 2))
+
+    def features(self, images, prep=None):
+        _require(images)
+        prep = prep or self._prepared()
+        x = self.rectify(images, prep=prep) if self.STN_ON else images.permute(0, 2, 3, 1)
+        return self.encode(x, prep)
+
+    def decode(self, feats, decode="beam", targets=None, prep=None):
+        mode = MODES[decode]
+        out = None
+        if DECODE_ONE_LAUNCH:
+            out = attn_decode(self.decoder, feats, mode, self.eos, targets, operands=(prep or self._prepared())["operands"])
+        if out is None:
+            out = decode_eager(self.decoder, feats, mode, self.eos, targets)
+        return out
+
+    @torch.no_grad()
+    def read(self, images, decode="beam"):
+        """images (B, 3, 32, 128) in [-1, 1] (`parse_aster_data`) on the GPU -> (ids (B, L) int32, scores (B, L) fp32) on the device, no
+        host synchronisation (on the one launch and on the step-by-step route alike).  decode: "beam" = beam_search(x, 5, eos), "greedy" = the
+        reference's `sample`."""
+        if decode not in ("beam", "greedy"):
+            raise ValueError("decode must be 'beam' or 'greedy', got %r" % (decode,))
+        prep = self._prepared()
+        return self.decode(self.features(images, prep), decode, prep=prep)
+
+    def forward(self, input_dict):
+        if self.training:
+            raise NotImplementedError("tatt_amd.ASTER is an evaluation recogniser: the decoder's backward and the sequence cross entropy "
+                                      "are not implemented; call .eval() (training ASTER needs the reference)")
+        ids, scores = self.read(input_dict["images"], "beam")
+        return {"losses": {}, "output": {"pred_rec": ids, "pred_rec_score": scores}}
+
+
+def infer_bilstm(seq, rnn):
+    from .infer import bilstm_eval
+    return bilstm_eval(seq, rnn)
+
+
+def _require(x):
+    if not x.is_cuda:
+        raise RuntimeError("tatt_amd: inputs must be on an AMD GPU (x.device=%s); the product path has no CPU fallback (the CPU "
+                           "restatement lives in tests/ and is test infrastructure)." % x.device)

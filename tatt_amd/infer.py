@@ -210,6 +210,13 @@ class _Fold:
         bn_fold(self.conv.weight, self.conv.bias, self.bn, self.w, self.b)
 
 
+def _refuse_aster(m, who):
+    from .aster import ASTER
+    if isinstance(m, ASTER):
+        raise TypeError("%s: an ASTER recogniser is not captured into a session (its attention decoder is not graph-captured); evaluate "
+                        "with tatt_amd.io.evaluate(model, batches, recognizer=<ASTER>), which reads SR / LR / HR with it" % who)
+
+
 def _check_module(m, what):
     if m is None:
         return
@@ -283,6 +290,7 @@ class InferenceSession:
                  voc_type: str = "lower", full_metrics: bool = False):
         from .tsrn import TSRN, TSRN_TL_TRANS
         from .tbsrn import TBSRN
+        _refuse_aster(recognizer, "InferenceSession")
         _check_module(generator, "generator")
         _check_module(prior, "prior CRNN")
         _check_module(recognizer, "recogniser CRNN")
@@ -664,6 +672,7 @@ def evaluate_session(generator, batches: Iterable, prior=None, recognizer=None, 
     bicubic baseline, tatt_bicubic_resize of LR against HR) and, with a recogniser, 'ned' / 'ned_lr' / 'ned_hr' (mean normalised edit
     distance of the SR / LR / HR decodings, tatt_ctc_greedy_score in place of the match launch) and 'ned_skipped' (images whose
     filtered label has more than LABEL_CAP = 64 characters: the means leave them out).  Sessions of the two modes are kept apart."""
+    _refuse_aster(recognizer, "evaluate_session")
     return evaluate_session_async(generator, batches, prior, recognizer, voc_type, sessions, export, full_metrics).result()
 
 
@@ -763,6 +772,7 @@ class SuperResolver:
     def __init__(self, generator, prior=None, recognizer=None, batch_size: int = 48, lr_size=(16, 64), mask: bool = True,
                  rule: str = "floor", keep_sr: bool = False, long_lines: bool = False, stride: int = 32, reader=None):
         from .io import DeviceCollator, DeviceExporter
+        _refuse_aster(recognizer, "SuperResolver")
         _check_module(generator, "generator")
         _check_module(prior, "prior CRNN")
         _check_module(recognizer, "recogniser CRNN")

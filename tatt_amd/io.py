@@ -308,9 +308,14 @@ def evaluate(model: torch.nn.Module, batches: Iterable, prior_fn=None, recognize
     F.interpolate(images_lr, hr_size, mode="bicubic") against HR (:1417-1418,1452), and with a recogniser 'ned' / 'ned_lr' / 'ned_hr',
     the mean of edit_distance(pred, label) / (max(len(pred), len(label)) + 1e-10) over the images (:1531-1556,1633-1635; both
     strings through str_filt), and 'ned_skipped': the images whose filtered label has more than LABEL_CAP characters, which the
-    means leave out (the same rule as the device path, `infer.evaluate_session`)."""
+    means leave out (the same rule as the device path, `infer.evaluate_session`).
+    A `tatt_amd.ASTER` recogniser (--test_model ASTER) is read through parse_aster_data, beam search and get_string_aster instead and
+    returns the same keys (`_evaluate_aster`: the ids stay on the device, one copy at the end)."""
     from .losses import SSIM, calculate_psnr
     from .crnn import bicubic_resize, parse_crnn_data
+    from .aster import ASTER
+    if isinstance(recognizer, ASTER):
+        return _evaluate_aster(model, batches, prior_fn, recognizer, voc_type, full_metrics)
     was_training = model.training
     model.eval()
     ssim = SSIM()
@@ -361,6 +366,78 @@ def evaluate(model: torch.nn.Module, batches: Iterable, prior_fn=None, recognize
         if full_metrics:
             res.update(ned=ned["sr"] / (n_scored + 1e-10), ned_lr=ned["lr"] / (n_scored + 1e-10), ned_hr=ned["hr"] / (n_scored + 1e-10),
                        ned_skipped=n_skipped)
+    return res
+
+
+@torch.no_grad()
+def _evaluate_aster(model, batches, prior_fn, recognizer, voc_type, full_metrics):
+    """`evaluate` with an ASTER recogniser (the reference's --test_model ASTER: parse_aster_data -> beam search -> get_string_aster, both
+    strings through str_filt; interfaces/super_resolution.py:1374-1396).  The ids of every batch stay on the device; ONE copy at the end
+    brings them and the image metrics back, and the strings are decoded on the host from it."""
+    from .losses import SSIM, calculate_psnr
+    from .crnn import bicubic_resize
+    from .aster import AsterInfo, get_string_aster, parse_aster_data
+    info = getattr(recognizer, "info", None)
+    if info is None:
+        voc = {13: "digit", 39: "lower", 65: "upper", 97: "all"}.get(recognizer.rec_num_classes)
+        if voc is None:
+            raise ValueError("io.evaluate: no vocabulary has %d classes (digit 13, lower 39, upper 65, all 97); set recognizer.info to "
+                             "the AsterInfo it was trained with" % recognizer.rec_num_classes)
+        info = AsterInfo(voc)
+    elif info.rec_num_classes != recognizer.rec_num_classes:
+        raise ValueError("io.evaluate: recognizer.info has %d classes, the recogniser %d" % (info.rec_num_classes, recognizer.rec_num_classes))
+    was_training, rec_was_training = model.training, recognizer.training
+    model.eval()
+    recognizer.eval()
+    ssim = SSIM()
+    dev = next(model.parameters()).device
+    sums = torch.zeros(4, device=dev)                  # psnr, ssim, psnr_lr, ssim_lr
+    n = 0
+    ids, all_labels = {"sr": [], "lr": [], "hr": []}, []
+    for batch in batches:
+        lr, hr = batch[0], batch[1]
+        tp = batch[2] if len(batch) > 2 and batch[2] is not None else (prior_fn(lr) if prior_fn is not None else None)
+        labels = batch[3] if len(batch) > 3 else None
+        out = model(lr, tp) if tp is not None else model(lr)
+        sr = out[0] if isinstance(out, tuple) else out
+        sums[0] += calculate_psnr(sr[:, :3], hr[:, :3])
+        sums[1] += ssim(sr[:, :3], hr[:, :3])
+        if full_metrics:
+            up = bicubic_resize(lr[:, :3], hr.shape[-2:])
+            sums[2] += calculate_psnr(up, hr[:, :3])
+            sums[3] += ssim(up, hr[:, :3])
+        n += 1
+        if labels is not None:
+            for name, img in (("sr", sr), ("lr", lr), ("hr", hr)):
+                ids[name].append(recognizer.read(parse_aster_data(img[:, :3]), "beam")[0])
+            all_labels += list(labels)
+    model.train(was_training)
+    recognizer.train(rec_was_training)
+    L = recognizer.max_len_labels
+    flat = [t.reshape(-1) for k in ("sr", "lr", "hr") for t in ids[k]]
+    host = torch.cat(flat + [sums.view(torch.int32)]).cpu()                    # the evaluation's one host synchronisation
+    s4 = host[-4:].view(torch.float32).tolist()
+    res = {"psnr": s4[0] / max(n, 1), "ssim": s4[1] / max(n, 1), "n_batches": n}
+    if full_metrics:
+        res.update(psnr_lr=s4[2] / max(n, 1), ssim_lr=s4[3] / max(n, 1))
+    n_img = len(all_labels)
+    if n_img:
+        want = [str_filt(t, voc_type) for t in all_labels]
+        scored = [len(t) <= LABEL_CAP for t in want]
+        acc, ned = {}, {}
+        off = 0
+        for name in ("sr", "lr", "hr"):
+            rows = host[off:off + n_img * L].view(n_img, L)
+            off += n_img * L
+            pred = [str_filt(p, voc_type) for p in get_string_aster(rows, info)]
+            acc[name] = sum(p == t for p, t in zip(pred, want))
+            ned[name] = sum(edit_distance(p, t) / (max(len(p), len(t)) + 1e-10) for p, t, ok in zip(pred, want, scored) if ok)
+        res.update(accuracy=round(acc["sr"] / n_img, 4), accuracy_lr=round(acc["lr"] / n_img, 4), accuracy_hr=round(acc["hr"] / n_img, 4),
+                   n_images=n_img)
+        if full_metrics:
+            n_scored = sum(scored)
+            res.update(ned=ned["sr"] / (n_scored + 1e-10), ned_lr=ned["lr"] / (n_scored + 1e-10), ned_hr=ned["hr"] / (n_scored + 1e-10),
+                       ned_skipped=len(scored) - n_scored)
     return res
 
 
