@@ -10,7 +10,11 @@ Every decoding also returns, per row, its smallest DECISION MARGIN -- how far th
   beam:   the smallest gap between a selected and an unselected candidate score at any step, and between the final first and second
           sequence score.  Gaps between two candidates at -inf (ended beams, which the tie rule orders) are not gaps of the arithmetic
           and are left out.
-A test compares ids only on rows whose margin exceeds its bound."""
+A test compares ids only on rows whose margin exceeds its bound.
+
+Further down: the front (squeeze, STN head, TPS grid, sampler) and the encoder (ResNet-45, 2 x BiLSTM) restated stage by stage in plain
+torch on the CPU with the number format as a parameter (`stn_in`, `ctrl`, `src`, `rect`, `feats`), pinned by tests/test_aster.py against
+the arrays the reference recorded."""
 import numpy as np
 import torch
 
@@ -260,6 +264,137 @@ def e2e_model(cls, **kw):
     m = cls(**kw)
     scale_fc(perturb(m, PERTURB_SEED))
     return shift_eos(m, kw["eos"], E2E_EOS_SHIFT)
+
+
+# ---- the front and the encoder (reference recognizer_builder.py:74-82, stn_head.py:86-96, tps_spatial_transformer.py:100-115,
+# resnet_aster.py:49-61,113-133), restated on the CPU with the number format as a parameter.  Parameters come from a state_dict of the
+# recogniser and are cast to `dtype`, which is what the reference's own `.double()` run does with them. ---------------------------------
+TPS_IN, TPS_OUT, BN_EPS = (32, 64), (32, 100), 1e-5
+ENC_STRIDES = {1: (2, 2), 2: (2, 2), 3: (2, 1), 4: (2, 1), 5: (2, 1)}          # the first block of layer<k>: stride of conv1 and downsample
+ENC_BLOCKS = {1: 3, 2: 4, 3: 6, 4: 6, 5: 3}
+STAGES = ("stn_in", "ctrl", "src", "rect", "feats")
+
+
+def _params(sd, dtype):
+    return lambda k: sd[k].detach().cpu().to(dtype)
+
+
+def batch_norm_eval(x, mean, var, gamma, beta, eps=BN_EPS):
+    """eval BatchNorm over dimension 1 of x (B, C, ...)"""
+    shape = (1, -1) + (1,) * (x.dim() - 2)
+    return (x - mean.view(shape)) / torch.sqrt(var.view(shape) + eps) * gamma.view(shape) + beta.view(shape)
+
+
+def _bn(g, prefix, x):
+    return batch_norm_eval(x, g(prefix + ".running_mean"), g(prefix + ".running_var"), g(prefix + ".weight"), g(prefix + ".bias"))
+
+
+def stn_in(images, dtype=torch.float64):
+    """the image squeezed to the STN head's 32 x 64: bilinear, align_corners=True"""
+    return torch.nn.functional.interpolate(images.detach().cpu().to(dtype), TPS_IN, mode="bilinear", align_corners=True)
+
+
+def ctrl(sd, x, dtype=torch.float64):
+    """STN head on the squeezed image x (B, 3, 32, 64) -> control points (B, 20, 2)"""
+    g = _params(sd, dtype)
+    h = x.detach().cpu().to(dtype)
+    for i in (0, 2, 4, 6, 8, 10):
+        p = "stn_head.stn_convnet.%d" % i
+        h = torch.nn.functional.conv2d(h, g(p + ".0.weight"), g(p + ".0.bias"), padding=1)
+        h = torch.relu(_bn(g, p + ".1", h))
+        if i != 10:
+            h = torch.nn.functional.max_pool2d(h, 2, 2)
+    h = h.reshape(h.shape[0], -1)                                         # (channel, row, column) order
+    h = h @ g("stn_head.stn_fc1.0.weight").t() + g("stn_head.stn_fc1.0.bias")
+    h = torch.relu(_bn(g, "stn_head.stn_fc1.1", h))
+    h = (0.1 * h) @ g("stn_head.stn_fc2.weight").t() + g("stn_head.stn_fc2.bias")
+    return h.reshape(h.shape[0], -1, 2)
+
+
+def src(sd, ctrl_pts, dtype=torch.float64, inverse_kernel=None):
+    """sampling positions (B, 32 * 100, 2) in [0, 1] image coordinates: repr @ (inverse_kernel @ [ctrl; padding])"""
+    g = _params(sd, dtype)
+    inv = g("tps.inverse_kernel") if inverse_kernel is None else torch.as_tensor(inverse_kernel).to(dtype)
+    c = ctrl_pts.detach().cpu().to(dtype)
+    Y = torch.cat([c, g("tps.padding_matrix").expand(c.shape[0], 3, 2)], 1)
+    return g("tps.target_coordinate_repr") @ (inv @ Y)
+
+
+def sample(images, grid01, size, dtype=torch.float64):
+    """bilinear sampling at positions in [0, 1] (clamped), zero padding, align_corners=False -> (B, C, size[0], size[1])"""
+    x = images.detach().cpu().to(dtype)
+    grid = 2.0 * grid01.detach().cpu().to(dtype).clamp(0, 1) - 1.0
+    return torch.nn.functional.grid_sample(x, grid.view(x.shape[0], size[0], size[1], 2), mode="bilinear", padding_mode="zeros",
+                                           align_corners=False)
+
+
+def rect(images, src_pts, dtype=torch.float64):
+    """the rectified image (B, 3, 32, 100)"""
+    return sample(images, src_pts, TPS_OUT, dtype)
+
+
+def lstm_layer(x, wih, whh, bih, bhh, reverse=False):
+    """one direction of an LSTM layer, x (B, T, I) -> (B, T, H); gate order i | f | g | o"""
+    B, T, _ = x.shape
+    H = whh.shape[1]
+    h, c = x.new_zeros(B, H), x.new_zeros(B, H)
+    gi = x @ wih.t() + bih
+    out = [None] * T
+    for t in (range(T - 1, -1, -1) if reverse else range(T)):
+        a = gi[:, t] + h @ whh.t() + bhh
+        i, f, gg, o = torch.sigmoid(a[:, :H]), torch.sigmoid(a[:, H:2 * H]), torch.tanh(a[:, 2 * H:3 * H]), torch.sigmoid(a[:, 3 * H:])
+        c = f * c + i * gg
+        h = o * torch.tanh(c)
+        out[t] = h
+    return torch.stack(out, 1)
+
+
+def bilstm(g, prefix, x, layers=2):
+    for l in range(layers):
+        w = lambda n, sfx: g("%s.%s_l%d%s" % (prefix, n, l, sfx))
+        x = torch.cat([lstm_layer(x, w("weight_ih", sfx), w("weight_hh", sfx), w("bias_ih", sfx), w("bias_hh", sfx), reverse=bool(sfx))
+                       for sfx in ("", "_reverse")], 2)
+    return x
+
+
+def encoder_maps(sd, x, dtype=torch.float64):
+    """ResNet-45 on the rectified image (B, 3, 32, W) -> its last map (B, 512, 1, W / 4)"""
+    g = _params(sd, dtype)
+    conv = torch.nn.functional.conv2d
+    h = x.detach().cpu().to(dtype)
+    h = torch.relu(_bn(g, "encoder.layer0.1", conv(h, g("encoder.layer0.0.weight"), padding=1)))
+    for li in range(1, 6):
+        for bi in range(ENC_BLOCKS[li]):
+            p = "encoder.layer%d.%d" % (li, bi)
+            stride = ENC_STRIDES[li] if bi == 0 else (1, 1)
+            o = torch.relu(_bn(g, p + ".bn1", conv(h, g(p + ".conv1.weight"), stride=stride)))
+            o = _bn(g, p + ".bn2", conv(o, g(p + ".conv2.weight"), padding=1))
+            res = _bn(g, p + ".downsample.1", conv(h, g(p + ".downsample.0.weight"), stride=stride)) if bi == 0 else h
+            h = torch.relu(o + res)
+    return h
+
+
+def feats(sd, x, dtype=torch.float64):
+    """encoder features (B, W / 4, 512): ResNet-45, then the two-layer bidirectional LSTM over the columns"""
+    h = encoder_maps(sd, x, dtype)
+    assert h.shape[2] == 1
+    return bilstm(_params(sd, dtype), "encoder.rnn", h[:, :, 0, :].transpose(1, 2))
+
+
+def front(sd, images, dtype=torch.float64, inverse_kernel=None):
+    """squeeze -> STN head -> TPS grid -> sampler, each stage on the one before -> {stage: tensor} for STAGES[:4]"""
+    out = {"stn_in": stn_in(images, dtype)}
+    out["ctrl"] = ctrl(sd, out["stn_in"], dtype)
+    out["src"] = src(sd, out["ctrl"], dtype, inverse_kernel)
+    out["rect"] = rect(images, out["src"], dtype)
+    return out
+
+
+def front_and_encoder(sd, images, dtype=torch.float64, inverse_kernel=None):
+    """the chain as the recogniser runs it -> {stage: tensor} for STAGES"""
+    out = front(sd, images, dtype, inverse_kernel)
+    out["feats"] = feats(sd, out["rect"], dtype)
+    return out
 
 
 def margin_bound(ref_err, maxabs):

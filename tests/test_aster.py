@@ -110,6 +110,26 @@ def test_restatement_reproduces_the_reference_recogniser(e2e):
     assert np.abs(lg - e2e["forced_logits"]).max() <= 1.0001 * float(e2e["err_forced"])
 
 
+def test_restatement_reproduces_the_reference_front_and_encoder(e2e):
+    """The float64 restatement of the front and the encoder (aster_ref.stn_in / ctrl / src / rect / feats) on the fixture's images, with
+    the recorded TPS kernel inverse cast to float64: each stage within err_<stage> + 1e-9 x max |value| of the fp32 array the reference
+    recorded.  err_<stage> is the distance of exactly that array from the reference's own `.double()` run on the same doubled state
+    (tools/gen_golden_aster.py), and a correct restatement is that run -- the bound is derived, not chosen."""
+    m = R.e2e_model(tatt_amd.ASTER, **KW)
+    got = R.front_and_encoder(m.state_dict(), torch.from_numpy(e2e["images"]), torch.float64, inverse_kernel=e2e["tps_inverse_kernel"])
+    assert tuple(got["feats"].shape) == (3, 25, 512) and got["feats"].dtype == torch.float64
+    worst = []
+    for name in R.STAGES:
+        want = e2e[name].astype(np.float64)
+        dist = float(np.abs(got[name].numpy() - want).max())
+        bound = float(e2e["err_" + name]) + 1e-9 * float(np.abs(want).max())
+        print("restatement vs recorded fp32 %-6s: distance %.6e, recorded err_%s %.6e, bound %.6e" % (name, dist, name,
+                                                                                                       float(e2e["err_" + name]), bound))
+        worst.append((name, dist, bound))
+    for name, dist, bound in worst:
+        assert dist <= bound, (name, dist, bound)
+
+
 def test_all_beams_can_end(dec):
     """`end_all_beams` does what the GPU tests rely on: every hypothesis of every image has ended well before L"""
     for eos in (36, 0):
