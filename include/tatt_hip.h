@@ -989,6 +989,28 @@ int tatt_attn_decode(const float* x, const float* xproj, const float* WsT, const
 int tatt_beam_backtrack(const int* sym, const int* pred, const float* score, int* ids, int* ws, int L, int B, int K, int eos,
                         hipStream_t st);
 
+/* ---- the MORAN recogniser (reference model/moran/; csrc/moran.hip) ------------------------------------------------------------------ */
+/* The tail of the MORN rectifier in ONE launch (morn.py:62-69 for the first pass, :76-82 for the second).  o (B,h,w): the offsets
+ * network's output.  Per output pixel of the Ho x Wo regular grid (the reference's fp32 grid: float64 arange * 2 / (n - 1) - 1 rounded
+ * once): g = grid_sample(maxpool_{2,1}(relu(o)) - maxpool_{2,1}(relu(-o)), grid); acc (B,Ho,Wo) = g if `first` else acc + g;
+ * out (B,Ho,Wo,C) = grid_sample(x, (gx, gy + acc)), x (B,C,H,W) read as x[b*xsn + c*xsc + y*xsh + x*xsw].  Both samplers are bilinear,
+ * zeros padding, align_corners=False (how the installed torch runs the reference's calls).
+ * Returns 1 for h < 2, w < 2, C > 4, h * w > 4096, Ho < 2 or Wo < 2. */
+int tatt_morn_rectify(const float* o, int h, int w, float* acc, int first, const float* x, long xsn, long xsc, long xsh,
+                      long xsw, float* out, int B, int C, int H, int W, int Ho, int Wo, hipStream_t st);
+/* One direction of the ASRN attention decoder (asrn_res.py:39-65 the cell, :127-155 the test-mode loop), all L steps in ONE launch, one
+ * work-group per image, no synchronisation between work-groups.  feats, fproj (B,T,256): encoder features and i2h(feats);
+ * WhT (256,256) = h2h.weight^T, bh (256); wv (256) = score.weight; E2 (C+1, 768) = char_embeddings W_ih[:, 256:]^T + b_ih;
+ * WicT (256,768) = W_ih[:, :256]^T (the context comes first in the GRU input); WhhT (256,768) = W_hh^T, bhh (768);
+ * genT (256, C) = generator.weight^T, genb (C).  The embedding row of step 0 is 0 (greedy) or targets[b, 0] (forced).
+ * mode 0 forced: the embedding row of step i is targets[b, i] (B,L) int, clamped to [0, C] -> logits (B,L,C);
+ * mode 1 greedy: y = argmax + 1, ties to the lower class, no stop at '$' -> logits (B,L,C) and ids (B,L) int.
+ * Takes H = 256 (hidden = feature = embedding size), T <= 32, 2 <= C <= 64, L <= 64; anything else returns 1. */
+int tatt_moran_decode(const float* feats, const float* fproj, const float* WhT, const float* bh, const float* wv,
+                      const float* E2, const float* WicT, const float* WhhT, const float* bhh, const float* genT,
+                      const float* genb, const int* targets, float* logits, int* ids, int B, int T, int C, int L, int H,
+                      int mode, hipStream_t st);
+
 #ifdef __cplusplus
 }
 #endif

@@ -4,6 +4,7 @@
     from tatt_amd import TBSRN                    # drop-in for the reference's model/tbsrn.py class
     from tatt_amd import CRNN                     # drop-in for the reference's model/crnn/crnn.py text-prior generator
     from tatt_amd import ASTER                    # drop-in for the reference's model/recognizer RecognizerBuilder (evaluation only)
+    from tatt_amd import MORAN                    # drop-in for the reference's model/moran MORAN (evaluation only)
 
 Host code is Python on PyTorch-ROCm (device memory, streams, autograd tape, torch.distributed/RCCL);
 all arithmetic of the path runs in hand-written HIP kernels (tatt_amd/csrc -> lib/libtatt_hip.so, C ABI in
@@ -14,9 +15,11 @@ from .tbsrn import TBSRN  # noqa: F401
 from .crnn import CRNN  # noqa: F401
 from .aster import ASTER  # noqa: F401
 from . import aster  # noqa: F401
+from .moran import MORAN  # noqa: F401
+from . import moran  # noqa: F401
 from . import torch_ops  # noqa: F401  (registers torch.ops.tatt_hip.*: the operator-registry view of the kernels)
 
-__all__ = ["TSRN", "TSRN_TL_TRANS", "TBSRN", "CRNN", "ASTER", "set_arithmetic", "get_arithmetic", "sync_check"]
+__all__ = ["TSRN", "TSRN_TL_TRANS", "TBSRN", "CRNN", "ASTER", "MORAN", "set_arithmetic", "get_arithmetic", "sync_check"]
 
 
 def set_arithmetic(mode: str) -> None:

@@ -217,6 +217,14 @@ def _refuse_aster(m, who):
                         "with tatt_amd.io.evaluate(model, batches, recognizer=<ASTER>), which reads SR / LR / HR with it" % who)
 
 
+def _refuse_moran(m, who):
+    from .moran import MORAN
+    if isinstance(m, MORAN):
+        raise TypeError("%s: a MORAN recogniser is not captured into a session (its rectifier and attention decoder are not "
+                        "graph-captured); evaluate with tatt_amd.io.evaluate(model, batches, recognizer=<MORAN>), which reads SR / LR / HR "
+                        "with it" % who)
+
+
 def _check_module(m, what):
     if m is None:
         return
@@ -291,6 +299,7 @@ class InferenceSession:
         from .tsrn import TSRN, TSRN_TL_TRANS
         from .tbsrn import TBSRN
         _refuse_aster(recognizer, "InferenceSession")
+        _refuse_moran(recognizer, "InferenceSession")
         _check_module(generator, "generator")
         _check_module(prior, "prior CRNN")
         _check_module(recognizer, "recogniser CRNN")
@@ -673,6 +682,7 @@ def evaluate_session(generator, batches: Iterable, prior=None, recognizer=None, 
     distance of the SR / LR / HR decodings, tatt_ctc_greedy_score in place of the match launch) and 'ned_skipped' (images whose
     filtered label has more than LABEL_CAP = 64 characters: the means leave them out).  Sessions of the two modes are kept apart."""
     _refuse_aster(recognizer, "evaluate_session")
+    _refuse_moran(recognizer, "evaluate_session")
     return evaluate_session_async(generator, batches, prior, recognizer, voc_type, sessions, export, full_metrics).result()
 
 
@@ -773,6 +783,7 @@ class SuperResolver:
                  rule: str = "floor", keep_sr: bool = False, long_lines: bool = False, stride: int = 32, reader=None):
         from .io import DeviceCollator, DeviceExporter
         _refuse_aster(recognizer, "SuperResolver")
+        _refuse_moran(recognizer, "SuperResolver")
         _check_module(generator, "generator")
         _check_module(prior, "prior CRNN")
         _check_module(recognizer, "recogniser CRNN")

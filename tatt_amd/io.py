@@ -310,12 +310,16 @@ def evaluate(model: torch.nn.Module, batches: Iterable, prior_fn=None, recognize
     strings through str_filt), and 'ned_skipped': the images whose filtered label has more than LABEL_CAP characters, which the
     means leave out (the same rule as the device path, `infer.evaluate_session`).
     A `tatt_amd.ASTER` recogniser (--test_model ASTER) is read through parse_aster_data, beam search and get_string_aster instead and
-    returns the same keys (`_evaluate_aster`: the ids stay on the device, one copy at the end)."""
+    returns the same keys (`_evaluate_aster`: the ids stay on the device, one copy at the end).  A `tatt_amd.MORAN` recogniser
+    (--test_model MORAN) is read through parse_moran_data, 20 greedy steps of the L2R decoder and get_string_moran, in the same way."""
     from .losses import SSIM, calculate_psnr
     from .crnn import bicubic_resize, parse_crnn_data
     from .aster import ASTER
+    from .moran import MORAN
     if isinstance(recognizer, ASTER):
         return _evaluate_aster(model, batches, prior_fn, recognizer, voc_type, full_metrics)
+    if isinstance(recognizer, MORAN):
+        return _evaluate_moran(model, batches, prior_fn, recognizer, voc_type, full_metrics)
     was_training = model.training
     model.eval()
     ssim = SSIM()
@@ -374,8 +378,6 @@ def _evaluate_aster(model, batches, prior_fn, recognizer, voc_type, full_metrics
     """`evaluate` with an ASTER recogniser (the reference's --test_model ASTER: parse_aster_data -> beam search -> get_string_aster, both
     strings through str_filt; interfaces/super_resolution.py:1374-1396).  The ids of every batch stay on the device; ONE copy at the end
     brings them and the image metrics back, and the strings are decoded on the host from it."""
-    from .losses import SSIM, calculate_psnr
-    from .crnn import bicubic_resize
     from .aster import AsterInfo, get_string_aster, parse_aster_data
     info = getattr(recognizer, "info", None)
     if info is None:
@@ -386,6 +388,30 @@ def _evaluate_aster(model, batches, prior_fn, recognizer, voc_type, full_metrics
         info = AsterInfo(voc)
     elif info.rec_num_classes != recognizer.rec_num_classes:
         raise ValueError("io.evaluate: recognizer.info has %d classes, the recogniser %d" % (info.rec_num_classes, recognizer.rec_num_classes))
+    return _evaluate_ids(model, batches, prior_fn, recognizer, voc_type, full_metrics,
+                         lambda img: recognizer.read(parse_aster_data(img[:, :3]), "beam")[0], recognizer.max_len_labels,
+                         lambda rows: get_string_aster(rows, info))
+
+
+@torch.no_grad()
+def _evaluate_moran(model, batches, prior_fn, recognizer, voc_type, full_metrics):
+    """`evaluate` with a MORAN recogniser (the reference's --test_model MORAN: parse_moran_data -> the model in test mode -> the arg-max
+    of the L2R rows -> the alphabet's characters cut at the first '$', both strings through str_filt;
+    interfaces/super_resolution.py:1401-1405).  `MORAN.read` runs the L2R decoder only (the reference computes the R2L rows and throws
+    them away).  One host copy, as in `_evaluate_aster`."""
+    from .moran import ALPHABET, MAX_ITER, get_string_moran, parse_moran_data
+    if recognizer.nclass != len(ALPHABET) or recognizer.nc != 1:
+        raise ValueError("io.evaluate: the MORAN recogniser must read one channel and have %d classes (0-9a-z$), got nc=%d, nclass=%d"
+                         % (len(ALPHABET), recognizer.nc, recognizer.nclass))
+    return _evaluate_ids(model, batches, prior_fn, recognizer, voc_type, full_metrics,
+                         lambda img: recognizer.read(parse_moran_data(img[:, :3], recognizer.targetW)[0], MAX_ITER)[0], MAX_ITER,
+                         get_string_moran)
+
+
+def _evaluate_ids(model, batches, prior_fn, recognizer, voc_type, full_metrics, read, L, strings):
+    """the loop `_evaluate_aster` and `_evaluate_moran` share: read(img) -> (B, L) int32 ids on the device, strings(rows) -> B strings"""
+    from .losses import SSIM, calculate_psnr
+    from .crnn import bicubic_resize
     was_training, rec_was_training = model.training, recognizer.training
     model.eval()
     recognizer.eval()
@@ -409,11 +435,10 @@ def _evaluate_aster(model, batches, prior_fn, recognizer, voc_type, full_metrics
         n += 1
         if labels is not None:
             for name, img in (("sr", sr), ("lr", lr), ("hr", hr)):
-                ids[name].append(recognizer.read(parse_aster_data(img[:, :3]), "beam")[0])
+                ids[name].append(read(img))
             all_labels += list(labels)
     model.train(was_training)
     recognizer.train(rec_was_training)
-    L = recognizer.max_len_labels
     flat = [t.reshape(-1) for k in ("sr", "lr", "hr") for t in ids[k]]
     host = torch.cat(flat + [sums.view(torch.int32)]).cpu()                    # the evaluation's one host synchronisation
     s4 = host[-4:].view(torch.float32).tolist()
@@ -429,7 +454,7 @@ def _evaluate_aster(model, batches, prior_fn, recognizer, voc_type, full_metrics
         for name in ("sr", "lr", "hr"):
             rows = host[off:off + n_img * L].view(n_img, L)
             off += n_img * L
-            pred = [str_filt(p, voc_type) for p in get_string_aster(rows, info)]
+            pred = [str_filt(p, voc_type) for p in strings(rows)]
             acc[name] = sum(p == t for p, t in zip(pred, want))
             ned[name] = sum(edit_distance(p, t) / (max(len(p), len(t)) + 1e-10) for p, t, ok in zip(pred, want, scored) if ok)
         res.update(accuracy=round(acc["sr"] / n_img, 4), accuracy_lr=round(acc["lr"] / n_img, 4), accuracy_hr=round(acc["hr"] / n_img, 4),

@@ -1,0 +1,449 @@
+"""The MORAN recogniser for evaluation (reference model/moran/: MORAN = MORN rectifier -> ASRN = ResNet + 2 x BidirectionalLSTM ->
+attention decoder), the third recogniser of the TATT / TextZoom tables (the reference's `--test_model MORAN`).
+
+`MORAN` is a drop-in for the reference's `MORAN` as its eval loop builds it (`MORAN_init`, interfaces/base.py:674-692): same arguments,
+same `state_dict` keys, order and shapes (427 entries for `MORAN(1, 37, 256, 32, 100, BidirDecoder=True)`), seed for seed the same initial
+weights (sub-modules are constructed and initialised in the reference's order; torch.nn layers are parameter holders only), so a
+checkpoint saved by the reference loads with `load_state_dict(strict=True)`.  MORN's sampling grids are plain attributes in the
+reference, not buffers; here they are computed inside the kernel.
+
+EVAL ONLY.  `forward(..., test=True)` in eval mode returns the reference's rows; anything else raises: the training path needs
+`fracPickup`, the random bypass of the rectifier and a backward, none of which are part of this package.
+
+SAMPLING MODE.  Both `grid_sample` calls of MORN run as the installed torch runs them: bilinear, zeros padding,
+**align_corners=False**.  The reference was written for a torch whose default was align_corners=True; this module mirrors the
+reference as it executes today, and the fixtures (tools/gen_golden_moran.py) are recorded that way.
+
+All arithmetic runs in HIP kernels (no CPU fallback).  Eval BatchNorm is folded into the preceding convolution on the device
+(tatt_bn_fold); the convolutions are the shared implicit-GEMM kernels on strided views.  A stride-s 3 x 3 convolution with pad 1 equals the
+stride-1 'same' result read at [:, ::sh, ::sw] (the same products, exactly), so the ten strided 3 x 3 convolutions run at stride 1 and
+hand the sub-sampled VIEW to the next convolution, which reads by strides; a copy is made only where the flat `add_relu` needs one.
+The tail of the rectifier is ONE launch per pass (tatt_morn_rectify) and the 20 greedy steps of a decoder direction are ONE launch
+(tatt_moran_decode, csrc/moran.hip), with `decode_eager` as the step-by-step route on the shared operators for geometries that launch
+refuses (and as the timing yardstick of tools/bench_moran.py).
+"""
+from __future__ import annotations
+
+import string
+
+import numpy as np
+import torch
+from torch import nn
+
+from . import functional as Fh
+from . import ops
+from ._lib import LIB
+from .aster import _require, add_relu, gru_cell, infer_bilstm
+from .ops import ACT_NONE, ACT_RELU, ACT_TANH
+from .tsrn import _Holder
+
+ALPHABET = string.digits + string.ascii_lowercase + "$"          # interfaces/base.py:676
+MAX_ITER = 20                                                     # parse_moran_data: every image is read for 20 steps
+EMB = 256                                                         # asrn_res.py:229-232: num_embeddings of every Attention
+MODES = {"forced": 0, "greedy": 1}
+
+DECODE_ONE_LAUNCH = True          # test / A-B hook: False -> `MORAN.decode` always takes `decode_eager`
+LAUNCHES = {"one_launch": 0, "eager": 0}      # how often each decoder route ran (tests, tools/bench_moran.py)
+
+
+# ---- the reference's helpers (interfaces/base.py:694-710, interfaces/super_resolution.py's MORAN branch) ----------------------------
+def parse_moran_data(imgs, in_width=100):
+    """(B, >=3, H, W) images in [0, 1] on the GPU -> (tensor (B, 1, 32, in_width), length, text, text): the luminance of the bicubic
+    resize (`parse_crnn_data`'s kernel), `length` = 20 per image (int32) and `text` = zeros (int64, 20 per image: the reference encodes
+    '0' * 20), both on the host as in the reference."""
+    from .crnn import parse_crnn_data
+    B = imgs.shape[0]
+    length = torch.full((B,), MAX_ITER, dtype=torch.int32)
+    text = torch.zeros(B * MAX_ITER, dtype=torch.int64)
+    return parse_crnn_data(imgs, in_width), length, text, text
+
+
+def get_string_moran(ids):
+    """(B, L) class ids (tensor, array or lists) -> B strings: the alphabet's characters joined and cut at the first '$'
+    (converter_moran.decode(...) then .split('$')[0] in the reference's loop)."""
+    if torch.is_tensor(ids):
+        ids = ids.cpu().numpy()
+    return ["".join(ALPHABET[int(i)] for i in row).split("$")[0] for row in np.asarray(ids)]
+
+
+# ---- parameter holders (attribute names = the reference's => identical state_dict keys) --------------------------------------------
+class MORN(_Holder):
+    """reference morn.py:6-44 (the grids are computed in tatt_morn_rectify)"""
+
+    def __init__(self, nc, targetH, targetW, maxBatch=256):
+        super().__init__()
+        self.targetH, self.targetW, self.maxBatch = targetH, targetW, maxBatch
+        self.cnn = nn.Sequential(
+            nn.MaxPool2d(2, 2),
+            nn.Conv2d(nc, 64, 3, 1, 1), nn.BatchNorm2d(64), nn.ReLU(True), nn.MaxPool2d(2, 2),
+            nn.Conv2d(64, 128, 3, 1, 1), nn.BatchNorm2d(128), nn.ReLU(True), nn.MaxPool2d(2, 2),
+            nn.Conv2d(128, 64, 3, 1, 1), nn.BatchNorm2d(64), nn.ReLU(True),
+            nn.Conv2d(64, 16, 3, 1, 1), nn.BatchNorm2d(16), nn.ReLU(True),
+            nn.Conv2d(16, 1, 3, 1, 1), nn.BatchNorm2d(1))
+        self.pool = nn.MaxPool2d(2, 1)
+
+
+MORN_CONVS = (1, 5, 9, 12, 15)            # indices of the convolutions in MORN.cnn; the BatchNorm follows each
+MORN_POOL_AFTER = (1, 5)                  # ... and a 2 x 2 pool follows these two (one more precedes the first)
+
+
+class BidirectionalLSTM(_Holder):
+    def __init__(self, nIn, nHidden, nOut):
+        super().__init__()
+        self.rnn = nn.LSTM(nIn, nHidden, bidirectional=True)
+        self.embedding = nn.Linear(nHidden * 2, nOut)
+
+
+class AttentionCell(_Holder):
+    def __init__(self, input_size, hidden_size, num_embeddings=128):
+        super().__init__()
+        self.i2h = nn.Linear(input_size, hidden_size, bias=False)
+        self.h2h = nn.Linear(hidden_size, hidden_size)
+        self.score = nn.Linear(hidden_size, 1, bias=False)
+        self.rnn = nn.GRUCell(input_size + num_embeddings, hidden_size)
+        self.hidden_size, self.input_size, self.num_embeddings = hidden_size, input_size, num_embeddings
+
+
+class Attention(_Holder):
+    def __init__(self, input_size, hidden_size, num_classes, num_embeddings=128):
+        super().__init__()
+        self.attention_cell = AttentionCell(input_size, hidden_size, num_embeddings)
+        self.input_size, self.hidden_size = input_size, hidden_size
+        self.generator = nn.Linear(hidden_size, num_classes)
+        self.char_embeddings = nn.Parameter(torch.randn(num_classes + 1, num_embeddings))
+        self.num_embeddings, self.num_classes = num_embeddings, num_classes
+
+
+def _conv_bn(c_in, c_out, k, stride, pad):
+    return nn.Sequential(nn.Conv2d(c_in, c_out, k, stride, pad), nn.BatchNorm2d(c_out, momentum=0.01))
+
+
+class Residual_block(_Holder):
+    """reference asrn_res.py:157-186: relu(residual + conv2(conv1(x))), no activation between conv1 and conv2"""
+
+    def __init__(self, c_in, c_out, stride):
+        super().__init__()
+        self.downsample = None
+        first = (stride[0] if isinstance(stride, tuple) else stride) > 1
+        if first:
+            self.downsample = _conv_bn(c_in, c_out, 3, stride, 1)
+            self.conv1 = _conv_bn(c_in, c_out, 3, stride, 1)
+        else:
+            self.conv1 = _conv_bn(c_in, c_out, 1, stride, 0)
+        self.conv2 = _conv_bn(c_out, c_out, 3, 1, 1)
+        self.relu = nn.ReLU()
+        self.stride = (tuple(stride) if isinstance(stride, tuple) else (stride, stride)) if first else (1, 1)
+
+
+class ResNet(_Holder):
+    def __init__(self, c_in):
+        super().__init__()
+        self.block0 = _conv_bn(c_in, 32, 3, 1, 1)
+        self.block1 = self._make_layer(32, 32, 2, 3)
+        self.block2 = self._make_layer(32, 64, 2, 4)
+        self.block3 = self._make_layer(64, 128, (2, 1), 6)
+        self.block4 = self._make_layer(128, 256, (2, 1), 6)
+        self.block5 = self._make_layer(256, 512, (2, 1), 3)
+
+    @staticmethod
+    def _make_layer(c_in, c_out, stride, repeat=3):
+        return nn.Sequential(Residual_block(c_in, c_out, stride), *[Residual_block(c_out, c_out, 1) for _ in range(repeat - 1)])
+
+
+class ASRN(_Holder):
+    """reference asrn_res.py:214-239"""
+
+    def __init__(self, imgH, nc, nclass, nh, BidirDecoder=False):
+        super().__init__()
+        assert imgH % 16 == 0, "imgH must be a multiple of 16"
+        self.cnn = ResNet(nc)
+        self.rnn = nn.Sequential(BidirectionalLSTM(512, nh, nh), BidirectionalLSTM(nh, nh, nh))
+        self.BidirDecoder = BidirDecoder
+        if BidirDecoder:
+            self.attentionL2R = Attention(nh, nh, nclass, EMB)
+            self.attentionR2L = Attention(nh, nh, nclass, EMB)
+        else:
+            self.attention = Attention(nh, nh, nclass, EMB)
+        for m in self.modules():
+            if isinstance(m, nn.Conv2d):
+                nn.init.kaiming_normal_(m.weight, mode="fan_out", a=0)
+            elif isinstance(m, nn.BatchNorm2d):
+                nn.init.constant_(m.weight, 1)
+                nn.init.constant_(m.bias, 0)
+
+
+# ---- device entry points -----------------------------------------------------------------------------------------------------------
+def morn_rectify(o, x_nchw, size, acc=None):
+    """The rectifier's tail in ONE launch (tatt_morn_rectify).  o (B, h, w) contiguous: the offsets network's output; x_nchw (B, C <= 4,
+    H, W): any strides; size = (Ho, Wo).  acc None: the first pass (offsets_grid = g), else offsets_grid += g in place.
+    -> (x_rect NHWC (B, Ho, Wo, C), offsets_grid (B, Ho, Wo))"""
+    ops._check_dev(x_nchw)
+    ops._check_dev(o)
+    B, C, H, W = x_nchw.shape
+    assert o.is_contiguous() and o.dim() == 3 and o.shape[0] == B
+    first = acc is None
+    if first:
+        acc = ops.new(x_nchw, B, size[0], size[1])
+    assert acc.is_contiguous() and tuple(acc.shape) == (B, size[0], size[1])
+    out = ops.new(x_nchw, B, size[0], size[1], C)
+    ops.call("tatt_morn_rectify", ops.P(o), o.shape[1], o.shape[2], ops.P(acc), int(first), ops.P(x_nchw), *x_nchw.stride(), ops.P(out),
+             B, C, H, W, size[0], size[1], ops.stream())
+    return out, acc
+
+
+def decoder_operands(att: Attention):
+    """What tatt_moran_decode reads, from one direction's parameters: the transposed weights and E2 = char_embeddings W_ih[:, H:]^T + b_ih
+    (step-invariant; one GEMM).  Built once per parameter set by `MORAN`; tests call it directly."""
+    cell = att.attention_cell
+    H = att.hidden_size
+    W = cell.rnn.weight_ih                               # (3H, H + EMB): the context's columns first
+    C1, E = att.char_embeddings.shape
+    G = W.shape[0]
+    E2 = ops.new(W, C1, G)
+    ops.gemm(att.char_embeddings, E, 1, W[:, H:], 1, W.shape[1], E2, G, 1, C1, G, E, bias=cell.rnn.bias_ih)
+    return {"WhT": cell.h2h.weight.t().contiguous(), "bh": cell.h2h.bias, "wv": cell.score.weight.reshape(-1).contiguous(), "E2": E2,
+            "WicT": W[:, :H].t().contiguous(), "WhhT": cell.rnn.weight_hh.t().contiguous(), "bhh": cell.rnn.bias_hh,
+            "genT": att.generator.weight.t().contiguous(), "genb": att.generator.bias}
+
+
+def _one_launch_takes(att, T, L):
+    return att.hidden_size == 256 and att.input_size == 256 and att.num_embeddings == 256 and 1 <= T <= 32 and \
+        2 <= att.num_classes <= 64 and 1 <= L <= 64
+
+
+def _steps(att, feats, mode, steps, targets):
+    if mode not in (0, 1):
+        raise ValueError("mode must be 0 (forced) or 1 (greedy), got %r" % (mode,))
+    if feats.dim() != 3 or feats.shape[2] != att.input_size:
+        raise ValueError("feats must be (B, T, %d), got %s" % (att.input_size, tuple(feats.shape)))
+    if mode == 0:
+        if targets is None or targets.dim() != 2 or targets.shape[0] != feats.shape[0]:
+            raise ValueError("forced decoding needs targets of shape (B, L)")
+        return targets.shape[1]
+    if steps is None or steps < 1:
+        raise ValueError("greedy decoding needs steps >= 1")
+    return int(steps)
+
+
+def attn_decode(att: Attention, feats, mode, steps=None, targets=None, operands=None):
+    """One direction of the decoder in ONE launch (tatt_moran_decode): feats (B, T, 256) encoder features -> logits (B, L, C) [mode 0:
+    the embedding row of step i is targets[b, i]] or (ids (B, L) int32, logits) [mode 1: greedy].  None when the launch refuses the
+    geometry (the caller takes `decode_eager`)."""
+    ops._check_dev(feats)
+    L = _steps(att, feats, mode, steps, targets)
+    B, T, D = feats.shape
+    C = att.num_classes
+    if not _one_launch_takes(att, T, L):
+        return None                                   # (what the entry point itself refuses; asked first so that no operand is built)
+    op = operands if operands is not None else decoder_operands(att)
+    fc = Fh._c(feats)
+    fproj = ops.linear_fwd(fc.reshape(B * T, D), att.attention_cell.i2h.weight)
+    logits = ops.new(feats, B, L, C)
+    ids = tg = None
+    if mode == 0:
+        tg = targets.to(device=feats.device, dtype=torch.int32).contiguous()
+    else:
+        ids = torch.empty(B, L, dtype=torch.int32, device=feats.device)
+    rc = getattr(LIB, "tatt_moran_decode")(ops.P(fc), ops.P(fproj), ops.P(op["WhT"]), ops.P(op["bh"]), ops.P(op["wv"]), ops.P(op["E2"]),
+                                           ops.P(op["WicT"]), ops.P(op["WhhT"]), ops.P(op["bhh"]), ops.P(op["genT"]), ops.P(op["genb"]),
+                                           ops.P(tg), ops.P(logits), ops.P(ids), B, T, C, L, att.hidden_size, mode, ops.stream())
+    if rc == 1:
+        return None
+    if rc != 0:
+        raise RuntimeError("tatt_moran_decode failed with code %d" % rc)
+    LAUNCHES["one_launch"] += 1
+    return logits if mode == 0 else (ids, logits)
+
+
+def decode_eager(att: Attention, feats, mode, steps=None, targets=None):
+    """`attn_decode` step by step on the shared operators (about a dozen launches per step): the route for geometries the one launch
+    refuses, and the timing yardstick.  Same results, same tie rule (torch's arg-max returns the first maximum), and like the one
+    launch no host synchronisation."""
+    ops._check_dev(feats)
+    L = _steps(att, feats, mode, steps, targets)
+    B, T, D = feats.shape
+    C, H = att.num_classes, att.hidden_size
+    cell = att.attention_cell
+    dev = feats.device
+    fc = Fh._c(feats)
+    fproj = ops.linear_fwd(fc.reshape(B * T, D), cell.i2h.weight).view(B, T, H)
+    fp_tr = fproj.permute(1, 0, 2).contiguous().view(T * B, H)                  # row t * B + b
+    h = torch.zeros(B, H, device=dev)
+    if mode == 0:
+        tg = targets.to(dev).long().clamp(0, C)
+        y = tg[:, 0]
+    else:
+        y = torch.zeros(B, dtype=torch.long, device=dev)
+    seed = Fh.seed_tensor(dev)
+    outs, out_ids = [], []
+    for i in range(L):
+        hp = ops.linear_fwd(h, cell.h2h.weight, cell.h2h.bias)
+        th = ops.act_fwd(ops.add_rowbcast(fp_tr, hp, B), ACT_TANH)
+        e = ops.new(feats, B, T)
+        ops.gemm(th, H, 1, cell.score.weight, 1, 0, e, T, 1, B, 1, H, Z=T, bsA=B * H, bsC=1)
+        ops.call("tatt_softmax_rows_fwd", ops.P(e), None, B, T, 0.0, ops.P(seed), 0, ops.stream())
+        ctx = ops.new(feats, B, D)
+        ops.gemm(e, T, 1, fc, D, 1, ctx, D, 1, 1, D, T, Z=B, bsA=T, bsB=T * D, bsC=D)
+        emb = att.char_embeddings.index_select(0, y)
+        gi = ops.linear_fwd(ctx, cell.rnn.weight_ih, cell.rnn.bias_ih, x2b=emb)
+        gh = ops.linear_fwd(h, cell.rnn.weight_hh, cell.rnn.bias_hh)
+        h = gru_cell(gi, gh, h)
+        logits = ops.linear_fwd(h, att.generator.weight, att.generator.bias)
+        outs.append(logits)
+        if mode == 0:
+            if i + 1 < L:
+                y = tg[:, i + 1]
+        else:
+            y = logits.argmax(1)
+            out_ids.append(y)
+            y = y + 1
+    LAUNCHES["eager"] += 1
+    lg = torch.stack(outs, 1)
+    return lg if mode == 0 else (torch.stack(out_ids, 1).int(), lg)
+
+
+# ---- the recogniser ----------------------------------------------------------------------------------------------------------------
+class MORAN(nn.Module):
+    """Drop-in for the reference's MORAN (eval only; see the module docstring).  `inputDataType` and `CUDA` are accepted and ignored;
+    `maxBatch` keeps the reference's assertion."""
+
+    def __init__(self, nc, nclass, nh, targetH, targetW, BidirDecoder=False, inputDataType="torch.cuda.FloatTensor", maxBatch=256,
+                 CUDA=True):
+        super().__init__()
+        self.nc, self.nclass, self.nh, self.targetH, self.targetW, self.BidirDecoder = nc, nclass, nh, targetH, targetW, BidirDecoder
+        self.MORN = MORN(nc, targetH, targetW, maxBatch)
+        self.ASRN = ASRN(targetH, nc, nclass, nh, BidirDecoder)
+        self._prep = None
+
+    # -- derived operands (folded filters, the decoders' transposed weights), rebuilt when a parameter or buffer changed: the same
+    # (data_ptr, _version) rule as `ASTER._prepared` -- a write that bumps no counter leaves them stale.  `read` checks once.
+    def _signature(self):
+        return tuple((t.data_ptr(), t._version) for t in list(self.parameters()) + list(self.buffers()))
+
+    def _attention(self, reverse=False):
+        if self.BidirDecoder:
+            return self.ASRN.attentionR2L if reverse else self.ASRN.attentionL2R
+        if reverse:
+            raise ValueError("tatt_amd.MORAN: reverse=True needs BidirDecoder=True (this model has one decoder)")
+        return self.ASRN.attention
+
+    def _prepared(self):
+        sig = self._signature()
+        if self._prep is None or self._prep["sig"] != sig:
+            from .infer import bn_fold
+            folds = {}
+            for i in MORN_CONVS:
+                folds[("morn", i)] = bn_fold(self.MORN.cnn[i].weight, self.MORN.cnn[i].bias, self.MORN.cnn[i + 1])
+            cnn = self.ASRN.cnn
+            folds["b0"] = bn_fold(cnn.block0[0].weight, cnn.block0[0].bias, cnn.block0[1])
+            for li in range(1, 6):
+                for bi, blk in enumerate(getattr(cnn, "block%d" % li)):
+                    folds[(li, bi, 1)] = bn_fold(blk.conv1[0].weight, blk.conv1[0].bias, blk.conv1[1])
+                    folds[(li, bi, 2)] = bn_fold(blk.conv2[0].weight, blk.conv2[0].bias, blk.conv2[1])
+                    if blk.downsample is not None:
+                        folds[(li, bi, 0)] = bn_fold(blk.downsample[0].weight, blk.downsample[0].bias, blk.downsample[1])
+            operands = {}
+            for rev in ((False, True) if self.BidirDecoder else (False,)):
+                att = self._attention(rev)
+                operands[rev] = decoder_operands(att) if _one_launch_takes(att, 1, 1) else None
+            self._prep = {"sig": sig, "folds": folds, "operands": operands}
+        return self._prep
+
+    # -- the stages
+    def _check_input(self, x):
+        _require(x)
+        if x.dim() != 4 or tuple(x.shape[1:]) != (self.nc, self.targetH, self.targetW):
+            raise ValueError("tatt_amd.MORAN reads (B, %d, %d, %d) images, got %s" % (self.nc, self.targetH, self.targetW, tuple(x.shape)))
+        assert x.shape[0] <= self.MORN.maxBatch
+
+    def offsets(self, x, prep=None):
+        """x (B, nc, H, W) view (any strides) -> MORN.cnn(x) as (B, h, w) (one channel): morn.py:61"""
+        folds = (prep or self._prepared())["folds"]
+        h = ops.maxpool_fwd(ops.to_contiguous(x.permute(0, 2, 3, 1)), 2, 2)
+        for i in MORN_CONVS:
+            w, b = folds[("morn", i)]
+            h = ops.conv2d_forward(h, w, b, ACT_RELU if i != MORN_CONVS[-1] else ACT_NONE)
+            if i in MORN_POOL_AFTER:
+                h = ops.maxpool_fwd(h, 2, 2)
+        return h.reshape(h.shape[0], h.shape[1], h.shape[2])
+
+    def rectify(self, x, prep=None, want_offsets=False):
+        """x (B, nc, targetH, targetW) -> the rectified image, NHWC (B, targetH, targetW, nc): MORN.forward with test=True, enhance=1
+        [, offsets_grid (B, targetH, targetW)]"""
+        prep = prep or self._prepared()
+        size = (self.targetH, self.targetW)
+        rect, acc = morn_rectify(self.offsets(x, prep), x, size)
+        rect, acc = morn_rectify(self.offsets(rect.permute(0, 3, 1, 2), prep), x, size, acc)
+        return (rect, acc) if want_offsets else rect
+
+    def encode(self, x_nhwc, prep=None):
+        """ASRN's ResNet + 2 x BidirectionalLSTM on an NHWC image (B, 32, W, nc) -> features (B, T, nh)"""
+        folds = (prep or self._prepared())["folds"]
+        w, b = folds["b0"]
+        h = ops.conv2d_forward(x_nhwc, w, b, ACT_NONE)
+        for li in range(1, 6):
+            for bi, blk in enumerate(getattr(self.ASRN.cnn, "block%d" % li)):
+                sh, sw = blk.stride
+                w, b = folds[(li, bi, 1)]
+                o = ops.conv2d_forward(h, w, b, ACT_NONE)
+                if blk.downsample is not None:
+                    # a strided 3 x 3 with pad 1 is the stride-1 'same' map read at [::sh, ::sw]: conv2 reads the view by its strides
+                    o = o[:, ::sh, ::sw, :]
+                    w, b = folds[(li, bi, 0)]
+                    res = Fh._c(ops.conv2d_forward(h, w, b, ACT_NONE)[:, ::sh, ::sw, :])
+                else:
+                    res = h
+                w, b = folds[(li, bi, 2)]
+                h = add_relu(ops.conv2d_forward(o, w, b, ACT_NONE), res)
+        B, Hh, Wd, Cc = h.shape
+        if Hh != 1:
+            raise ValueError("tatt_amd.MORAN reads images 32 pixels high (the feature map must be one row high, got %d)" % Hh)
+        seq = Fh._c(h.reshape(B, Wd, Cc).permute(1, 0, 2))                     # time-major for the LSTM kernels
+        for layer in self.ASRN.rnn:
+            rec = infer_bilstm(seq, layer.rnn)
+            T, _, H2 = rec.shape
+            seq = ops.linear_fwd(rec.reshape(T * B, H2), layer.embedding.weight, layer.embedding.bias).view(T, B, -1)
+        return Fh._c(seq.permute(1, 0, 2))
+
+    def decode(self, feats, steps=MAX_ITER, targets=None, reverse=False, prep=None):
+        """feats (B, T, nh) -> (ids (B, steps) int32, logits (B, steps, nclass)) greedy, or the logits (B, L, nclass) of a forced
+        decoding when `targets` (B, L) gives every step's embedding row"""
+        att = self._attention(reverse)
+        mode = 0 if targets is not None else 1
+        out = None
+        if DECODE_ONE_LAUNCH:
+            out = attn_decode(att, feats, mode, steps, targets, operands=(prep or self._prepared())["operands"][bool(reverse)])
+        if out is None:
+            out = decode_eager(att, feats, mode, steps, targets)
+        return out
+
+    @torch.no_grad()
+    def read(self, images, steps=MAX_ITER, reverse=False):
+        """images (B, nc, targetH, targetW) in [0, 1] (`parse_moran_data`) on the GPU -> (ids (B, steps) int32, logits (B, steps, nclass))
+        on the device, no host synchronisation.  Runs the L2R decoder only (reverse=True: the R2L one instead)."""
+        self._check_input(images)
+        prep = self._prepared()
+        return self.decode(self.encode(self.rectify(images, prep), prep), steps, reverse=reverse, prep=prep)
+
+    @torch.no_grad()
+    def forward(self, x, length, text=None, text_rev=None, test=False, debug=False):
+        """The reference's call in test mode: -> (preds_L2R, preds_R2L) with BidirDecoder, else one tensor; each (sum(length), nclass):
+        image b's first length[b] steps, image after image.  debug=True returns (preds, None): the demo collage is not built.
+        `length` is read on the HOST (it is a host tensor in the reference's loop); a device tensor is copied, which waits for the device."""
+        if self.training or not test:
+            raise NotImplementedError("tatt_amd.MORAN is an evaluation recogniser: call .eval() and pass test=True (the training path "
+                                      "needs fracPickup, the rectifier's random bypass and a backward; training MORAN needs the reference)")
+        self._check_input(x)
+        lens = [int(v) for v in (length.cpu().tolist() if torch.is_tensor(length) else length)]
+        if len(lens) != x.shape[0]:
+            raise ValueError("length must have one entry per image")
+        steps = max(lens)
+        prep = self._prepared()
+        feats = self.encode(self.rectify(x, prep), prep)
+        row = torch.tensor([b * steps + i for b, n in enumerate(lens) for i in range(n)], dtype=torch.long).to(x.device)
+        outs = []
+        for rev in ((False, True) if self.BidirDecoder else (False,)):
+            _, logits = self.decode(feats, steps, reverse=rev, prep=prep)
+            outs.append(logits.reshape(x.shape[0] * steps, -1).index_select(0, row))
+        preds = tuple(outs) if self.BidirDecoder else outs[0]
+        return (preds, None) if debug else preds
