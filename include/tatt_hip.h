@@ -354,6 +354,14 @@ int tatt_gru32_bwd2(const float* gates, const float* out, const float* dout, con
  * where dWhh_c (192, 32) = [dW_hh forward; dW_hh reverse] */
 int tatt_gru_wgrad_frag(const float* frag, const float* x, const float* xb, float* ws1, float* ws2, int nseq, int T,
                         int s_in, long stride_hi, long stride_lo, long stride_t, int G, hipStream_t st);
+/* The same for a block whose forward projection read x through tatt_tokgemm_sb_in: x is transformed while it is staged, bit for bit as
+ * there.  Exactly one of: in_mean, in_rstd, in_gamma, in_beta (64 floats each; x becomes (x - mean) * rstd * gamma + beta, rounded as
+ * tatt_bn_apply), or in_add (M, 64) contiguous and 16-byte aligned (x becomes x + in_add; without xb only); the others NULL, else
+ * returns 1.  xb and the fragment stream are read as they are. */
+int tatt_gru_wgrad_frag_in(const float* frag, const float* x, const float* xb, float* ws1, float* ws2, int nseq, int T,
+                           int s_in, long stride_hi, long stride_lo, long stride_t, int G, const float* in_mean,
+                           const float* in_rstd, const float* in_gamma, const float* in_beta, const float* in_add,
+                           hipStream_t st);
 
 /* backward step, fused form: dh = dhseq_next + dhcarry + dgh_cur @ whh, then the gate part of the NEXT step on the same tile:
  * dgi_acc += input-side gate grads, dgh_next = recurrent-side gate grads, dhcarry = dh*z  (whhT = whh transposed) */
@@ -507,6 +515,14 @@ int tatt_softmax_rows_bwd(const float* P, float* dP, long rows, int L, float pdr
  * (128, 192), (64, 192), (64, 64), (64, 128). */
 int tatt_tokgemm_sb(const float* X1, const float* X2, int K1, const float* Wp, const float* bias, float* Y1, float* Y2, int N1,
                     int M, int N, int K, hipStream_t st);
+/* The forward projection of a GruBlock that follows a BatchNorm or a residual sum, without that map in memory: columns [0, K1) of
+ * every token row are transformed in registers before the hi / lo split.  Exactly one of: in_mean, in_rstd, in_gamma, in_beta (64
+ * floats each; the columns become (x - mean) * rstd * gamma + beta, rounded as tatt_bn_apply rounds it), or in_add (M, K1) contiguous
+ * and 16-byte aligned (the columns become X1 + in_add; K = K1 only); the others NULL, else returns 1.  K1 = 64, N = 192, K = 64 or 128;
+ * the columns from X2 pass unchanged; the result equals tatt_tokgemm_sb on the materialised map bit for bit. */
+int tatt_tokgemm_sb_in(const float* X1, const float* X2, int K1, const float* Wp, const float* bias, float* Y1, float* Y2, int N1,
+                       int M, int N, int K, const float* in_mean, const float* in_rstd, const float* in_gamma,
+                       const float* in_beta, const float* in_add, hipStream_t st);
 /* The same with an epilogue: act = 1 (ReLU) after the bias; accum != 0: Y += instead of Y = (sums of data gradients into one map).
  * Also takes (N, K) = (128, 128) and (128, 64): the TBSRN FeatureEnhancer projections (reference model/tbsrn.py:77-151). */
 int tatt_tokgemm_sb_ex(const float* X1, const float* X2, int K1, const float* Wp, const float* bias, float* Y1, float* Y2, int N1,

@@ -70,6 +70,12 @@ __device__ __forceinline__ float apply_act(float x, int act) {
         default: return x;
     }
 }
+// BatchNorm of one element from its statistics, rounded as bn_apply_v4_kernel (norm.hip) rounds (v - mean) * rstd * gamma + beta under
+// -ffp-contract=fast: the difference, one product, then ONE fused multiply-add.  Written out, so that a consumer that normalises its
+// input on the way in (tatt_tokgemm_sb_in, tatt_gru_wgrad_frag_in) sees bit for bit the map tatt_bn_apply would have written.
+__device__ __forceinline__ float bn_affine_f(float v, float mean, float rstd, float gamma, float beta) {
+    return __builtin_fmaf((v - mean) * rstd, gamma, beta);
+}
 // derivative of act at pre-activation u
 __device__ __forceinline__ float act_grad(float u, int act) {
     switch (act) {

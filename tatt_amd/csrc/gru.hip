@@ -1440,30 +1440,63 @@ TATT_API int tatt_gru_compose_batch(const float* const* ptrs, const int* Ks, int
 }
 // dW_ih_d (96x64) = dW'_d W_c^T + db'_d b_c^T ;  dW_c (64xK) = sum_d W_ih_d^T dW'_d ;  db_c (64) = sum_d W_ih_d^T db'_d ;
 // dW_hh_d (96x32) = the d-th diagonal block of dWhh (192x64) = dgh^T hprev
-__global__ void gru_tail_kernel(const float* __restrict__ dWp, const float* __restrict__ dbp,
+// ~3 MFLOP on matrices of a few KB: the time is load latency, not arithmetic.  No thread walks a chain of dependent-in-time global
+// loads: the products of dW_ih read both operands from LDS (the four dW' rows of the block beside the transposed W_c chunk, each
+// staged with all of a thread's loads in flight at once), the two over the 96 rows request GT_RB rows of both operands before the
+// first multiply-add of the batch.  Every output keeps its two interleaved fmaf chains s0, s1 in the same order, so the results are
+// what the first version (one global load pair per step) gave, bit for bit.
+#define GT_RB 16                                 // rows of a batch (96 = 6 batches): 4 GT_RB loads in flight per thread
+// s0 += sum_row wf[row][c] a[row][k], s1 += the same for the reverse direction (rows 96 .. 191 of a), row by row in order
+__device__ __forceinline__ void gt_rows96(const float* __restrict__ wf, const float* __restrict__ wr, const float* __restrict__ a,
+                                          long lda, float& s0, float& s1) {
+    for (int r0 = 0; r0 < 96; r0 += GT_RB) {
+        float f[GT_RB], g[GT_RB], u[GT_RB], v[GT_RB];
+#pragma unroll
+        for (int j = 0; j < GT_RB; ++j) {
+            f[j] = wf[(r0 + j) * 64];
+            g[j] = wr[(r0 + j) * 64];
+            u[j] = a[(long)(r0 + j) * lda];
+            v[j] = a[(long)(96 + r0 + j) * lda];
+        }
+#pragma unroll
+        for (int j = 0; j < GT_RB; ++j) {
+            s0 = fmaf(f[j], u[j], s0);
+            s1 = fmaf(g[j], v[j], s1);
+        }
+    }
+}
+__global__ __launch_bounds__(256) void gru_tail_kernel(const float* __restrict__ dWp, const float* __restrict__ dbp,
                                 const float* __restrict__ Wc, const float* __restrict__ bc,
                                 const float* __restrict__ wih_f, const float* __restrict__ wih_r,
                                 float* __restrict__ dwih_f, float* __restrict__ dwih_r, float* __restrict__ dWc,
                                 float* __restrict__ dbc, int K, const float* __restrict__ dWhh,
                                 float* __restrict__ dwhh_f, float* __restrict__ dwhh_r, int whh_ld) {
     int idx = blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx < 2 * 96 * 64) {   // 48 whole blocks; a wave = one row (d, r), lane = c.  W_c goes through LDS transposed, 64 k at a time:
-        // read straight from memory each lane would walk its own row of W_c (64 cache lines per load instruction)
+    if (idx < 2 * 96 * 64) {   // 48 whole blocks; a wave = one row (d, r), lane = c.  W_c goes through LDS transposed, 64 k at a time
+        // (read straight from memory each lane would walk its own row of W_c: 64 cache lines per load instruction), and the block's
+        // four rows of dW' beside it
         __shared__ float WcT[64 * 65];
-        const int d = idx / 6144, r = (idx % 6144) / 64, c = idx & 63;
+        __shared__ float As[4][64];
+        const int d = idx / 6144, r = (idx % 6144) / 64, c = idx & 63, w = threadIdx.x >> 6;
         const float* a = dWp + (long)(96 * d + r) * K;
         float s0 = dbp[96 * d + r] * bc[c], s1 = 0.f;
         for (int kc = 0; kc < K; kc += 64) {
             const int kn = K - kc < 64 ? K - kc : 64;
-            __syncthreads();
-            for (int e = threadIdx.x; e < 4096; e += 256) {
-                const int cc = e >> 6, k = e & 63;
-                if (k < kn) WcT[k * 65 + cc] = Wc[(long)cc * K + kc + k];
+            float wv[16];
+#pragma unroll
+            for (int j = 0; j < 16; ++j) {                              // element e = threadIdx.x + 256 j: column cc = e >> 6, k = e & 63 = c
+                const int cc = w + 4 * j;
+                wv[j] = c < kn ? Wc[(long)cc * K + kc + c] : 0.f;
             }
+            const float av = c < kn ? a[kc + c] : 0.f;
+            __syncthreads();
+#pragma unroll
+            for (int j = 0; j < 16; ++j) WcT[c * 65 + w + 4 * j] = wv[j];
+            As[w][c] = av;
             __syncthreads();
             for (int k = 0; k < kn; k += 2) {
-                s0 = fmaf(a[kc + k], WcT[k * 65 + c], s0);
-                s1 = fmaf(a[kc + k + 1], WcT[(k + 1) * 65 + c], s1);
+                s0 = fmaf(As[w][k], WcT[k * 65 + c], s0);
+                s1 = fmaf(As[w][k + 1], WcT[(k + 1) * 65 + c], s1);
             }
         }
         (d ? dwih_r : dwih_f)[r * 64 + c] = s0 + s1;
@@ -1473,20 +1506,14 @@ __global__ void gru_tail_kernel(const float* __restrict__ dWp, const float* __re
     if (idx < 64 * K) {
         const int c = idx / K, k = idx - c * K;
         float s0 = 0.f, s1 = 0.f;
-        for (int row = 0; row < 96; ++row) {
-            s0 = fmaf(wih_f[row * 64 + c], dWp[(long)row * K + k], s0);
-            s1 = fmaf(wih_r[row * 64 + c], dWp[(long)(96 + row) * K + k], s1);
-        }
+        gt_rows96(wih_f + c, wih_r + c, dWp + k, K, s0, s1);
         dWc[idx] = s0 + s1;
         return;
     }
     idx -= 64 * K;
     if (idx < 64) {
         float s0 = 0.f, s1 = 0.f;
-        for (int row = 0; row < 96; ++row) {
-            s0 = fmaf(wih_f[row * 64 + idx], dbp[row], s0);
-            s1 = fmaf(wih_r[row * 64 + idx], dbp[96 + row], s1);
-        }
+        gt_rows96(wih_f + idx, wih_r + idx, dbp, 1, s0, s1);
         dbc[idx] = s0 + s1;
         return;
     }

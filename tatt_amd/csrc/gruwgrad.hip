@@ -223,6 +223,12 @@ struct GruWfP {
     int nK, T8, s_in;
     long stride_hi, stride_lo, stride_t;
 };
+// input transform of x (tatt_gru_wgrad_frag_in), the one tatt_tokgemm_sb_in applied in the forward: GF_IN_BN: BatchNorm of x from its
+// statistics;  GF_IN_ADD: x + add, add (M, 64) contiguous.  xb and the fragment stream are untouched.
+#define GF_IN_NONE 0
+#define GF_IN_BN 1
+#define GF_IN_ADD 2
+struct GruWfIn { const float* mean; const float* rstd; const float* gamma; const float* beta; const float* add; };
 template <int PITCH>
 __device__ __forceinline__ void gf_frag(const float* __restrict__ col, gw_bf16x8& hi, gw_bf16x8& lo) {
     float v[8];
@@ -237,8 +243,8 @@ __device__ __forceinline__ void gf_frag(const float* __restrict__ col, gw_bf16x8
         lo[e] = l[0]; lo[e + 1] = l[1];
     }
 }
-template <bool HAS_XB>
-__global__ __launch_bounds__(GF_THREADS) void gru_wgrad_frag_kernel(GruWfP p) {
+template <bool HAS_XB, int IN>
+__global__ __launch_bounds__(GF_THREADS) void gru_wgrad_frag_kernel(GruWfP p, GruWfIn q) {
     constexpr int K = HAS_XB ? 128 : 64, NT = K / 16, PITCH = K + 2, NV = 32 * K / 4, VPT = (NV + GF_THREADS - 1) / GF_THREADS;
     __shared__ __attribute__((aligned(16))) float gf_T[32 * PITCH];            // token-major image of the chunk's x | xb rows
     __shared__ __attribute__((aligned(16))) float gf_F[NT * 2 * 64 * 4];       // their fragments: [tile][hi, lo][lane][4]
@@ -249,7 +255,16 @@ __global__ __launch_bounds__(GF_THREADS) void gru_wgrad_frag_kernel(GruWfP p) {
     const int a_slot = d * 8 + gate * 2;                           // dgi rows of (d, gate): the A operand of dW'
     const int ah_slot = gate == 2 ? d * 8 + 6 : a_slot;            // dgh rows of (d, gate): dgi's for r / z, the gn fragments for n
     const int bh_slot = 16 + d * 2;                                // h_{t-1} of direction d
-    f32x4 xpre[VPT], apre[12];
+    f32x4 xpre[VPT], xadd[IN == GF_IN_ADD ? VPT : 1], apre[12];
+    // input transform: GF_THREADS is a multiple of K / 4, so a thread stages the same channel quad of every row it touches -- its
+    // per-channel constants are loaded once; in_x: that quad lies in x (not xb)
+    const int cq = t % (K / 4);
+    const bool in_x = IN != GF_IN_NONE && (!HAS_XB || cq < 16);
+    float in_mu[4], in_rs[4], in_g[4], in_b[4];
+    if (IN == GF_IN_BN && in_x) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) { in_mu[e] = q.mean[4 * cq + e]; in_rs[e] = q.rstd[4 * cq + e]; in_g[e] = q.gamma[4 * cq + e]; in_b[e] = q.beta[4 * cq + e]; }
+    }
     auto fetch = [&](int c) {
 #pragma unroll
         for (int i = 0; i < VPT; ++i) {
@@ -260,6 +275,7 @@ __global__ __launch_bounds__(GF_THREADS) void gru_wgrad_frag_kernel(GruWfP p) {
                 const long tok = (long)(s / p.s_in) * p.stride_hi + (long)(s % p.s_in) * p.stride_lo + (long)(8 * w + (row & 7)) * p.stride_t;
                 xpre[i] = (!HAS_XB || c4 < 16) ? *reinterpret_cast<const f32x4*>(p.x + tok * 64 + 4 * c4)
                                                : *reinterpret_cast<const f32x4*>(p.xb + tok * 64 + 4 * (c4 - 16));
+                if (IN == GF_IN_ADD && in_x) xadd[i] = *reinterpret_cast<const f32x4*>(q.add + tok * 64 + 4 * c4);
             }
         }
         const float* base = p.frag + (long)c * (20 * 2 * 256) + lane * 4;
@@ -279,8 +295,14 @@ __global__ __launch_bounds__(GF_THREADS) void gru_wgrad_frag_kernel(GruWfP p) {
             if (NV % GF_THREADS == 0 || f < NV) {
                 const int row = f / (K / 4), c4 = f - row * (K / 4);
                 float* dst = gf_T + row * PITCH + 4 * c4;          // rows are 8-byte aligned (PITCH = 2 mod 4): two 8-byte stores
-                *reinterpret_cast<float2*>(dst) = make_float2(xpre[i][0], xpre[i][1]);
-                *reinterpret_cast<float2*>(dst + 2) = make_float2(xpre[i][2], xpre[i][3]);
+                f32x4 v = xpre[i];
+                if (IN == GF_IN_BN && in_x) {
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) v[e] = bn_affine_f(v[e], in_mu[e], in_rs[e], in_g[e], in_b[e]);
+                }
+                if (IN == GF_IN_ADD && in_x) v = v + xadd[i];
+                *reinterpret_cast<float2*>(dst) = make_float2(v[0], v[1]);
+                *reinterpret_cast<float2*>(dst + 2) = make_float2(v[2], v[3]);
             }
         }
     };
@@ -354,8 +376,32 @@ TATT_API int tatt_gru_wgrad_frag(const float* frag, const float* x, const float*
     const int nK = (int)((long)nseq * (T / 8) / 4);
     if (G < 1 || G > nK || G > 256) return 2;
     GruWfP p = {frag, x, xb, ws1, ws2, nK, T / 8, s_in, stride_hi, stride_lo, stride_t};
-    if (xb) hipLaunchKernelGGL(gru_wgrad_frag_kernel<true>, dim3(G), dim3(GF_THREADS), 0, st, p);
-    else hipLaunchKernelGGL(gru_wgrad_frag_kernel<false>, dim3(G), dim3(GF_THREADS), 0, st, p);
+    const GruWfIn q = {};
+    if (xb) hipLaunchKernelGGL((gru_wgrad_frag_kernel<true, GF_IN_NONE>), dim3(G), dim3(GF_THREADS), 0, st, p, q);
+    else hipLaunchKernelGGL((gru_wgrad_frag_kernel<false, GF_IN_NONE>), dim3(G), dim3(GF_THREADS), 0, st, p, q);
+    return LAUNCH_CHECK();
+}
+// tatt_gru_wgrad_frag for a block whose forward projection took its x through tatt_tokgemm_sb_in: the same transform is applied to x
+// while the chunk is staged (exactly one of: the four BatchNorm vectors, 64 floats each; in_add (M, 64) contiguous, 16-byte aligned, xb null),
+// so the weight gradients see the map the forward projected without it ever being written.
+TATT_API int tatt_gru_wgrad_frag_in(const float* frag, const float* x, const float* xb, float* ws1, float* ws2, int nseq, int T,
+                                    int s_in, long stride_hi, long stride_lo, long stride_t, int G, const float* in_mean,
+                                    const float* in_rstd, const float* in_gamma, const float* in_beta, const float* in_add,
+                                    hipStream_t st) {
+    if (nseq <= 0 || T <= 0 || T % 8 || ((long)nseq * (T / 8)) % 4 || s_in <= 0) return 1;
+    const int nK = (int)((long)nseq * (T / 8) / 4);
+    if (G < 1 || G > nK || G > 256) return 2;
+    const bool bn = in_mean && in_rstd && in_gamma && in_beta;
+    if (bn == (in_add != nullptr) || (!bn && (in_mean || in_rstd || in_gamma || in_beta))) return 1;
+    if (in_add && (((uintptr_t)in_add & 15) || xb)) return 1;
+    GruWfP p = {frag, x, xb, ws1, ws2, nK, T / 8, s_in, stride_hi, stride_lo, stride_t};
+    const GruWfIn q = {in_mean, in_rstd, in_gamma, in_beta, in_add};
+    if (xb) {
+        hipLaunchKernelGGL((gru_wgrad_frag_kernel<true, GF_IN_BN>), dim3(G), dim3(GF_THREADS), 0, st, p, q);
+    } else {
+        if (bn) hipLaunchKernelGGL((gru_wgrad_frag_kernel<false, GF_IN_BN>), dim3(G), dim3(GF_THREADS), 0, st, p, q);
+        else hipLaunchKernelGGL((gru_wgrad_frag_kernel<false, GF_IN_ADD>), dim3(G), dim3(GF_THREADS), 0, st, p, q);
+    }
     return LAUNCH_CHECK();
 }
 

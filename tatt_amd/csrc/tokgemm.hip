@@ -28,6 +28,12 @@ struct TokGemmP {
     const float* gate; float gate_scale;
     const float* addend;                             // Y = ... + addend (same shape as Y, one destination): a sum that leaves its operand intact
 };
+// input transform of columns [0, K1) (tatt_tokgemm_sb_in), applied in registers between the global load and the hi / lo split:
+// TG_IN_BN: BatchNorm from its statistics (64 channels each);  TG_IN_ADD: X1 + add, add (M, K1) contiguous
+#define TG_IN_NONE 0
+#define TG_IN_BN 1
+#define TG_IN_ADD 2
+struct TokGemmIn { const float* mean; const float* rstd; const float* gamma; const float* beta; const float* add; };
 
 __device__ __forceinline__ void tg_split(f32x4 v, uint2& hi, uint2& lo) {
     const tg_bf16x2 h0 = __builtin_convertvector((tg_f32x2){v[0], v[1]}, tg_bf16x2), h1 = __builtin_convertvector((tg_f32x2){v[2], v[3]}, tg_bf16x2);
@@ -39,8 +45,9 @@ __device__ __forceinline__ void tg_split(f32x4 v, uint2& hi, uint2& lo) {
 
 // NCB: 16-column blocks per wave (N = 64 NCB); KS: k-steps of 32 (K = 32 KS)
 // EPI: the dropout / gate epilogues are compiled in (kept out of the GruBlock instantiations, which sit at the register limit)
-template <int NCB, int KS, bool EPI>
-__global__ __launch_bounds__(512, 1) void tokgemm_sb_kernel(TokGemmP p) {
+// IN: the input transform compiled in (TG_IN_*; the GruBlock forward shapes only); q is read by those instantiations alone
+template <int NCB, int KS, bool EPI, int IN>
+__global__ __launch_bounds__(512, 1) void tokgemm_sb_kernel(TokGemmP p, TokGemmIn q) {
     constexpr int K = 32 * KS, N = 64 * NCB;
     constexpr int PW = K / 2 + 8;                            // tile pitch in 32-bit words (two bf16 each)
     constexpr int IMG = 64 * PW;                             // words of one image (hi or lo) of one tile
@@ -62,36 +69,61 @@ __global__ __launch_bounds__(512, 1) void tokgemm_sb_kernel(TokGemmP p) {
 #pragma unroll
     for (int cb = 0; cb < NCB; ++cb) bj[cb] = p.bias ? p.bias[16 * (nq * NCB + cb) + am] : 0.f;
     const int K2 = K - p.K1;
+    // input transform: 512 is a multiple of K / 4, so a thread stages the same channel quad of every row it touches; in_x1: that quad
+    // lies in X1 (the transformed half).  The BatchNorm constants wait in LDS behind the tile buffers ([mean | rstd | gamma | beta] x 64)
+    // and are read back per stash: held in registers across the products, the sixteen of them spill at K = 128
+    const int cq = 4 * (t % (K / 4));
+    const bool in_x1 = IN != TG_IN_NONE && cq < 64;          // (K1 = 64 for these instantiations: checked by the entry)
+    const float* const in_src = (cq < 64 ? p.X1 : p.X2) + (cq & 63);
+    float* const in_c = reinterpret_cast<float*>(tg_smem + 4 * IMG);
+    if (IN == TG_IN_BN) {
+        if (t < 256) in_c[t] = (t < 64 ? q.mean : t < 128 ? q.rstd : t < 192 ? q.gamma : q.beta)[t & 63];
+        __syncthreads();
+    }
     // this thread's share of a tile: F4 vectors; vector v covers row (idx / (K/4)), columns 4 (idx % (K/4)) ..
-    auto fetch = [&](int tl, f32x4 (&r)[F4]) {
+    // (ra: the addend of TG_IN_ADD, requested with X1 -- one tile ahead)
+    auto fetch = [&](int tl, f32x4 (&r)[F4], f32x4 (&ra)[IN == TG_IN_ADD ? F4 : 1]) {
 #pragma unroll
         for (int i = 0; i < F4; ++i) {
             const int idx = t + 512 * i, row = idx / (K / 4), c4 = 4 * (idx - row * (K / 4));
             const long m = (long)tl * 64 + row;
-            r[i] = c4 < p.K1 ? *reinterpret_cast<const f32x4*>(p.X1 + m * p.K1 + c4)
-                             : *reinterpret_cast<const f32x4*>(p.X2 + m * K2 + (c4 - p.K1));
+            if constexpr (IN == TG_IN_NONE) {
+                r[i] = c4 < p.K1 ? *reinterpret_cast<const f32x4*>(p.X1 + m * p.K1 + c4)
+                                 : *reinterpret_cast<const f32x4*>(p.X2 + m * K2 + (c4 - p.K1));
+            } else {                                         // K1 = 64 and K = 64 or 128: this thread's quad has one source, of row pitch 64
+                r[i] = *reinterpret_cast<const f32x4*>(in_src + m * 64);
+                if (IN == TG_IN_ADD) ra[i] = *reinterpret_cast<const f32x4*>(q.add + m * 64 + cq);
+            }
         }
     };
-    auto stash = [&](unsigned* buf, const f32x4 (&r)[F4]) {
+    auto stash = [&](unsigned* buf, const f32x4 (&r)[F4], const f32x4 (&ra)[IN == TG_IN_ADD ? F4 : 1]) {
 #pragma unroll
         for (int i = 0; i < F4; ++i) {
             const int idx = t + 512 * i, row = idx / (K / 4), c4 = 4 * (idx - row * (K / 4));
+            f32x4 v = r[i];
+            if (IN == TG_IN_BN && in_x1) {
+                const f32x4 mu = *reinterpret_cast<const f32x4*>(in_c + cq), rs = *reinterpret_cast<const f32x4*>(in_c + 64 + cq);
+                const f32x4 g = *reinterpret_cast<const f32x4*>(in_c + 128 + cq), b = *reinterpret_cast<const f32x4*>(in_c + 192 + cq);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) v[e] = bn_affine_f(v[e], mu[e], rs[e], g[e], b[e]);
+            }
+            if (IN == TG_IN_ADD && in_x1) v = v + ra[i];
             uint2 hi, lo;
-            tg_split(r[i], hi, lo);
+            tg_split(v, hi, lo);
             unsigned* d = buf + row * PW + c4 / 2;
             *reinterpret_cast<uint2*>(d) = hi;
             *reinterpret_cast<uint2*>(d + IMG) = lo;
         }
     };
-    f32x4 pre[F4];
-    fetch(tile, pre);
-    stash(tg_smem, pre);
+    f32x4 pre[F4], prea[IN == TG_IN_ADD ? F4 : 1];
+    fetch(tile, pre, prea);
+    stash(tg_smem, pre, prea);
     __syncthreads();
     int buf = 0;
     while (true) {
         const int next = tile + gridDim.x;
         const bool has_next = next < ntiles;
-        if (has_next) fetch(next, pre);
+        if (has_next) fetch(next, pre, prea);
         const unsigned* Xs = tg_smem + buf * 2 * IMG + (32 * mh + am) * PW + 4 * kq;
         // what the epilogue reads back from memory (the gate, the destination when accumulating) is requested BEFORE the products
         // (behind them the loads would queue between the stores: 51 us instead of 17 for the gated 128 x 128 launch); the small
@@ -165,7 +197,7 @@ __global__ __launch_bounds__(512, 1) void tokgemm_sb_kernel(TokGemmP p) {
             }
         }
         if (!has_next) break;
-        stash(tg_smem + (buf ^ 1) * 2 * IMG, pre);
+        stash(tg_smem + (buf ^ 1) * 2 * IMG, pre, prea);
         __syncthreads();
         tile = next;
         buf ^= 1;
@@ -236,15 +268,15 @@ TATT_API int tatt_tokgemm_pack_batch(const float* const* ptrs, const int* dims, 
     return LAUNCH_CHECK();
 }
 
-template <int NCB, int KS, bool EPI>
-static int tg_launch_epi(const TokGemmP& p, hipStream_t st) {
-    constexpr int lds = 2 * 2 * 64 * (32 * KS / 2 + 8) * 4;
+template <int NCB, int KS, bool EPI, int IN = TG_IN_NONE>
+static int tg_launch_epi(const TokGemmP& p, hipStream_t st, const TokGemmIn& q = TokGemmIn{}) {
+    constexpr int lds = 2 * 2 * 64 * (32 * KS / 2 + 8) * 4 + (IN == TG_IN_BN ? 4 * 64 * 4 : 0);
     static TattPerDevice once;
     tatt_per_device(once, [] {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(tokgemm_sb_kernel<NCB, KS, EPI>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(tokgemm_sb_kernel<NCB, KS, EPI, IN>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
     });
     const int ntiles = p.M / 64;
-    hipLaunchKernelGGL((tokgemm_sb_kernel<NCB, KS, EPI>), dim3(ntiles < 256 ? ntiles : 256), dim3(512), lds, st, p);
+    hipLaunchKernelGGL((tokgemm_sb_kernel<NCB, KS, EPI, IN>), dim3(ntiles < 256 ? ntiles : 256), dim3(512), lds, st, p, q);
     return LAUNCH_CHECK();
 }
 template <int NCB, int KS>
@@ -296,6 +328,24 @@ TATT_API int tatt_tokgemm_sb_add(const float* X, const float* Wp, const float* b
     if (M < 64 || M % 64 || !addend || addend == Y || N > 128 || K > 128) return 1;
     TokGemmP p = {X, nullptr, K, Wp, bias, Y, nullptr, N, M, ACT_NONE, 0, 0.f, nullptr, 0u, nullptr, 1.f, addend};
     return tg_dispatch(p, N, K, st);
+}
+// tatt_tokgemm_sb with an input transform of the X1 columns, for the forward projections of a GruBlock that follows a BatchNorm or a
+// residual sum (the normalised map / the sum is never written to memory).  Exactly one of the two:
+//   in_mean, in_rstd, in_gamma, in_beta (64 floats each): columns [0, K1) are (x - mean) * rstd * gamma + beta, rounded as tatt_bn_apply
+//   in_add (M, K1) contiguous, 16-byte aligned: columns [0, K1) are X1 + in_add; K = K1 only (the second prefetched map does not fit
+//   the registers of the K = 128 instantiation)
+// K1 = 64, N = 192, K = 64 or 128 (the columns from X2 pass unchanged); everything else as tatt_tokgemm_sb.
+TATT_API int tatt_tokgemm_sb_in(const float* X1, const float* X2, int K1, const float* Wp, const float* bias, float* Y1, float* Y2, int N1,
+                                int M, int N, int K, const float* in_mean, const float* in_rstd, const float* in_gamma,
+                                const float* in_beta, const float* in_add, hipStream_t st) {
+    if (M < 64 || M % 64 || K1 != 64 || N != 192 || (K != 64 && K != 128) || N1 < 0 || N1 > N || (K1 < K && !X2) || (N1 < N && !Y2)) return 1;
+    const bool bn = in_mean && in_rstd && in_gamma && in_beta;
+    if (bn == (in_add != nullptr) || (!bn && (in_mean || in_rstd || in_gamma || in_beta))) return 1;
+    if (in_add && (((uintptr_t)in_add & 15) || K != K1)) return 1;
+    TokGemmP p = {X1, X2, K1, Wp, bias, Y1, Y2, N1, M, ACT_NONE, 0, 0.f, nullptr, 0u, nullptr, 1.f, nullptr};
+    const TokGemmIn q = {in_mean, in_rstd, in_gamma, in_beta, in_add};
+    if (K == 128) return tg_launch_epi<3, 4, false, TG_IN_BN>(p, st, q);
+    return bn ? tg_launch_epi<3, 2, false, TG_IN_BN>(p, st, q) : tg_launch_epi<3, 2, false, TG_IN_ADD>(p, st, q);
 }
 // the (N, K) the kernel is instantiated for; anything else: 1
 template <class F> static int tg_shapes(int N, int K, const F& f) {

@@ -885,15 +885,22 @@ def gru_precompose_done():
 TOKGEMM_SB = True           # test / A-B hook: False -> the exact-fp32 MFMA GEMMs for the GRU input projections
 GRU_WGRAD_SB = True         # test / A-B hook: False -> three fp32-MFMA weight-gradient GEMMs per GruBlock instead of the fused pass
 GRU_WGRAD_FRAG = True       # test / A-B hook: False -> tatt_gru_wgrad_sb from dgi / dgh / hprev (round 3) instead of the fragment stream
+SRB_IN_FOLD = True          # test / A-B hook: False -> bn2 and the residual sum of a residual block are written out (tatt_bn_apply, tatt_axpby)
+                            # in front of gru1 / gru2 instead of being applied by the GruBlocks' own kernels on the way in
 
 
-def _tokgemm(X1, X2, Wpk, bias, N, K, N1=None):
-    """[X1 | X2] (M, K) @ W^T (+ bias) through tatt_tokgemm_sb -> (Y1 (M, N1), Y2 (M, N - N1) or None)"""
+def _tokgemm(X1, X2, Wpk, bias, N, K, N1=None, in_bn=None, in_add=None):
+    """[X1 | X2] (M, K) @ W^T (+ bias) through tatt_tokgemm_sb -> (Y1 (M, N1), Y2 (M, N - N1) or None).
+    in_bn = (mean, rstd, gamma, beta): X1 stands for its BatchNorm; in_add: for X1 + in_add (tatt_tokgemm_sb_in)"""
     M, K1 = X1.shape
     N1 = N if N1 is None else N1
     Y1 = ops.new(X1, M, N1)
     Y2 = ops.new(X1, M, N - N1) if N1 < N else None
-    ops.call("tatt_tokgemm_sb", ops.P(X1), ops.P(X2), K1, ops.P(Wpk), ops.P(bias), ops.P(Y1), ops.P(Y2), N1, M, N, K, ops.stream())
+    if in_bn is None and in_add is None:
+        ops.call("tatt_tokgemm_sb", ops.P(X1), ops.P(X2), K1, ops.P(Wpk), ops.P(bias), ops.P(Y1), ops.P(Y2), N1, M, N, K, ops.stream())
+    else:
+        ops.call("tatt_tokgemm_sb_in", ops.P(X1), ops.P(X2), K1, ops.P(Wpk), ops.P(bias), ops.P(Y1), ops.P(Y2), N1, M, N, K,
+                 *[ops.P(t) for t in (in_bn or (None,) * 4)], ops.P(in_add), ops.stream())
     return Y1, Y2
 
 
@@ -905,11 +912,20 @@ class GruBlockFn(Function):
         gi = W_ih (W_c x + b_c) + b_ih = (W_ih W_c) x + (W_ih b_c + b_ih)
     (a 192 x K matrix product of a few kFLOP) and the token matrix is streamed ONCE per direction of the pass instead of three
     times: forward = 1 GEMM + recurrence; backward = recurrence + 1 GEMM for dx (+1 for the concatenated half) + 2 split-K
-    GEMMs for the weight gradients; the gradients of W_ih, W_c, b_c follow from the composed ones by tiny products."""
+    GEMMs for the weight gradients; the gradients of W_ih, W_c, b_c follow from the composed ones by tiny products.
+
+    Folded input (`gru_block` decides; only where `_gru_in_foldable`): with in_mean .. in_beta, x is the PRE-BatchNorm map and the
+    block's input is its BatchNorm (train mode, statistics of ConvBnFn); with in_add, the input is x + in_add.  The token GEMM and
+    the weight-gradient pass apply the transform while they stage their operands (tatt_tokgemm_sb_in, tatt_gru_wgrad_frag_in:
+    bit for bit the map tatt_bn_apply / tatt_axpby would have written), so that map exists neither in the forward nor among the
+    saved activations; the backward turns the gradient of the input into those of x, gamma, beta (the ops.bn_bwd call of
+    BatchNormApplyFn.backward) or hands it to both addends."""
 
     @staticmethod
-    def forward(ctx, x, xb, conv_w, conv_b, wih_f, whh_f, bih_f, bhh_f, wih_r, whh_r, bih_r, bhh_r, vertical):
+    def forward(ctx, x, xb, conv_w, conv_b, wih_f, whh_f, bih_f, bhh_f, wih_r, whh_r, bih_r, bhh_r, vertical,
+                in_mean=None, in_rstd=None, in_gamma=None, in_beta=None, in_add=None):
         B, H, W, K1 = x.shape
+        in_bn = (in_mean, in_rstd, in_gamma, in_beta) if in_mean is not None else None
         Wc = conv_w.reshape(conv_w.shape[0], -1)                 # (64, K)
         K = Wc.shape[1]
         x2 = x.reshape(-1, K1)
@@ -928,14 +944,15 @@ class GruBlockFn(Function):
             Wfk, Wbk = ops.new(x, 192 * K), ops.new(x, 192 * K)
             ops.call("tatt_tokgemm_pack", ops.P(Wp), ops.P(Wfk), 192, K, K, 0, ops.stream())
             ops.call("tatt_tokgemm_pack", ops.P(Wp), ops.P(Wbk), K, 192, K, 1, ops.stream())
+        assert use_tg or (in_bn is None and in_add is None)
         if use_tg:
-            gi, _ = _tokgemm(x2, xb2, Wfk, bp, 192, K)
+            gi, _ = _tokgemm(x2, xb2, Wfk, bp, 192, K, in_bn=in_bn, in_add=None if in_add is None else in_add.reshape(-1, K1))
         else:
             gi = ops.linear_fwd(x2, Wp, bp, x2b=xb2)
             Wbk = None
         geom = ops.seq_geom(B, H, W, vertical)
         out, gates = ops.gru32_fwd(gi, whh_f, bhh_f, whh_r, bhh_r, geom, save=any(ctx.needs_input_grad))
-        ctx.save_for_backward(x, xb, Wc, Wp, gates, out, wih_f, whh_f, wih_r, whh_r, conv_b, Wbk)
+        ctx.save_for_backward(x, xb, Wc, Wp, gates, out, wih_f, whh_f, wih_r, whh_r, conv_b, Wbk, in_mean, in_rstd, in_gamma, in_beta, in_add)
         ctx.geom = geom
         ctx.wshape = conv_w.shape
         ctx.leaves = (conv_w, conv_b, wih_f, whh_f, bih_f, bhh_f, wih_r, whh_r, bih_r, bhh_r)
@@ -943,31 +960,42 @@ class GruBlockFn(Function):
 
     @staticmethod
     def backward(ctx, dout):
-        x, xb, Wc, Wp, gates, out, wih_f, whh_f, wih_r, whh_r, conv_b, Wbk = ctx.saved_tensors
+        x, xb, Wc, Wp, gates, out, wih_f, whh_f, wih_r, whh_r, conv_b, Wbk, in_mean, in_rstd, in_gamma, in_beta, in_add = ctx.saved_tensors
         K1 = x.shape[-1]
         K = Wc.shape[1]
         x2 = x.reshape(-1, K1)
         xb2 = xb.reshape(-1, K - K1) if xb is not None else None
+        in_bn = (in_mean, in_rstd, in_gamma, in_beta) if in_mean is not None else None
+        add2 = in_add.reshape(-1, K1) if in_add is not None else None
+        folded = in_bn is not None or in_add is not None
+        need_dx = ctx.needs_input_grad[0] or any(ctx.needs_input_grad[13:])        # (the gradient of the block's input, whoever receives it)
         # round 4: the recurrence leaves the weight-gradient pass's operands in MFMA fragment order (no dgh / hprev round trip)
-        use_frag = (GRU_WGRAD_FRAG and GRU_WGRAD_SB and K in (64, 128) and K1 == 64 and ops.gru_frag_ok(ctx.geom)
-                    and x2.is_contiguous() and (xb2 is None or xb2.is_contiguous()))
+        # (a folded input was admitted on these conditions in the forward, `_gru_in_foldable`: its weight gradients have this route only)
+        use_frag = folded or (GRU_WGRAD_FRAG and GRU_WGRAD_SB and K in (64, 128) and K1 == 64 and ops.gru_frag_ok(ctx.geom)
+                              and x2.is_contiguous() and (xb2 is None or xb2.is_contiguous()))
         dgh = hprev = frag = None
         if use_frag:
             dgi, frag = ops.gru32_bwd_frag(gates, out, _c(dout).reshape(-1, 64), whh_f, whh_r, ctx.geom)
         else:
             dgi, dgh, hprev = ops.gru32_bwd(gates, out, _c(dout).reshape(-1, 64), whh_f, whh_r, ctx.geom)
         dxb = None
-        if Wbk is not None and ctx.needs_input_grad[0] and (xb is None or ctx.needs_input_grad[1]):
+        if Wbk is not None and need_dx and (xb is None or ctx.needs_input_grad[1]):
             dx, dxb = _tokgemm(dgi, None, Wbk, None, K, 192, K1)      # dx | dxb = dgi Wp on the bf16 matrix cores (split operands)
             dx = dx.reshape(x.shape)
             dxb = dxb.reshape(xb.shape) if xb is not None else None
-        elif xb is not None and ctx.needs_input_grad[0] and ctx.needs_input_grad[1] and K == 2 * K1:
+        elif xb is not None and need_dx and ctx.needs_input_grad[1] and K == 2 * K1:
             dx, dxb = ops.linear_bwd_input_halves(dgi, Wp)          # both halves of the concatenated input: one launch
             dx, dxb = dx.reshape(x.shape), dxb.reshape(xb.shape)
         else:
-            dx = ops.linear_bwd_input(dgi, Wp, col0=0, ncols=K1).reshape(x.shape) if ctx.needs_input_grad[0] else None
+            dx = ops.linear_bwd_input(dgi, Wp, col0=0, ncols=K1).reshape(x.shape) if need_dx else None
             if xb is not None and ctx.needs_input_grad[1]:
                 dxb = ops.linear_bwd_input(dgi, Wp, col0=K1, ncols=K - K1).reshape(xb.shape)
+        dgam = dbet = dadd = None
+        if in_bn is not None and dx is not None:                      # dx is the gradient of bn(x): BatchNormApplyFn.backward's call
+            dx, dgam, dbet = ops.bn_bwd(x2, dx.reshape(-1, K1), in_mean, in_rstd, in_gamma, in_beta, ACT_NONE, True)
+            dx = dx.reshape(x.shape)
+        elif in_add is not None:
+            dadd = dx                                                 # the sum hands its gradient to both addends
         geom = ctx.geom
 
         def param_grads():
@@ -976,7 +1004,7 @@ class GruBlockFn(Function):
             dWp = ops.new(dgi, 192, K)
             if use_frag:
                 dWhh = ops.new(dgi, 192, 32)                          # compact: [forward; reverse]
-                ops.gru_wgrad_frag(frag, x2, xb2, geom, dWp, dWhh, dbp, dbhh)
+                ops.gru_wgrad_frag(frag, x2, xb2, geom, dWp, dWhh, dbp, dbhh, in_bn=in_bn, in_add=add2)
             elif GRU_WGRAD_SB and K in (64, 128) and K1 == 64 and ops.gru_wgrad_fusable(dgi, dgh, x2, xb2, hprev):
                 dWhh = ops.new(dgi, 192, 64)                          # one pass over the tokens for all four results (split-bf16 MFMA)
                 ops.gru_wgrad_sb(dgi, dgh, x2, xb2, hprev, dWp, dWhh, dbp, dbhh)
@@ -993,16 +1021,43 @@ class GruBlockFn(Function):
                      ops.P(wih_f), ops.P(wih_r), ops.P(dwih_f), ops.P(dwih_r), ops.P(dWc), ops.P(dbc), K, ops.P(dWhh),
                      ops.P(dwhh_f), ops.P(dwhh_r), ops.stream())
             return (dWc.reshape(ctx.wshape), dbc, dwih_f, dwhh_f, dbp[:96], dbhh[:96], dwih_r, dwhh_r, dbp[96:], dbhh[96:])
-        return (dx, dxb) + tuple(SIDE.submit(ctx.leaves, param_grads, dgi, dgh, hprev, frag, x, xb, Wp, Wc)) + (None,)
+        # (everything the deferred closure reads is kept alive: see ConvBnFn.backward)
+        pg = SIDE.submit(ctx.leaves, param_grads, dgi, dgh, hprev, frag, x, xb, Wp, Wc, in_mean, in_rstd, in_gamma, in_beta, in_add)
+        return (dx, dxb) + tuple(pg) + (None, None, None, dgam, dbet, dadd)
+
+
+def _gru_in_foldable(x, xb, blk, vertical, is_sum):
+    """Do both kernels that can apply an input transform take this GruBlock?  The token GEMM (TOKGEMM_SB and its shapes) and the
+    fragment route of the weight gradients; K1 = 64; a sum only without a concatenated half."""
+    if not (SRB_IN_FOLD and TOKGEMM_SB and GRU_WGRAD_FRAG and GRU_WGRAD_SB) or not x.is_cuda or x.dtype != torch.float32:
+        return False
+    B, H, W, K1 = x.shape
+    Wc = blk.conv1.weight
+    K = Wc.numel() // Wc.shape[0]
+    if K1 != 64 or K != K1 + (0 if xb is None else xb.shape[-1]) or K not in (64, 128) or (is_sum and xb is not None):
+        return False
+    return (B * H * W) % 64 == 0 and ops.gru_frag_ok(ops.seq_geom(B, H, W, vertical))
 
 
 def gru_block(x, blk, vertical, xb=None):
-    """blk: a GruBlock parameter holder (conv1 = 1x1 nn.Conv2d, gru = nn.GRU(64, 32, bidirectional))."""
+    """blk: a GruBlock parameter holder (conv1 = 1x1 nn.Conv2d, gru = nn.GRU(64, 32, bidirectional)).
+    x: the input map, or (y, mean, rstd, gamma, beta) = "the train-mode BatchNorm of y under these statistics" (ConvBnFn's), or
+    (a, b) = "a + b": where `_gru_in_foldable`, the block's kernels apply the transform themselves; anywhere else the map is
+    written out first (BatchNormApplyFn / AddFn) and the block proceeds on it."""
     g = blk.gru
-    return GruBlockFn.apply(_c(x), None if xb is None else _c(xb), blk.conv1.weight, blk.conv1.bias,
+    xb = None if xb is None else _c(xb)
+    extra = (None,) * 5
+    if isinstance(x, tuple):
+        x0 = _c(x[0])
+        if _gru_in_foldable(x0, xb, blk, vertical, len(x) == 2):
+            extra = (x[1], x[2], x[3], x[4], None) if len(x) == 5 else (None, None, None, None, _c(x[1]))
+            x = x0
+        else:
+            x = BatchNormApplyFn.apply(x[0], x[1], x[2], x[3], x[4], ACT_NONE) if len(x) == 5 else add(x[0], x[1])
+    return GruBlockFn.apply(_c(x), xb, blk.conv1.weight, blk.conv1.bias,
                             g.weight_ih_l0, g.weight_hh_l0, g.bias_ih_l0, g.bias_hh_l0,
                             g.weight_ih_l0_reverse, g.weight_hh_l0_reverse, g.bias_ih_l0_reverse, g.bias_hh_l0_reverse,
-                            vertical)
+                            vertical, *extra)
 
 
 # --------------------------------------------------------------------------------------------------

@@ -977,16 +977,21 @@ def gru32_bwd_frag(gates, out, dout, whh_f, whh_r, geom):
 GRU_WGRAD_FRAG_GROUPS = 128   # persistent work-groups (= partial slabs) of tatt_gru_wgrad_frag
 
 
-def gru_wgrad_frag(frag, x2, xb2, geom, dWp, dWhh_c, dbp, dbhh):
+def gru_wgrad_frag(frag, x2, xb2, geom, dWp, dWhh_c, dbp, dbhh, in_bn=None, in_add=None):
     """dWp (192, K) = dgi^T [x2 | xb2], dbp = dgi.sum(0), dWhh_c (192, 32) = [dW_hh fwd; dW_hh rev], dbhh = dgh.sum(0) from the
-    fragment stream of gru32_bwd_frag: one streaming pass (tatt_gru_wgrad_frag) + two (deferrable) split-K reductions."""
+    fragment stream of gru32_bwd_frag: one streaming pass (tatt_gru_wgrad_frag) + two (deferrable) split-K reductions.
+    in_bn = (mean, rstd, gamma, beta): x2 stands for its BatchNorm; in_add: for x2 + in_add (tatt_gru_wgrad_frag_in)."""
     _check_dev(frag)
     nseq, T = geom[0], geom[1]
     K = 128 if xb2 is not None else 64
     G = max(1, min(nseq * T // 32, GRU_WGRAD_FRAG_GROUPS, 256))
     ws1 = _split_ws(new(frag, G * 192 * K + G * 192))
     ws2 = _split_ws(new(frag, G * 192 * 32 + G * 192))
-    call("tatt_gru_wgrad_frag", P(frag), P(x2), P(xb2), P(ws1), P(ws2), *geom, G, stream())
+    if in_bn is None and in_add is None:
+        call("tatt_gru_wgrad_frag", P(frag), P(x2), P(xb2), P(ws1), P(ws2), *geom, G, stream())
+    else:
+        call("tatt_gru_wgrad_frag_in", P(frag), P(x2), P(xb2), P(ws1), P(ws2), *geom, G, *[P(t) for t in (in_bn or (None,) * 4)],
+             P(in_add), stream())
     call("tatt_splitk_reduce", P(ws1), P(dWp), 192, K, G, 0, 0, 0.0, P(dbp), 192, stream())
     call("tatt_splitk_reduce", P(ws2), P(dWhh_c), 192, 32, G, 0, 0, 0.0, P(dbhh), 192, stream())
 

@@ -298,6 +298,11 @@ def _srb(x, tp_map, blk: RecurrentResidualBlock):
         else:
             y1, st1 = Fh.conv_bn(x, blk.conv1, blk.bn1)
             y2, st2 = Fh.conv_bn(y1, blk.conv2, blk.bn2, prev=(st1, blk.bn1, ACT_MISH))
+            if Fh.SRB_IN_FOLD:
+                # bn2 and the residual sum are per-element and feed one consumer each, the token GEMM of gru1 / gru2: the GruBlocks
+                # apply them on the way in (where their kernels can; else they write the map out as below): 2 launches and ~63 MB less
+                r = Fh.gru_block((y2, st2[0], st2[1], blk.bn2.weight, blk.bn2.bias), blk.gru1, True, xb=tp_map)
+                return Fh.gru_block((x_res, r), blk.gru2, False)
             r = Fh.bn_apply_stats(y2, st2, blk.bn2, ACT_NONE)
     else:
         r = Fh.conv2d(x, blk.conv1.weight, blk.conv1.bias)
