@@ -973,7 +973,7 @@ int tatt_affine_sample_fwd(const float* x, long xsn, long xsc, long xsh, long xs
 int tatt_affine_sample_bwd(const float* theta, const float* dout, float* dimg, int B, int C, int H, int W,
                            hipStream_t st);
 
-/* ---- the ASTER recogniser (reference model/recognizer/; csrc/aster.hip) ------------------------------------------------------------ */
+/* ---- the ASTER recogniser (reference model/recognizer/; csrc/aster.hip, its decoder csrc/attndec.hip) ------------------------------- */
 /* y (B,C,Ho,Wo contiguous) = F.interpolate(x, (Ho, Wo), mode="bilinear", align_corners=True) (recognizer_builder.py:77: the STN head
  * reads the image squeezed to 32 x 64); x[b*xsn + c*xsc + h*xsh + w*xsw] */
 int tatt_resize_bilinear_ac(const float* x, long xsn, long xsc, long xsh, long xsw, float* y, int B, int C, int H, int W,
@@ -1005,7 +1005,7 @@ int tatt_attn_decode(const float* x, const float* xproj, const float* WsT, const
 int tatt_beam_backtrack(const int* sym, const int* pred, const float* score, int* ids, int* ws, int L, int B, int K, int eos,
                         hipStream_t st);
 
-/* ---- the MORAN recogniser (reference model/moran/; csrc/moran.hip) ------------------------------------------------------------------ */
+/* ---- the MORAN recogniser (reference model/moran/; csrc/moran.hip, its decoder csrc/attndec.hip) ------------------------------------ */
 /* The tail of the MORN rectifier in ONE launch (morn.py:62-69 for the first pass, :76-82 for the second).  o (B,h,w): the offsets
  * network's output.  Per output pixel of the Ho x Wo regular grid (the reference's fp32 grid: float64 arange * 2 / (n - 1) - 1 rounded
  * once): g = grid_sample(maxpool_{2,1}(relu(o)) - maxpool_{2,1}(relu(-o)), grid); acc (B,Ho,Wo) = g if `first` else acc + g;

@@ -14,8 +14,10 @@ backward and the sequence cross entropy are not part of this package.
 All arithmetic runs in HIP kernels (no CPU fallback).  Eval BatchNorm is folded into the preceding convolution / linear layer on the
 device (tatt_bn_fold); the convolutions are the shared implicit-GEMM kernels on strided views (a strided 1 x 1 convolution is a
 stride-1 one on a sub-sampled view); the BiLSTM layers are `infer.bilstm_eval` (one launch per layer); the attention decoder's
-`max_len_labels` steps are ONE launch (tatt_attn_decode, csrc/aster.hip), with `decode_eager` as the step-by-step route on the shared
-operators for geometries that launch refuses (and as the timing yardstick of tools/bench_aster.py).
+`max_len_labels` steps are ONE launch (tatt_attn_decode, csrc/attndec.hip), with `decode_eager` as the step-by-step route on the shared
+operators for geometries that launch refuses (and as the timing yardstick of tools/bench_aster.py).  The decoder itself -- its
+operands, the launch, one step -- is attn_decoder.py, shared with MORAN; here are ASTER's `DecoderSpec` and what ASTER does with a
+step's logits.
 
 Early exit: a greedy row stops at its first EOS, and a beam whose five hypotheses have all ended only keeps its bookkeeping going.
 What `get_string_aster` reads -- the ids up to and including a row's first EOS -- equals the reference's; beyond a greedy row's
@@ -30,20 +32,18 @@ import numpy as np
 import torch
 from torch import nn
 
+from . import attn_decoder as AD
 from . import functional as Fh
 from . import ops
-from ._lib import LIB
-from .ops import ACT_NONE, ACT_RELU, ACT_TANH
+from .attn_decoder import BEAM_WIDTH, Prepared, _require, add_relu, encoder_tail, infer_bilstm      # noqa: F401 (add_relu: public here)
+from .ops import ACT_NONE, ACT_RELU
 from .tsrn import _Holder, STNHead, TPSSpatialTransformer
 
 TPS_INPUTSIZE = (32, 64)          # recognizer_builder.py:20-24
 TPS_OUTPUTSIZE = (32, 100)
 NUM_CONTROL_POINTS = 20
 TPS_MARGINS = (0.05, 0.05)
-BEAM_WIDTH = 5
 MODES = {"forced": 0, "greedy": 1, "beam": 2}
-
-DECODE_ONE_LAUNCH = True          # test / A-B hook: False -> `ASTER.decode` always takes `decode_eager`
 LAUNCHES = {"one_launch": 0, "eager": 0}      # how often each decoder route ran (tests, tools/bench_aster.py)
 
 
@@ -187,34 +187,27 @@ def grid_sample_sized(x_nchw, src, size):
     return out
 
 
-def add_relu(a, b):
-    assert a.shape == b.shape and a.is_contiguous() and b.is_contiguous()
-    y = torch.empty_like(a)
-    ops.call("tatt_add_relu", ops.P(a), ops.P(b), ops.P(y), a.numel(), ops.stream())
-    return y
+def _entry_args(v):
+    """tatt_attn_decode's arguments in the order of include/tatt_hip.h"""
+    return (v["x"], v["xproj"], v["WsT"], v["bs"], v["wv"], v["wb"], v["E2"], v["WicT"], v["WhhT"], v["bhh"], v["fcT"], v["fcb"], v["targets"],
+            v["logits"], v["ids"], v["scores"], v["B"], v["T"], v["C"], v["L"], v["D"], v["D"], v["D"], v["eos"], v["mode"], v["beam"])
 
 
-def gru_cell(gi, gh, h):
-    R, H = h.shape
-    out = torch.empty_like(h)
-    ops.call("tatt_gru_cell", ops.P(gi), ops.P(gh), ops.P(h), ops.P(out), R, H, ops.stream())
-    return out
+def decoder_spec(head: AttentionRecognitionHead):
+    """ASTER's head as attn_decoder sees it: <BOS> = the embedding's last row starts a row, an arg-max is its own embedding row, forced
+    step i reads targets[:, i - 1]; forced decoding returns the logits, greedy and beam (ids, scores)"""
+    du = head.decoder
+    au, gru = du.attention_unit, du.gru
+    return AD.DecoderSpec(Ws=au.sEmbed.weight, bs=au.sEmbed.bias, Wx=au.xEmbed.weight, bx=au.xEmbed.bias, wv=au.wEmbed.weight,
+                          wb=au.wEmbed.bias, emb=du.tgt_embedding.weight, Wih=gru.weight_ih_l0, bih=gru.bias_ih_l0, Whh=gru.weight_hh_l0,
+                          bhh=gru.bias_hh_l0, Wfc=du.fc.weight, bfc=du.fc.bias, emb_first=True, y0=head.num_classes, yadd=0, tshift=-1,
+                          dims=(head.sDim, head.attDim, head.in_planes), D=512, max_T=32, max_C=128, max_L=100, entry="tatt_attn_decode", entry_args=_entry_args,
+                          outputs={0: ("logits",), 1: ("ids", "scores"), 2: ("ids", "scores")})
 
 
 def decoder_operands(head: AttentionRecognitionHead):
-    """What tatt_attn_decode reads, from the decoder's parameters: the transposed weights and E2 = tgt_embedding W_ih[:, :att]^T + b_ih
-    (step-invariant; one GEMM).  Built once per parameter set by `ASTER`; tests call it directly."""
-    du = head.decoder
-    au, gru = du.attention_unit, du.gru
-    att = head.attDim
-    C1 = du.tgt_embedding.weight.shape[0]
-    G = gru.weight_ih_l0.shape[0]
-    E2 = ops.new(gru.weight_ih_l0, C1, G)
-    W = gru.weight_ih_l0                              # (3 sDim, att + xDim): B(k, j) = W[j, k] for k < att
-    ops.gemm(du.tgt_embedding.weight, att, 1, W, 1, W.shape[1], E2, G, 1, C1, G, att, bias=gru.bias_ih_l0)
-    return {"WsT": au.sEmbed.weight.t().contiguous(), "bs": au.sEmbed.bias, "wv": au.wEmbed.weight.reshape(-1).contiguous(),
-            "wb": au.wEmbed.bias, "E2": E2, "WicT": W[:, att:].t().contiguous(), "WhhT": gru.weight_hh_l0.t().contiguous(),
-            "bhh": gru.bias_hh_l0, "fcT": du.fc.weight.t().contiguous(), "fcb": du.fc.bias}
+    """What tatt_attn_decode reads (`attn_decoder.operands`).  Built once per parameter set by `ASTER`; tests call it directly."""
+    return AD.operands(decoder_spec(head))
 
 
 def _check_mode(head, mode, targets, x):
@@ -233,31 +226,10 @@ def attn_decode(head: AttentionRecognitionHead, x, mode, eos=0, targets=None, op
     geometry (the caller takes `decode_eager`)."""
     ops._check_dev(x)
     L = _check_mode(head, mode, targets, x)
-    B, T, D = x.shape
-    C = head.num_classes
-    du = head.decoder
-    xc = Fh._c(x)
-    if head.sDim != 512 or head.attDim != 512 or D != 512 or T > 32 or not 2 <= C <= 128 or L > 100 or (mode == 2 and C < 5):
-        return None                                   # (what the entry point itself refuses; asked first so that no operand is built)
-    op = operands if operands is not None else decoder_operands(head)
-    xproj = ops.linear_fwd(xc.reshape(B * T, D), du.attention_unit.xEmbed.weight, du.attention_unit.xEmbed.bias)
-    logits = ids = scores = tg = None
-    if mode == 0:
-        tg = targets.to(device=x.device, dtype=torch.int32).contiguous()
-        logits = ops.new(x, B, L, C)
-    else:
-        ids = torch.empty(B, L, dtype=torch.int32, device=x.device)
-        scores = ops.new(x, B, L)
-    rc = getattr(LIB, "tatt_attn_decode")(ops.P(xc), ops.P(xproj), ops.P(op["WsT"]), ops.P(op["bs"]), ops.P(op["wv"]), ops.P(op["wb"]),
-                                          ops.P(op["E2"]), ops.P(op["WicT"]), ops.P(op["WhhT"]), ops.P(op["bhh"]), ops.P(op["fcT"]),
-                                          ops.P(op["fcb"]), ops.P(tg), ops.P(logits), ops.P(ids), ops.P(scores), B, T, C, L, head.sDim,
-                                          head.attDim, D, int(eos), mode, BEAM_WIDTH, ops.stream())
-    if rc == 1:
-        return None
-    if rc != 0:
-        raise RuntimeError("tatt_attn_decode failed with code %d" % rc)
-    LAUNCHES["one_launch"] += 1
-    return logits if mode == 0 else (ids, scores)
+    out = AD.one_launch(decoder_spec(head), x, mode, L, eos, targets, operands)
+    if out is not None:
+        LAUNCHES["one_launch"] += 1
+    return out
 
 
 def beam_backtrack(sym, pred, score, eos):
@@ -297,22 +269,13 @@ def decode_eager(head: AttentionRecognitionHead, x, mode, eos=0, targets=None):
     """`attn_decode` step by step on the shared operators (about a dozen launches per step; torch does the beam's bookkeeping, one
     launch its backtracking: tatt_beam_backtrack): the route for geometries the one launch refuses, and the timing yardstick.  Same
     results, same tie rule, and like the one launch no host synchronisation."""
-    ops._check_dev(x)
     L = _check_mode(head, mode, targets, x)
-    B, T, D = x.shape
-    C, sD, aD = head.num_classes, head.sDim, head.attDim
-    du = head.decoder
-    au, gru = du.attention_unit, du.gru
+    B, C, dev = x.shape[0], head.num_classes, x.device
     K = BEAM_WIDTH if mode == 2 else 1
     R = B * K
-    dev = x.device
-    xc = Fh._c(x)
-    xproj = ops.linear_fwd(xc.reshape(B * T, D), au.xEmbed.weight, au.xEmbed.bias).view(B, T, aD)
-    xr = xc if K == 1 else xc.repeat_interleave(K, 0).contiguous()
-    xp_tr = (xproj if K == 1 else xproj.repeat_interleave(K, 0)).permute(1, 0, 2).contiguous().view(T * R, aD)     # row t * R + r
-    s = torch.zeros(R, sD, device=dev)
+    step = AD.Step(decoder_spec(head), x, K)
+    s = torch.zeros(R, head.sDim, device=dev)
     y = torch.full((R,), C, dtype=torch.long, device=dev)
-    seed = Fh.seed_tensor(dev)
     if mode == 2:
         seq = torch.full((B, K), float("-inf"), device=dev)
         seq[:, 0] = 0.0
@@ -321,18 +284,7 @@ def decode_eager(head: AttentionRecognitionHead, x, mode, eos=0, targets=None):
         st_sym, st_pred, st_score = [], [], []
     outs, out_ids, out_scores = [], [], []
     for i in range(L):
-        sproj = ops.linear_fwd(s, au.sEmbed.weight, au.sEmbed.bias)
-        th = ops.act_fwd(ops.add_rowbcast(xp_tr, sproj, R), ACT_TANH)
-        e = ops.new(x, R, T)
-        ops.gemm(th, aD, 1, au.wEmbed.weight, 1, 0, e, T, 1, R, 1, aD, bias=au.wEmbed.bias, Z=T, bsA=R * aD, bsC=1)
-        ops.call("tatt_softmax_rows_fwd", ops.P(e), None, R, T, 0.0, ops.P(seed), 0, ops.stream())
-        ctx = ops.new(x, R, D)
-        ops.gemm(e, T, 1, xr, D, 1, ctx, D, 1, 1, D, T, Z=R, bsA=T, bsB=T * D, bsC=D)
-        yproj = du.tgt_embedding.weight.index_select(0, y)
-        gi = ops.linear_fwd(yproj, gru.weight_ih_l0, gru.bias_ih_l0, x2b=ctx)
-        gh = ops.linear_fwd(s, gru.weight_hh_l0, gru.bias_hh_l0)
-        s = gru_cell(gi, gh, s)
-        logits = ops.linear_fwd(s, du.fc.weight, du.fc.bias)
+        logits, s = step(s, y)
         if mode == 0:
             outs.append(logits)
             y = targets[:, i].to(dev).long().clamp(0, C)
@@ -367,7 +319,7 @@ def decode_eager(head: AttentionRecognitionHead, x, mode, eos=0, targets=None):
 
 
 # ---- the recogniser ----------------------------------------------------------------------------------------------------------------
-class ASTER(nn.Module):
+class ASTER(Prepared):
     """Drop-in for the reference's RecognizerBuilder (eval only; see the module docstring)."""
 
     def __init__(self, arch="ResNet_ASTER", rec_num_classes=97, sDim=512, attDim=512, max_len_labels=100, eos=94, STN_ON=True):
@@ -383,42 +335,28 @@ class ASTER(nn.Module):
         if STN_ON:
             self.tps = TPSSpatialTransformer(output_image_size=TPS_OUTPUTSIZE, num_control_points=NUM_CONTROL_POINTS, margins=TPS_MARGINS)
             self.stn_head = STNHead(in_planes=3, num_ctrlpoints=NUM_CONTROL_POINTS, activation="none")
-        self._prep = None
         self.info = None              # optional AsterInfo: the vocabulary `io.evaluate` decodes with (None: the one with rec_num_classes classes)
 
-    # -- derived operands (folded filters, the decoder's transposed weights), rebuilt when a parameter or buffer changed.  A change is seen
-    # through the tensors' addresses and version counters: a write that bumps no counter (through `.data`, or by a kernel of this library)
-    # leaves the derived operands stale -- assign through `load_state_dict` / `copy_` / in-place torch operators.  The check walks all
-    # ~500 tensors, so `read` does it once and hands the result to its stages (`prep=`).
-    def _signature(self):
-        return tuple((t.data_ptr(), t._version) for t in list(self.parameters()) + list(self.buffers()))
+    def _derive(self):
+        from .infer import bn_fold
+        folds = {}
 
-    def _prepared(self):
-        sig = self._signature()
-        if self._prep is None or self._prep["sig"] != sig:
-            from .infer import bn_fold
-            folds = {}
+        def fold(key, lin, bn):
+            folds[key] = bn_fold(lin.weight, lin.bias, bn)
 
-            def fold(key, lin, bn):
-                w = lin.weight
-                folds[key] = bn_fold(w, lin.bias, bn)
-
-            fold("l0", self.encoder.layer0[0], self.encoder.layer0[1])
-            for li in range(1, 6):
-                for bi, blk in enumerate(getattr(self.encoder, "layer%d" % li)):
-                    fold((li, bi, 1), blk.conv1, blk.bn1)
-                    fold((li, bi, 2), blk.conv2, blk.bn2)
-                    if blk.downsample is not None:
-                        fold((li, bi, 0), blk.downsample[0], blk.downsample[1])
-            if self.STN_ON:
-                for i in (0, 2, 4, 6, 8, 10):
-                    fold(("stn", i), self.stn_head.stn_convnet[i][0], self.stn_head.stn_convnet[i][1])
-                fold("fc1", self.stn_head.stn_fc1[0], self.stn_head.stn_fc1[1])
-            operands = None
-            if self.sDim == 512 and self.attDim == 512 and 2 <= self.rec_num_classes <= 128:
-                operands = decoder_operands(self.decoder)
-            self._prep = {"sig": sig, "folds": folds, "operands": operands}
-        return self._prep
+        fold("l0", self.encoder.layer0[0], self.encoder.layer0[1])
+        for li in range(1, 6):
+            for bi, blk in enumerate(getattr(self.encoder, "layer%d" % li)):
+                fold((li, bi, 1), blk.conv1, blk.bn1)
+                fold((li, bi, 2), blk.conv2, blk.bn2)
+                if blk.downsample is not None:
+                    fold((li, bi, 0), blk.downsample[0], blk.downsample[1])
+        if self.STN_ON:
+            for i in (0, 2, 4, 6, 8, 10):
+                fold(("stn", i), self.stn_head.stn_convnet[i][0], self.stn_head.stn_convnet[i][1])
+            fold("fc1", self.stn_head.stn_fc1[0], self.stn_head.stn_fc1[1])
+        spec = decoder_spec(self.decoder)
+        return {"folds": folds, "operands": AD.operands(spec) if spec.takes() else None}
 
     # -- the stages
     def control_points(self, images, prep=None):
@@ -462,14 +400,8 @@ class ASTER(nn.Module):
                 else:
                     res = h
                 h = add_relu(o, res)
-        B, Hh, Wd, Cc = h.shape
-        if Hh != 1:
-            raise ValueError("tatt_amd.ASTER reads images 32 pixels high (the feature map must be one row high, got %d)" % Hh)
-        seq = Fh._c(h.reshape(B, Wd, Cc).permute(1, 0, 2))                     # time-major for the LSTM kernels
         rnn = self.encoder.rnn
-        seq = infer_bilstm(seq, rnn)
-        seq = infer_bilstm(seq, _Layer1View(rnn))
-        return Fh._c(seq.permute(1, 0, 2))
+        return encoder_tail(h, (lambda seq: infer_bilstm(seq, rnn), lambda seq: infer_bilstm(seq, _Layer1View(rnn))), "ASTER")
 
     def features(self, images, prep=None):
         _require(images)
@@ -479,9 +411,7 @@ class ASTER(nn.Module):
 
     def decode(self, feats, decode="beam", targets=None, prep=None):
         mode = MODES[decode]
-        out = None
-        if DECODE_ONE_LAUNCH:
-            out = attn_decode(self.decoder, feats, mode, self.eos, targets, operands=(prep or self._prepared())["operands"])
+        out = attn_decode(self.decoder, feats, mode, self.eos, targets, operands=(prep or self._prepared())["operands"])
         if out is None:
             out = decode_eager(self.decoder, feats, mode, self.eos, targets)
         return out
@@ -503,13 +433,3 @@ class ASTER(nn.Module):
         ids, scores = self.read(input_dict["images"], "beam")
         return {"losses": {}, "output": {"pred_rec": ids, "pred_rec_score": scores}}
 
-
-def infer_bilstm(seq, rnn):
-    from .infer import bilstm_eval
-    return bilstm_eval(seq, rnn)
-
-
-def _require(x):
-    if not x.is_cuda:
-        raise RuntimeError("tatt_amd: inputs must be on an AMD GPU (x.device=%s); the product path has no CPU fallback (the CPU "
-                           "restatement lives in tests/ and is test infrastructure)." % x.device)

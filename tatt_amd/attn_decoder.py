@@ -1,0 +1,195 @@
+"""What the attention recognisers (aster.py, moran.py) share: the attention decoder both heads run, and the plumbing around it.
+
+The two decoders are one algorithm -- additive attention over the encoder positions, context, one GRU cell, a linear head -- and differ
+in data only, which a `DecoderSpec` states: the parameter tensors, the column order of `W_ih`, three token conventions, the sizes the one
+launch takes and its C entry (csrc/attndec.hip).  On a spec work
+  `operands`    the transposed weights and E2 the one launch reads (built once per parameter set),
+  `one_launch`  all L steps in ONE launch, or None where the launch refuses the geometry,
+  `Step`        one step on the shared operators (about a dozen launches): the route for refused geometries and the tests' second
+                implementation.
+What is done with a step's logits (EOS masking, the beam's bookkeeping, arg-max + 1) stays with the recognisers.
+
+Also here: `Prepared` (the cache of operands derived from a recogniser's parameters), `encoder_tail`, `add_relu`, `gru_cell`.
+"""
+from __future__ import annotations
+
+from dataclasses import dataclass
+from typing import Callable, Optional
+
+import torch
+from torch import nn
+
+from . import functional as Fh
+from . import ops
+from ._lib import LIB
+from .ops import ACT_TANH
+
+BEAM_WIDTH = 5
+
+
+def _require(x):
+    if not x.is_cuda:
+        raise RuntimeError("tatt_amd: inputs must be on an AMD GPU (x.device=%s); the product path has no CPU fallback (the CPU "
+                           "restatement lives in tests/ and is test infrastructure)." % x.device)
+
+
+def add_relu(a, b):
+    assert a.shape == b.shape and a.is_contiguous() and b.is_contiguous()
+    y = torch.empty_like(a)
+    ops.call("tatt_add_relu", ops.P(a), ops.P(b), ops.P(y), a.numel(), ops.stream())
+    return y
+
+
+def gru_cell(gi, gh, h):
+    R, H = h.shape
+    out = torch.empty_like(h)
+    ops.call("tatt_gru_cell", ops.P(gi), ops.P(gh), ops.P(h), ops.P(out), R, H, ops.stream())
+    return out
+
+
+def infer_bilstm(seq, rnn):
+    from .infer import bilstm_eval
+    return bilstm_eval(seq, rnn)
+
+
+def encoder_tail(h, layers, who):
+    """The end of both encoders: the last feature map h (B, 1, W, C) NHWC -> time-major (W, B, C) -> `layers` (callables on time-major
+    sequences: the BiLSTM layers) -> features (B, W, out)"""
+    B, Hh, Wd, Cc = h.shape
+    if Hh != 1:
+        raise ValueError("tatt_amd.%s reads images 32 pixels high (the feature map must be one row high, got %d)" % (who, Hh))
+    seq = Fh._c(h.reshape(B, Wd, Cc).permute(1, 0, 2))                     # time-major for the LSTM kernels
+    for layer in layers:
+        seq = layer(seq)
+    return Fh._c(seq.permute(1, 0, 2))
+
+
+class Prepared(nn.Module):
+    """A recogniser with operands derived from its parameters (folded filters, the decoder's transposed weights): `_derive()` builds them,
+    `_prepared()` hands them out and rebuilds them when a parameter or buffer changed.  A change is seen through the tensors' addresses
+    and version counters: a write that bumps no counter (through `.data`, or by a kernel of this library) leaves the derived operands
+    stale -- assign through `load_state_dict` / `copy_` / in-place torch operators.  The check walks all ~500 tensors, so `read` does it
+    once and hands the result to its stages (`prep=`)."""
+    _prep = None
+
+    def _signature(self):
+        return tuple((t.data_ptr(), t._version) for t in list(self.parameters()) + list(self.buffers()))
+
+    def _prepared(self):
+        sig = self._signature()
+        if self._prep is None or self._prep["sig"] != sig:
+            self._prep = dict(self._derive(), sig=sig)
+        return self._prep
+
+
+@dataclass(frozen=True)
+class DecoderSpec:
+    """One decoder head, as data.  Per step and row: sProj = Ws s + bs;  e_t = wv . tanh(sProj + Wx x_t + bx) + wb;  alpha = softmax_t(e);
+    ctx = sum_t alpha_t x_t;  s' = GRU([emb[y], ctx] or [ctx, emb[y]], s);  logits = Wfc s' + bfc."""
+    Ws: torch.Tensor                  # state projection
+    bs: torch.Tensor
+    Wx: torch.Tensor                  # feature projection
+    bx: Optional[torch.Tensor]
+    wv: torch.Tensor                  # score vector (1, att)
+    wb: Optional[torch.Tensor]
+    emb: torch.Tensor                 # embedding table (C + 1, E)
+    Wih: torch.Tensor
+    bih: torch.Tensor
+    Whh: torch.Tensor
+    bhh: torch.Tensor
+    Wfc: torch.Tensor                 # output layer
+    bfc: torch.Tensor
+    emb_first: bool                   # the embedding's columns of W_ih come before the context's
+    y0: int                           # embedding row of step 0 (not forced)
+    yadd: int                         # embedding row after an arg-max c: c + yadd
+    tshift: int                       # forced: the embedding row of step i is targets[:, i + tshift] (y0 where that is before the first)
+    dims: tuple                       # the head's sizes that the one launch needs equal to D
+    D: int                            # ... and its limits
+    max_T: int
+    max_C: int
+    max_L: int
+    entry: str                        # the C entry, and its argument list (without the stream) from `one_launch`'s values by name
+    entry_args: Callable
+    outputs: dict                     # mode -> what the entry returns, in the recogniser's order (names of `logits`, `ids`, `scores`)
+
+    @property
+    def C(self):
+        return self.Wfc.shape[0]
+
+    def takes(self, T=1, L=1, mode=0):
+        """whether the one launch takes this geometry (what the entry point itself refuses, asked first so that no operand is built)"""
+        return all(d == self.D for d in self.dims) and 1 <= T <= self.max_T and 2 <= self.C <= self.max_C and 1 <= L <= self.max_L and \
+            (mode != 2 or self.C >= BEAM_WIDTH)
+
+
+def operands(spec: DecoderSpec):
+    """What the one launch reads, from the decoder's parameters: the transposed weights and E2 = emb W_ih[:, embedding columns]^T + b_ih
+    (step-invariant; one GEMM).  Built once per parameter set by the recognisers."""
+    W = spec.Wih                                      # (3 sDim, E + xDim)
+    C1, E = spec.emb.shape
+    G, K = W.shape
+    We, Wc = (W[:, :E], W[:, E:]) if spec.emb_first else (W[:, K - E:], W[:, :K - E])
+    E2 = ops.new(W, C1, G)
+    ops.gemm(spec.emb, E, 1, We, 1, K, E2, G, 1, C1, G, E, bias=spec.bih)      # B(k, j) = We[j, k]
+    return {"WsT": spec.Ws.t().contiguous(), "bs": spec.bs, "wv": spec.wv.reshape(-1).contiguous(), "wb": spec.wb, "E2": E2,
+            "WicT": Wc.t().contiguous(), "WhhT": spec.Whh.t().contiguous(), "bhh": spec.bhh, "fcT": spec.Wfc.t().contiguous(),
+            "fcb": spec.bfc}
+
+
+def one_launch(spec: DecoderSpec, feats, mode, L, eos=0, targets=None, prepared=None):
+    """The decoder in ONE launch: feats (B, T, D) encoder features, mode 0 forced (`targets` (B, L)) / 1 greedy / 2 beam -> the outputs
+    `spec.outputs[mode]` names (one tensor, or a tuple): logits (B, L, C), ids (B, L) int32, scores (B, L).  None when the launch refuses
+    the geometry (the caller goes step by step)."""
+    ops._check_dev(feats)
+    B, T, D = feats.shape
+    if D != spec.D or not spec.takes(T, L, mode):
+        return None
+    op = prepared if prepared is not None else operands(spec)
+    xc = Fh._c(feats)
+    xproj = ops.linear_fwd(xc.reshape(B * T, D), spec.Wx, spec.bx)
+    out = {"logits": None, "ids": None, "scores": None}
+    for name in spec.outputs[mode]:
+        out[name] = torch.empty(B, L, dtype=torch.int32, device=feats.device) if name == "ids" else \
+            ops.new(feats, *((B, L, spec.C) if name == "logits" else (B, L)))
+    tg = targets.to(device=feats.device, dtype=torch.int32).contiguous() if mode == 0 else None
+    vals = dict(op, x=xc, xproj=xproj, targets=tg, B=B, T=T, C=spec.C, L=L, D=D, eos=int(eos), mode=mode, beam=BEAM_WIDTH, **out)
+    rc = getattr(LIB, spec.entry)(*[ops.P(v) if v is None or torch.is_tensor(v) else v for v in spec.entry_args(vals)], ops.stream())
+    if rc == 1:
+        return None
+    if rc != 0:
+        raise RuntimeError("%s failed with code %d" % (spec.entry, rc))
+    res = tuple(out[name] for name in spec.outputs[mode])
+    return res[0] if len(res) == 1 else res
+
+
+class Step:
+    """The decoder step by step on the shared operators: `Step(spec, feats, K)` projects the features once (every image's rows K
+    times: the beams), then `step(s, y)` -> (logits (R, C), s' (R, sDim)) from the states s (R, sDim) and embedding rows y (R,), R = B * K.
+    No host synchronisation."""
+
+    def __init__(self, spec: DecoderSpec, feats, K=1):
+        ops._check_dev(feats)
+        B, T, D = feats.shape
+        self.spec, self.R, self.T = spec, B * K, T
+        xc = Fh._c(feats)
+        xproj = ops.linear_fwd(xc.reshape(B * T, D), spec.Wx, spec.bx).view(B, T, -1)
+        self.x = xc if K == 1 else xc.repeat_interleave(K, 0).contiguous()
+        self.xp_tr = (xproj if K == 1 else xproj.repeat_interleave(K, 0)).permute(1, 0, 2).contiguous().view(T * self.R, -1)     # row t * R + r
+        self.seed = Fh.seed_tensor(feats.device)
+
+    def __call__(self, s, y):
+        sp, R, T, x = self.spec, self.R, self.T, self.x
+        aD, D = self.xp_tr.shape[1], x.shape[2]
+        sproj = ops.linear_fwd(s, sp.Ws, sp.bs)
+        th = ops.act_fwd(ops.add_rowbcast(self.xp_tr, sproj, R), ACT_TANH)
+        e = ops.new(x, R, T)
+        ops.gemm(th, aD, 1, sp.wv, 1, 0, e, T, 1, R, 1, aD, bias=sp.wb, Z=T, bsA=R * aD, bsC=1)
+        ops.call("tatt_softmax_rows_fwd", ops.P(e), None, R, T, 0.0, ops.P(self.seed), 0, ops.stream())
+        ctx = ops.new(x, R, D)
+        ops.gemm(e, T, 1, x, D, 1, ctx, D, 1, 1, D, T, Z=R, bsA=T, bsB=T * D, bsC=D)
+        emb = sp.emb.index_select(0, y)
+        first, second = (emb, ctx) if sp.emb_first else (ctx, emb)
+        gi = ops.linear_fwd(first, sp.Wih, sp.bih, x2b=second)
+        gh = ops.linear_fwd(s, sp.Whh, sp.bhh)
+        s = gru_cell(gi, gh, s)
+        return ops.linear_fwd(s, sp.Wfc, sp.bfc), s

@@ -210,19 +210,13 @@ class _Fold:
         bn_fold(self.conv.weight, self.conv.bias, self.bn, self.w, self.b)
 
 
-def _refuse_aster(m, who):
+def _refuse_attention_recognizer(m, who):
     from .aster import ASTER
-    if isinstance(m, ASTER):
-        raise TypeError("%s: an ASTER recogniser is not captured into a session (its attention decoder is not graph-captured); evaluate "
-                        "with tatt_amd.io.evaluate(model, batches, recognizer=<ASTER>), which reads SR / LR / HR with it" % who)
-
-
-def _refuse_moran(m, who):
     from .moran import MORAN
-    if isinstance(m, MORAN):
-        raise TypeError("%s: a MORAN recogniser is not captured into a session (its rectifier and attention decoder are not "
-                        "graph-captured); evaluate with tatt_amd.io.evaluate(model, batches, recognizer=<MORAN>), which reads SR / LR / HR "
-                        "with it" % who)
+    if isinstance(m, (ASTER, MORAN)):
+        raise TypeError("%s: %s recogniser is not captured into a session (its attention decoder, and MORAN's rectifier, are not "
+                        "graph-captured); evaluate with tatt_amd.io.evaluate(model, batches, recognizer=<%s>), which reads SR / LR / HR "
+                        "with it" % (who, "an ASTER" if isinstance(m, ASTER) else "a MORAN", type(m).__name__))
 
 
 def _check_module(m, what):
@@ -298,8 +292,7 @@ class InferenceSession:
                  voc_type: str = "lower", full_metrics: bool = False):
         from .tsrn import TSRN, TSRN_TL_TRANS
         from .tbsrn import TBSRN
-        _refuse_aster(recognizer, "InferenceSession")
-        _refuse_moran(recognizer, "InferenceSession")
+        _refuse_attention_recognizer(recognizer, "InferenceSession")
         _check_module(generator, "generator")
         _check_module(prior, "prior CRNN")
         _check_module(recognizer, "recogniser CRNN")
@@ -681,8 +674,7 @@ def evaluate_session(generator, batches: Iterable, prior=None, recognizer=None, 
     bicubic baseline, tatt_bicubic_resize of LR against HR) and, with a recogniser, 'ned' / 'ned_lr' / 'ned_hr' (mean normalised edit
     distance of the SR / LR / HR decodings, tatt_ctc_greedy_score in place of the match launch) and 'ned_skipped' (images whose
     filtered label has more than LABEL_CAP = 64 characters: the means leave them out).  Sessions of the two modes are kept apart."""
-    _refuse_aster(recognizer, "evaluate_session")
-    _refuse_moran(recognizer, "evaluate_session")
+    _refuse_attention_recognizer(recognizer, "evaluate_session")
     return evaluate_session_async(generator, batches, prior, recognizer, voc_type, sessions, export, full_metrics).result()
 
 
@@ -782,8 +774,7 @@ class SuperResolver:
     def __init__(self, generator, prior=None, recognizer=None, batch_size: int = 48, lr_size=(16, 64), mask: bool = True,
                  rule: str = "floor", keep_sr: bool = False, long_lines: bool = False, stride: int = 32, reader=None):
         from .io import DeviceCollator, DeviceExporter
-        _refuse_aster(recognizer, "SuperResolver")
-        _refuse_moran(recognizer, "SuperResolver")
+        _refuse_attention_recognizer(recognizer, "SuperResolver")
         _check_module(generator, "generator")
         _check_module(prior, "prior CRNN")
         _check_module(recognizer, "recogniser CRNN")

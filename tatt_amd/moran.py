@@ -19,8 +19,9 @@ All arithmetic runs in HIP kernels (no CPU fallback).  Eval BatchNorm is folded 
 stride-1 'same' result read at [:, ::sh, ::sw] (the same products, exactly), so the ten strided 3 x 3 convolutions run at stride 1 and
 hand the sub-sampled VIEW to the next convolution, which reads by strides; a copy is made only where the flat `add_relu` needs one.
 The tail of the rectifier is ONE launch per pass (tatt_morn_rectify) and the 20 greedy steps of a decoder direction are ONE launch
-(tatt_moran_decode, csrc/moran.hip), with `decode_eager` as the step-by-step route on the shared operators for geometries that launch
-refuses (and as the timing yardstick of tools/bench_moran.py).
+(tatt_moran_decode, csrc/attndec.hip), with `decode_eager` as the step-by-step route on the shared operators for geometries that launch
+refuses (and as the timing yardstick of tools/bench_moran.py).  The decoder itself -- its operands, the launch, one step -- is
+attn_decoder.py, shared with ASTER; here are MORAN's `DecoderSpec` and what MORAN does with a step's logits.
 """
 from __future__ import annotations
 
@@ -30,19 +31,17 @@ import numpy as np
 import torch
 from torch import nn
 
+from . import attn_decoder as AD
 from . import functional as Fh
 from . import ops
-from ._lib import LIB
-from .aster import _require, add_relu, gru_cell, infer_bilstm
-from .ops import ACT_NONE, ACT_RELU, ACT_TANH
+from .attn_decoder import Prepared, _require, add_relu, encoder_tail, infer_bilstm
+from .ops import ACT_NONE, ACT_RELU
 from .tsrn import _Holder
 
 ALPHABET = string.digits + string.ascii_lowercase + "$"          # interfaces/base.py:676
 MAX_ITER = 20                                                     # parse_moran_data: every image is read for 20 steps
 EMB = 256                                                         # asrn_res.py:229-232: num_embeddings of every Attention
 MODES = {"forced": 0, "greedy": 1}
-
-DECODE_ONE_LAUNCH = True          # test / A-B hook: False -> `MORAN.decode` always takes `decode_eager`
 LAUNCHES = {"one_launch": 0, "eager": 0}      # how often each decoder route ran (tests, tools/bench_moran.py)
 
 
@@ -191,24 +190,27 @@ def morn_rectify(o, x_nchw, size, acc=None):
     return out, acc
 
 
-def decoder_operands(att: Attention):
-    """What tatt_moran_decode reads, from one direction's parameters: the transposed weights and E2 = char_embeddings W_ih[:, H:]^T + b_ih
-    (step-invariant; one GEMM).  Built once per parameter set by `MORAN`; tests call it directly."""
+def _entry_args(v):
+    """tatt_moran_decode's arguments in the order of include/tatt_hip.h"""
+    return (v["x"], v["xproj"], v["WsT"], v["bs"], v["wv"], v["E2"], v["WicT"], v["WhhT"], v["bhh"], v["fcT"], v["fcb"], v["targets"], v["logits"],
+            v["ids"], v["B"], v["T"], v["C"], v["L"], v["D"], v["mode"])
+
+
+def decoder_spec(att: Attention):
+    """One direction's `Attention` as attn_decoder sees it: row 0 starts a greedy row, an arg-max c reads row c + 1, forced step i reads
+    targets[:, i], no bias on the score or the feature projection, the context's columns of W_ih first; forced decoding returns the
+    logits, greedy (ids, logits)"""
     cell = att.attention_cell
-    H = att.hidden_size
-    W = cell.rnn.weight_ih                               # (3H, H + EMB): the context's columns first
-    C1, E = att.char_embeddings.shape
-    G = W.shape[0]
-    E2 = ops.new(W, C1, G)
-    ops.gemm(att.char_embeddings, E, 1, W[:, H:], 1, W.shape[1], E2, G, 1, C1, G, E, bias=cell.rnn.bias_ih)
-    return {"WhT": cell.h2h.weight.t().contiguous(), "bh": cell.h2h.bias, "wv": cell.score.weight.reshape(-1).contiguous(), "E2": E2,
-            "WicT": W[:, :H].t().contiguous(), "WhhT": cell.rnn.weight_hh.t().contiguous(), "bhh": cell.rnn.bias_hh,
-            "genT": att.generator.weight.t().contiguous(), "genb": att.generator.bias}
+    return AD.DecoderSpec(Ws=cell.h2h.weight, bs=cell.h2h.bias, Wx=cell.i2h.weight, bx=None, wv=cell.score.weight, wb=None,
+                          emb=att.char_embeddings, Wih=cell.rnn.weight_ih, bih=cell.rnn.bias_ih, Whh=cell.rnn.weight_hh,
+                          bhh=cell.rnn.bias_hh, Wfc=att.generator.weight, bfc=att.generator.bias, emb_first=False, y0=0, yadd=1, tshift=0,
+                          dims=(att.hidden_size, att.input_size, att.num_embeddings), D=256, max_T=32, max_C=64, max_L=64,
+                          entry="tatt_moran_decode", entry_args=_entry_args, outputs={0: ("logits",), 1: ("ids", "logits")})
 
 
-def _one_launch_takes(att, T, L):
-    return att.hidden_size == 256 and att.input_size == 256 and att.num_embeddings == 256 and 1 <= T <= 32 and \
-        2 <= att.num_classes <= 64 and 1 <= L <= 64
+def decoder_operands(att: Attention):
+    """What tatt_moran_decode reads (`attn_decoder.operands`).  Built once per parameter set by `MORAN`; tests call it directly."""
+    return AD.operands(decoder_spec(att))
 
 
 def _steps(att, feats, mode, steps, targets):
@@ -231,64 +233,28 @@ def attn_decode(att: Attention, feats, mode, steps=None, targets=None, operands=
     geometry (the caller takes `decode_eager`)."""
     ops._check_dev(feats)
     L = _steps(att, feats, mode, steps, targets)
-    B, T, D = feats.shape
-    C = att.num_classes
-    if not _one_launch_takes(att, T, L):
-        return None                                   # (what the entry point itself refuses; asked first so that no operand is built)
-    op = operands if operands is not None else decoder_operands(att)
-    fc = Fh._c(feats)
-    fproj = ops.linear_fwd(fc.reshape(B * T, D), att.attention_cell.i2h.weight)
-    logits = ops.new(feats, B, L, C)
-    ids = tg = None
-    if mode == 0:
-        tg = targets.to(device=feats.device, dtype=torch.int32).contiguous()
-    else:
-        ids = torch.empty(B, L, dtype=torch.int32, device=feats.device)
-    rc = getattr(LIB, "tatt_moran_decode")(ops.P(fc), ops.P(fproj), ops.P(op["WhT"]), ops.P(op["bh"]), ops.P(op["wv"]), ops.P(op["E2"]),
-                                           ops.P(op["WicT"]), ops.P(op["WhhT"]), ops.P(op["bhh"]), ops.P(op["genT"]), ops.P(op["genb"]),
-                                           ops.P(tg), ops.P(logits), ops.P(ids), B, T, C, L, att.hidden_size, mode, ops.stream())
-    if rc == 1:
-        return None
-    if rc != 0:
-        raise RuntimeError("tatt_moran_decode failed with code %d" % rc)
-    LAUNCHES["one_launch"] += 1
-    return logits if mode == 0 else (ids, logits)
+    out = AD.one_launch(decoder_spec(att), feats, mode, L, -1, targets, operands)
+    if out is not None:
+        LAUNCHES["one_launch"] += 1
+    return out
 
 
 def decode_eager(att: Attention, feats, mode, steps=None, targets=None):
     """`attn_decode` step by step on the shared operators (about a dozen launches per step): the route for geometries the one launch
     refuses, and the timing yardstick.  Same results, same tie rule (torch's arg-max returns the first maximum), and like the one
     launch no host synchronisation."""
-    ops._check_dev(feats)
     L = _steps(att, feats, mode, steps, targets)
-    B, T, D = feats.shape
-    C, H = att.num_classes, att.hidden_size
-    cell = att.attention_cell
-    dev = feats.device
-    fc = Fh._c(feats)
-    fproj = ops.linear_fwd(fc.reshape(B * T, D), cell.i2h.weight).view(B, T, H)
-    fp_tr = fproj.permute(1, 0, 2).contiguous().view(T * B, H)                  # row t * B + b
-    h = torch.zeros(B, H, device=dev)
+    B, C, dev = feats.shape[0], att.num_classes, feats.device
+    step = AD.Step(decoder_spec(att), feats)
+    h = torch.zeros(B, att.hidden_size, device=dev)
     if mode == 0:
         tg = targets.to(dev).long().clamp(0, C)
         y = tg[:, 0]
     else:
         y = torch.zeros(B, dtype=torch.long, device=dev)
-    seed = Fh.seed_tensor(dev)
     outs, out_ids = [], []
     for i in range(L):
-        hp = ops.linear_fwd(h, cell.h2h.weight, cell.h2h.bias)
-        th = ops.act_fwd(ops.add_rowbcast(fp_tr, hp, B), ACT_TANH)
-        e = ops.new(feats, B, T)
-        ops.gemm(th, H, 1, cell.score.weight, 1, 0, e, T, 1, B, 1, H, Z=T, bsA=B * H, bsC=1)
-        ops.call("tatt_softmax_rows_fwd", ops.P(e), None, B, T, 0.0, ops.P(seed), 0, ops.stream())
-        ctx = ops.new(feats, B, D)
-        ops.gemm(e, T, 1, fc, D, 1, ctx, D, 1, 1, D, T, Z=B, bsA=T, bsB=T * D, bsC=D)
-        emb = att.char_embeddings.index_select(0, y)
-        gi = ops.linear_fwd(ctx, cell.rnn.weight_ih, cell.rnn.bias_ih, x2b=emb)
-        gh = ops.linear_fwd(h, cell.rnn.weight_hh, cell.rnn.bias_hh)
-        h = gru_cell(gi, gh, h)
-        logits = ops.linear_fwd(h, att.generator.weight, att.generator.bias)
+        logits, h = step(h, y)
         outs.append(logits)
         if mode == 0:
             if i + 1 < L:
@@ -303,7 +269,7 @@ def decode_eager(att: Attention, feats, mode, steps=None, targets=None):
 
 
 # ---- the recogniser ----------------------------------------------------------------------------------------------------------------
-class MORAN(nn.Module):
+class MORAN(Prepared):
     """Drop-in for the reference's MORAN (eval only; see the module docstring).  `inputDataType` and `CUDA` are accepted and ignored;
     `maxBatch` keeps the reference's assertion."""
 
@@ -313,12 +279,6 @@ class MORAN(nn.Module):
         self.nc, self.nclass, self.nh, self.targetH, self.targetW, self.BidirDecoder = nc, nclass, nh, targetH, targetW, BidirDecoder
         self.MORN = MORN(nc, targetH, targetW, maxBatch)
         self.ASRN = ASRN(targetH, nc, nclass, nh, BidirDecoder)
-        self._prep = None
-
-    # -- derived operands (folded filters, the decoders' transposed weights), rebuilt when a parameter or buffer changed: the same
-    # (data_ptr, _version) rule as `ASTER._prepared` -- a write that bumps no counter leaves them stale.  `read` checks once.
-    def _signature(self):
-        return tuple((t.data_ptr(), t._version) for t in list(self.parameters()) + list(self.buffers()))
 
     def _attention(self, reverse=False):
         if self.BidirDecoder:
@@ -327,27 +287,24 @@ class MORAN(nn.Module):
             raise ValueError("tatt_amd.MORAN: reverse=True needs BidirDecoder=True (this model has one decoder)")
         return self.ASRN.attention
 
-    def _prepared(self):
-        sig = self._signature()
-        if self._prep is None or self._prep["sig"] != sig:
-            from .infer import bn_fold
-            folds = {}
-            for i in MORN_CONVS:
-                folds[("morn", i)] = bn_fold(self.MORN.cnn[i].weight, self.MORN.cnn[i].bias, self.MORN.cnn[i + 1])
-            cnn = self.ASRN.cnn
-            folds["b0"] = bn_fold(cnn.block0[0].weight, cnn.block0[0].bias, cnn.block0[1])
-            for li in range(1, 6):
-                for bi, blk in enumerate(getattr(cnn, "block%d" % li)):
-                    folds[(li, bi, 1)] = bn_fold(blk.conv1[0].weight, blk.conv1[0].bias, blk.conv1[1])
-                    folds[(li, bi, 2)] = bn_fold(blk.conv2[0].weight, blk.conv2[0].bias, blk.conv2[1])
-                    if blk.downsample is not None:
-                        folds[(li, bi, 0)] = bn_fold(blk.downsample[0].weight, blk.downsample[0].bias, blk.downsample[1])
-            operands = {}
-            for rev in ((False, True) if self.BidirDecoder else (False,)):
-                att = self._attention(rev)
-                operands[rev] = decoder_operands(att) if _one_launch_takes(att, 1, 1) else None
-            self._prep = {"sig": sig, "folds": folds, "operands": operands}
-        return self._prep
+    def _derive(self):
+        from .infer import bn_fold
+        folds = {}
+        for i in MORN_CONVS:
+            folds[("morn", i)] = bn_fold(self.MORN.cnn[i].weight, self.MORN.cnn[i].bias, self.MORN.cnn[i + 1])
+        cnn = self.ASRN.cnn
+        folds["b0"] = bn_fold(cnn.block0[0].weight, cnn.block0[0].bias, cnn.block0[1])
+        for li in range(1, 6):
+            for bi, blk in enumerate(getattr(cnn, "block%d" % li)):
+                folds[(li, bi, 1)] = bn_fold(blk.conv1[0].weight, blk.conv1[0].bias, blk.conv1[1])
+                folds[(li, bi, 2)] = bn_fold(blk.conv2[0].weight, blk.conv2[0].bias, blk.conv2[1])
+                if blk.downsample is not None:
+                    folds[(li, bi, 0)] = bn_fold(blk.downsample[0].weight, blk.downsample[0].bias, blk.downsample[1])
+        operands = {}
+        for rev in ((False, True) if self.BidirDecoder else (False,)):
+            spec = decoder_spec(self._attention(rev))
+            operands[rev] = AD.operands(spec) if spec.takes() else None
+        return {"folds": folds, "operands": operands}
 
     # -- the stages
     def _check_input(self, x):
@@ -395,24 +352,22 @@ class MORAN(nn.Module):
                     res = h
                 w, b = folds[(li, bi, 2)]
                 h = add_relu(ops.conv2d_forward(o, w, b, ACT_NONE), res)
-        B, Hh, Wd, Cc = h.shape
-        if Hh != 1:
-            raise ValueError("tatt_amd.MORAN reads images 32 pixels high (the feature map must be one row high, got %d)" % Hh)
-        seq = Fh._c(h.reshape(B, Wd, Cc).permute(1, 0, 2))                     # time-major for the LSTM kernels
-        for layer in self.ASRN.rnn:
-            rec = infer_bilstm(seq, layer.rnn)
-            T, _, H2 = rec.shape
-            seq = ops.linear_fwd(rec.reshape(T * B, H2), layer.embedding.weight, layer.embedding.bias).view(T, B, -1)
-        return Fh._c(seq.permute(1, 0, 2))
+
+        def lstm_linear(layer):
+            def run(seq):
+                rec = infer_bilstm(seq, layer.rnn)
+                T, B, H2 = rec.shape
+                return ops.linear_fwd(rec.reshape(T * B, H2), layer.embedding.weight, layer.embedding.bias).view(T, B, -1)
+            return run
+
+        return encoder_tail(h, [lstm_linear(layer) for layer in self.ASRN.rnn], "MORAN")
 
     def decode(self, feats, steps=MAX_ITER, targets=None, reverse=False, prep=None):
         """feats (B, T, nh) -> (ids (B, steps) int32, logits (B, steps, nclass)) greedy, or the logits (B, L, nclass) of a forced
         decoding when `targets` (B, L) gives every step's embedding row"""
         att = self._attention(reverse)
         mode = 0 if targets is not None else 1
-        out = None
-        if DECODE_ONE_LAUNCH:
-            out = attn_decode(att, feats, mode, steps, targets, operands=(prep or self._prepared())["operands"][bool(reverse)])
+        out = attn_decode(att, feats, mode, steps, targets, operands=(prep or self._prepared())["operands"][bool(reverse)])
         if out is None:
             out = decode_eager(att, feats, mode, steps, targets)
         return out

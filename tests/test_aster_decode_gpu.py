@@ -185,3 +185,75 @@ def test_beam_backtrack_kernel():
                                for a, t in ((sym, torch.int32), (pred, torch.int32), (score, torch.float32)))
         ops.call("tatt_beam_backtrack", ops.P(dsym), ops.P(dpred), ops.P(dscore), ops.P(ids), ops.P(ws), L, B, K, eos, ops.stream())
         assert np.array_equal(ids.cpu().numpy(), want), (eos, surgery, C)
+
+
+# ---- the widest geometry the one launch takes: T = 32 fills the softmax wave, C = 128 both classes of every lane of the arg-max and all
+# 640 candidates of the beam.  Error bars as above, from this geometry's own numbers (tests/golden/attn_decode_limits.npz).
+LIMIT_FORCED = (2, 3, 128, 32, 1)              # (B, L, C, T, feature seed)
+# (B, L, C, T, feature seed, eos) -- seed: the first at which both rows' greedy and beam margins exceed the bound, found by
+# tools/gen_golden_aster.py with the float64 specification on the CPU and recorded in the fixture
+LIMIT_DECODE = (2, 6, 128, 32, 1, 125)
+
+
+@pytest.fixture(scope="module")
+def lim():
+    lim = np.load(os.path.join(GOLD, "attn_decode_limits.npz"))
+    assert tuple(lim["aster_forced_case"]) == LIMIT_FORCED and tuple(lim["aster_decode_case"]) == LIMIT_DECODE
+    return lim
+
+
+def _limit_inputs(case):
+    B, L, C, T, seed = case[:5]
+    return R.features(B, T, seed), torch.randint(0, C, (B, L), generator=torch.Generator().manual_seed(seed))
+
+
+@pytest.mark.parametrize("arithmetic", ["split_bf16", "fp32"], indirect=True)
+def test_forced_logits_at_the_limits(arithmetic, lim):
+    B, L, C, T, _ = LIMIT_FORCED
+    head, P = _head(C)
+    if "limit_forced" not in _CACHE:
+        x, tg = _limit_inputs(LIMIT_FORCED)
+        _CACHE["limit_forced"] = (x, tg, R.forced(P, x.numpy(), tg.numpy()))
+    x, tg, want = _CACHE["limit_forced"]
+    bar, _ = R.margin_bound(lim["aster_forced_ref_err"], lim["aster_forced_maxabs"])
+    before = aster.LAUNCHES["one_launch"]
+    for route in (aster.attn_decode, aster.decode_eager):
+        got = route(head, x.to(DEV), 0, targets=tg.to(DEV))
+        assert got is not None and tuple(got.shape) == (B, L, C)
+        err = float(np.abs(got.cpu().numpy().astype(np.float64) - want).max())
+        print("forced at the limits %s %s: error %.3e, reference fp32 %.3e, bar %.3e" % (arithmetic, route.__name__, err,
+                                                                                        lim["aster_forced_ref_err"], bar))
+        assert err <= bar, (route.__name__, err, bar)
+    assert aster.LAUNCHES["one_launch"] == before + 1
+    tatt_amd.sync_check()
+
+
+def test_greedy_and_beam_at_the_limits(lim):
+    B, L, C, T, _, eos = LIMIT_DECODE
+    head, P = _head(C, L)
+    x = _limit_inputs(LIMIT_DECODE)[0]
+    g_ids, g_scores, g_margin = R.greedy(P, x.numpy(), L, eos)
+    b_ids, b_margin = R.beam(P, x.numpy(), L, eos)
+    bar, need = R.margin_bound(max(lim["aster_forced_ref_err"], lim["aster_decode_ref_err"]),
+                               max(lim["aster_forced_maxabs"], lim["aster_decode_maxabs"]))
+    assert (g_margin > need).all() and (b_margin > need).all(), (g_margin, b_margin, need)      # (the seed: every row is compared)
+    xd = x.to(DEV)
+    before = aster.LAUNCHES["one_launch"]
+    for route in (aster.attn_decode, aster.decode_eager):
+        ids, scores = route(head, xd, 1, eos)
+        assert ids.dtype == torch.int32 and tuple(ids.shape) == (B, L) and tuple(scores.shape) == (B, L)
+        ids, scores = ids.cpu().numpy(), scores.cpu().numpy()
+        got, want = R.upto_eos(ids, eos), R.upto_eos(g_ids, eos)
+        for r in range(B):
+            assert got[r] == want[r], (route.__name__, "greedy", r, got[r], want[r])
+            n = len(want[r])
+            err = np.abs(scores[r, :n] - g_scores[r, :n]).max()
+            print("greedy at the limits %s row %d: score error %.3e, bar %.3e" % (route.__name__, r, err, bar))
+            assert err <= bar, (route.__name__, r)
+            assert (ids[r, n:] == eos).all() and (scores[r, n:] == 0).all()          # beyond the first EOS: EOS / 0
+        ids, scores = route(head, xd, 2, eos)
+        assert ids.dtype == torch.int32 and tuple(ids.shape) == (B, L)
+        assert bool((scores == 1).all())
+        assert R.upto_eos(ids.cpu().numpy(), eos) == R.upto_eos(b_ids, eos), (route.__name__, "beam")
+    assert aster.LAUNCHES["one_launch"] == before + 2
+    tatt_amd.sync_check()

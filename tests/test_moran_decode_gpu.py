@@ -128,3 +128,63 @@ def test_refused_geometries_take_the_eager_route(T, C, L, dec):
     assert np.abs(lg[:, 0] - want_lg[:, 0]).max() <= bar                           # the first step depends on no decision
     for r in np.nonzero(margin > need)[0]:
         assert np.array_equal(got_ids[r].cpu().numpy(), want_ids[r]) and np.abs(lg[r] - want_lg[r]).max() <= bar
+
+
+# ---- the widest geometry the one launch takes: T = 32 fills the softmax wave and the LDS staging, C = 64 every lane of the arg-max.
+# Error bars as above, from this geometry's own numbers (tests/golden/attn_decode_limits.npz).
+LIMIT_FORCED = (2, 2, 64, 32, 1)               # (B, L, C, T, feature seed)
+# seed: the first at which both rows' greedy margins exceed the bound in both directions, found by tools/gen_golden_moran.py with the
+# float64 specification on the CPU and recorded in the fixture
+LIMIT_GREEDY = (2, 4, 64, 32, 1)
+
+
+@pytest.fixture(scope="module")
+def lim():
+    lim = np.load(os.path.join(GOLD, "attn_decode_limits.npz"))
+    assert tuple(lim["moran_forced_case"]) == LIMIT_FORCED and tuple(lim["moran_greedy_case"]) == LIMIT_GREEDY
+    return lim
+
+
+def _limit_inputs(case):
+    B, L, C, T, seed = case
+    return R.features(B, T, seed), torch.randint(0, C + 1, (B, L), generator=torch.Generator().manual_seed(seed))
+
+
+@pytest.mark.parametrize("d", [0, 1])
+def test_forced_logits_at_the_limits(d, lim):
+    B, L, C, T, _ = LIMIT_FORCED
+    att, P = _head(d, C)
+    x, tg = _limit_inputs(LIMIT_FORCED)
+    want = R.forced(P, x.numpy(), tg.numpy())
+    bar, _ = R.margin_bound(lim["moran_forced_ref_err"][d], lim["moran_forced_maxabs"][d])
+    before = moran.LAUNCHES["one_launch"]
+    for route in (moran.attn_decode, moran.decode_eager):
+        got = route(att, x.to(DEV), 0, targets=tg.to(DEV))
+        assert got is not None and tuple(got.shape) == (B, L, C)
+        err = float(np.abs(got.cpu().numpy().astype(np.float64) - want).max())
+        print("forced at the limits %s %s: error %.3e, reference fp32 %.3e, bar %.3e" % (DIRS[d], route.__name__, err,
+                                                                                        lim["moran_forced_ref_err"][d], bar))
+        assert err <= bar, (route.__name__, err, bar)
+    assert moran.LAUNCHES["one_launch"] == before + 1
+
+
+@pytest.mark.parametrize("d", [0, 1])
+def test_greedy_at_the_limits(d, lim):
+    B, L, C, T, _ = LIMIT_GREEDY
+    att, P = _head(d, C)
+    x = _limit_inputs(LIMIT_GREEDY)[0]
+    want_ids, want_lg, margin = R.greedy(P, x.numpy(), L)
+    bar, need = R.margin_bound(max(lim["moran_forced_ref_err"].max(), lim["moran_greedy_ref_err"].max()),
+                               max(lim["moran_forced_maxabs"].max(), lim["moran_greedy_maxabs"].max()))
+    assert (margin > need).all(), (margin, need)                                  # (the seed: every row is compared)
+    before = moran.LAUNCHES["one_launch"]
+    for route in (moran.attn_decode, moran.decode_eager):
+        ids, lg = route(att, x.to(DEV), 1, steps=L)
+        assert ids.dtype == torch.int32 and tuple(ids.shape) == (B, L) and tuple(lg.shape) == (B, L, C)
+        ids, lg = ids.cpu().numpy(), lg.cpu().numpy().astype(np.float64)
+        assert np.array_equal(ids, want_ids), (route.__name__, ids, want_ids)
+        err = np.abs(lg - want_lg).max()
+        print("greedy at the limits %s %s: logits error %.3e, bar %.3e" % (DIRS[d], route.__name__, err, bar))
+        assert err <= bar
+        assert np.array_equal(lg.argmax(2), ids)                                  # the ids are the arg-max of the logits returned
+    assert moran.LAUNCHES["one_launch"] == before + 1

@@ -8,6 +8,9 @@ tools/gen_golden.py; the tests never import the reference.
   tests/golden/aster_e2e.npz     the whole recogniser (97 classes; seeds, `perturb`, fc.weight x 30 and the EOS shift: tests/aster_ref.py) on 3 images: STN input, control
                                  points, sampling grid, rectified image, encoder features, forced logits, greedy ids / scores, beam ids,
                                  the float64 versions' distance (the unit of the error bars), margins, and init checksums
+  tests/golden/attn_decode_limits.npz (the `aster_*` entries; `--limits` writes these alone)
+                                 the decoder at the widest geometry its one launch takes (T = 32, C = 128): per case the reference's
+                                 fp32 error against float64 and the largest |logit|, and the feature seed of the greedy / beam case
 No weights are stored (84 MB): the tests rebuild them from the seeds.
 """
 import os
@@ -37,6 +40,54 @@ def images(B, seed=R.IMG_SEED):
     return torch.nn.functional.interpolate(low, (32, 128), mode="bilinear", align_corners=False) * 2 - 1
 
 
+# the widest geometries: (B, L, C, T) of the forced and of the greedy / beam case, its EOS, the forced case's feature seed
+LIMIT_FORCED, LIMIT_DECODE, LIMIT_EOS, LIMIT_FORCED_SEED = (2, 3, 128, 32), (2, 6, 128, 32), 125, 1
+
+
+def limit_inputs(case, seed):
+    B, L, C, T = case
+    return R.features(B, T, seed), torch.randint(0, C, (B, L), generator=torch.Generator().manual_seed(seed))
+
+
+def merge_limits(entries):
+    """tests/golden/attn_decode_limits.npz is shared with tools/gen_golden_moran.py: replace this generator's entries, keep the others"""
+    path = os.path.join(GOLD, "attn_decode_limits.npz")
+    out = dict(np.load(path)) if os.path.exists(path) else {}
+    out.update(entries)
+    np.savez_compressed(path, **out)
+
+
+def limits(RefHead):
+    C = LIMIT_FORCED[2]
+    head = R.make_head(R.HEAD_SEED, C)
+    ref = RefHead(C, 512, 512, 512, 100)
+    ref.load_state_dict(head.state_dict())
+    P = R.decoder_params(head.state_dict(), "decoder.")
+
+    def ref_err(case, seed):
+        x, tg = limit_inputs(case, seed)
+        want = R.forced(P, x.numpy(), tg.numpy())
+        return np.abs(ref([x, tg, [case[1]] * case[0]]).numpy() - want).max(), np.abs(want).max()
+
+    fe, fm = ref_err(LIMIT_FORCED, LIMIT_FORCED_SEED)
+    for seed in range(1, 100):      # the first feature seed at which every row's greedy and beam margin exceeds the bound
+        de, dm = ref_err(LIMIT_DECODE, seed)
+        _, need = R.margin_bound(max(fe, de), max(fm, dm))
+        x = limit_inputs(LIMIT_DECODE, seed)[0].numpy()
+        g_ids, _, gm = R.greedy(P, x, LIMIT_DECODE[1], LIMIT_EOS)
+        b_ids, bm = R.beam(P, x, LIMIT_DECODE[1], LIMIT_EOS)
+        print("limits: seed", seed, "bound %.3e" % need, "greedy margins", gm, "beam margins", bm)
+        if (gm > need).all() and (bm > need).all():
+            break
+    else:
+        raise AssertionError("no feature seed below 100 clears the margin bound")
+    print("limits: forced reference fp32 error %.3e at max|logit| %.2f, decode %.3e at %.2f, seed %d" % (fe, fm, de, dm, seed))
+    print("limits: greedy", R.upto_eos(g_ids, LIMIT_EOS), "beam", R.upto_eos(b_ids, LIMIT_EOS))
+    merge_limits({"aster_forced_case": np.array(LIMIT_FORCED + (LIMIT_FORCED_SEED,)), "aster_forced_ref_err": np.array(fe),
+                  "aster_forced_maxabs": np.array(fm), "aster_decode_case": np.array(LIMIT_DECODE + (seed, LIMIT_EOS)),
+                  "aster_decode_ref_err": np.array(de), "aster_decode_maxabs": np.array(dm)})
+
+
 def main():
     import_reference()
     import types
@@ -46,6 +97,9 @@ def main():
     from model.recognizer.attention_recognition_head import AttentionRecognitionHead as RefHead
     import tatt_amd
     torch.set_grad_enabled(False)
+    limits(RefHead)
+    if "--limits" in sys.argv[1:]:
+        return
 
     # ---- the decoder alone ------------------------------------------------------------------------------------------------------------
     out = {}

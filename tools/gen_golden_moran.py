@@ -10,6 +10,9 @@ the reference.  Both grid_sample calls run as the installed torch runs them (ali
                                  offsets_grid, rectified image, encoder features, L2R / R2L rows and ids, the float64 run's distance per
                                  stage (the unit of the error bars; for the sampler also alone, at the recorded offsets), margins, the
                                  key list, shapes, init checksums and an id table with its decoded strings
+  tests/golden/attn_decode_limits.npz (the `moran_*` entries; `--limits` writes these alone)
+                                 the decoder at the widest geometry its one launch takes (T = 32, C = 64): per case and direction the
+                                 reference's fp32 error against float64 and the largest |logit|, and the greedy case's feature seed
 No weights are stored (81 MB): the tests rebuild them from the seeds.
 """
 import os
@@ -74,6 +77,47 @@ def to_double(ref):
     return ref
 
 
+# the widest geometries: (B, L, C, T) of the forced and of the greedy case, the forced case's feature seed
+LIMIT_FORCED, LIMIT_GREEDY, LIMIT_FORCED_SEED = (2, 2, 64, 32), (2, 4, 64, 32), 1
+
+
+def limit_inputs(case, seed):
+    B, L, C, T = case
+    return R.features(B, T, seed), torch.randint(0, C + 1, (B, L), generator=torch.Generator().manual_seed(seed))
+
+
+def limits(RefAttention):
+    from gen_golden_aster import merge_limits
+    C = LIMIT_FORCED[2]
+    heads = []
+    for d in range(2):
+        att = R.make_attention(R.HEAD_SEED + d, C)
+        ref = RefAttention(256, 256, C, 256, CUDA=False)
+        ref.load_state_dict(att.state_dict())
+        heads.append((ref, R.decoder_params(att.state_dict(), "")))
+
+    def ref_err(case, seed):
+        x, tg = limit_inputs(case, seed)
+        wants = [R.forced(P, x.numpy(), tg.numpy()) for _, P in heads]
+        return (np.array([np.abs(cell_forced(ref, x, tg).numpy() - w).max() for (ref, _), w in zip(heads, wants)]),
+                np.array([np.abs(w).max() for w in wants]))
+
+    fe, fm = ref_err(LIMIT_FORCED, LIMIT_FORCED_SEED)
+    for seed in range(1, 100):      # the first feature seed at which every row's greedy margin exceeds the bound, in both directions
+        ge, gm = ref_err(LIMIT_GREEDY, seed)
+        _, need = R.margin_bound(max(fe.max(), ge.max()), max(fm.max(), gm.max()))
+        x = limit_inputs(LIMIT_GREEDY, seed)[0].numpy()
+        margins = np.stack([R.greedy(P, x, LIMIT_GREEDY[1])[2] for _, P in heads])
+        print("limits: seed", seed, "bound %.3e" % need, "greedy margins", margins)
+        if (margins > need).all():
+            break
+    else:
+        raise AssertionError("no feature seed below 100 clears the margin bound")
+    print("limits: forced reference fp32 error", fe, "at max|logit|", fm, "greedy", ge, "at", gm, "seed", seed)
+    merge_limits({"moran_forced_case": np.array(LIMIT_FORCED + (LIMIT_FORCED_SEED,)), "moran_forced_ref_err": fe, "moran_forced_maxabs": fm,
+                  "moran_greedy_case": np.array(LIMIT_GREEDY + (seed,)), "moran_greedy_ref_err": ge, "moran_greedy_maxabs": gm})
+
+
 def main():
     import_reference()
     from model.moran.moran import MORAN as RefMORAN
@@ -83,6 +127,9 @@ def main():
     from tatt_amd import moran
     torch.set_grad_enabled(False)
     kw = dict(BidirDecoder=True, inputDataType="torch.FloatTensor", CUDA=False)
+    limits(RefAttention)
+    if "--limits" in sys.argv[1:]:
+        return
 
     # ---- the decoder alone ------------------------------------------------------------------------------------------------------------
     out = {}
