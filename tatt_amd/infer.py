@@ -861,38 +861,9 @@ class SuperResolver:
         windows go through the sessions in batches of `batch_size` exactly as `long_lines` runs them, `DeviceExporter.scene` merges,
         up-scales and pastes on the device and copies the canvas back once.  Byte for byte `io.super_resolve_scene_host` on the same SR
         windows.  No boxes: the up-scaled picture, no session runs.  Not with a recogniser (ValueError)."""
-        from .io import line_plan, scene_layers
-        if self.rec is not None:
-            raise ValueError("SuperResolver: a recogniser cannot read tiled lines (scene); pass recognizer=None")
-        if not (isinstance(feather, int) and not isinstance(feather, bool) and feather >= 0):
-            raise ValueError("SuperResolver.scene: feather must be an int >= 0; got %r" % (feather,))
-        h, w = self.lr_size
-        line_plan((w, h), self.lr_size, self.stride)                 # (raises for a stride outside [w / 2, w])
-        fresh, buf, boxes = set(), None, list(boxes)
-        with torch.cuda.device(self.device):
-            stack, lines, scene_dev = self.collator.scene_windows(image, boxes, self.stride)
-            N = stack.shape[0]
-            for i in range(0, N, self.B):
-                n = min(self.B, N - i)
-                sr = self._session(n, fresh).run(stack[i:i + n], text_prior=self._zero_prior(n))[0]
-                if buf is None:                                      # (in the layout the session leaves: a plain copy per batch)
-                    cl = sr.stride(1) == 1 and not sr.is_contiguous()
-                    buf = torch.empty((N,) + tuple(sr.shape[1:]), dtype=sr.dtype, device=sr.device,
-                                      memory_format=torch.channels_last if cl else torch.contiguous_format)
-                buf[i:i + n].copy_(sr)                               # the session's output is static: the next replay overwrites it
-            if buf is not None:
-                H, W = buf.shape[2:]
-                if H % h or W % w or H // h != W // w:
-                    raise ValueError("the SR windows %d x %d are no integer multiple of the LR window %d x %d" % (H, W, h, w))
-                scale = H // h
-            else:
-                scale = self._scale()
-            boxes = [tuple(int(v) for v in b) for b in boxes]        # (checked by scene_windows)
-            pending = self.exporter.scene(scene_dev, buf, lines, boxes, scale, feather)
-            reading = self._read(pending, scale)
-        if not self.keep_sr:
-            return PendingScene(pending, reading=reading)
-        return PendingScene(pending, buf, stack, lines, boxes, scene_layers(boxes), reading)
+        from .io import scene_layers
+        return self._scene("scene", image, boxes, feather, self.collator.scene_windows, self.exporter.scene,
+                           lambda b: tuple(int(v) for v in b), scene_layers)
 
     def scene_quads(self, image, quads, feather: int = 0) -> PendingScene:
         """`scene` for a detector's QUADRILATERALS: image: an RGB PIL image, quads: four integer corner points per text instance,
@@ -905,38 +876,47 @@ class SuperResolver:
         once.  Byte for byte `io.super_resolve_quads_host` on the same SR windows; axis-aligned quads give the bytes of `scene` on their
         boxes.  No quads: the up-scaled picture, no session runs.  Not with a recogniser (ValueError).  With keep_sr the PendingScene's
         `boxes` are the checked quads and `layers` their paste layers (`io.quad_layers`)."""
-        from .io import line_plan, quad_layers
+        from .io import quad_layers
+        return self._scene("scene_quads", image, quads, feather, self.collator.quad_windows, self.exporter.scene_quads,
+                           lambda q: tuple((int(x), int(y)) for x, y in q), quad_layers)
+
+    def _scene(self, who, image, boxes, feather, windows, export, norm, layers) -> PendingScene:
+        """`scene` and `scene_quads` (`who`): windows = the collator's method that cuts them, export = the exporter's that pastes them,
+        norm(box) = a box as the PendingScene keeps it, layers(boxes) = their paste layers"""
+        from .io import line_plan
         if self.rec is not None:
-            raise ValueError("SuperResolver: a recogniser cannot read tiled lines (scene_quads); pass recognizer=None")
+            raise ValueError("SuperResolver: a recogniser cannot read tiled lines (%s); pass recognizer=None" % who)
         if not (isinstance(feather, int) and not isinstance(feather, bool) and feather >= 0):
-            raise ValueError("SuperResolver.scene_quads: feather must be an int >= 0; got %r" % (feather,))
+            raise ValueError("SuperResolver.%s: feather must be an int >= 0; got %r" % (who, feather))
         h, w = self.lr_size
         line_plan((w, h), self.lr_size, self.stride)                 # (raises for a stride outside [w / 2, w])
-        fresh, buf, quads = set(), None, list(quads)
+        boxes = list(boxes)
         with torch.cuda.device(self.device):
-            stack, lines, scene_dev = self.collator.quad_windows(image, quads, self.stride)
-            N = stack.shape[0]
-            for i in range(0, N, self.B):
-                n = min(self.B, N - i)
-                sr = self._session(n, fresh).run(stack[i:i + n], text_prior=self._zero_prior(n))[0]
-                if buf is None:                                      # (in the layout the session leaves: a plain copy per batch)
-                    cl = sr.stride(1) == 1 and not sr.is_contiguous()
-                    buf = torch.empty((N,) + tuple(sr.shape[1:]), dtype=sr.dtype, device=sr.device,
-                                      memory_format=torch.channels_last if cl else torch.contiguous_format)
-                buf[i:i + n].copy_(sr)                               # the session's output is static: the next replay overwrites it
-            if buf is not None:
-                H, W = buf.shape[2:]
-                if H % h or W % w or H // h != W // w:
-                    raise ValueError("the SR windows %d x %d are no integer multiple of the LR window %d x %d" % (H, W, h, w))
-                scale = H // h
-            else:
-                scale = self._scale()
-            quads = [tuple((int(x), int(y)) for x, y in q) for q in quads]        # (checked by quad_windows)
-            pending = self.exporter.scene_quads(scene_dev, buf, lines, quads, scale, feather)
+            stack, lines, scene_dev = windows(image, boxes, self.stride)
+            buf, scale = self._run_windows(stack)
+            boxes = [norm(b) for b in boxes]                         # (checked by `windows`)
+            pending = export(scene_dev, buf, lines, boxes, scale, feather)
             reading = self._read(pending, scale)
         if not self.keep_sr:
             return PendingScene(pending, reading=reading)
-        return PendingScene(pending, buf, stack, lines, quads, quad_layers(quads), reading)
+        return PendingScene(pending, buf, stack, lines, boxes, layers(boxes), reading)
+
+    def _run_windows(self, stack):
+        """a window stack through the sessions in batches of `batch_size` -> (buf, scale): the ONE (n_windows, C, H, W) buffer of all SR
+        windows, each batch's SR copied into it on the stream, and H // h; (None, `_scale()`) for an empty stack"""
+        from .lines import sr_scale
+        fresh, buf, N = set(), None, stack.shape[0]
+        for i in range(0, N, self.B):
+            n = min(self.B, N - i)
+            sr = self._session(n, fresh).run(stack[i:i + n], text_prior=self._zero_prior(n))[0]
+            if buf is None:                                          # (in the layout the session leaves: a plain copy per batch)
+                cl = sr.stride(1) == 1 and not sr.is_contiguous()
+                buf = torch.empty((N,) + tuple(sr.shape[1:]), dtype=sr.dtype, device=sr.device,
+                                  memory_format=torch.channels_last if cl else torch.contiguous_format)
+            buf[i:i + n].copy_(sr)                                   # the session's output is static: the next replay overwrites it
+        if buf is None:
+            return None, self._scale()
+        return buf, sr_scale(*buf.shape[2:], *self.lr_size)
 
     def _read(self, pending, scale):
         """with a reader: its launches on the blended lines of `pending` (a PendingExport of lines / scene / scene_quads), enqueued right
@@ -967,27 +947,14 @@ class SuperResolver:
 
     def _lines(self, images, out_sizes) -> PendingUpscale:
         """the long_lines call: windows of all images -> sessions over batches of windows -> one SR buffer -> one blend launch"""
-        h, w = self.lr_size
-        fresh, buf = set(), None
         with_text = self.reader is not None
         if not images:
             return PendingUpscale([], with_text, None, reading=self.reader.read(None, [], 1) if with_text else None)
         with torch.cuda.device(self.device):
             stack, lines = self.collator.windows(images, self.stride)
-            N = stack.shape[0]
-            for i in range(0, N, self.B):
-                n = min(self.B, N - i)
-                sr = self._session(n, fresh).run(stack[i:i + n], text_prior=self._zero_prior(n))[0]
-                if buf is None:                                      # (in the layout the session leaves: a plain copy per batch)
-                    cl = sr.stride(1) == 1 and not sr.is_contiguous()
-                    buf = torch.empty((N,) + tuple(sr.shape[1:]), dtype=sr.dtype, device=sr.device,
-                                      memory_format=torch.channels_last if cl else torch.contiguous_format)
-                buf[i:i + n].copy_(sr)                               # the session's output is static: the next replay overwrites it
-            H, W = buf.shape[2:]
-            if H % h or W % w or H // h != W // w:
-                raise ValueError("the SR windows %d x %d are no integer multiple of the LR window %d x %d" % (H, W, h, w))
-            pending = self.exporter.lines(buf, lines, H // h, out_sizes=out_sizes)
-            reading = self._read(pending, H // h)
+            buf, scale = self._run_windows(stack)
+            pending = self.exporter.lines(buf, lines, scale, out_sizes=out_sizes)
+            reading = self._read(pending, scale)
         keep = self.keep_sr
         return PendingUpscale([(pending, None, None)], with_text, buf if keep else None, stack if keep else None, lines if keep else None,
                               reading)

@@ -533,7 +533,23 @@ def collate_fill(flat, arrays, desc, vecs):
     return head, pix, used
 
 
-class DeviceCollator:
+class _Limits:
+    """the limit tables of the C layer, each read once per instance: `self._limits` (declared by the class that uses this) maps a
+    `*_limits` function (`collate_limits`, `line_limits`, ...) to what it returned"""
+
+    def _lim(self, limits):
+        if limits not in self._limits:
+            self._limits[limits] = limits()
+        return self._limits[limits]
+
+
+def _ptrs(base, hbase, off):
+    """a table `off` bytes into the device buffer and into its pinned slot: the (device, host) pointer pair the launches take"""
+    import ctypes
+    return ctypes.c_void_p(base + off), ctypes.c_void_p(hbase + off)
+
+
+class DeviceCollator(_Limits):
     """`collate_pil_batch` with the image stacks built on the GPU: collate(samples) takes what `collate_pil_batch` takes ((img_HR, img_lr,
     img_HRy, img_lry, label_str) with RGB PIL images) and returns the same 9-tuple with `images_HR` / `images_lr` BIT FOR BIT equal to the
     host path's, on `device`.  `want_yuv=False` (the TATT recipes never read those members): `images_HRy` / `images_lry` are None; True:
@@ -542,7 +558,8 @@ class DeviceCollator:
     pixels together -- and enqueues ONE non-blocking copy to a persistent device buffer and ONE launch (tatt_collate_images: resize +
     ToTensor + mask for every image) on the current stream; it never waits for the device.  A slot is rewritten only after the event
     recorded behind its previous copy (the discipline of `TextPriorSR.set_labels`); a batch that outgrows the slots re-allocates them after
-    waiting for those events.  The image stacks are views of one freshly allocated tensor per call.  Decoding stays with the caller."""
+    waiting for those events.  The image stacks are views of one freshly allocated tensor per call.  Decoding stays with the caller.
+    Every entry point goes through `_stage`, the one place that holds this discipline."""
 
     def __init__(self, imgH: int = 32, imgW: int = 128, down_sample_scale: int = 2, mask: bool = True, device="cuda",
                  want_yuv: bool = False, ring: int = 3, alphabet: str = ALPHABET):
@@ -554,18 +571,16 @@ class DeviceCollator:
             raise ValueError("DeviceCollator: ring must be at least 1")
         self.hr_size, self.lr_size = (imgW, imgH), (imgW // down_sample_scale, imgH // down_sample_scale)
         self.mask, self.want_yuv, self.ring, self.alphabet = bool(mask), bool(want_yuv), int(ring), alphabet
-        self._limits = self._line_limits = None
+        self._limits = {}
         self._host, self._events, self._dev_buf, self._i, self._last = [], [], None, 0, None
 
     def plan(self, samples):
         """-> (collate_plan(...) of the batch's items, label strings, members): items ordered HR x B, lr x B[, HRy x B, lry x B]"""
         hr, lr, hry, lry, labels = zip(*samples)
         members = [(hr, self.hr_size), (lr, self.lr_size)] + ([(hry, self.hr_size), (lry, self.lr_size)] if self.want_yuv else [])
-        if self._limits is None:
-            self._limits = collate_limits()
         images = [im for ims, _ in members for im in ims]
         sizes = [size for ims, size in members for _ in ims]
-        return collate_plan(images, sizes, self.mask, self._limits), labels, members
+        return collate_plan(images, sizes, self.mask, self._lim(collate_limits)), labels, members
 
     def _slot(self, need):
         """the next staging slot (a pinned uint8 tensor of at least `need` bytes), free to be written"""
@@ -583,8 +598,31 @@ class DeviceCollator:
             self._events[k].synchronize()
         return k, self._host[k]
 
+    def _stage(self, need, used, fill, launch):
+        """One call's staging step, on the current stream: take a slot and a device buffer of at least `need` bytes, fill(flat) the slot
+        (flat: its writable uint8 array), copy its first `used` bytes to the device (ONE non-blocking copy), record the slot's event, run
+        launch(base, hbase) -- the device buffer's and the slot's address; it enqueues the call's launches and allocates their output --
+        and record the event the next call on ANOTHER stream waits for.  -> what `launch` returns.  Never waits for the device (but for a
+        slot's own event, and to re-allocate outgrown slots: `_slot`)."""
+        with torch.cuda.device(self.device):
+            stream = torch.cuda.current_stream()
+            moved = self._last is not None and self._last[0] != stream
+            if moved:
+                stream.wait_event(self._last[1])             # the one device buffer: the previous call's launch still reads it
+            k, host = self._slot(need)
+            if moved:
+                self._dev_buf.record_stream(stream)
+            fill(host.numpy())
+            self._dev_buf[:used].copy_(host[:used], non_blocking=True)
+            ev = self._events[k] = self._events[k] if self._events[k] is not None else torch.cuda.Event()
+            ev.record(stream)
+            out = launch(self._dev_buf.data_ptr(), host.data_ptr())
+            done = self._last[1] if self._last is not None else torch.cuda.Event()
+            done.record(stream)
+            self._last = (stream, done)
+        return out
+
     def __call__(self, samples):
-        import ctypes
         from . import ops
         samples = list(samples)
         (arrays, desc, nbytes, out_floats), labels, members = self.plan(samples)
@@ -592,27 +630,15 @@ class DeviceCollator:
         vecs, masks, tics = collate_labels(labels, self.alphabet)
         vecs_np = vecs.numpy()
         head, pix, used = collate_fill(None, arrays, desc, vecs_np)
-        with torch.cuda.device(self.device):
-            stream = torch.cuda.current_stream()
-            moved = self._last is not None and self._last[0] != stream
-            if moved:
-                stream.wait_event(self._last[1])             # the one device buffer: the previous call's launch still reads it
-            k, host = self._slot(used)
-            if moved:
-                self._dev_buf.record_stream(stream)
-            collate_fill(host.numpy(), arrays, desc, vecs_np)
-            self._dev_buf[:used].copy_(host[:used], non_blocking=True)
-            ev = self._events[k] = self._events[k] if self._events[k] is not None else torch.cuda.Event()
-            ev.record(stream)
+
+        def launch(base, hbase):
             out = torch.empty(out_floats + vecs.numel(), dtype=torch.float32, device=self.device)
-            base = self._dev_buf.data_ptr()
-            ops.call("tatt_collate_images", ctypes.c_void_p(base + pix), nbytes, ctypes.c_void_p(base),
-                     ctypes.c_void_p(host.data_ptr()), n, ops.P(out), out_floats, ops.stream())
+            ops.call("tatt_collate_images", _ptrs(base, hbase, pix)[0], nbytes, *_ptrs(base, hbase, 0), n, ops.P(out), out_floats,
+                     ops.stream())
             vecs_dev = out[out_floats:].view(vecs.shape)     # (device-to-device, behind the one host-to-device copy)
             vecs_dev.copy_(self._dev_buf[head:head + vecs.numel() * 4].view(torch.float32).view(vecs.shape), non_blocking=True)
-            done = self._last[1] if self._last is not None else torch.cuda.Event()
-            done.record(stream)
-            self._last = (stream, done)
+            return out, vecs_dev
+        out, vecs_dev = self._stage(used, used, lambda flat: collate_fill(flat, arrays, desc, vecs_np), launch)
         C, stacks, o = 3 + int(self.mask), [], 0
         for _, (w, h) in members:
             stacks.append(out[o:o + B * C * h * w].view(B, C, h, w))
@@ -620,38 +646,28 @@ class DeviceCollator:
         return (stacks[0], None, stacks[1], stacks[2] if self.want_yuv else None, stacks[3] if self.want_yuv else None, tuple(labels),
                 vecs_dev, masks, tics)
 
+    def _windows(self, kernel, pix, nbytes, n, out_floats):
+        """-> the launch of `_stage` for ONE window kernel (tatt_collate_images, tatt_line_windows and tatt_scene_windows share an
+        argument list): the sources `pix` bytes into the buffer, the descriptor table of n rows at its start"""
+        from . import ops
+
+        def launch(base, hbase):
+            out = torch.empty(out_floats, dtype=torch.float32, device=self.device)
+            ops.call(kernel, _ptrs(base, hbase, pix)[0], nbytes, *_ptrs(base, hbase, 0), n, ops.P(out), out_floats, ops.stream())
+            return out
+        return launch
+
     def stack(self, images, size):
         """RGB PIL images, size = (width, height) -> ONE (n, 3 + mask, height, width) stack on the device, bit for bit
         `torch.stack([resize_normalize(im, size, mask) for im in images])`: the plan / fill / launch of `__call__` without the sample
         tuples and the labels (what `tatt_amd.infer.SuperResolver` feeds its sessions with).  Never waits for the device."""
-        import ctypes
         import numpy as np
-        from . import ops
         images = list(images)
-        if self._limits is None:
-            self._limits = collate_limits()
-        arrays, desc, nbytes, out_floats = collate_plan(images, [tuple(size)] * len(images), self.mask, self._limits)
+        arrays, desc, nbytes, out_floats = collate_plan(images, [tuple(size)] * len(images), self.mask, self._lim(collate_limits))
         none = np.zeros(0, np.float32)
         _, pix, used = collate_fill(None, arrays, desc, none)
-        with torch.cuda.device(self.device):
-            stream = torch.cuda.current_stream()
-            moved = self._last is not None and self._last[0] != stream
-            if moved:
-                stream.wait_event(self._last[1])
-            k, host = self._slot(used)
-            if moved:
-                self._dev_buf.record_stream(stream)
-            collate_fill(host.numpy(), arrays, desc, none)
-            self._dev_buf[:used].copy_(host[:used], non_blocking=True)
-            ev = self._events[k] = self._events[k] if self._events[k] is not None else torch.cuda.Event()
-            ev.record(stream)
-            out = torch.empty(out_floats, dtype=torch.float32, device=self.device)
-            base = self._dev_buf.data_ptr()
-            ops.call("tatt_collate_images", ctypes.c_void_p(base + pix), nbytes, ctypes.c_void_p(base),
-                     ctypes.c_void_p(host.data_ptr()), len(arrays), ops.P(out), out_floats, ops.stream())
-            done = self._last[1] if self._last is not None else torch.cuda.Event()
-            done.record(stream)
-            self._last = (stream, done)
+        out = self._stage(used, used, lambda flat: collate_fill(flat, arrays, desc, none),
+                          self._windows("tatt_collate_images", pix, nbytes, len(arrays), out_floats))
         return out.view(len(images), 3 + int(self.mask), size[1], size[0])
 
     def windows(self, images, stride: int = 32):
@@ -660,36 +676,13 @@ class DeviceCollator:
         `torch.cat([line_windows_host(im, (h, w), stride, mask) for im in images])`; lines[i] = Line(wl, starts, first window index), what
         `DeviceExporter.lines` needs.  One upload per line (not per window), one copy, one launch (tatt_line_windows) through the ring of
         `stack`.  Never waits for the device."""
-        import ctypes
-        from . import ops
-        from .lines import line_limits, lines_fill, lines_plan
-        images = list(images)
-        if self._line_limits is None:
-            self._line_limits = line_limits()
         w, h = self.lr_size
-        arrays, desc, lines, nbytes, out_floats = lines_plan(images, (h, w), stride, self.mask, self._line_limits)
+        arrays, desc, lines, nbytes, out_floats = lines_plan(list(images), (h, w), stride, self.mask, self._lim(line_limits))
         if not lines:
             raise ValueError("DeviceCollator.windows: no images")
         pix, used = lines_fill(None, arrays, desc)
-        with torch.cuda.device(self.device):
-            stream = torch.cuda.current_stream()
-            moved = self._last is not None and self._last[0] != stream
-            if moved:
-                stream.wait_event(self._last[1])
-            k, host = self._slot(used)
-            if moved:
-                self._dev_buf.record_stream(stream)
-            lines_fill(host.numpy(), arrays, desc)
-            self._dev_buf[:used].copy_(host[:used], non_blocking=True)
-            ev = self._events[k] = self._events[k] if self._events[k] is not None else torch.cuda.Event()
-            ev.record(stream)
-            out = torch.empty(out_floats, dtype=torch.float32, device=self.device)
-            base = self._dev_buf.data_ptr()
-            ops.call("tatt_line_windows", ctypes.c_void_p(base + pix), nbytes, ctypes.c_void_p(base), ctypes.c_void_p(host.data_ptr()),
-                     len(desc), ops.P(out), out_floats, ops.stream())
-            done = self._last[1] if self._last is not None else torch.cuda.Event()
-            done.record(stream)
-            self._last = (stream, done)
+        out = self._stage(used, used, lambda flat: lines_fill(flat, arrays, desc),
+                          self._windows("tatt_line_windows", pix, nbytes, len(desc), out_floats))
         return out.view(len(desc), 3 + int(self.mask), h, w), lines
 
     def scene_windows(self, scene, boxes, stride: int = 32):
@@ -700,38 +693,19 @@ class DeviceCollator:
         descriptor table and the host-resized fallback sources (`scene_plan`), from a pinned slot with one copy; one launch
         (tatt_scene_windows) reads every window out of its box's rectangle.  No boxes: the upload alone, an empty stack.  Never waits
         for the device."""
-        import ctypes
-        from . import ops
-        from .lines import line_limits
-        from .scene import scene_fill, scene_plan
-        if self._line_limits is None:
-            self._line_limits = line_limits()
         w, h = self.lr_size
-        plan = scene_plan(scene, boxes, (h, w), stride, self.mask, self._line_limits)
+        plan = scene_plan(scene, boxes, (h, w), stride, self.mask, self._lim(line_limits))
         pix, used = scene_fill(None, plan)
+        n = len(plan.desc)
+        launch = self._windows("tatt_scene_windows", pix, plan.nbytes, n, plan.out_floats) if n else (
+            lambda base, hbase: torch.empty(0, dtype=torch.float32, device=self.device))
+        out = self._stage(used, used, lambda flat: scene_fill(flat, plan), launch)
+        return out.view(n, 3 + int(self.mask), h, w), plan.lines, self._scene_dev(pix, plan)
+
+    def _scene_dev(self, pix, plan):
+        """the scene's (Hs, Ws, 3) pixels where the last upload left them: the first source behind the tables"""
         Hs, Ws = plan.arrays[0].shape[:2]
-        with torch.cuda.device(self.device):
-            stream = torch.cuda.current_stream()
-            moved = self._last is not None and self._last[0] != stream
-            if moved:
-                stream.wait_event(self._last[1])
-            k, host = self._slot(used)
-            if moved:
-                self._dev_buf.record_stream(stream)
-            scene_fill(host.numpy(), plan)
-            self._dev_buf[:used].copy_(host[:used], non_blocking=True)
-            ev = self._events[k] = self._events[k] if self._events[k] is not None else torch.cuda.Event()
-            ev.record(stream)
-            out = torch.empty(plan.out_floats, dtype=torch.float32, device=self.device)
-            base = self._dev_buf.data_ptr()
-            if len(plan.desc):
-                ops.call("tatt_scene_windows", ctypes.c_void_p(base + pix), plan.nbytes, ctypes.c_void_p(base),
-                         ctypes.c_void_p(host.data_ptr()), len(plan.desc), ops.P(out), plan.out_floats, ops.stream())
-            done = self._last[1] if self._last is not None else torch.cuda.Event()
-            done.record(stream)
-            self._last = (stream, done)
-        scene_dev = self._dev_buf[pix:pix + Hs * Ws * 3].view(Hs, Ws, 3)
-        return out.view(len(plan.desc), 3 + int(self.mask), h, w), plan.lines, scene_dev
+        return self._dev_buf[pix:pix + Hs * Ws * 3].view(Hs, Ws, 3)
 
     def quad_windows(self, scene, quads, stride: int = 32):
         """RGB PIL image and quadrilateral boxes (four integer corner points each, `quad_check`) -> (stack, lines, scene_dev): ONE
@@ -742,45 +716,25 @@ class DeviceCollator:
         launch resizes the crops beyond `line_limits()` to (wl, h) on the device (none in the common case: no launch), ONE
         tatt_scene_windows launch reads every window out of its crop (`quad_plan`).  No quads: the upload alone, an empty stack.  Never
         waits for the device."""
-        import ctypes
         from . import ops
-        from .lines import line_limits
-        from .quads import quad_fill, quad_limits, quad_plan
-        from .scene import scene_limits
-        if self._line_limits is None:
-            self._line_limits = line_limits()
-        if getattr(self, "_quad_limits", None) is None:
-            self._quad_limits = (scene_limits(), quad_limits())
         w, h = self.lr_size
-        plan = quad_plan(scene, quads, (h, w), stride, self.mask, self._line_limits, *self._quad_limits)
+        plan = quad_plan(scene, quads, (h, w), stride, self.mask, self._lim(line_limits), self._lim(scene_limits), self._lim(quad_limits))
         o_warp, o_resize, o_desc, pix, used, total = quad_fill(None, plan)
-        Hs, Ws = plan.arrays[0].shape[:2]
-        with torch.cuda.device(self.device):
-            stream = torch.cuda.current_stream()
-            moved = self._last is not None and self._last[0] != stream
-            if moved:
-                stream.wait_event(self._last[1])
-            k, host = self._slot(total)                              # (the device buffer holds the crops behind the upload)
-            if moved:
-                self._dev_buf.record_stream(stream)
-            quad_fill(host.numpy(), plan)
-            self._dev_buf[:used].copy_(host[:used], non_blocking=True)
-            ev = self._events[k] = self._events[k] if self._events[k] is not None else torch.cuda.Event()
-            ev.record(stream)
+
+        def launch(base, hbase):
             out = torch.empty(plan.out_floats, dtype=torch.float32, device=self.device)
-            base, hbase = self._dev_buf.data_ptr(), host.data_ptr()
-            buf, at = ctypes.c_void_p(base + pix), lambda o: (ctypes.c_void_p(base + o), ctypes.c_void_p(hbase + o))
+            buf = _ptrs(base, hbase, pix)[0]
             if len(plan.warp):
-                ops.call("tatt_warp_u8", buf, plan.nbytes, *at(o_warp), len(plan.warp), buf, plan.nbytes, ops.stream())
+                ops.call("tatt_warp_u8", buf, plan.nbytes, *_ptrs(base, hbase, o_warp), len(plan.warp), buf, plan.nbytes, ops.stream())
             if len(plan.resize):
-                ops.call("tatt_resize_u8", buf, plan.nbytes, *at(o_resize), len(plan.resize), buf, plan.nbytes, ops.stream())
+                ops.call("tatt_resize_u8", buf, plan.nbytes, *_ptrs(base, hbase, o_resize), len(plan.resize), buf, plan.nbytes,
+                         ops.stream())
             if len(plan.desc):
-                ops.call("tatt_scene_windows", buf, plan.nbytes, *at(o_desc), len(plan.desc), ops.P(out), plan.out_floats, ops.stream())
-            done = self._last[1] if self._last is not None else torch.cuda.Event()
-            done.record(stream)
-            self._last = (stream, done)
-        scene_dev = self._dev_buf[pix:pix + Hs * Ws * 3].view(Hs, Ws, 3)
-        return out.view(len(plan.desc), 3 + int(self.mask), h, w), plan.lines, scene_dev
+                ops.call("tatt_scene_windows", buf, plan.nbytes, *_ptrs(base, hbase, o_desc), len(plan.desc), ops.P(out), plan.out_floats,
+                         ops.stream())
+            return out
+        out = self._stage(total, used, lambda flat: quad_fill(flat, plan), launch)       # (the device buffer holds the crops behind the upload)
+        return out.view(len(plan.desc), 3 + int(self.mask), h, w), plan.lines, self._scene_dev(pix, plan)
 
 
 # ---- image export on the device (csrc/export.hip) -----------------------------------------------------------------------------------
@@ -909,6 +863,19 @@ def panel_layout(B, H, W, gap: int = 0):
     return height, stride, origins
 
 
+def _tables(*tables):
+    """int32 tables laid behind each other, every one 16-byte aligned -> (head: the words to stage in front of the pixels, the offset of
+    every table in words)"""
+    import numpy as np
+    offs = [0]
+    for t in tables[:-1]:
+        offs.append(offs[-1] + -(-t.size // 4) * 4)
+    head = np.zeros(offs[-1] + tables[-1].size, np.int32)
+    for o, t in zip(offs, tables):
+        head[o:o + t.size] = t.reshape(-1)
+    return head, offs
+
+
 class _ExportSlot:
     """one pinned staging buffer of the exporter's ring: [descriptor rows | pixels]"""
 
@@ -958,7 +925,7 @@ class PendingExport:
             self._slot = None
 
 
-class DeviceExporter:
+class DeviceExporter(_Limits):
     """`export_pil_batch` with the pixels made on the GPU: exporter(images, sizes) takes a (B, C, H, W) fp32 tensor on the device (any
     strides: the channels-last SR tensors are read as they are) and returns a `PendingExport` whose `result()` is BYTE FOR BYTE the host
     path's list of PIL images.  Per call, on the current stream: the descriptor rows go host-to-device from a pinned slot (non-blocking),
@@ -980,7 +947,7 @@ class DeviceExporter:
             raise ValueError("DeviceExporter: ring must be at least 1")
         _rule_code(rule)
         self.rule, self.ring = rule, int(ring)
-        self._limits = self._line_limits = None
+        self._limits = {}
         self._slots, self._i = [_ExportSlot() for _ in range(self.ring)], 0
         self._dev_buf, self._last = None, None
         self._alloc = lambda n: torch.empty(n, dtype=torch.uint8, pin_memory=True)
@@ -1059,10 +1026,8 @@ class DeviceExporter:
 
     def __call__(self, images, sizes=None, c0: int = 0) -> PendingExport:
         self._check(images, c0)
-        if self._limits is None:
-            self._limits = export_limits()
         B, _, H, W = images.shape
-        desc, resize, nbytes = export_plan(B, H, W, sizes, self.rule, self._limits, c0=c0)
+        desc, resize, nbytes = export_plan(B, H, W, sizes, self.rule, self._lim(export_limits), c0=c0)
         views = [(int(d[5]), int(d[2]), int(d[3]), int(d[6]), r) for d, r in zip(desc, resize)]
         return self._enqueue([(images, desc)], nbytes, views)
 
@@ -1076,8 +1041,6 @@ class DeviceExporter:
         eval loop the LR member is NOT pinned to the reference (cf. `rgb_to_yuv_u8`).  The HR size must lie within `export_limits()`."""
         for t in (lr, sr, hr):
             self._check(t, 0)
-        if self._limits is None:
-            self._limits = export_limits()
         B, _, H, W = hr.shape
         if tuple(sr.shape[2:]) != (H, W) or sr.shape[0] != B or lr.shape[0] != B:
             raise ValueError("panels: sr %s and hr %s must agree in batch and size, lr %s in batch" % (
@@ -1087,7 +1050,7 @@ class DeviceExporter:
         height, stride, origins = panel_layout(B, H, W, gap)
         jobs, nbytes = [], 0
         for m, (t, rule) in enumerate(((lr, lr_rule or self.rule), (sr, self.rule), (hr, self.rule))):
-            desc, resize, end = export_plan(B, t.shape[2], t.shape[3], (W, H), rule, self._limits, pitch=[3 * W] * B, origin=origins[m])
+            desc, resize, end = export_plan(B, t.shape[2], t.shape[3], (W, H), rule, self._lim(export_limits), pitch=[3 * W] * B, origin=origins[m])
             if any(r is not None for r in resize):
                 raise ValueError("panels: resizing %d x %d to %d x %d is beyond export_limits()" % (t.shape[2], t.shape[3], H, W))
             jobs.append((t, desc))
@@ -1096,6 +1059,26 @@ class DeviceExporter:
         views = [(b * stride, height, W, 3 * W, None) for b in range(B)]
         return self._enqueue(jobs, nbytes, views, zero=gap > 0)
 
+    def _blend(self, sr_windows, lines, scale, c0):
+        """sr_windows (n_windows, C, H, W) and the Line records of its lines -> ((desc, starts, nbytes) of `blend_plan`, H), the
+        [(byte offset, H, W, pitch)] of the blended lines, and blend(base, hbase, o_starts, pix): the ONE tatt_line_blend launch, its
+        rows at the start of the tables, its window starts `o_starts` words into them, its canvases from `pix` on.  No lines: empty
+        tables, H = 0, no launch (sr_windows is not looked at)."""
+        import ctypes
+        import numpy as np
+        from . import ops
+        from .lines import BLEND_DESC
+        if not lines:
+            return (np.zeros((0, BLEND_DESC), np.int32), np.zeros(0, np.int32), 0, 0), [], lambda base, hbase, o_starts, pix: None
+        self._check(sr_windows, c0)
+        B, C, H, W = sr_windows.shape
+        desc, starts, nbytes = blend_plan(lines, B, H, W, scale, self.rule, c0, self._lim(line_limits))
+
+        def blend(base, hbase, o_starts, pix):
+            ops.call("tatt_line_blend", ops.P(sr_windows), *sr_windows.stride(), B, C, H, W, *_ptrs(base, hbase, 0), len(desc),
+                     *_ptrs(base, hbase, o_starts * 4), int(starts.size), ctypes.c_void_p(base + pix), nbytes, ops.stream())
+        return (desc, starts, nbytes, H), [(int(d[6]), H, scale * int(d[2]), int(d[7])) for d in desc], blend
+
     def lines(self, sr_windows, lines, scale: int, c0: int = 0, out_sizes=None) -> PendingExport:
         """The SR windows of text lines merged into one image per line: sr_windows (n_windows, C, H, W) fp32 on the device (any strides),
         lines: the Line records of `DeviceCollator.windows`, scale = H // h -> a PendingExport whose `result()` is BYTE FOR BYTE
@@ -1103,33 +1086,28 @@ class DeviceExporter:
         (scale * wl, H) each.  The line rows and window starts go host-to-device from a pinned slot, ONE launch (tatt_line_blend) for all
         lines, ONE non-blocking copy of all canvases back.  out_sizes[i] = (width, height): PIL resizes the finished line in `result()`
         (quantisation and blending happen before the resize on both paths)."""
-        import ctypes
-        import numpy as np
-        from . import ops
-        from .lines import blend_plan, line_limits
         self._check(sr_windows, c0)
         lines = list(lines)
-        if self._line_limits is None:
-            self._line_limits = line_limits()
         if out_sizes is not None and len(out_sizes) != len(lines):
             raise ValueError("%d out_sizes for %d lines" % (len(out_sizes), len(lines)))
-        B, C, H, W = sr_windows.shape
-        desc, starts, nbytes = blend_plan(lines, B, H, W, scale, self.rule, c0, self._line_limits)
+        if not lines:
+            raise ValueError("DeviceExporter.lines: no lines for the %d SR windows" % sr_windows.shape[0])
+        (desc, starts, nbytes, _), canvases, blend = self._blend(sr_windows, lines, scale, c0)
         views = []
-        for i, d in enumerate(desc):
-            size = (scale * int(d[2]), H)
-            want = size if out_sizes is None else (int(out_sizes[i][0]), int(out_sizes[i][1]))
-            views.append((int(d[6]), H, size[0], int(d[7]), None if want == size else want))
-        rows = -(-desc.size // 4) * 4                                   # (the starts table 16-byte aligned behind the rows)
-        head = np.zeros(rows + starts.size, np.int32)
-        head[:desc.size], head[rows:] = desc.reshape(-1), starts
+        for i, (off, H, W, pitch) in enumerate(canvases):
+            want = (W, H) if out_sizes is None else (int(out_sizes[i][0]), int(out_sizes[i][1]))
+            views.append((off, H, W, pitch, None if want == (W, H) else want))
+        head, (_, o_starts) = _tables(desc, starts)
+        return self._enqueue([], nbytes, views, head=head, launch=lambda base, hbase, pix: blend(base, hbase, o_starts, pix),
+                             canvases=canvases)
 
-        def launch(base, hbase, pix):
-            ops.call("tatt_line_blend", ops.P(sr_windows), *sr_windows.stride(), B, C, H, W, ctypes.c_void_p(base), ctypes.c_void_p(hbase),
-                     len(desc), ctypes.c_void_p(base + rows * 4), ctypes.c_void_p(hbase + rows * 4), int(starts.size),
-                     ctypes.c_void_p(base + pix), nbytes, ops.stream())
-        canvases = [(int(d[6]), H, scale * int(d[2]), int(d[7])) for d in desc]
-        return self._enqueue([], nbytes, views, head=head, launch=launch, canvases=canvases)
+    def _scene(self, who, scene_dev, sr_windows, lines, scale, c0):
+        """what `scene` and `scene_quads` (`who`) share in front of their paste plans: the check of the scene tensor and the blend of
+        the lines -> (Hs, Ws), then what `_blend` returns"""
+        if not (isinstance(scene_dev, torch.Tensor) and scene_dev.dim() == 3 and scene_dev.shape[2] == 3 and
+                scene_dev.dtype == torch.uint8 and scene_dev.is_contiguous() and scene_dev.device.type == "cuda"):
+            raise ValueError("DeviceExporter.%s takes the contiguous (Hs, Ws, 3) uint8 scene on the device" % who)
+        return (int(scene_dev.shape[0]), int(scene_dev.shape[1])), *self._blend(sr_windows, list(lines), scale, c0)
 
     def scene(self, scene_dev, sr_windows, lines, boxes, scale: int, feather: int = 0, c0: int = 0) -> PendingExport:
         """The finished scene: scene_dev: the (Hs, Ws, 3) uint8 scene on the device (`DeviceCollator.scene_windows`), sr_windows
@@ -1141,48 +1119,23 @@ class DeviceExporter:
         layer (`scene_layers`: boxes that do not intersect share a launch) resizes the line canvases into their rectangles, feathered
         against what the canvas holds, and ONE non-blocking copy brings the buffer into the pinned slot.  Never waits for the device."""
         import ctypes
-        import numpy as np
         from . import ops
-        from .lines import BLEND_DESC, blend_plan, line_limits
-        from .scene import RESIZE_DESC, paste_plan, scene_limits
-        if not (isinstance(scene_dev, torch.Tensor) and scene_dev.dim() == 3 and scene_dev.shape[2] == 3 and
-                scene_dev.dtype == torch.uint8 and scene_dev.is_contiguous() and scene_dev.device.type == "cuda"):
-            raise ValueError("DeviceExporter.scene takes the contiguous (Hs, Ws, 3) uint8 scene on the device")
-        lines, boxes = list(lines), list(boxes)
-        if self._line_limits is None:
-            self._line_limits = line_limits()
-        if getattr(self, "_scene_limits", None) is None:
-            self._scene_limits = scene_limits()
-        Hs, Ws = int(scene_dev.shape[0]), int(scene_dev.shape[1])
-        if lines:
-            self._check(sr_windows, c0)
-            B, C, H, W = sr_windows.shape
-            bdesc, starts, bbytes = blend_plan(lines, B, H, W, scale, self.rule, c0, self._line_limits)
-        else:
-            B = C = H = W = 0
-            bdesc, starts, bbytes = np.zeros((0, BLEND_DESC), np.int32), np.zeros(0, np.int32), 0
-        plan = paste_plan((Ws, Hs), boxes, bdesc, bbytes, scale, H, feather, self._scene_limits)
-        at = lambda n: -(-n // 4) * 4                                  # (every table 16-byte aligned)
-        o_starts = at(bdesc.size)
-        o_rows = o_starts + at(starts.size)
-        head = np.zeros(o_rows + plan.rows.size, np.int32)
-        head[:bdesc.size], head[o_starts:o_starts + starts.size], head[o_rows:] = bdesc.reshape(-1), starts, plan.rows.reshape(-1)
+        from .scene import RESIZE_DESC
+        (Hs, Ws), (bdesc, starts, bbytes, H), canvases, blend = self._scene("scene", scene_dev, sr_windows, lines, scale, c0)
+        plan = paste_plan((Ws, Hs), list(boxes), bdesc, bbytes, scale, H, feather, self._lim(scene_limits))
+        head, (_, o_starts, o_rows) = _tables(bdesc, starts, plan.rows)
         views = [(plan.canvas_off, scale * Hs, scale * Ws, plan.pitch, None)]
         nbytes, src_bytes = plan.nbytes, Hs * Ws * 3
 
         def launch(base, hbase, pix):
             out = ctypes.c_void_p(base + pix)
-            if lines:
-                ops.call("tatt_line_blend", ops.P(sr_windows), *sr_windows.stride(), B, C, H, W, ctypes.c_void_p(base),
-                         ctypes.c_void_p(hbase), len(bdesc), ctypes.c_void_p(base + o_starts * 4), ctypes.c_void_p(hbase + o_starts * 4),
-                         int(starts.size), out, max(bbytes, 1), ops.stream())
-            row = lambda r: (ctypes.c_void_p(base + (o_rows + r * RESIZE_DESC) * 4), ctypes.c_void_p(hbase + (o_rows + r * RESIZE_DESC) * 4))
+            blend(base, hbase, o_starts, pix)
+            row = lambda r: _ptrs(base, hbase, (o_rows + r * RESIZE_DESC) * 4)
             ops.call("tatt_resize_u8", ops.P(scene_dev), src_bytes, *row(0), 1, out, nbytes, ops.stream())
             r = 1
             for n in plan.counts:                                      # the line canvases lie in front of the canvas, in the same buffer
                 ops.call("tatt_resize_u8", out, plan.canvas_off, *row(r), n, out, nbytes, ops.stream())
                 r += n
-        canvases = [(int(d[6]), H, scale * int(d[2]), int(d[7])) for d in bdesc]
         return self._enqueue([], nbytes, views, head=head, launch=launch, canvases=canvases)
 
     def scene_quads(self, scene_dev, sr_windows, lines, quads, scale: int, feather: int = 0, c0: int = 0) -> PendingExport:
@@ -1196,47 +1149,20 @@ class DeviceExporter:
         (`quad_layers`: quads whose bounding boxes do not intersect share a launch) warps the rectangles into their quads, feathered
         against what the canvas holds, and ONE non-blocking copy brings the buffer into the pinned slot.  Never waits for the device."""
         import ctypes
-        import numpy as np
         from . import ops
-        from .lines import BLEND_DESC, blend_plan, line_limits
-        from .quads import QUAD_DESC, quad_limits, quad_paste_plan
-        from .scene import RESIZE_DESC, scene_limits
-        if not (isinstance(scene_dev, torch.Tensor) and scene_dev.dim() == 3 and scene_dev.shape[2] == 3 and
-                scene_dev.dtype == torch.uint8 and scene_dev.is_contiguous() and scene_dev.device.type == "cuda"):
-            raise ValueError("DeviceExporter.scene_quads takes the contiguous (Hs, Ws, 3) uint8 scene on the device")
-        lines, quads = list(lines), list(quads)
-        if self._line_limits is None:
-            self._line_limits = line_limits()
-        if getattr(self, "_scene_limits", None) is None:
-            self._scene_limits = scene_limits()
-        if getattr(self, "_quad_limits", None) is None:
-            self._quad_limits = quad_limits()
-        Hs, Ws = int(scene_dev.shape[0]), int(scene_dev.shape[1])
-        if lines:
-            self._check(sr_windows, c0)
-            B, C, H, W = sr_windows.shape
-            bdesc, starts, bbytes = blend_plan(lines, B, H, W, scale, self.rule, c0, self._line_limits)
-        else:
-            B = C = H = W = 0
-            bdesc, starts, bbytes = np.zeros((0, BLEND_DESC), np.int32), np.zeros(0, np.int32), 0
-        plan = quad_paste_plan((Ws, Hs), quads, bdesc, bbytes, scale, H, feather, self._scene_limits, self._quad_limits)
-        at = lambda n: -(-n // 4) * 4                                  # (every table 16-byte aligned)
-        o_starts = at(bdesc.size)
-        o_rows = o_starts + at(starts.size)
-        o_warp = o_rows + at(plan.resize.size)
-        head = np.zeros(o_warp + plan.warp.size, np.int32)
-        head[:bdesc.size], head[o_starts:o_starts + starts.size] = bdesc.reshape(-1), starts
-        head[o_rows:o_rows + plan.resize.size], head[o_warp:] = plan.resize.reshape(-1), plan.warp.reshape(-1)
+        from .quads import QUAD_DESC
+        from .scene import RESIZE_DESC
+        (Hs, Ws), (bdesc, starts, bbytes, H), canvases, blend = self._scene("scene_quads", scene_dev, sr_windows, lines, scale, c0)
+        quads = list(quads)
+        plan = quad_paste_plan((Ws, Hs), quads, bdesc, bbytes, scale, H, feather, self._lim(scene_limits), self._lim(quad_limits))
+        head, (_, o_starts, o_rows, o_warp) = _tables(bdesc, starts, plan.resize, plan.warp)
         views = [(plan.canvas_off, scale * Hs, scale * Ws, plan.pitch, None)]
         nbytes, src_bytes, n = plan.nbytes, Hs * Ws * 3, len(quads)
 
         def launch(base, hbase, pix):
             out = ctypes.c_void_p(base + pix)
-            if lines:
-                ops.call("tatt_line_blend", ops.P(sr_windows), *sr_windows.stride(), B, C, H, W, ctypes.c_void_p(base),
-                         ctypes.c_void_p(hbase), len(bdesc), ctypes.c_void_p(base + o_starts * 4), ctypes.c_void_p(hbase + o_starts * 4),
-                         int(starts.size), out, max(bbytes, 1), ops.stream())
-            row = lambda o: (ctypes.c_void_p(base + o * 4), ctypes.c_void_p(hbase + o * 4))
+            blend(base, hbase, o_starts, pix)
+            row = lambda o: _ptrs(base, hbase, o * 4)
             ops.call("tatt_resize_u8", ops.P(scene_dev), src_bytes, *row(o_rows), 1, out, nbytes, ops.stream())
             if n:                                                      # the line canvases lie in front of the rectangles, in the same buffer
                 ops.call("tatt_resize_u8", out, max(bbytes, 1), *row(o_rows + RESIZE_DESC), n, out, plan.canvas_off, ops.stream())
@@ -1244,7 +1170,6 @@ class DeviceExporter:
             for c in plan.counts:                                      # the rectangles lie in front of the canvas
                 ops.call("tatt_warp_u8", out, plan.canvas_off, *row(o_warp + r * QUAD_DESC), c, out, nbytes, ops.stream())
                 r += c
-        canvases = [(int(d[6]), H, scale * int(d[2]), int(d[7])) for d in bdesc]
         return self._enqueue([], nbytes, views, head=head, launch=launch, canvases=canvases)
 
 

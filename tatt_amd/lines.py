@@ -103,6 +103,13 @@ def blend_windows_host(sr, starts, wl: int, scale: int, rule: str = "floor", c0:
     return ((2 * num + den) // (2 * den)).astype(np.uint8)
 
 
+def sr_scale(H, W, h, w):
+    """the (H, W) SR window of an (h, w) LR window -> the model's integer scale; ValueError where the two sides do not agree on one"""
+    if H % h or W % w or H // h != W // w:
+        raise ValueError("the SR windows %d x %d are no integer multiple of the LR window %d x %d" % (H, W, h, w))
+    return H // h
+
+
 def super_resolve_lines_host(images, run_windows, lr_size=(16, 64), stride: int = 32, mask: bool = True, rule: str = "floor", c0: int = 0,
                              out_sizes=None):
     """The composition on the host: per RGB PIL image `line_windows_host` -> `run_windows` (a callable: (n, 3 + mask, h, w) window stack
@@ -114,14 +121,29 @@ def super_resolve_lines_host(images, run_windows, lr_size=(16, 64), stride: int 
     for i, img in enumerate(images):
         wl, starts = line_plan(img.size, lr_size, stride)
         sr = run_windows(line_windows_host(img, lr_size, stride, mask))
-        H, W = sr.shape[2:]
-        if H % h or W % w or H // h != W // w:
-            raise ValueError("the SR windows %d x %d are no integer multiple of the LR window %d x %d" % (H, W, h, w))
-        im = Image.fromarray(blend_windows_host(sr, starts, wl, H // h, rule, c0), "RGB")
+        im = Image.fromarray(blend_windows_host(sr, starts, wl, sr_scale(*sr.shape[2:], h, w), rule, c0), "RGB")
         if out_sizes is not None and tuple(out_sizes[i]) != im.size:
             im = im.resize(tuple(out_sizes[i]), Image.BICUBIC)
         out.append(im)
     return out
+
+
+def _super_resolve_boxes_host(windows_host, compose_host, what, scene, boxes, run_windows, lr_size, stride, mask, rule, c0, feather, scale):
+    """`super_resolve_scene_host` and `super_resolve_quads_host` around their own `*_windows_host` and `*_compose_host`;
+    what = (the prefix of their messages, their word for a box)"""
+    from PIL import Image
+    stack, lines = windows_host(scene, boxes, lr_size, stride, mask)
+    images = []
+    for ln in lines:
+        sr = run_windows(stack[ln.first:ln.first + len(ln.starts)])
+        s = sr_scale(*sr.shape[2:], *lr_size)
+        if scale is not None and scale != s:
+            raise ValueError("%s: scale %r given, the model's is %d" % (what[0], scale, s))
+        scale = s
+        images.append(Image.fromarray(blend_windows_host(sr, ln.starts, ln.wl, scale, rule, c0), "RGB"))
+    if scale is None:
+        raise ValueError("%s: no %s and no scale" % what)
+    return compose_host(scene, boxes, images, scale, feather)
 
 
 # ---- host halves of the launches ------------------------------------------------------------------------------------------------------

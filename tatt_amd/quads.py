@@ -33,7 +33,7 @@ import numbers
 from collections import namedtuple
 from fractions import Fraction
 
-from .lines import Line, _line_takes, blend_windows_host, line_limits, line_plan, line_windows_host
+from .lines import Line, _line_takes, _super_resolve_boxes_host, line_limits, line_plan, line_windows_host
 from .scene import RESIZE_DESC, SCENE_DESC, SCENE_MIN_SIDE, scene_layers, scene_limits
 
 QUAD_MAX_TAPER = 2        # opposite sides of a quad differ in length by at most this factor (a two-tap sampler aliases beyond it)
@@ -309,22 +309,8 @@ def super_resolve_quads_host(scene, quads, run_windows, lr_size=(16, 64), stride
     """The composition on the host: `quad_windows_host` -> per quad `run_windows` (a callable: the (n, 3 + mask, h, w) windows of ONE
     quad -> their (n, C, H, W) SR windows) -> `blend_windows_host` -> `quad_compose_host`.  The scale is H // h; `scale` must be given
     when there is no quad to take it from (and is checked against the model's otherwise)."""
-    from PIL import Image
-    h, w = lr_size
-    stack, lines = quad_windows_host(scene, quads, lr_size, stride, mask)
-    images = []
-    for ln in lines:
-        sr = run_windows(stack[ln.first:ln.first + len(ln.starts)])
-        H, W = sr.shape[2:]
-        if H % h or W % w or H // h != W // w:
-            raise ValueError("the SR windows %d x %d are no integer multiple of the LR window %d x %d" % (H, W, h, w))
-        if scale is not None and scale != H // h:
-            raise ValueError("quads: scale %r given, the model's is %d" % (scale, H // h))
-        scale = H // h
-        images.append(Image.fromarray(blend_windows_host(sr, ln.starts, ln.wl, scale, rule, c0), "RGB"))
-    if scale is None:
-        raise ValueError("quads: no quads and no scale")
-    return quad_compose_host(scene, quads, images, scale, feather)
+    return _super_resolve_boxes_host(quad_windows_host, quad_compose_host, ("quads", "quads"), scene, quads, run_windows, lr_size, stride,
+                                     mask, rule, c0, feather, scale)
 
 
 # ---- host halves of the launches ------------------------------------------------------------------------------------------------------

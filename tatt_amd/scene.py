@@ -20,7 +20,7 @@ from __future__ import annotations
 import numbers
 from collections import namedtuple
 
-from .lines import Line, _line_takes, blend_windows_host, line_limits, line_plan, line_windows_host
+from .lines import Line, _line_takes, _super_resolve_boxes_host, line_limits, line_plan, line_windows_host
 
 SCENE_MIN_SIDE = 4        # shortest side of a box: with it no paste shrinks by more than 16 : 1 (one window is 4 : 1, a line 16 rows high)
 SCENE_DESC = 16           # ints per window row of tatt_scene_windows (include/tatt_hip.h)
@@ -151,22 +151,8 @@ def super_resolve_scene_host(scene, boxes, run_windows, lr_size=(16, 64), stride
     """The composition on the host: `scene_windows_host` -> per box `run_windows` (a callable: the (n, 3 + mask, h, w) windows of ONE box
     -> their (n, C, H, W) SR windows) -> `blend_windows_host` -> `scene_compose_host`.  The scale is H // h; `scale` must be given when
     there is no box to take it from (and is checked against the model's otherwise)."""
-    from PIL import Image
-    h, w = lr_size
-    stack, lines = scene_windows_host(scene, boxes, lr_size, stride, mask)
-    images = []
-    for ln in lines:
-        sr = run_windows(stack[ln.first:ln.first + len(ln.starts)])
-        H, W = sr.shape[2:]
-        if H % h or W % w or H // h != W // w:
-            raise ValueError("the SR windows %d x %d are no integer multiple of the LR window %d x %d" % (H, W, h, w))
-        if scale is not None and scale != H // h:
-            raise ValueError("scene: scale %r given, the model's is %d" % (scale, H // h))
-        scale = H // h
-        images.append(Image.fromarray(blend_windows_host(sr, ln.starts, ln.wl, scale, rule, c0), "RGB"))
-    if scale is None:
-        raise ValueError("scene: no boxes and no scale")
-    return scene_compose_host(scene, boxes, images, scale, feather)
+    return _super_resolve_boxes_host(scene_windows_host, scene_compose_host, ("scene", "boxes"), scene, boxes, run_windows, lr_size, stride,
+                                     mask, rule, c0, feather, scale)
 
 
 # ---- host halves of the launches ------------------------------------------------------------------------------------------------------

@@ -197,3 +197,93 @@ def test_slot_is_handed_out_only_after_its_event():
         assert host is col._host[k]
         assert log[before:] == ([k] if col._events[k] is not None else [])   # waited for this slot's event, and only for it
     assert got == [0, 1, 2, 0, 1] and log == [0, 2, 0]
+
+
+def test_stage_orders_wait_slot_copy_launch_and_done(monkeypatch):
+    """the staging step every entry point goes through, without a device (fake streams and events, host tensors for both buffers): the
+    stream waits for the previous call's `done` only when the stream moved; then the slot's own event; then fill, the copy of the used
+    prefix and the slot's event; then the caller's launches; then `done` is recorded and `_last` names this stream.  A call that needs
+    more device bytes than it uploads (`quad_windows`) sizes slot and device buffer by the larger number and copies only the smaller."""
+    from tatt_amd import io
+    log, cur, made = [], [None], []
+
+    class Stream:
+        def __init__(self, name):
+            self.name = name
+
+        def wait_event(self, ev):
+            log.append(("wait", self.name, ev.k))
+
+    class Ev:
+        def __init__(self):
+            self.k = "ev%d" % len(made)
+            made.append(self)
+
+        def synchronize(self):
+            log.append(("sync", self.k))
+
+        def record(self, stream):
+            log.append(("record", self.k, stream.name))
+
+    class DevBuf(torch.Tensor):
+        def record_stream(self, stream):
+            log.append(("record_stream", stream.name))
+
+    class NoDevice:
+        def __init__(self, device):
+            pass
+
+        def __enter__(self):
+            return self
+
+        def __exit__(self, *exc):
+            return False
+
+    def empty(n, dtype=None, pin_memory=False, device=None):
+        t = torch.zeros(n, dtype=dtype)
+        return t if device is None else t.as_subclass(DevBuf)
+
+    monkeypatch.setattr(torch.cuda, "device", NoDevice)
+    monkeypatch.setattr(torch.cuda, "current_stream", lambda: cur[0])
+    monkeypatch.setattr(torch.cuda, "Event", Ev)
+    monkeypatch.setattr(torch, "empty", empty)
+    col = io.DeviceCollator(device="cuda", ring=2)
+
+    def call(stream, need, used, v):
+        """one `_stage` on `stream` whose fill writes v over the whole slot -> (what it logged, the slot index it took)"""
+        cur[0], before = stream, len(log)
+
+        def fill(flat):
+            assert flat.dtype == np.uint8 and flat.size >= need
+            log.append(("fill", int(col._dev_buf[0])))               # (the device buffer still holds the previous call's bytes)
+            flat[:] = v
+
+        def launch(base, hbase):
+            k = (col._i - 1) % col.ring
+            assert base == col._dev_buf.data_ptr() and hbase == col._host[k].data_ptr()
+            assert col._dev_buf.numel() >= need and col._host[k].numel() >= need
+            assert (col._host[k] == v).all()                         # the slot was filled, all of it
+            assert (col._dev_buf[:used] == v).all() and not (col._dev_buf[used:need] == v).any()     # the used prefix, and only it
+            log.append(("launch", k))
+            return "out%d" % v
+        assert col._stage(need, used, fill, launch) == "out%d" % v
+        assert col._last[0] is stream
+        return log[before:], (col._i - 1) % col.ring
+
+    A, B = Stream("A"), Stream("B")
+    # the first call: nothing to wait for; the slots are allocated, slot 0's event and `done` are made
+    assert call(A, 100, 100, 1) == ([("fill", 0), ("record", "ev0", "A"), ("launch", 0), ("record", "ev1", "A")], 0)
+    done = col._last[1]
+    assert done is made[1] and col._events == [made[0], None]
+    # the same stream: no wait on `done`; slot 1 has no event yet; `done` is the same event, recorded again
+    assert call(A, 100, 100, 2) == ([("fill", 1), ("record", "ev2", "A"), ("launch", 1), ("record", "ev1", "A")], 1)
+    # another stream: it waits for `done` first, then the host for slot 0's own event, and the device buffer is handed to the stream
+    assert call(B, 100, 100, 3) == ([("wait", "B", "ev1"), ("sync", "ev0"), ("record_stream", "B"), ("fill", 2), ("record", "ev0", "B"),
+                                     ("launch", 0), ("record", "ev1", "B")], 0)
+    assert col._last == (B, done)
+    # more device bytes than uploaded bytes, beyond the slots: every event in flight is waited for, slots and device buffer are allocated
+    # for the LARGER number, the smaller is copied (the asserts of `launch`)
+    cap = col._host[0].numel()
+    assert call(B, 3 * cap, 200, 4) == ([("sync", "ev0"), ("sync", "ev2"), ("sync", "ev1"), ("fill", 0), ("record", "ev3", "B"),
+                                         ("launch", 1), ("record", "ev1", "B")], 1)
+    assert all(h.numel() >= 3 * cap for h in col._host) and col._dev_buf.numel() >= 3 * cap and col._last == (B, done)

@@ -165,3 +165,44 @@ def test_c_layer_refuses_what_it_does_not_take(dev):
     assert run([4000, 8, 24, 32, 128, 1, 0, 0]) == 3
     assert run([0, 8, 24, 32, 128, 1, 1, 0]) == 3
     torch.cuda.synchronize()
+
+
+def test_every_entry_point_through_one_ring_that_grows(dev):
+    """`stack`, `windows`, `scene_windows`, `quad_windows` and `__call__` in turn through ONE collator with a ring of two slots, twice,
+    the second round on larger inputs, so that the slots and the device buffer are re-allocated in the middle of the sequence: every
+    result is bit for bit its host path's, and `scene_dev` holds the scene's bytes until the next call"""
+    from tatt_amd import io
+    LR, size = (16, 64), (64, 16)
+    img = lambda seed, hs, ws, kind=None: Image.fromarray(
+        R.make_image(np.random.default_rng(seed), hs, ws, seed % 3 if kind is None else kind), "RGB")
+    col = io.DeviceCollator(imgH=16, imgW=64, down_sample_scale=1, mask=True, device=dev, ring=2)
+    rounds = [dict(scene=img(1, 48, 160, 1), boxes=[(5, 3, 155, 17), (100, 30, 160, 48)],
+                   quads=[((20, 10), (140, 30), (138, 46), (18, 26)), ((5, 26), (60, 26), (60, 46), (5, 46))],
+                   lines=[img(2, 9, 40), img(3, 23, 150)], samples=R.make_batch(31, B=2)),
+              dict(scene=img(4, 120, 400, 1), boxes=[(5, 3, 395, 40), (100, 60, 360, 118)],
+                   quads=[((20, 10), (380, 40), (376, 76), (16, 46)), ((5, 80), (200, 80), (200, 116), (5, 116))],
+                   lines=[img(5, 30, 400), img(6, 40, 600)], samples=R.make_batch(32, B=6))]
+    got, caps = [], []
+    for r in rounds:
+        got.append(col.stack(r["lines"], size))
+        caps.append(col._host[0].numel())
+        got.append(col.windows(r["lines"], 32))
+        caps.append(col._host[0].numel())
+        for entry, what in ((col.scene_windows, r["boxes"]), (col.quad_windows, r["quads"])):
+            stack, lines, scene_dev = entry(r["scene"], what, 32)
+            got.append((stack, lines))
+            caps.append(col._host[0].numel())
+            assert np.array_equal(scene_dev.cpu().numpy(), np.asarray(r["scene"]))       # (before the next call moves the buffer on)
+        got.append(col(r["samples"]))
+        caps.append(col._host[0].numel())
+    assert caps == sorted(caps) and len(set(caps[:5])) >= 2 and caps[5:] != [caps[4]] * 5 and len(col._host) == 2, caps
+    torch.cuda.synchronize()
+    for r, (stacked, (win, win_lines), (sw, sw_lines), (qw, qw_lines), batch) in zip(rounds, (got[:5], got[5:])):
+        assert torch.equal(stacked.cpu(), torch.stack([io.resize_normalize(im, size, True) for im in r["lines"]]))
+        want = [io.line_windows_host(im, LR, 32, True) for im in r["lines"]]
+        assert torch.equal(win.cpu(), torch.cat(want)) and [len(ln.starts) for ln in win_lines] == [len(w) for w in want]
+        want, lines = io.scene_windows_host(r["scene"], r["boxes"], LR, 32, True)
+        assert sw_lines == lines and torch.equal(sw.cpu(), want)
+        want, lines = io.quad_windows_host(r["scene"], r["quads"], LR, 32, True)
+        assert qw_lines == lines and torch.equal(qw.cpu(), want)
+        _same(batch, io.collate_pil_batch(r["samples"], imgH=16, imgW=64, down_sample_scale=1, mask=True, device=dev), members=(0, 2))
