@@ -957,6 +957,23 @@ int tatt_read_limits(int* out);
  * Returns 1 for geometries it does not take (T, C, cap < T, st_rec < 3 cap + 2). */
 int tatt_ctc_greedy_read(const float* logits, long st_t, long st_b, long st_c, int T, int B, int C, const int* index, int* record,
                          int n_rows, int cap, long st_rec, hipStream_t st);
+/* CTC prefix beam search (csrc/ctcbeam.hip; specification read.ctc_beam_read_host) of logits (T,B,C) fp32 by element strides, blank 0,
+ * one wave per image, log-soft-max and all path sums in float64: the nbest most probable STRINGS of an image, best first, each with
+ * logp = log of the sum over its alignments that the beam of `beam` prefixes kept.  A prefix is a node of the image's trie in LDS, found
+ * through a (parent, class) table before a node is made, so a string has one identity however often it leaves and re-enters the beam.
+ * Image b writes the record row index[b] (rows st_rec 32-bit words apart; an index outside 0 .. n_rows - 1 writes nothing):
+ *   [0] entries written n <= nbest (fewer where the logits allow fewer strings)  [1] flag  then n entries of es = 4 + cap + (cap & 1)
+ *   words, entry i at 2 + i es (8-byte aligned in a row that is): [0..1] the float64 logp as it is, low word first  [2] its length
+ *   [3] 0  [4 ..) cap classes (+ one pad word for an odd cap) padded with -1.  Words beyond the n entries are left as they were.
+ * flag 1, with [0] = 0 and nothing else written: a NaN or +inf logit, a step without a finite logit (-inf logits are legal otherwise),
+ * or a key the table could not place (impossible at the table's size).
+ * Returns 1 before any launch for: a null pointer, T outside 1 .. 256, C outside 1 .. 64, B or n_rows <= 0, not 1 <= nbest <= beam <= 16,
+ * cap < T, st_rec < 2 + nbest es. */
+int tatt_ctc_beam_read(const float* logits, long st_t, long st_b, long st_c, int T, int B, int C, int beam, int nbest,
+                       const int* index, int* record, int n_rows, int cap, long st_rec, hipStream_t st);
+/* out[0..4]: most steps T, most classes C and most beam entries of tatt_ctc_beam_read, the nodes of an image's trie (1 + 256 * 16) and
+ * the slots of its lookup table.  Host only: needs no GPU. */
+int tatt_beam_limits(int* out);
 /* calculate_psnr (reference utils/ssim_psnr.py:9-15) of two (B,C,H,W) images in [0,1] given by element strides, first 3 channels */
 int tatt_psnr(const float* a, long a_n, long a_c, long a_h, long a_w, const float* b, long b_n, long b_c, long b_h, long b_w,
               float* out, int B, int C, int H, int W, hipStream_t st);

@@ -1,0 +1,356 @@
+// CTC prefix beam search of the line reader (tatt_amd/read.py `ctc_beam_read_host` is the specification, tests/test_beam*.py hold the
+// kernel to it): the N most probable STRINGS of a line, each with its log-probability summed over its alignments.
+//   ctc_beam_read_kernel    one line per wave (a work-group of 64 lanes), no exchange between lines.  Per step: the log-soft-max in
+//                           float64 with lane = class; lane r < |beam| works out the stay candidate of beam entry r; lane c then holds the
+//                           candidates (r, c) of all r in registers (key r C + c: c = 0 is the stay candidate, c >= 1 the extension of r by
+//                           c); `beam` rounds of a wave maximum (ties to the lower key) pick the new beam in descending order.
+// A prefix is a node of the line's trie (parent node, class), at most 1 + T beam nodes, all in LDS.  IDENTITY IS THE NODE: a string has one
+// node for the whole launch, because a selected extension (parent, class) is looked up in an open-addressing table of the line before a
+// node is made -- also when its prefix had left the beam and comes back while strings that start with it stayed.  With unique nodes, "the
+// extension of q by c is the beam entry r" is exactly parent[node r] == node q and class[node r] == c: such an extension adds into r's
+// stay candidate and is no candidate of its own.  The table has CB_TABLE > 2 CB_NODES slots, so a probe sequence ends at an empty slot; it is
+// bounded by CB_TABLE all the same, and a key that cannot be placed raises the line's flag.
+// All of pb, pnb, lse and the log-soft-max are float64 (the logits are fp32); nothing is rounded to fp32 on the way into the record.
+// Every loop is bounded by T, C, CB_BEAM, CB_TABLE or a literal; the candidate registers are indexed by unrolled loops only (no scratch).
+// Wave-wide maxima, minima and sums go through data-parallel-primitive moves (row shifts, row broadcasts) and a lane read: no LDS, and
+// the result is the same in every lane.  The kernel is instantiated for 4, 8 and 16 beam entries; a launch takes the smallest that fits.
+#include "common.h"
+
+#define CB_MAX_T 256
+#define CB_MAX_C 64
+#define CB_BEAM 16
+#define CB_NODES (1 + CB_MAX_T * CB_BEAM)      // the root and at most `beam` new nodes per step
+#define CB_TABLE 16384                         // slots of the (parent, class) -> node table: a power of two above 2 CB_NODES
+#define CB_TABLE_BITS 14
+#define CB_EMPTY 0xffff
+#define CB_NEG (-__builtin_inf())
+
+static_assert(CB_TABLE > 2 * CB_NODES && CB_TABLE == 1 << CB_TABLE_BITS && CB_NODES < CB_EMPTY, "table and node ids");
+
+// 32-bit words of one entry of a record row: float64 logp (2) | length | pad | cap classes, an even count
+static __host__ __device__ inline int cb_entry_words(int cap) { return 4 + cap + (cap & 1); }
+
+__device__ __forceinline__ double cb_lse(double a, double b) {
+    const double m = a > b ? a : b, n = a > b ? b : a;
+    return n == CB_NEG ? m : m + log1p(exp(n - m));
+}
+
+__device__ __forceinline__ unsigned cb_hash(int parent, int c) {
+    return ((unsigned)(parent * CB_MAX_C + c) * 2654435761u) >> (32 - CB_TABLE_BITS);
+}
+
+// Wave maximum and sum by data-parallel-primitive moves: four shifts inside each row of 16 lanes leave the row's result in its lane 15,
+// two row broadcasts carry it on, lane 63 holds the wave's and hands it to every lane through scalar registers.  A lane without a source
+// takes the neutral element (its own value for the maximum, 0 for the sum).
+template <int CTRL, int ROWS>
+__device__ __forceinline__ double cb_add(double v) {
+    return v + __hiloint2double(__builtin_amdgcn_update_dpp(0, __double2hiint(v), CTRL, ROWS, 0xf, false),
+                                __builtin_amdgcn_update_dpp(0, __double2loint(v), CTRL, ROWS, 0xf, false));
+}
+__device__ __forceinline__ double cb_wave_sum(double v) {
+    v = cb_add<0x111, 0xf>(v);                                       // row_shr:1, 2, 4, 8
+    v = cb_add<0x112, 0xf>(v);
+    v = cb_add<0x114, 0xf>(v);
+    v = cb_add<0x118, 0xf>(v);
+    v = cb_add<0x142, 0xa>(v);                                       // row_bcast:15 into rows 1 and 3
+    v = cb_add<0x143, 0xc>(v);                                       // row_bcast:31 into rows 2 and 3
+    return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), 63), __builtin_amdgcn_readlane(__double2loint(v), 63));
+}
+template <int CTRL>
+__device__ __forceinline__ float cb_max(float v) {
+    const int i = __float_as_int(v);
+    return fmaxf(v, __int_as_float(__builtin_amdgcn_update_dpp(i, i, CTRL, 0xf, 0xf, false)));
+}
+__device__ __forceinline__ float cb_wave_max(float v) {
+    v = cb_max<0x111>(v);
+    v = cb_max<0x112>(v);
+    v = cb_max<0x114>(v);
+    v = cb_max<0x118>(v);
+    v = cb_max<0x142>(v);
+    v = cb_max<0x143>(v);
+    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 63));
+}
+
+template <int CTRL>
+__device__ __forceinline__ double cb_maxd(double v) {
+    const int lo = __double2loint(v), hi = __double2hiint(v);
+    return fmax(v, __hiloint2double(__builtin_amdgcn_update_dpp(hi, hi, CTRL, 0xf, 0xf, false),
+                                    __builtin_amdgcn_update_dpp(lo, lo, CTRL, 0xf, 0xf, false)));
+}
+__device__ __forceinline__ double cb_wave_maxd(double v) {           // (no NaN ever gets here)
+    v = cb_maxd<0x111>(v);
+    v = cb_maxd<0x112>(v);
+    v = cb_maxd<0x114>(v);
+    v = cb_maxd<0x118>(v);
+    v = cb_maxd<0x142>(v);
+    v = cb_maxd<0x143>(v);
+    return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), 63), __builtin_amdgcn_readlane(__double2loint(v), 63));
+}
+template <int CTRL>
+__device__ __forceinline__ int cb_mini(int v) {
+    const int o = __builtin_amdgcn_update_dpp(v, v, CTRL, 0xf, 0xf, false);
+    return o < v ? o : v;
+}
+__device__ __forceinline__ int cb_wave_mini(int v) {
+    v = cb_mini<0x111>(v);
+    v = cb_mini<0x112>(v);
+    v = cb_mini<0x114>(v);
+    v = cb_mini<0x118>(v);
+    v = cb_mini<0x142>(v);
+    v = cb_mini<0x143>(v);
+    return __builtin_amdgcn_readlane(v, 63);
+}
+
+// BM: the beam entries the kernel keeps registers and unrolled loops for (beam <= BM <= CB_BEAM): a launch takes the smallest that fits.
+template <int BM>
+__global__ __launch_bounds__(64) void ctc_beam_read_kernel(const float* __restrict__ logits, long st_t, long st_b, long st_c, int T,
+                                                           int C, int beam, int nbest, const int* __restrict__ index,
+                                                           int* __restrict__ record, int n_rows, int cap, long st_rec) {
+    __shared__ double lp[CB_MAX_C];                                  // the step's log-soft-max
+    __shared__ double pb[2][CB_BEAM], pnb[2][CB_BEAM], tot[2][CB_BEAM];      // the beam, by rank; [cur] is read, [cur ^ 1] written
+    __shared__ int node[2][CB_BEAM];
+    __shared__ double spb[CB_BEAM], spnb[CB_BEAM], stot[CB_BEAM];    // the stay candidate of every entry
+    __shared__ int ext_par[CB_BEAM], ext_cls[CB_BEAM];               // selected extensions that still need their node
+    __shared__ unsigned short kill[CB_BEAM * CB_MAX_C];              // [r][c] == t + 1: the extension of r by c went into a stay candidate
+    __shared__ unsigned short par[CB_NODES];                         // the trie
+    __shared__ unsigned char cls[CB_NODES];
+    __shared__ unsigned short table[CB_TABLE];                       // node id or CB_EMPTY
+    __shared__ int state_sh[2];                                      // nodes in use, flag
+    __shared__ int len_sh[CB_BEAM];
+    __shared__ int last_sh[CB_BEAM];                                 // the last class of every entry's prefix, -1 for the empty one
+    const int lane = threadIdx.x;
+    const float* x = logits + blockIdx.x * st_b + lane * st_c;
+
+    for (int i = lane; i < CB_TABLE; i += 64) table[i] = CB_EMPTY;
+    for (int i = lane; i < CB_BEAM * CB_MAX_C; i += 64) kill[i] = 0;
+    if (lane < 2 * CB_BEAM) {                                        // (entries beyond the beam are read, and selected away: keep them tame)
+        (&pb[0][0])[lane] = CB_NEG;
+        (&tot[0][0])[lane] = CB_NEG;
+        if (lane < CB_BEAM) {
+            stot[lane] = CB_NEG;
+            last_sh[lane] = -1;
+        }
+    }
+    __syncthreads();
+    if (lane == 0) {
+        par[0] = 0;
+        cls[0] = 0;
+        node[0][0] = 0;                                              // the empty prefix is the root
+        pb[0][0] = 0.0;
+        pnb[0][0] = CB_NEG;
+        tot[0][0] = 0.0;
+        state_sh[0] = 1;
+        state_sh[1] = 0;
+    }
+    int nb = 1, cur = 0, flag = 0;                                   // (the same in every lane)
+    float xn = lane < C ? x[0] : -INFINITY;
+    __syncthreads();
+
+#pragma unroll 1
+    for (int t = 0; t < T; ++t) {
+        const float xc = xn;
+        if (t + 1 < T) xn = lane < C ? x[(t + 1) * st_t] : -INFINITY;        // (in flight during this step)
+        // ---- the log-soft-max, lane = class ----
+        const float mx = cb_wave_max(xc);                              // (fmaxf skips a NaN: looked for on its own)
+        if (__ballot(xc != xc || xc == INFINITY) != 0 || mx == -INFINITY) {
+            flag = 1;
+            break;
+        }
+        const double d = (double)xc - (double)mx;
+        const double s = cb_wave_sum(lane < C ? exp(d) : 0.0);
+        const double lpc = d - log(s);                               // (-inf beyond C)
+        if (lane < C) lp[lane] = lpc;
+        __syncthreads();
+        // ---- lane r: the stay candidate of entry r, with the extension that spells the same string ----
+        if (lane < nb) {
+            const int nd = node[cur][lane];
+            const double a = tot[cur][lane] + lp[0];
+            double b = CB_NEG;
+            last_sh[lane] = nd != 0 ? cls[nd] : -1;
+            if (nd != 0) {
+                const int last = cls[nd], p = par[nd];
+                b = pnb[cur][lane] + lp[last];
+                int q = -1;                                          // (at most one: the nodes of a beam are distinct)
+#pragma unroll
+                for (int i = 0; i < BM; ++i)
+                    if (i < nb && node[cur][i] == p) q = i;
+                if (q >= 0) {
+                    const int last_q = p != 0 ? cls[p] : -1;
+                    b = cb_lse(b, (last == last_q ? pb[cur][q] : tot[cur][q]) + lp[last]);
+                    kill[q * CB_MAX_C + last] = (unsigned short)(t + 1);
+                }
+            }
+            spb[lane] = a;
+            spnb[lane] = b;
+            stot[lane] = cb_lse(a, b);
+        }
+        __syncthreads();
+        // ---- lane c: the candidates (r, c) of every r ----
+        double v[BM];                                                // (every load below is issued whatever nb is: no branch, one wait)
+#pragma unroll
+        for (int r = 0; r < BM; ++r) {
+            const double ext = (lane == last_sh[r] ? pb[cur][r] : tot[cur][r]) + lpc;
+            const bool struck = kill[r * CB_MAX_C + lane] == (unsigned short)(t + 1);
+            const double val = lane == 0 ? stot[r] : (struck ? CB_NEG : ext);
+            v[r] = r < nb && lane < C ? val : CB_NEG;
+        }
+        // ---- the `beam` largest, descending, ties to the lower key; lane i keeps the i-th ----
+        int nsel = 0, my_r = 0, my_c = 0;
+        double my_val = CB_NEG;
+        for (int i = 0; i < beam; ++i) {
+            double bv = CB_NEG;
+            int br = 0;
+#pragma unroll
+            for (int r = 0; r < BM; ++r)
+                if (v[r] > bv) { bv = v[r]; br = r; }                // (the lowest r among equals: this lane's lowest key)
+            const double top = cb_wave_maxd(bv);                     // (the same in every lane)
+            if (top == CB_NEG) break;                                // fewer candidates than `beam`
+            const unsigned long long eq = __ballot(bv == top);
+            int wc = __ffsll(eq) - 1;
+            int wr = __builtin_amdgcn_readlane(br, wc);
+            if (eq & (eq - 1)) {                                     // equal values in several lanes: the lowest key r C + c
+                const int k = cb_wave_mini(bv == top ? br * C + lane : 0x7fffffff);
+                wr = k / C;
+                wc = k - wr * C;
+            }
+            if (lane == wc) {
+#pragma unroll
+                for (int r = 0; r < BM; ++r)
+                    if (r == wr) v[r] = CB_NEG;
+            }
+            if (lane == i) { my_r = wr; my_c = wc; my_val = top; }
+            ++nsel;
+        }
+        nsel = __builtin_amdgcn_readfirstlane(nsel);
+        // ---- lane i: entry i of the new beam.  A selected extension LOOKS UP (parent, class) first: nothing writes the table meanwhile ----
+        const int nxt = cur ^ 1;
+        bool miss = false;
+        if (lane < nsel) {
+            const int r = my_r, c = my_c;
+            if (c == 0) {
+                node[nxt][lane] = node[cur][r];
+                pb[nxt][lane] = spb[r];
+                pnb[nxt][lane] = spnb[r];
+            } else {
+                const int p = node[cur][r];
+                pb[nxt][lane] = CB_NEG;
+                pnb[nxt][lane] = my_val;
+                const unsigned h = cb_hash(p, c);
+                int found = -1;
+                for (int probe = 0; probe < CB_TABLE; ++probe) {
+                    const int e = table[(h + probe) & (CB_TABLE - 1)];
+                    if (e == CB_EMPTY) break;
+                    if (par[e] == p && cls[e] == c) {
+                        found = e;
+                        break;
+                    }
+                }
+                miss = found < 0;
+                node[nxt][lane] = miss ? 0 : found;
+                ext_par[lane] = p;
+                ext_cls[lane] = c;
+            }
+            tot[nxt][lane] = my_val;
+        }
+        // ---- a node is made only where there was none: the keys of one step differ, so lane 0 places them one after the other ----
+        const unsigned long long todo = __ballot(miss);
+        if (todo != 0) {                                             // (the same in every lane)
+            __syncthreads();
+            if (lane == 0) {
+                int nn = state_sh[0], bad = 0;
+                for (int i = 0; i < nsel; ++i) {
+                    if (!((todo >> i) & 1)) continue;
+                    const int c = ext_cls[i], p = ext_par[i];
+                    const unsigned h = cb_hash(p, c);
+                    int made = -1;
+                    for (int probe = 0; probe < CB_TABLE && nn < CB_NODES; ++probe) {
+                        const unsigned slot = (h + probe) & (CB_TABLE - 1);
+                        if (table[slot] != CB_EMPTY) continue;       // (another key: this one is not in the table)
+                        par[nn] = (unsigned short)p;
+                        cls[nn] = (unsigned char)c;
+                        table[slot] = (unsigned short)nn;
+                        made = nn++;
+                        break;
+                    }
+                    if (made < 0) { bad = 1; made = 0; }
+                    node[nxt][i] = made;
+                }
+                state_sh[0] = nn;
+                if (bad) state_sh[1] = 1;
+            }
+        }
+        __syncthreads();
+        nb = nsel;
+        cur = nxt;
+        if (state_sh[1] != 0) {                                      // (cannot happen with the table sized as it is)
+            flag = 1;
+            break;
+        }
+    }
+
+    // ---- the record row ----
+    const int row = index[blockIdx.x];
+    if (row < 0 || row >= n_rows) return;
+    int* rec = record + row * st_rec;
+    if (flag) {
+        if (lane == 0) {
+            rec[0] = 0;
+            rec[1] = 1;
+        }
+        return;
+    }
+    const int n_out = nb < nbest ? nb : nbest, es = cb_entry_words(cap);
+    if (lane < n_out) {                                              // lane i walks entry i back to the root
+        int* e = rec + 2 + lane * es;
+        const int first = node[cur][lane];
+        int len = 0;
+        for (int nd = first; nd != 0 && len < T; nd = par[nd]) ++len;        // (a node's depth is at most the steps taken: len <= T <= cap)
+        const double lg = tot[cur][lane];
+        e[0] = __double2loint(lg);
+        e[1] = __double2hiint(lg);
+        e[2] = len;
+        e[3] = 0;
+        int nd = first;
+        for (int k = len - 1; k >= 0; --k) {
+            e[4 + k] = cls[nd];
+            nd = par[nd];
+        }
+        len_sh[lane] = len;
+    }
+    __syncthreads();
+    for (int i = 0; i < n_out; ++i) {
+        int* e = rec + 2 + i * es;
+        for (int k = len_sh[i] + lane; k < es - 4; k += 64) e[4 + k] = -1;
+    }
+    if (lane == 0) {
+        rec[0] = n_out;
+        rec[1] = 0;
+    }
+}
+
+TATT_API int tatt_ctc_beam_read(const float* logits, long st_t, long st_b, long st_c, int T, int B, int C, int beam, int nbest,
+                                const int* index, int* record, int n_rows, int cap, long st_rec, hipStream_t st) {
+    if (!logits || !index || !record) return 1;
+    if (T <= 0 || T > CB_MAX_T || B <= 0 || C <= 0 || C > CB_MAX_C || n_rows <= 0 || cap < T) return 1;
+    if (nbest < 1 || nbest > beam || beam > CB_BEAM || st_rec < 2 + (long)nbest * cb_entry_words(cap)) return 1;
+    if (beam <= 4)
+        hipLaunchKernelGGL(ctc_beam_read_kernel<4>, dim3(B), dim3(64), 0, st, logits, st_t, st_b, st_c, T, C, beam, nbest, index, record,
+                           n_rows, cap, st_rec);
+    else if (beam <= 8)
+        hipLaunchKernelGGL(ctc_beam_read_kernel<8>, dim3(B), dim3(64), 0, st, logits, st_t, st_b, st_c, T, C, beam, nbest, index, record,
+                           n_rows, cap, st_rec);
+    else
+        hipLaunchKernelGGL(ctc_beam_read_kernel<CB_BEAM>, dim3(B), dim3(64), 0, st, logits, st_t, st_b, st_c, T, C, beam, nbest, index,
+                           record, n_rows, cap, st_rec);
+    return LAUNCH_CHECK();
+}
+
+TATT_API int tatt_beam_limits(int* out) {
+    if (!out) return 1;
+    out[0] = CB_MAX_T;
+    out[1] = CB_MAX_C;
+    out[2] = CB_BEAM;
+    out[3] = CB_NODES;
+    out[4] = CB_TABLE;
+    return 0;
+}

@@ -771,10 +771,13 @@ class SuperResolver:
     bucket chunk one eager CRNN forward and one tatt_ctc_greedy_read launch, +1 copy; nothing waits before `result()`.  With
     long_lines `result()` is (images, texts) and `PendingUpscale.readings()` the `read.Reading` records; `scene` / `scene_quads` keep
     `result()` (the picture) and add `PendingScene.texts()` / `.readings()`, one per box in input order.  Lines are read before
-    `out_sizes` and `feather` apply.  A plain call on an instance with `reader=` and no `recognizer=` raises ValueError."""
+    `out_sizes` and `feather` apply.  A plain call on an instance with `reader=` and no `recognizer=` raises ValueError.
+    read_decode="beam" (read_beam, read_nbest) decodes with the CTC prefix beam search instead: one tatt_ctc_beam_read launch per
+    chunk in place of the greedy one, and `readings()` gives `read.BeamReading`s (text, logp, alternatives); `texts()` as before."""
 
     def __init__(self, generator, prior=None, recognizer=None, batch_size: int = 48, lr_size=(16, 64), mask: bool = True,
-                 rule: str = "floor", keep_sr: bool = False, long_lines: bool = False, stride: int = 32, reader=None):
+                 rule: str = "floor", keep_sr: bool = False, long_lines: bool = False, stride: int = 32, reader=None,
+                 read_decode: str = "greedy", read_beam: int = 8, read_nbest: int = 4):
         from .io import DeviceCollator, DeviceExporter
         _refuse_attention_recognizer(recognizer, "SuperResolver")
         _check_module(generator, "generator")
@@ -799,7 +802,8 @@ class SuperResolver:
         self.reader = None
         if reader is not None:
             from .read import LineReader
-            self.reader = LineReader(reader, batch_size=batch_size, device=self.device, w=self.lr_size[1])
+            self.reader = LineReader(reader, batch_size=batch_size, device=self.device, w=self.lr_size[1], decode=read_decode,
+                                     beam=read_beam, nbest=read_nbest)
 
     def _texts(self, sr):
         """-> (pinned (n, T + 1) int32: decoded classes | length, its event)"""
