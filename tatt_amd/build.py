@@ -18,12 +18,12 @@ SOURCES = ["gemm.hip", "conv3.hip", "conv3w.hip", "conv9.hip", "norm.hip", "elem
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden", "-ffp-contract=fast"]
 # per-source additions.  conv3.hip: the staging waves of the 3x3 kernels run beside MFMA waves on the same SIMD, and packed fp32 VALU forms
 # (what SLP vectorisation makes of adjacent scalar adds / fmas) take issue time from the matrix pipe (profiles/r06_conv3_sb4_roles.txt)
-# collate.hip: its coefficient tables must equal Pillow's double arithmetic bit for bit; a contracted multiply-add changes them (the last flag wins)
-# export.hip: the same tables (csrc/pil_resample.h), and its quantisation is one fp32 multiply then one fp32 add, never a fused multiply-add
-# lines.hip: both of the above (the tables on the way in, the quantisation on the way out)
-# scene.hip: the same tables, for the windows of boxes and for the tiled uint8 resampler
+# collate.hip, export.hip, lines.hip, scene.hip, read.hip: everything that includes csrc/pil_resample.h (Pillow's coefficient tables, the
+# resampling passes and the two kernel bodies built from them, the quantiser).  The tables must equal Pillow's double arithmetic bit for
+# bit and a contracted multiply-add changes them (the last flag wins); the quantiser (export.hip, lines.hip's blend) is one fp32
+# multiply then one fp32 add, never a fused multiply-add
 # quads.hip: integer arithmetic only; built like its siblings so that nothing in it can contract
-# read.hip: the same tables, and its luma is one fp32 multiply that must stay one
+# read.hip, further: its luma is one fp32 multiply that must stay one
 EXTRA_FLAGS = {"conv3.hip": ["-fno-slp-vectorize"], "conv3w.hip": ["-fno-slp-vectorize"], "sattn2.hip": ["-fno-slp-vectorize"],
                "collate.hip": ["-ffp-contract=off"], "export.hip": ["-ffp-contract=off"], "lines.hip": ["-ffp-contract=off"],
                "scene.hip": ["-ffp-contract=off"], "quads.hip": ["-ffp-contract=off"], "read.hip": ["-ffp-contract=off"]}
@@ -32,7 +32,7 @@ _INCLUDE = re.compile(rb'^[ \t]*#[ \t]*include[ \t]+"([^"]+)"', re.M)
 
 def _digest(paths, extra=()) -> str:
     """content hash of the files and the flags; a source or header also brings in the headers of its own directory that it includes
-    with quotes (csrc/pil_resample.h, shared by collate.hip and export.hip), each once, so that editing one rebuilds its users"""
+    with quotes (csrc/pil_resample.h, the resampler of collate, export, lines, scene and read.hip), each once, so that editing one rebuilds its users"""
     h = hashlib.sha256(" ".join(FLAGS + list(extra)).encode())
     todo, seen = list(paths), set()
     while todo:

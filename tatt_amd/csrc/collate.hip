@@ -7,21 +7,23 @@
 // Layout: one work-group of 256 threads per output image ("item"); no traffic between work-groups, no atomics, every loop bounded by
 // the item's sizes.  Every quantity the kernel reads (descriptor rows, pixels) comes from DEVICE memory, so a captured launch sees
 // whatever the staging copy in front of it wrote.
-//   phase 0  coefficient tables in LDS, in double, exactly as Pillow's precompute_coeffs + normalize_coeffs_8bpc (Resample.c): one
-//            thread per output column / row; weights summed in index order, divided by the sum, rounded to 22-bit fixed point.
-//            This file is compiled with -ffp-contract=off (tatt_amd/build.py): a fused multiply-add in the polynomial or in `center`
-//            changes coefficients.
-//   phase 1  horizontal pass, source (interleaved RGB in global memory) -> uint8 [H_src][OW][3] in LDS; acc = 2^21 + sum pixel * k in
-//            int32, clamp(acc >> 22, 0, 255).  Skipped when W_src == OW (Pillow skips it too: a copy, not a resample).
-//   phase 2  vertical pass (skipped when H_src == OH), straight into the float planes out[c][y][x] = float(v) / 255 (IEEE division),
-//            consecutive threads on consecutive x; with the mask, L = (19595 R + 38470 G + 7471 B + 0x8000) >> 16 per pixel into LDS
-//            and sum(L) reduced over the work-group in integers
-//   phase 3  mask plane: 1.0 where L * N <= sum(L), else 0.0 -- `0 if L > mean(L) else 255` without a rounding: L is an integer and
-//            sum(L) / N is at least 1 / N away from any larger integer.
+//   phase 0  coefficient tables in LDS, in double, exactly as Pillow's precompute_coeffs + normalize_coeffs_8bpc (col_coeffs): one thread
+//            per output column / row.  This file is compiled with -ffp-contract=off (tatt_amd/build.py).
+//   phase 1  horizontal pass (pil_horizontal), source (interleaved RGB in global memory) -> uint8 [H_src][OW][3] in LDS.  Skipped when
+//            W_src == OW (Pillow skips it too: a copy, not a resample).
+//   phase 2  vertical pass (pil_vertical, skipped when H_src == OH) straight into the float planes out[c][y][x] = float(v) / 255 (IEEE
+//            division), consecutive threads on consecutive x; with the mask, L = (19595 R + 38470 G + 7471 B + 0x8000) >> 16 per pixel
+//            into LDS and sum(L) reduced over the work-group in integers
+//   phase 3  mask plane: 1.0 where L * N <= sum(L), else 0.0 -- `0 if L > mean(L) else 255` without a rounding
+// The two passes are pil_resample.h's, shared with every resampling kernel; the source is addressed as a packed image (PilPacked).
+// The BODY around them -- layout with a static reduction block, check, sink, mask plane -- is this kernel's own copy of what
+// pil_window_body does for lines.hip and scene.hip: on that body, which computes the same, tatt_collate_images ran 0.3 us (0.5 %)
+// slower per batch of 96 items, outside the run-to-run spread, whichever way the source was addressed
+// (profiles/pil_resample_core_ab.txt).
 // LDS per item: tables ((4 W_src + 3 OW) + (4 H_src + 3 OH) ints at most, bounds 2 (OW + OH) ints), L (OH * OW bytes), the
 // intermediate (H_src * OW * 3 bytes): 138.3 KB at the limits below, of the CU's 160 KB.
 #include "common.h"
-#include "pil_resample.h"         // col_ksize, col_bicubic, col_coeffs, col_clip8 (shared with export.hip)
+#include "pil_resample.h"         // col_ksize, col_coeffs; pil_horizontal, pil_vertical, PilPacked
 
 #define COL_THREADS 256
 #define COL_DESC 8                     // ints per descriptor row: src byte offset, H_src, W_src, OH, OW, mask flag, out float offset, 0
@@ -55,43 +57,6 @@ static __host__ __device__ inline ColLayout col_layout(int hs, int ws, int oh, i
     g.inter = take(g.ksh ? hs * ow * 3 : 0);
     g.total = o;
     return g;
-}
-
-// phase 2 over the item's OH * OW pixels from s1 = uint8 [rows][OW][3] (the source itself or the horizontal pass's result); returns
-// this thread's share of sum(L)
-__device__ __forceinline__ int col_vertical(const unsigned char* __restrict__ s1, const int* kv, const int* bv, int ksv, int oh, int ow,
-                                            float* __restrict__ out, unsigned char* lum, int tid) {
-    const int N = oh * ow;
-    int lsum = 0;
-    for (int i = tid; i < N; i += COL_THREADS) {
-        const int y = i / ow, x = i - y * ow;
-        int r, g, b;
-        if (ksv) {
-            const int ymin = bv[2 * y], n = bv[2 * y + 1];
-            const int* k = kv + y * ksv;
-            const unsigned char* p = s1 + ((long)ymin * ow + x) * 3;
-            int a0 = 1 << (COL_PB - 1), a1 = a0, a2 = a0;
-            for (int t = 0; t < n; ++t, p += (long)ow * 3) {
-                const int kt = k[t];
-                a0 += p[0] * kt;
-                a1 += p[1] * kt;
-                a2 += p[2] * kt;
-            }
-            r = col_clip8(a0), g = col_clip8(a1), b = col_clip8(a2);
-        } else {
-            const unsigned char* p = s1 + (long)i * 3;
-            r = p[0], g = p[1], b = p[2];
-        }
-        out[i] = __fdiv_rn((float)r, 255.f);
-        out[N + i] = __fdiv_rn((float)g, 255.f);
-        out[2 * N + i] = __fdiv_rn((float)b, 255.f);
-        if (lum) {
-            const int L = (19595 * r + 38470 * g + 7471 * b + 0x8000) >> 16;
-            lum[i] = (unsigned char)L;
-            lsum += L;
-        }
-    }
-    return lsum;
 }
 
 __global__ __launch_bounds__(COL_THREADS) void collate_kernel(const unsigned char* __restrict__ packed, long packed_bytes,
@@ -131,29 +96,26 @@ __global__ __launch_bounds__(COL_THREADS) void collate_kernel(const unsigned cha
 
     // phase 1
     if (g.ksh) {
-        const int n1 = hs * ow;
-        for (int i = tid; i < n1; i += COL_THREADS) {
-            const int yy = i / ow, xx = i - yy * ow;
-            const int xmin = bh[2 * xx], n = bh[2 * xx + 1];
-            const int* k = kh + xx * g.ksh;
-            const unsigned char* p = src + ((long)yy * ws + xmin) * 3;
-            int a0 = 1 << (COL_PB - 1), a1 = a0, a2 = a0;
-            for (int x = 0; x < n; ++x, p += 3) {
-                const int kx = k[x];
-                a0 += p[0] * kx;
-                a1 += p[1] * kx;
-                a2 += p[2] * kx;
-            }
-            inter[i * 3] = (unsigned char)col_clip8(a0);
-            inter[i * 3 + 1] = (unsigned char)col_clip8(a1);
-            inter[i * 3 + 2] = (unsigned char)col_clip8(a2);
-        }
+        pil_horizontal<COL_THREADS>(src, PilPacked{ws}, 0, kh, bh, g.ksh, hs, ow, ow, inter, tid);
         __syncthreads();
     }
 
-    // phase 2 (two call sites: the source pointer is global memory in one and LDS in the other)
-    int lsum = g.ksh ? col_vertical(inter, kv, bv, g.ksv, oh, ow, out, lum, tid)
-                     : col_vertical(src, kv, bv, g.ksv, oh, ow, out, lum, tid);
+    // phase 2 (two call sites: the source pointer is LDS in one and global memory in the other)
+    const int n = oh * ow;
+    int lsum = 0;
+    auto sink = [&](int y, int x, int r, int gg, int b) {
+        const int i = y * ow + x;
+        out[i] = __fdiv_rn((float)r, 255.f);
+        out[n + i] = __fdiv_rn((float)gg, 255.f);
+        out[2 * n + i] = __fdiv_rn((float)b, 255.f);
+        if (lum) {
+            const int L = (19595 * r + 38470 * gg + 7471 * b + 0x8000) >> 16;
+            lum[i] = (unsigned char)L;
+            lsum += L;
+        }
+    };
+    if (g.ksh) pil_vertical<COL_THREADS>(inter, PilPacked{ow}, 0, kv, bv, g.ksv, 0, oh, ow, tid, sink);
+    else pil_vertical<COL_THREADS>(src, PilPacked{ow}, 0, kv, bv, g.ksv, 0, oh, ow, tid, sink);
     if (!mask) return;
 
     // phase 3
@@ -164,7 +126,6 @@ __global__ __launch_bounds__(COL_THREADS) void collate_kernel(const unsigned cha
     int total = 0;
 #pragma unroll
     for (int w = 0; w < COL_THREADS / 64; ++w) total += red[w];
-    const int n = (int)N;
     for (int i = tid; i < n; i += COL_THREADS) out[3 * n + i] = (int)lum[i] * n <= total ? 1.f : 0.f;
 }
 

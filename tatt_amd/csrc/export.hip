@@ -12,7 +12,7 @@
 //            that the add of rule 1 is not fused into it: float32(k) / 255 * 255 truncates back to k for every byte k only then);
 //            rule 0 ("floor", the eval loop): clip t to [0, 255], truncate; rule 1 ("round", save_image): t + 0.5f in one fp32 add,
 //            clip, truncate.  NaN -> 0 under both rules, +-inf clips.  Done on the fly wherever a pass reads a source sample.
-//   phase 0  coefficient tables in LDS, in double (pil_resample.h, shared with collate.hip)
+//   phase 0  coefficient tables in LDS, in double (pil_resample.h, as every resampling kernel)
 //   phase 1  horizontal pass, source -> uint8 [H][OW][3] in LDS; skipped when W == OW (Pillow skips it too)
 //   phase 2  vertical pass (skipped when H == OH), straight to out[offset + y * pitch + 3 x + c]; one BYTE per thread and step, so
 //            consecutive threads write consecutive bytes and read consecutive bytes of the intermediate
@@ -20,7 +20,7 @@
 // (H * OW * 3 bytes): 120,112 bytes at most over every geometry within the limits below, of the CU's 160 KB.  A launch asks for what its largest item needs (none at the
 // native size) and the kernel refuses a row that needs more.
 #include "common.h"
-#include "pil_resample.h"
+#include "pil_resample.h"         // col_ksize, col_coeffs, col_clip8, exp_quant
 
 #define EXP_THREADS 256
 #define EXP_DESC 8                     // ints per descriptor row: b, c0, OH, OW, rule, out byte offset, row pitch in bytes, 0
@@ -62,13 +62,6 @@ static __host__ __device__ inline int exp_check(const int* d, int B, int C, int 
     if (b < 0 || b >= B || c0 < 0 || c0 > C - 3) return 3;
     if (off < 0 || pitch < 3 * ow || (long)off + (long)(oh - 1) * pitch + 3L * ow > out_bytes) return 3;
     return 0;
-}
-
-__device__ __forceinline__ int exp_quant(float x, int rule) {
-    float t = __fmul_rn(x, 255.0f);
-    if (rule) t = __fadd_rn(t, 0.5f);
-    if (!(t > 0.0f)) return 0;                                      // negatives, -0.0, -inf and NaN
-    return t >= 255.0f ? 255 : (int)t;
 }
 
 __global__ __launch_bounds__(EXP_THREADS) void export_kernel(const float* __restrict__ src, long st_n, long st_c, long st_h, long st_w,

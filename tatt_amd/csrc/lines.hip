@@ -10,103 +10,34 @@
 // on the host before the launch and in the kernel.  Compiled with -ffp-contract=off (tatt_amd/build.py), for pil_resample.h's tables in
 // double and for the quantisation (one fp32 multiply, then one fp32 add).
 //
-// line_windows_kernel, one work-group of 256 threads per window, the phases of collate_kernel on the FULL-LINE geometry:
-//   phase 0  coefficient tables in LDS: rows x0 .. x0 + w - 1 of the horizontal table W_src -> wl, the vertical table H_src -> h
-//   phase 1  horizontal pass into LDS for those w columns only, uint8 [H_src][w][3]; skipped when W_src == wl (as Pillow skips it)
-//   phase 2  vertical pass (skipped when H_src == h) straight into the float planes, __fdiv_rn(v, 255); L per pixel into LDS
-//   phase 3  mask plane: 1.0 where L * N <= sum(L) over the WINDOW (not the line: each window must look like a training crop)
-// LDS per window at the limits below: horizontal table 32,768 + bounds 2,048, vertical table and bounds < 5,120, L 16,384, the
-// intermediate 65,536, the reduction 16: under 122 KB of the CU's 160 KB.  A launch asks for what its largest window needs.
+// line_windows_kernel, one work-group of 256 threads per window, is pil_window_body of pil_resample.h on the FULL-LINE geometry: the
+// coefficient rows x0 .. x0 + w - 1 of the table W_src -> wl, the horizontal pass for those w columns only, the vertical pass into the
+// float planes, the mask plane from the mean of the WINDOW (not the line: each window must look like a training crop).
+// LDS per window at the limits (LIN_* of line_limits.h): horizontal table 32,768 + bounds 2,048, vertical table and bounds < 5,120,
+// L 16,384, the intermediate 65,536, the reduction 16: under 122 KB of the CU's 160 KB.  A launch asks for what its largest window needs.
 //
 // line_blend_kernel, grid (lines, column tiles), one thread per output PIXEL and step: the windows that cover canvas column X are found
 // by a binary search in the line's table of window starts (LDS), each contributes its quantised value with the weight min(j + 1, W - j)
 // of its local column j, and the pixel is the weighted mean rounded half up, (2 N + D) / (2 D), in integers.
 #include "common.h"
-#include "pil_resample.h"         // col_ksize, col_coeffs, col_clip8 (shared with collate.hip and export.hip)
+#include "pil_resample.h"         // pil_win_layout, pil_window_body; exp_quant
+#include "line_limits.h"          // LIN_* limits, lin_takes (shared with scene.hip)
 
-#define LIN_THREADS 256
 #define LIN_DESC 12                    // ints per window row: src byte offset, H_src, W_src, h, wl, x0, w, mask flag, out float offset, 0, 0, 0
-#define LIN_MAX_ROWS 256               // source rows / columns the resampling passes take
-#define LIN_MAX_COLS 16384
-#define LIN_MAX_WL 4096                // widest line at the window height
-#define LIN_MAX_H 64                   // largest window
-#define LIN_MAX_W 256
-#define LIN_MAX_INTER 65536            // bytes of the horizontal pass's result (H_src * w * 3)
-#define LIN_MAX_TABLE 32768            // bytes of the horizontal coefficient rows (w * ksize * 4)
-#define LIN_LDS 126976                 // most dynamic LDS of a launch
 
 #define BLD_THREADS 256
 #define BLD_DESC 8                     // ints per line row: first window, windows, wl, scale, rule, c0, out byte offset, row pitch in bytes
 #define BLD_MAX_WINDOWS 1024           // windows of one line (its starts live in LDS)
 #define BLD_MAX_TILES 64               // grid.y
 
-struct LinLayout { int ksh, ksv, kh, bh, kv, bv, lum, inter, red, total; };
-
 // 0: the row is taken; 1: a reserved word is set; 2: geometry beyond tatt_line_limits; 3: the source or the planes leave packed / out
 static __host__ __device__ inline int lin_check(const int* d, long packed_bytes, long out_floats) {
     const int off = d[0], hs = d[1], ws = d[2], h = d[3], wl = d[4], x0 = d[5], w = d[6], out_off = d[8];
     if (d[9] != 0 || d[10] != 0 || d[11] != 0) return 1;
-    if (hs < 1 || ws < 1 || h < 1 || w < 1 || h > LIN_MAX_H || w > LIN_MAX_W || wl < w || wl > LIN_MAX_WL) return 2;
-    if (x0 < 0 || x0 > wl - w || hs > LIN_MAX_ROWS || ws > LIN_MAX_COLS) return 2;
-    if (ws != wl && ((long)hs * w * 3 > LIN_MAX_INTER || (long)w * col_ksize(ws, wl) * 4 > LIN_MAX_TABLE)) return 2;
+    if (!lin_takes(hs, ws, h, wl, x0, w)) return 2;
     if (off < 0 || off + (long)hs * ws * 3 > packed_bytes) return 3;
     if (out_off < 0 || out_off + (long)(3 + (d[7] != 0)) * h * w > out_floats) return 3;
     return 0;
-}
-
-// byte offsets of the window's LDS regions (16-byte aligned); only for rows lin_check accepted
-static __host__ __device__ inline LinLayout lin_layout(int hs, int ws, int h, int wl, int w, int mask) {
-    LinLayout g;
-    int o = 0;
-    auto take = [&o](int bytes) { const int at = o; o += (bytes + 15) & ~15; return at; };
-    g.ksh = ws == wl ? 0 : col_ksize(ws, wl);
-    g.ksv = hs == h ? 0 : col_ksize(hs, h);
-    g.kh = take(w * g.ksh * 4);
-    g.bh = take(g.ksh ? w * 8 : 0);
-    g.kv = take(h * g.ksv * 4);
-    g.bv = take(g.ksv ? h * 8 : 0);
-    g.lum = take(mask ? h * w : 0);
-    g.inter = take(g.ksh ? hs * w * 3 : 0);
-    g.red = take(mask ? (LIN_THREADS / 64) * 4 : 0);
-    g.total = o;
-    return g;
-}
-
-// phase 2 over the window's h * w pixels from s1 = uint8 rows of `pitch` pixels whose pixel 0 is the window's first column (the source
-// itself or the horizontal pass's result); returns this thread's share of sum(L)
-__device__ __forceinline__ int lin_vertical(const unsigned char* __restrict__ s1, int pitch, const int* kv, const int* bv, int ksv, int h,
-                                            int w, float* __restrict__ out, unsigned char* lum, int tid) {
-    const int N = h * w;
-    int lsum = 0;
-    for (int i = tid; i < N; i += LIN_THREADS) {
-        const int y = i / w, x = i - y * w;
-        int r, g, b;
-        if (ksv) {
-            const int ymin = bv[2 * y], n = bv[2 * y + 1];
-            const int* k = kv + y * ksv;
-            const unsigned char* p = s1 + ((long)ymin * pitch + x) * 3;
-            int a0 = 1 << (COL_PB - 1), a1 = a0, a2 = a0;
-            for (int t = 0; t < n; ++t, p += (long)pitch * 3) {
-                const int kt = k[t];
-                a0 += p[0] * kt;
-                a1 += p[1] * kt;
-                a2 += p[2] * kt;
-            }
-            r = col_clip8(a0), g = col_clip8(a1), b = col_clip8(a2);
-        } else {
-            const unsigned char* p = s1 + ((long)y * pitch + x) * 3;
-            r = p[0], g = p[1], b = p[2];
-        }
-        out[i] = __fdiv_rn((float)r, 255.f);
-        out[N + i] = __fdiv_rn((float)g, 255.f);
-        out[2 * N + i] = __fdiv_rn((float)b, 255.f);
-        if (lum) {
-            const int L = (19595 * r + 38470 * g + 7471 * b + 0x8000) >> 16;
-            lum[i] = (unsigned char)L;
-            lsum += L;
-        }
-    }
-    return lsum;
 }
 
 __global__ __launch_bounds__(LIN_THREADS) void line_windows_kernel(const unsigned char* __restrict__ packed, long packed_bytes,
@@ -122,65 +53,9 @@ __global__ __launch_bounds__(LIN_THREADS) void line_windows_kernel(const unsigne
     if (h < 1 || w < 1 || h > LIN_MAX_H || w > LIN_MAX_W || out_off < 0 || out_off + planes * N > out_floats) return;
     float* out = out_base + out_off;
     const bool ok = lin_check(d, packed_bytes, out_floats) == 0;
-    const LinLayout g = ok ? lin_layout(hs, ws, h, wl, w, mask) : LinLayout{};
-    if (!ok || g.total > lds_bytes) {
-        for (long i = tid; i < planes * N; i += LIN_THREADS) out[i] = __builtin_nanf("");
-        return;
-    }
-    const unsigned char* src = packed + src_off;
-    int* kh = (int*)(lin_lds + g.kh);
-    int* bh = (int*)(lin_lds + g.bh);
-    int* kv = (int*)(lin_lds + g.kv);
-    int* bv = (int*)(lin_lds + g.bv);
-    unsigned char* lum = mask ? lin_lds + g.lum : nullptr;
-    unsigned char* inter = lin_lds + g.inter;
-    int* red = (int*)(lin_lds + g.red);
-
-    // phase 0: row x0 + i of the line's horizontal table lands in row i of the window's (col_coeffs indexes by the line's column)
-    const int nh = g.ksh ? w : 0, nv = g.ksv ? h : 0;
-    for (int i = tid; i < nh + nv; i += LIN_THREADS) {
-        if (i < nh) col_coeffs(x0 + i, ws, wl, g.ksh, kh - (long)x0 * g.ksh, bh - 2L * x0);
-        else col_coeffs(i - nh, hs, h, g.ksv, kv, bv);
-    }
-    if (nh + nv) __syncthreads();
-
-    // phase 1
-    if (g.ksh) {
-        const int n1 = hs * w;
-        for (int i = tid; i < n1; i += LIN_THREADS) {
-            const int yy = i / w, xx = i - yy * w;
-            const int xmin = bh[2 * xx], n = bh[2 * xx + 1];
-            const int* k = kh + xx * g.ksh;
-            const unsigned char* p = src + ((long)yy * ws + xmin) * 3;
-            int a0 = 1 << (COL_PB - 1), a1 = a0, a2 = a0;
-            for (int x = 0; x < n; ++x, p += 3) {
-                const int kx = k[x];
-                a0 += p[0] * kx;
-                a1 += p[1] * kx;
-                a2 += p[2] * kx;
-            }
-            inter[i * 3] = (unsigned char)col_clip8(a0);
-            inter[i * 3 + 1] = (unsigned char)col_clip8(a1);
-            inter[i * 3 + 2] = (unsigned char)col_clip8(a2);
-        }
-        __syncthreads();
-    }
-
-    // phase 2 (two call sites: the source pointer is LDS in one and global memory in the other)
-    int lsum = g.ksh ? lin_vertical(inter, w, kv, bv, g.ksv, h, w, out, lum, tid)
-                     : lin_vertical(src + (long)x0 * 3, ws, kv, bv, g.ksv, h, w, out, lum, tid);
-    if (!mask) return;
-
-    // phase 3
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) lsum += __shfl_xor(lsum, o, 64);
-    if ((tid & 63) == 0) red[tid >> 6] = lsum;
-    __syncthreads();
-    int total = 0;
-#pragma unroll
-    for (int i = 0; i < LIN_THREADS / 64; ++i) total += red[i];
-    const int n = (int)N;
-    for (int i = tid; i < n; i += LIN_THREADS) out[3 * n + i] = (int)lum[i] * n <= total ? 1.f : 0.f;
+    const PilWinLayout g = ok ? pil_win_layout<LIN_THREADS>(hs, ws, h, wl, w, mask) : PilWinLayout{};
+    if (!ok || g.total > lds_bytes) return pil_win_refuse<LIN_THREADS>(out, planes * N, tid);
+    pil_window_body<LIN_THREADS>(packed + src_off, (long)(3 * ws), g, lin_lds, hs, ws, h, wl, x0, w, mask, out, tid);
 }
 
 TATT_API int tatt_line_limits(int* out) {
@@ -204,7 +79,7 @@ TATT_API int tatt_line_windows(const unsigned char* packed, long packed_bytes, c
         const int* d = desc_host + (long)i * LIN_DESC;
         const int rc = lin_check(d, packed_bytes, out_floats);
         if (rc) return rc;
-        const int total = lin_layout(d[1], d[2], d[3], d[4], d[6], d[7] != 0).total;
+        const int total = pil_win_layout<LIN_THREADS>(d[1], d[2], d[3], d[4], d[6], d[7] != 0).total;
         if (total > LIN_LDS) return 2;
         if (total > lds) lds = total;
     }
@@ -238,13 +113,6 @@ static inline bool bld_starts_ok(const int* s, int n, int wl, int w) {
     return true;
 }
 
-__device__ __forceinline__ int bld_quant(float x, int rule) {       // export.hip's exp_quant
-    float t = __fmul_rn(x, 255.0f);
-    if (rule) t = __fadd_rn(t, 0.5f);
-    if (!(t > 0.0f)) return 0;                                      // negatives, -0.0, -inf and NaN
-    return t >= 255.0f ? 255 : (int)t;
-}
-
 __global__ __launch_bounds__(BLD_THREADS) void line_blend_kernel(const float* __restrict__ src, long st_n, long st_c, long st_h, long st_w,
                                                                  int B, int C, int H, int W, const int* __restrict__ desc,
                                                                  const int* __restrict__ starts, int n_starts,
@@ -275,9 +143,9 @@ __global__ __launch_bounds__(BLD_THREADS) void line_blend_kernel(const float* __
             if (j >= W) continue;                                    // (only a stale table: the search already skipped these)
             const int wt = min(j + 1, W - j);
             const float* p = s + k * st_n + y * st_h + j * st_w;
-            n0 += wt * bld_quant(p[0], rule);
-            n1 += wt * bld_quant(p[st_c], rule);
-            n2 += wt * bld_quant(p[2 * st_c], rule);
+            n0 += wt * exp_quant(p[0], rule);
+            n1 += wt * exp_quant(p[st_c], rule);
+            n2 += wt * exp_quant(p[2 * st_c], rule);
             den += wt;
         }
         unsigned char* q = out + (long)y * pitch + 3 * X;

@@ -7,29 +7,24 @@
 //                           sum exp(x - max) across the wave, i.e. the soft-max probability 1 / sum of the decision; repeats merged, blank 0
 //                           dropped; one record row per image, scattered through an index array so that the launches of all buckets of a
 //                           call fill ONE record buffer in input order.
-// line_luma_kernel tiles the output like resize_u8_kernel of scene.hip (grid (tile, line), 256 threads, th x 64 output pixels per
-// work-group; the tile's coefficient rows, then the horizontal pass of the source rows it names into LDS, then the vertical pass); the
-// few lines of tile geometry are restated here rather than moved out of scene.hip, whose kernel stays as it was measured.  Like its
-// siblings: no traffic between work-groups, no atomics, every loop bounded by descriptor values that were checked, every quantity read
-// from DEVICE memory, the same check on the host before the launch and in the kernel.  Compiled with -ffp-contract=off (tatt_amd/build.py)
-// for pil_resample.h's tables in double.
+// line_luma_kernel tiles the output as resize_u8_kernel of scene.hip does: grid (tile, line), 256 threads, pil_tile_body of pil_resample.h
+// (th x 64 output pixels per work-group; the tile's coefficient rows, the horizontal pass of the source rows it names into LDS, the
+// vertical pass) with the luma store as its sink.  Like its siblings: no traffic between work-groups, no atomics, every loop bounded by
+// descriptor values that were checked, every quantity read from DEVICE memory, the same check on the host before the launch and in the
+// kernel.  Compiled with -ffp-contract=off (tatt_amd/build.py) for pil_resample.h's tables in double.
 #include "common.h"
-#include "pil_resample.h"         // col_ksize, col_coeffs, col_clip8
+#include "pil_resample.h"         // pil_tile_layout, pil_tiles, pil_tile_body
 
 #define RD_THREADS 256
 #define RD_DESC 8                      // ints per line row: src byte offset, H, W, pitch, rw, float offset of the target, 0, 0
 #define RD_OH 32                       // the recogniser's input height
-#define RD_TW 64                       // tile width
 #define RD_MAX_RW 1020                 // widest input: T = rw / 4 + 1 <= 256 steps
 #define RD_MAX_DOWN 16                 // largest in / out per axis (ksize <= 65)
 #define RD_MAX_W 32768                 // widest line canvas
-#define RD_INTER_ROWS 192              // rows of the horizontal pass's result a tile keeps in LDS
 #define RD_MAX_LINES 65535             // grid.y
 #define RD_LDS 65536                   // no tile needs more: 64 * 65 * 4 + 512 + th * ksv * 4 + 8 th + 192 * 192 with th * ksv <= 32 * 9 or th <= 8
 #define RD_MAX_T 256
 #define RD_MAX_C 64
-
-struct RdLayout { int ksh, ksv, th, span, kh, bh, kv, bv, inter, total; };
 
 // 0: the row is taken; 1: a reserved word is set; 2: geometry beyond tatt_read_limits; 3: the source rectangle or the target leaves its buffer
 static __host__ __device__ inline int rd_check(const int* d, long src_bytes, long out_floats) {
@@ -42,64 +37,6 @@ static __host__ __device__ inline int rd_check(const int* d, long src_bytes, lon
     return 0;
 }
 
-// an upper bound of the source samples that n consecutive output samples of a pass in -> out name (rsz_span of scene.hip)
-static __host__ __device__ inline int rd_span(int in, int out, int n) {
-    const double scale = (double)in / out, fs = scale < 1.0 ? 1.0 : scale;
-    const long s = (long)ceil((n - 1) * scale + 4.0 * fs) + 2;
-    return s > in ? in : (int)s;
-}
-
-// tile height and LDS regions of a line (16-byte aligned); only for rows rd_check accepted
-static __host__ __device__ inline RdLayout rd_layout(int hs, int ws, int rw) {
-    RdLayout g;
-    int o = 0;
-    auto take = [&o](int bytes) { const int at = o; o += (bytes + 15) & ~15; return at; };
-    g.ksh = ws == rw ? 0 : col_ksize(ws, rw);
-    g.ksv = hs == RD_OH ? 0 : col_ksize(hs, RD_OH);
-    g.th = RD_OH;
-    if (g.ksv)
-        while (g.th > 1 && rd_span(hs, RD_OH, g.th) > RD_INTER_ROWS) g.th >>= 1;
-    g.span = g.ksv ? rd_span(hs, RD_OH, g.th) : g.th;
-    g.kh = take(RD_TW * g.ksh * 4);
-    g.bh = take(g.ksh ? RD_TW * 8 : 0);
-    g.kv = take(g.th * g.ksv * 4);
-    g.bv = take(g.ksv ? g.th * 8 : 0);
-    g.inter = take(g.ksh ? g.span * RD_TW * 3 : 0);
-    g.total = o;
-    return g;
-}
-
-static __host__ __device__ inline int rd_tiles(int rw, int th) { return ((RD_OH + th - 1) / th) * ((rw + RD_TW - 1) / RD_TW); }
-
-// the vertical pass and the luma of one tile: s1 = uint8 rows `row_bytes` apart, row 0 = source row `r0`, pixel 0 = the tile's first column
-// (LDS or global memory)
-__device__ __forceinline__ void rd_column(const unsigned char* s1, long row_bytes, int r0, const int* kv, const int* bv, int ksv, int y0,
-                                          int x0, int tn, int tw, int rw, float* __restrict__ out, int tid) {
-    const float inv = (float)(1.0 / 255000.0);
-    const int n2 = tn * tw;
-    for (int i = tid; i < n2; i += RD_THREADS) {
-        const int y = i / tw, x = i - y * tw;
-        int r, g, b;
-        if (ksv) {
-            const int ymin = bv[2 * y], n = bv[2 * y + 1];
-            const int* k = kv + y * ksv;
-            const unsigned char* p = s1 + (ymin - r0) * row_bytes + x * 3;
-            int a0 = 1 << (COL_PB - 1), a1 = a0, a2 = a0;
-            for (int t = 0; t < n; ++t, p += row_bytes) {
-                const int kt = k[t];
-                a0 += p[0] * kt;
-                a1 += p[1] * kt;
-                a2 += p[2] * kt;
-            }
-            r = col_clip8(a0), g = col_clip8(a1), b = col_clip8(a2);
-        } else {
-            const unsigned char* p = s1 + (y0 + y - r0) * row_bytes + x * 3;
-            r = p[0], g = p[1], b = p[2];
-        }
-        out[(long)(y0 + y) * rw + x0 + x] = (float)(299 * r + 587 * g + 114 * b) * inv;       // (n <= 255000: exact in fp32)
-    }
-}
-
 __global__ __launch_bounds__(RD_THREADS) void line_luma_kernel(const unsigned char* __restrict__ src_base, long src_bytes,
                                                                const int* __restrict__ desc, float* __restrict__ out_base,
                                                                long out_floats, int lds_bytes) {
@@ -107,68 +44,21 @@ __global__ __launch_bounds__(RD_THREADS) void line_luma_kernel(const unsigned ch
     const int tid = threadIdx.x;
     const int* d = desc + (long)blockIdx.y * RD_DESC;
     const int hs = d[1], ws = d[2], rw = d[4], fo = d[5];
-    const long sp = d[3];
     // The host entry refuses such rows before it launches; a replayed launch re-checks so that a stale row cannot reach outside the
     // buffers: the line's own target (when it lies inside) is filled with NaN by the work-groups of its grid row, nothing else is touched.
     if (rw < 1 || rw > RD_MAX_RW || fo < 0 || fo + (long)RD_OH * rw > out_floats) return;
     float* out = out_base + fo;
     const bool ok = rd_check(d, src_bytes, out_floats) == 0;
-    const RdLayout g = ok ? rd_layout(hs, ws, rw) : RdLayout{};
+    const PilTileLayout g = ok ? pil_tile_layout(hs, ws, RD_OH, rw) : PilTileLayout{};
     if (!ok || g.total > lds_bytes) {
         for (int i = blockIdx.x * RD_THREADS + tid; i < RD_OH * rw; i += gridDim.x * RD_THREADS) out[i] = __builtin_nanf("");
         return;
     }
-    if ((int)blockIdx.x >= rd_tiles(rw, g.th)) return;
-    const int tiles_x = (rw + RD_TW - 1) / RD_TW;
-    const int ty = blockIdx.x / tiles_x, tx = blockIdx.x - ty * tiles_x;
-    const int y0 = ty * g.th, x0 = tx * RD_TW;
-    const int tn = min(g.th, RD_OH - y0), tw = min(RD_TW, rw - x0);
-    const unsigned char* src = src_base + d[0];
-    int* kh = (int*)(rd_lds + g.kh);
-    int* bh = (int*)(rd_lds + g.bh);
-    int* kv = (int*)(rd_lds + g.kv);
-    int* bv = (int*)(rd_lds + g.bv);
-    unsigned char* inter = rd_lds + g.inter;
-
-    // phase 0: rows x0 .. x0 + tw - 1 and y0 .. y0 + tn - 1 of the two tables land in rows 0 .. of the tile's
-    const int nh = g.ksh ? tw : 0, nv = g.ksv ? tn : 0;
-    for (int i = tid; i < nh + nv; i += RD_THREADS) {
-        if (i < nh) col_coeffs(x0 + i, ws, rw, g.ksh, kh - (long)x0 * g.ksh, bh - 2L * x0);
-        else col_coeffs(y0 + i - nh, hs, RD_OH, g.ksv, kv - (long)y0 * g.ksv, bv - 2L * y0);
-    }
-    if (nh + nv) __syncthreads();
-
-    // the source rows the tile reads: first sample of its first output row .. last sample of its last one (both increase with the row)
-    const int r0 = g.ksv ? bv[0] : y0;
-    const int nr = g.ksv ? bv[2 * (tn - 1)] + bv[2 * (tn - 1) + 1] - r0 : tn;
-    if (g.ksh && nr > g.span) return;                                // (rd_span bounds it: never taken, and the same in every thread)
-
-    // phase 1: the horizontal pass, rounded to uint8 as Pillow rounds its intermediate image
-    if (g.ksh) {
-        const int n1 = nr * tw;
-        for (int i = tid; i < n1; i += RD_THREADS) {
-            const int yy = i / tw, xx = i - yy * tw;
-            const int xmin = bh[2 * xx], n = bh[2 * xx + 1];
-            const int* k = kh + xx * g.ksh;
-            const unsigned char* p = src + (r0 + yy) * sp + xmin * 3L;
-            int a0 = 1 << (COL_PB - 1), a1 = a0, a2 = a0;
-            for (int x = 0; x < n; ++x, p += 3) {
-                const int kx = k[x];
-                a0 += p[0] * kx;
-                a1 += p[1] * kx;
-                a2 += p[2] * kx;
-            }
-            unsigned char* q = inter + (yy * RD_TW + xx) * 3;
-            q[0] = (unsigned char)col_clip8(a0);
-            q[1] = (unsigned char)col_clip8(a1);
-            q[2] = (unsigned char)col_clip8(a2);
-        }
-        __syncthreads();
-    }
-
-    // phase 2 (two call sites: the source pointer is LDS in one and global memory in the other)
-    if (g.ksh) rd_column(inter, RD_TW * 3L, r0, kv, bv, g.ksv, y0, x0, tn, tw, rw, out, tid);
-    else rd_column(src + x0 * 3L, sp, 0, kv, bv, g.ksv, y0, x0, tn, tw, rw, out, tid);
+    if ((long)blockIdx.x >= pil_tiles(RD_OH, rw, g.th)) return;
+    const float inv = (float)(1.0 / 255000.0);
+    pil_tile_body<RD_THREADS>(src_base + d[0], d[3], g, rd_lds, hs, ws, RD_OH, rw, blockIdx.x, tid, [&](int Y, int X, int r, int gg, int b) {
+        out[(long)Y * rw + X] = (float)(299 * r + 587 * gg + 114 * b) * inv;                  // (n <= 255000: exact in fp32)
+    });
 }
 
 TATT_API int tatt_line_luma(const unsigned char* src, long src_bytes, const int* desc, const int* desc_host, int n_lines, float* out,
@@ -180,10 +70,10 @@ TATT_API int tatt_line_luma(const unsigned char* src, long src_bytes, const int*
         const int* d = desc_host + (long)i * RD_DESC;
         const int rc = rd_check(d, src_bytes, out_floats);
         if (rc) return rc;
-        const RdLayout g = rd_layout(d[1], d[2], d[4]);
+        const PilTileLayout g = pil_tile_layout(d[1], d[2], RD_OH, d[4]);
         if (g.total > RD_LDS) return 2;
         if (g.total > lds) lds = g.total;
-        const int t = rd_tiles(d[4], g.th);
+        const int t = (int)pil_tiles(RD_OH, d[4], g.th);
         if (t > tiles) tiles = t;
     }
     hipLaunchKernelGGL(line_luma_kernel, dim3(tiles, n_lines), dim3(RD_THREADS), (size_t)lds, st, src, src_bytes, desc, out, out_floats,

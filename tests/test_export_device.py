@@ -33,14 +33,36 @@ def test_header_declares_and_library_exports_the_export_entry_points():
 def test_shared_resampler_header_is_included_not_copied():
     import os
     from tatt_amd.build import CSRC
-    for name in ("collate.hip", "export.hip"):
+    # the tables | the quantiser | the tap loop, the stride forms and the two passes | the window family's layout and body | the tile
+    # family's span, layout, tile count and body
+    shared = ("col_bicubic(double", "void col_coeffs(", "int col_clip8(", "int col_ksize(",
+              "int exp_quant(float",
+              "PilRgb pil_taps(", "struct PilPacked", "long pil_at(", "void pil_horizontal(", "void pil_vertical(",
+              "struct PilWinLayout", "PilWinLayout pil_win_layout(", "void pil_window_body(",
+              "int pil_span(", "struct PilTileLayout", "PilTileLayout pil_tile_layout(", "long pil_tiles(", "void pil_tile_body(")
+    # the window limits and the geometry check that lines.hip and scene.hip share: line_limits.h, included by those two alone
+    limits = ("#define LIN_THREADS", "#define LIN_MAX_ROWS", "#define LIN_MAX_WL", "#define LIN_MAX_TABLE", "#define LIN_LDS", "bool lin_takes(")
+    # what a copy of a pass looks like, whatever it is called: the accumulator's rounding term
+    copies = ("1 << (COL_PB - 1)",)
+    for name in ("collate.hip", "export.hip", "lines.hip", "scene.hip", "read.hip"):
         txt = open(os.path.join(CSRC, name)).read()
         assert '#include "pil_resample.h"' in txt
-        for fn in ("col_bicubic(double", "void col_coeffs(", "int col_clip8(", "int col_ksize("):
+        assert ('#include "line_limits.h"' in txt) == (name in ("lines.hip", "scene.hip")), name
+        for fn in shared + limits + (copies if name != "export.hip" else ()):  # (export.hip keeps its one-byte-per-thread passes over floats)
             assert fn not in txt, (name, fn)
+        assert "SCW_MAX" not in txt
     hdr = open(os.path.join(CSRC, "pil_resample.h")).read()
-    for fn in ("col_bicubic(double", "void col_coeffs(", "int col_clip8(", "int col_ksize("):
-        assert fn in hdr, fn
+    for fn in shared:
+        assert hdr.count(fn) == (2 if fn == "long pil_at(" else 1), fn      # (pil_at: one overload per stride form)
+    assert hdr.count(copies[0]) == 1
+    lim = open(os.path.join(CSRC, "line_limits.h")).read()
+    for fn in limits:
+        assert hdr.count(fn) == 0 and lim.count(fn) == 1, fn
+    # collate_kernel runs the shared passes from a body of its own (measured: collate.hip's header); the window kernels run the shared body
+    col = open(os.path.join(CSRC, "collate.hip")).read()
+    assert "pil_horizontal<COL_THREADS>(" in col and col.count("pil_vertical<COL_THREADS>(") == 2 and "pil_window_body<" not in col
+    for name in ("lines.hip", "scene.hip"):
+        assert open(os.path.join(CSRC, name)).read().count("pil_window_body<LIN_THREADS>(") == 1, name
 
 
 def _pil(q, size):

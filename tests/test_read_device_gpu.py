@@ -111,6 +111,36 @@ def test_line_luma_entry_refuses_and_a_stale_row_gives_nan(dev):
     assert bool((out == 7).all())
 
 
+@pytest.mark.parametrize("src_hw,rw", (((11, 37), 40), ((200, 90), 80)), ids=("one-tile-up", "halved-tiles-down"))
+def test_line_luma_is_the_luma_of_what_resize_u8_writes(dev, src_hw, rw):
+    """the two tile entries share one body and differ in the pixel's sink: tatt_line_luma equals read.py's luma arithmetic on the bytes
+    tatt_resize_u8 (feather 0) writes for the same source and target (32, rw), and both equal the host path.  11 x 37 -> 32 x 40 is one
+    tile of an up-scale; 200 x 90 -> 32 x 80 shrinks 6.25 : 1 in the vertical, where 32 output rows would name 221 > 192 source rows, so
+    the tile height halves to 16: tiles whose first source row is not 0, two tile columns, the second ragged and 16 wide"""
+    from tatt_amd import io, ops, read
+    lim = io.scene_limits()
+    hs, ws = src_hw
+    a = R.make_image(np.random.default_rng(hs + ws), hs, ws, 1)
+    buf, ((off, _, _, pitch),) = _upload(dev, [a], (11,))
+    if hs == 200:                                                    # the case is what the docstring says it is
+        span = lambda n: int(np.ceil((n - 1) * hs / 32 + 4 * hs / 32)) + 2
+        assert lim["tile_h"] == 32 and span(32) == 221 > lim["inter_rows"] >= span(16) and rw - lim["tile_w"] == 16
+
+    def run(name, row, out):
+        host = torch.tensor([row], dtype=torch.int32)
+        desc = host.to(dev)
+        rc = getattr(ops.LIB, name)(ops.P(buf), buf.numel(), ctypes.c_void_p(desc.data_ptr()), ctypes.c_void_p(host.data_ptr()), 1, ops.P(out),
+                                    out.numel(), ops.stream())
+        assert rc == 0, (name, rc)
+        return out.cpu()
+    luma = run("tatt_line_luma", [off, hs, ws, pitch, rw, 0, 0, 0], torch.full((32 * rw,), 7.0, device=dev)).view(32, rw)
+    rgb = run("tatt_resize_u8", [off, hs, ws, pitch, 0, 32, rw, 3 * rw, 0] + [0] * 7,
+              torch.full((32 * rw * 3,), 7, dtype=torch.uint8, device=dev)).view(32, rw, 3).numpy().astype(np.int32)
+    n = 299 * rgb[..., 0] + 587 * rgb[..., 1] + 114 * rgb[..., 2]
+    assert torch.equal(luma, torch.from_numpy(n.astype(np.float32) * np.float32(1.0 / 255000.0)))
+    assert torch.equal(luma, torch.from_numpy(read.line_luma_host(a, rw)))
+
+
 # ---- the decoding -------------------------------------------------------------------------------------------------------------------
 def _logits(seed, T, B, C=37):
     x = torch.randn(T, B, C, generator=torch.Generator().manual_seed(seed)) * 3

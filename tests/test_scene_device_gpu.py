@@ -92,6 +92,57 @@ def test_windows_entry_refuses_and_a_stale_row_gives_nan(dev):
     assert bool((out == 7).all())
 
 
+def _windows_entry(dev, name, buf, rows, floats):
+    """one launch of a window entry on raw descriptor rows -> its float output"""
+    from tatt_amd import ops
+    src = torch.from_numpy(buf).to(dev)
+    host = torch.tensor(rows, dtype=torch.int32)
+    desc = host.to(dev)
+    out = torch.full((floats,), 7.0, device=dev)
+    rc = getattr(ops.LIB, name)(ops.P(src), src.numel(), ctypes.c_void_p(desc.data_ptr()), ctypes.c_void_p(host.data_ptr()), len(rows),
+                                ops.P(out), out.numel(), ops.stream())
+    assert rc == 0, (name, rc)
+    return out.cpu()
+
+
+def _embedded(a, bx, by, pad):
+    """a's pixels as the box at (bx, by) of a larger guard-filled image whose rows are `pad` bytes wider than the box's right edge"""
+    hs, ws = a.shape[:2]
+    pitch = 3 * (bx + ws) + pad
+    buf = np.full((by + hs) * pitch, GUARD, np.uint8)
+    np.lib.stride_tricks.as_strided(buf[by * pitch + 3 * bx:], a.shape, (pitch, 3, 1))[...] = a
+    return buf, pitch
+
+
+@pytest.mark.parametrize("mask", (True, False), ids=("mask", "rgb"))
+def test_the_three_window_entries_agree(dev, mask):
+    """tatt_collate_images, tatt_line_windows and tatt_scene_windows run one window body: a whole image is the window x0 = 0, w = wl, a
+    box is a source with a row pitch and an origin.  Target 4 x 8; sources that take both passes, the horizontal one alone, the vertical
+    one alone, neither, and a down-scale (ksize > 5).  Then three windows of one line: the two entries that cut windows, against the host"""
+    from tatt_amd import io
+    h, w, m = 4, 8, int(mask)
+    K = (3 + m) * h * w
+    for hs, ws in ((5, 7), (4, 7), (5, 8), (4, 8), (37, 50)):
+        a = R.make_image(np.random.default_rng(64 * hs + ws), hs, ws, (hs + ws) % 3)
+        want = io.resize_normalize(Image.fromarray(a, "RGB"), (w, h), mask).reshape(-1)
+        col = _windows_entry(dev, "tatt_collate_images", a.reshape(-1), [[0, hs, ws, h, w, m, 0, 0]], K)
+        lin = _windows_entry(dev, "tatt_line_windows", a.reshape(-1), [[0, hs, ws, h, w, 0, w, m, 0, 0, 0, 0]], K)
+        buf, pitch = _embedded(a, 3, 2, 5)
+        scw = _windows_entry(dev, "tatt_scene_windows", buf, [[0, hs, ws, h, w, 0, w, m, 0, pitch, 3, 2, 0, 0, 0, 0]], K)
+        assert torch.equal(col, lin) and torch.equal(lin, scw), (hs, ws)
+        assert torch.equal(col, want), (hs, ws, int((col != want).sum()))
+    hs, ws, wl, starts = 5, 25, 20, (0, 6, 12)
+    a = R.make_image(np.random.default_rng(9), hs, ws, 1)
+    want = io.line_windows_host(Image.fromarray(a, "RGB"), (h, w), 6, mask).reshape(-1)
+    assert want.numel() == 3 * K
+    lin = _windows_entry(dev, "tatt_line_windows", a.reshape(-1), [[0, hs, ws, h, wl, x0, w, m, k * K, 0, 0, 0] for k, x0 in enumerate(starts)],
+                         3 * K)
+    buf, pitch = _embedded(a, 3, 2, 5)
+    scw = _windows_entry(dev, "tatt_scene_windows", buf,
+                         [[0, hs, ws, h, wl, x0, w, m, k * K, pitch, 3, 2, 0, 0, 0, 0] for k, x0 in enumerate(starts)], 3 * K)
+    assert torch.equal(lin, scw) and torch.equal(lin, want), int((lin != want).sum())
+
+
 # ---- the tiled resampler ------------------------------------------------------------------------------------------------------------
 def _resize_cases():
     from tatt_amd import io
