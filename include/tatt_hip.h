@@ -974,6 +974,34 @@ int tatt_ctc_beam_read(const float* logits, long st_t, long st_b, long st_c, int
 /* out[0..4]: most steps T, most classes C and most beam entries of tatt_ctc_beam_read, the nodes of an image's trie (1 + 256 * 16) and
  * the slots of its lookup table.  Host only: needs no GPU. */
 int tatt_beam_limits(int* out);
+/* Lexicon decoding (csrc/ctclex.hip; specification read.ctc_lexicon_read_host): scores[b][k] = the exact CTC log-probability (blank 0,
+ * the forward recursion of read.ctc_string_logp_host in float64) of word k of a closed list under the logits (T,B,C) fp32 of image b,
+ * given by element strides.  The list is packed by the host (read.Lexicon): codes: the class ids of all words one after the other
+ * (n_codes ints; the buffer holds at least one), words: K rows of 4 ints
+ *   [0] the word's length L <= 31  [1] the offset of its codes  [2] the caller's index of the word, 0 .. K - 1  [3] 0
+ * sorted by segment class: first the k16 words run in segments of 16 lanes (2 L + 1 <= 16), then the k32 of 32 lanes, then the k64 of 64
+ * (a word may sit in a wider class than its length asks for, never in a narrower one); k16 + k32 + k64 = K.  One launch per non-empty
+ * class, grid (tiles of 256 / lanes words, B).  scores: (B, K) float64, rows st_sc doubles apart, written at the CALLER's index: -inf
+ * where no alignment of T steps spells the word; NaN for every word of an image with a NaN or +inf logit or a step without a finite
+ * logit, and for a word whose length, offset or codes (outside 1 .. C - 1) are out of range; a row whose own index is out of range is
+ * not written.
+ * Returns 1 before any launch for: a null pointer, T outside 1 .. 256, C outside 1 .. 64, B outside 1 .. 65535, K outside 1 .. 65536,
+ * n_codes < 0, a negative class count or k16 + k32 + k64 != K, st_sc < K. */
+int tatt_ctc_lexicon_score(const float* logits, long st_t, long st_b, long st_c, int T, int B, int C, const int* codes, int n_codes,
+                           const int* words, int K, int k16, int k32, int k64, double* scores, long st_sc, hipStream_t st);
+/* The nbest <= 16 words of largest FINITE score of every image (descending, ties to the lower word index: comparisons only) and
+ * logz = m + log sum_k exp(scores[b][k] - m), m the largest score, in float64; one work-group per image.  Image b writes the record row
+ * index[b] (rows st_rec 32-bit words apart; an index outside 0 .. n_rows - 1 writes nothing):
+ *   [0] entries written n <= nbest (fewer where fewer words have an alignment)  [1] flag  [2..3] the float64 logz as it is, low word
+ *   first (-inf without a finite score)  then n entries of 4 words, entry i at 4 + 4 i: [0..1] the float64 logp  [2] the word's index
+ *   [3] 0.  Words beyond the n entries are left as they were.
+ * flag 1, with [0] = 0 and logz = NaN: every score of the image is a NaN (what tatt_ctc_lexicon_score writes for a flagged image).
+ * Returns 1 before any launch for: a null pointer, B or n_rows <= 0, K outside 1 .. 65536, st_sc < K, nbest outside 1 .. 16,
+ * st_rec < 4 + 4 nbest. */
+int tatt_ctc_lexicon_select(const double* scores, long st_sc, int B, int K, int nbest, const int* index, int* record, int n_rows,
+                            long st_rec, hipStream_t st);
+/* out[0..4]: most steps T, most classes C, the longest word, most words K of a lexicon and most entries nbest.  Host only: needs no GPU. */
+int tatt_lexicon_limits(int* out);
 /* calculate_psnr (reference utils/ssim_psnr.py:9-15) of two (B,C,H,W) images in [0,1] given by element strides, first 3 channels */
 int tatt_psnr(const float* a, long a_n, long a_c, long a_h, long a_w, const float* b, long b_n, long b_c, long b_h, long b_w,
               float* out, int B, int C, int H, int W, hipStream_t st);

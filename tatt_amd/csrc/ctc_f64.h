@@ -1,0 +1,73 @@
+// Float64 helpers shared by the CTC decoders that sum path probabilities on the device (ctcbeam.hip, ctclex.hip): the log-sum-exp of
+// two terms as the host specification states it (tatt_amd/read.py `_beam_real`), and wave-wide maxima, minima and sums.
+#pragma once
+#include "common.h"
+
+#define CB_NEG (-__builtin_inf())
+
+__device__ __forceinline__ double cb_lse(double a, double b) {
+    const double m = a > b ? a : b, n = a > b ? b : a;
+    return n == CB_NEG ? m : m + log1p(exp(n - m));
+}
+
+// Wave maximum and sum by data-parallel-primitive moves: four shifts inside each row of 16 lanes leave the row's result in its lane 15,
+// two row broadcasts carry it on, lane 63 holds the wave's and hands it to every lane through scalar registers.  A lane without a source
+// takes the neutral element (its own value for the maximum, 0 for the sum).
+template <int CTRL, int ROWS>
+__device__ __forceinline__ double cb_add(double v) {
+    return v + __hiloint2double(__builtin_amdgcn_update_dpp(0, __double2hiint(v), CTRL, ROWS, 0xf, false),
+                                __builtin_amdgcn_update_dpp(0, __double2loint(v), CTRL, ROWS, 0xf, false));
+}
+__device__ __forceinline__ double cb_wave_sum(double v) {
+    v = cb_add<0x111, 0xf>(v);                                       // row_shr:1, 2, 4, 8
+    v = cb_add<0x112, 0xf>(v);
+    v = cb_add<0x114, 0xf>(v);
+    v = cb_add<0x118, 0xf>(v);
+    v = cb_add<0x142, 0xa>(v);                                       // row_bcast:15 into rows 1 and 3
+    v = cb_add<0x143, 0xc>(v);                                       // row_bcast:31 into rows 2 and 3
+    return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), 63), __builtin_amdgcn_readlane(__double2loint(v), 63));
+}
+template <int CTRL>
+__device__ __forceinline__ float cb_max(float v) {
+    const int i = __float_as_int(v);
+    return fmaxf(v, __int_as_float(__builtin_amdgcn_update_dpp(i, i, CTRL, 0xf, 0xf, false)));
+}
+__device__ __forceinline__ float cb_wave_max(float v) {
+    v = cb_max<0x111>(v);
+    v = cb_max<0x112>(v);
+    v = cb_max<0x114>(v);
+    v = cb_max<0x118>(v);
+    v = cb_max<0x142>(v);
+    v = cb_max<0x143>(v);
+    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 63));
+}
+
+template <int CTRL>
+__device__ __forceinline__ double cb_maxd(double v) {
+    const int lo = __double2loint(v), hi = __double2hiint(v);
+    return fmax(v, __hiloint2double(__builtin_amdgcn_update_dpp(hi, hi, CTRL, 0xf, 0xf, false),
+                                    __builtin_amdgcn_update_dpp(lo, lo, CTRL, 0xf, 0xf, false)));
+}
+__device__ __forceinline__ double cb_wave_maxd(double v) {           // (no NaN ever gets here)
+    v = cb_maxd<0x111>(v);
+    v = cb_maxd<0x112>(v);
+    v = cb_maxd<0x114>(v);
+    v = cb_maxd<0x118>(v);
+    v = cb_maxd<0x142>(v);
+    v = cb_maxd<0x143>(v);
+    return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), 63), __builtin_amdgcn_readlane(__double2loint(v), 63));
+}
+template <int CTRL>
+__device__ __forceinline__ int cb_mini(int v) {
+    const int o = __builtin_amdgcn_update_dpp(v, v, CTRL, 0xf, 0xf, false);
+    return o < v ? o : v;
+}
+__device__ __forceinline__ int cb_wave_mini(int v) {
+    v = cb_mini<0x111>(v);
+    v = cb_mini<0x112>(v);
+    v = cb_mini<0x114>(v);
+    v = cb_mini<0x118>(v);
+    v = cb_mini<0x142>(v);
+    v = cb_mini<0x143>(v);
+    return __builtin_amdgcn_readlane(v, 63);
+}

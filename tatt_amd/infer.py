@@ -773,11 +773,14 @@ class SuperResolver:
     `result()` (the picture) and add `PendingScene.texts()` / `.readings()`, one per box in input order.  Lines are read before
     `out_sizes` and `feather` apply.  A plain call on an instance with `reader=` and no `recognizer=` raises ValueError.
     read_decode="beam" (read_beam, read_nbest) decodes with the CTC prefix beam search instead: one tatt_ctc_beam_read launch per
-    chunk in place of the greedy one, and `readings()` gives `read.BeamReading`s (text, logp, alternatives); `texts()` as before."""
+    chunk in place of the greedy one, and `readings()` gives `read.BeamReading`s (text, logp, alternatives); `texts()` as before.
+    read_decode="lexicon" (read_lexicon = a `read.Lexicon` or a list of words, read_nbest <= 16) reads every line against that closed
+    list: per chunk the tatt_ctc_lexicon_score launches and one tatt_ctc_lexicon_select launch in place of the greedy one, and
+    `readings()` gives `read.LexiconReading`s (text, logp, posterior, alternatives); every text is a word of the list."""
 
     def __init__(self, generator, prior=None, recognizer=None, batch_size: int = 48, lr_size=(16, 64), mask: bool = True,
                  rule: str = "floor", keep_sr: bool = False, long_lines: bool = False, stride: int = 32, reader=None,
-                 read_decode: str = "greedy", read_beam: int = 8, read_nbest: int = 4):
+                 read_decode: str = "greedy", read_beam: int = 8, read_nbest: int = 4, read_lexicon=None):
         from .io import DeviceCollator, DeviceExporter
         _refuse_attention_recognizer(recognizer, "SuperResolver")
         _check_module(generator, "generator")
@@ -803,7 +806,7 @@ class SuperResolver:
         if reader is not None:
             from .read import LineReader
             self.reader = LineReader(reader, batch_size=batch_size, device=self.device, w=self.lr_size[1], decode=read_decode,
-                                     beam=read_beam, nbest=read_nbest)
+                                     beam=read_beam, nbest=read_nbest, lexicon=read_lexicon)
 
     def _texts(self, sr):
         """-> (pinned (n, T + 1) int32: decoded classes | length, its event)"""

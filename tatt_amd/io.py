@@ -1180,6 +1180,7 @@ from .scene import (SCENE_MIN_SIDE, paste_plan, scene_check, scene_compose_host,
 from .quads import (QUAD_MAX_TAPER, QUAD_SHIFT, quad_bbox, quad_check, quad_compose_host, quad_fill, quad_layers,  # noqa: E402,F401
                     quad_limits, quad_matrices, quad_paste_plan, quad_plan, quad_rectify_host, quad_size, quad_windows_host,
                     super_resolve_quads_host, warp_inside_host, warp_u8_host)
-from .read import (READ_MAX, READ_QUANTUM, BeamDecoded, BeamReading, Reading, beam_limits, ctc_beam_read_host,  # noqa: E402,F401
-                   ctc_greedy_read_host, ctc_string_logp_host, line_luma_host, read_limits, read_lines_host, read_plan, read_squeezed,
+from .read import (READ_MAX, READ_QUANTUM, BeamDecoded, BeamReading, Lexicon, LexiconDecoded, LexiconReading, Reading,  # noqa: E402,F401
+                   beam_limits, ctc_beam_read_host, ctc_greedy_read_host, ctc_lexicon_read_host,
+                   ctc_string_logp_host, lexicon_limits, line_luma_host, read_limits, read_lines_host, read_plan, read_squeezed,
                    read_width)

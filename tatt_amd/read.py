@@ -16,8 +16,10 @@ passed in as a callable):
 * `read_plan`: buckets, descriptor rows and float offsets -- the host half shared by both paths.
 * `read_lines_host`: the composition.
 `LineReader` is the device path: one tatt_line_luma launch for all lines of a call, per bucket chunk the folded eval forward of the
-session and one tatt_ctc_greedy_read launch (decode="beam": one tatt_ctc_beam_read launch of csrc/ctcbeam.hip in its place), one copy
-of the record buffer back.
+session and one tatt_ctc_greedy_read launch (decode="beam": one tatt_ctc_beam_read launch of csrc/ctcbeam.hip in its place;
+decode="lexicon": the score and select launches of csrc/ctclex.hip), one copy of the record buffer back.
+Reading against a closed list of words: `Lexicon` (the words as class ids, packed for the device), `ctc_lexicon_scores_host` /
+`ctc_lexicon_read_host` (the specification: `ctc_string_logp_host` of every word, the N best, the normaliser over the list).
 """
 from __future__ import annotations
 
@@ -37,6 +39,9 @@ Reading = namedtuple("Reading", "text conf chars char_conf steps rw squeezed")
 Decoded = namedtuple("Decoded", "classes steps char_conf conf")
 BeamReading = namedtuple("BeamReading", "text logp alternatives rw squeezed")
 BeamDecoded = namedtuple("BeamDecoded", "entries flag margin reentry", defaults=(None, None))
+LexiconReading = namedtuple("LexiconReading", "text logp posterior alternatives rw squeezed")
+LexiconDecoded = namedtuple("LexiconDecoded", "entries logz flag margin", defaults=(None,))
+LEXICON_SEGMENTS = (16, 32, 64)   # lanes of a word's segment on the device: the smallest that holds its 2 L + 1 states
 ReadPlan = namedtuple("ReadPlan", "buckets desc offsets floats rws squeezed")
 
 
@@ -224,10 +229,15 @@ def ctc_string_logp_host(logits_row, classes, real=None):
     if any(not 1 <= c < C for c in classes):
         raise ValueError("ctc_string_logp_host: class ids are 1 .. %d; got %r" % (C - 1, classes))
     real, exp, log, lse = _beam_real(real)
-    neg = real("-inf")
     lps = [_log_softmax_row(r, real, exp, log) for r in x.to(torch.float32).tolist()]
     if any(lp is None for lp in lps):
         return real("nan")
+    return _string_logp(lps, classes, real, lse)
+
+
+def _string_logp(lps, classes, real, lse):
+    """the forward recursion of `ctc_string_logp_host` on a line's log-soft-max rows"""
+    neg = real("-inf")
     ext = [0]
     for c in classes:
         ext += [c, 0]
@@ -251,6 +261,128 @@ def ctc_string_logp_host(logits_row, classes, real=None):
 def _alphabet():
     from .io import ALPHABET
     return "-" + ALPHABET
+
+
+def _segment(length: int, min_segment: int = 16) -> int:
+    """lanes of the segment a word of `length` characters runs in: the smallest of 16, 32, 64 that holds its 2 L + 1 states, not below
+    `min_segment`"""
+    return next(g for g in LEXICON_SEGMENTS if 2 * length + 1 <= g and g >= min_segment)
+
+
+class Lexicon:
+    """A closed list of words to read lines against (`ctc_lexicon_read_host`, `LineReader(decode="lexicon")`).
+
+    Words are lower-cased and mapped to class ids through `alphabet`: alphabet[0] stands for the blank and is no character of a word;
+    the default is the reader's, "-" + io.ALPHABET.  ValueError, naming the word, for a character outside the alphabet, a word longer
+    than lexicon_limits()["length"], a duplicate after lower-casing (it would be counted twice in logz); for an empty list and more than
+    lexicon_limits()["words"] words.  The empty word "" is legal.
+    `words`, `classes`, len() and every word index anywhere are in the CALLER's order.  For the device the words are sorted once by
+    segment class (`_segment`; min_segment = 64 puts every word into a whole wave): `order` packed position -> caller's index,
+    `segments` the class of every word (caller's order), `counts` words per class (a class's words are one range of the packed order,
+    so the three counts are the whole tile table), `codes` the class ids of all words in packed order, `table` (K, 4) int32 per packed
+    word [length, offset of its codes, caller's index, 0].  Both arrays are uploaded once per device and kept."""
+    LENGTH, WORDS = 31, 65536                                        # tatt_lexicon_limits, stated here so that a list needs no library
+
+    def __init__(self, words, alphabet=None, min_segment: int = 16):
+        import numpy as np
+        if isinstance(words, str):
+            raise ValueError("Lexicon takes a list of words, not one string")
+        words = [str(w).lower() for w in words]
+        self.alphabet = _alphabet() if alphabet is None else str(alphabet)
+        if min_segment not in LEXICON_SEGMENTS:
+            raise ValueError("Lexicon: min_segment is one of %r; got %r" % (LEXICON_SEGMENTS, min_segment))
+        if not words:
+            raise ValueError("Lexicon: an empty list of words")
+        if len(words) > self.WORDS:
+            raise ValueError("Lexicon: %d words; at most %d" % (len(words), self.WORDS))
+        a2d = {ch: i for i, ch in enumerate(self.alphabet) if i >= 1}
+        seen, classes = set(), []
+        for w in words:
+            if len(w) > self.LENGTH:
+                raise ValueError("Lexicon: the word %r has %d characters; at most %d" % (w, len(w), self.LENGTH))
+            for ch in w:
+                if ch not in a2d:
+                    raise ValueError("Lexicon: the word %r has the character %r, which the alphabet %r lacks" % (w, ch, self.alphabet[1:]))
+            if w in seen:
+                raise ValueError("Lexicon: the word %r appears twice (after lower-casing)" % (w,))
+            seen.add(w)
+            classes.append([a2d[ch] for ch in w])
+        self.words, self.classes, self.min_segment = words, classes, int(min_segment)
+        self.n_classes = len(self.alphabet)
+        self.segments = [_segment(len(c), self.min_segment) for c in classes]
+        self.order = sorted(range(len(words)), key=lambda k: (self.segments[k], k))
+        self.counts = tuple(sum(1 for g in self.segments if g == G) for G in LEXICON_SEGMENTS)
+        table, codes = np.zeros((len(words), 4), np.int32), []
+        for p, k in enumerate(self.order):
+            table[p, :3] = (len(classes[k]), len(codes), k)
+            codes += classes[k]
+        self.table, self.codes, self.n_codes = table, np.asarray(codes + [0], np.int32), len(codes)     # (never an empty buffer)
+        self._dev = {}
+
+    def __len__(self):
+        return len(self.words)
+
+    def device(self, device):
+        """-> (codes, table) on `device`, uploaded once"""
+        device = torch.device(device)
+        if device.type == "cuda" and device.index is None:           # ("cuda" and "cuda:0" are one upload)
+            device = torch.device("cuda", torch.cuda.current_device())
+        if device not in self._dev:
+            self._dev[device] = (torch.from_numpy(self.codes).to(device), torch.from_numpy(self.table).to(device))
+        return self._dev[device]
+
+
+def ctc_lexicon_scores_host(logits, lexicon: Lexicon, real=None):
+    """logits (T, B, C) -> per line the list score[k] = ctc_string_logp_host(logits[:, b], lexicon.classes[k], real), k in the caller's
+    order (the log-soft-max of a line is worked out once); a line `ctc_beam_read_host` would flag gives None"""
+    T, B, C, rows = _beam_rows(logits, "ctc_lexicon_scores_host")
+    if lexicon.n_classes > C:
+        raise ValueError("ctc_lexicon_scores_host: the lexicon's alphabet has %d classes, the logits %d" % (lexicon.n_classes, C))
+    real, exp, log, lse = _beam_real(real)
+    out = []
+    for row in rows:
+        lps = [_log_softmax_row(x, real, exp, log) for x in row]
+        out.append(None if any(lp is None for lp in lps) else [_string_logp(lps, c, real, lse) for c in lexicon.classes])
+    return out
+
+
+def _lexicon_decode(scores, nbest: int = 4, details: bool = False, real=None) -> LexiconDecoded:
+    """the scores of one line's words (None: a flagged line) -> LexiconDecoded, as `ctc_lexicon_read_host` states it"""
+    real, exp, log, _ = _beam_real(real)
+    inf = float("inf")
+    if scores is None:
+        return LexiconDecoded([], float("nan"), 1, inf) if details else LexiconDecoded([], float("nan"), 1)
+    finite = sorted((k for k, v in enumerate(scores) if v == v and abs(v) != inf), key=lambda k: (-scores[k], k))
+    entries = [(k, scores[k]) for k in finite[:nbest]]
+    logz = real("-inf")
+    if finite:
+        m, z = scores[finite[0]], real(0.0)
+        for v in scores:
+            if v == v:
+                z = z + exp(v - m)
+        logz = m + log(z)
+    if not details:
+        return LexiconDecoded(entries, logz, 0)
+    head = [scores[k] for k in finite[:nbest + 1]]
+    return LexiconDecoded(entries, logz, 0, min([float(a - b) for a, b in zip(head, head[1:])], default=inf))
+
+
+def ctc_lexicon_read_host(logits, lexicon: Lexicon, nbest: int = 4, details: bool = False, real=None, scores=None):
+    """logits (T, B, C) -> one LexiconDecoded(entries, logz, flag[, margin]) per line: the line read against a closed list of words.
+
+    score[k] = ctc_string_logp_host(logits[:, b], lexicon.classes[k], real), the exact CTC log-probability of word k.  `entries`: the
+    `nbest` words of largest FINITE score as (word index, logp), descending, ties to the lower word index; shorter where fewer words
+    have an alignment of T steps.  logz = m + log(sum_k exp(score[k] - m)), m the largest score and the sum taken in ascending word
+    index: the log-probability that the line is one of the lexicon's words (-inf when no word has an alignment).  A line
+    `ctc_beam_read_host` would flag (a NaN, a +inf, a step without a finite logit) gives entries = [], logz = nan, flag = 1.
+    details=True adds `margin`: the smallest gap between neighbours among the first nbest + 1 finite scores (inf with one or none).
+    `real` as in `ctc_beam_read_host`; `scores`: what `ctc_lexicon_scores_host(logits, lexicon, real)` gave, to save working it out again."""
+    nbest = int(nbest)
+    if nbest < 1:
+        raise ValueError("ctc_lexicon_read_host: nbest >= 1 expected; got %r" % (nbest,))
+    if scores is None:
+        scores = ctc_lexicon_scores_host(logits, lexicon, real)
+    return [_lexicon_decode(row, nbest, details, real) for row in scores]
 
 
 def _reading(dec: Decoded, rw: int, squeezed: bool) -> Reading:
@@ -435,13 +567,108 @@ def _beam_reading(dec: BeamDecoded, rw: int, squeezed: bool) -> BeamReading:
     return BeamReading(text, logp, alts, rw, squeezed)
 
 
-class PendingReading:
-    """What `LineReader.read` started.  `result()` is the only host wait: -> one Reading (decode="beam": one BeamReading) per line, in
-    input order.  With keep_logits: `logits` [(line indices of the chunk, its (T, n, C) logits on the device)]."""
+def lexicon_limits():
+    """tatt_lexicon_limits: {'steps', 'classes', 'length', 'words', 'nbest'}: most steps T and classes C of tatt_ctc_lexicon_score, the
+    longest word and most words of a lexicon, most entries of tatt_ctc_lexicon_select.  A host-only entry: needs no GPU."""
+    from ._lib import LIB
+    out = (ctypes.c_int * 5)()
+    if LIB.tatt_lexicon_limits(out) != 0:
+        raise RuntimeError("tatt_lexicon_limits failed")
+    return dict(zip(("steps", "classes", "length", "words", "nbest"), (int(v) for v in out)))
 
-    def __init__(self, host, event, cap, plan, logits=None, nbest=None):
+
+def lexicon_record_words(nbest: int) -> int:
+    """32-bit words of a lexicon record row for `nbest` entries: [0] entries written, [1] flag, [2:4] logz, then 4 words per entry"""
+    return 4 + 4 * int(nbest)
+
+
+def _check_nbest(what, nbest):
+    if not (isinstance(nbest, int) and 1 <= nbest <= lexicon_limits()["nbest"]):
+        raise ValueError("%s: 1 <= nbest <= %d expected; got nbest = %r" % (what, lexicon_limits()["nbest"], nbest))
+
+
+def ctc_lexicon_score(logits, lexicon: Lexicon, scores):
+    """The tatt_ctc_lexicon_score launches (one per non-empty segment class of the lexicon, at most three): logits (T, B, C) fp32 on
+    the device (any strides), scores (B, K) float64 on the device with contiguous rows: scores[b][k] = the exact CTC log-probability
+    of lexicon.words[k] on line b (specification `ctc_lexicon_scores_host`; NaN on every word of a flagged line).  ValueError for what
+    the entry refuses (T, C, B), before any launch."""
+    from . import ops
+    from ._lib import LIB
+    ops._check_dev(logits)
+    T, B, C = logits.shape
+    K = len(lexicon)
+    if scores.dtype != torch.float64 or scores.dim() != 2 or scores.stride(1) != 1 or tuple(scores.shape) != (B, K) or \
+            scores.device != logits.device:
+        raise ValueError("ctc_lexicon_score: scores must be a (%d, %d) float64 tensor with contiguous rows on %s" % (B, K, logits.device))
+    if lexicon.n_classes > C:
+        raise ValueError("ctc_lexicon_score: the lexicon's alphabet has %d classes, the logits %d" % (lexicon.n_classes, C))
+    codes, table = lexicon.device(logits.device)
+    rc = LIB.tatt_ctc_lexicon_score(ops.P(logits), *logits.stride(), T, B, C, ops.P(codes), lexicon.n_codes, ops.P(table), K,
+                                    *lexicon.counts, ops.P(scores), scores.stride(0), ops.stream())
+    if rc == 1:
+        raise ValueError("tatt_ctc_lexicon_score refuses T = %d, B = %d, C = %d, K = %d" % (T, B, C, K))
+    if rc != 0:
+        raise RuntimeError("tatt_ctc_lexicon_score failed with code %d" % rc)
+    return scores
+
+
+def ctc_lexicon_select(scores, index, record, nbest: int = 4):
+    """ONE tatt_ctc_lexicon_select launch: scores (B, K) float64 on the device with contiguous rows, index (B,) int32 on the device:
+    the record row of every line, record (n_rows, >= lexicon_record_words(nbest)) int32 on the device, rows contiguous (see
+    `parse_lexicon_records`).  ValueError for what the entry refuses, before any launch."""
+    from . import ops
+    from ._lib import LIB
+    if not scores.is_cuda:
+        raise RuntimeError("tatt_amd kernels need tensors on an AMD GPU (HIP device); got %s. There is no CPU fallback in the product "
+                           "path." % scores.device)
+    if scores.dtype != torch.float64 or scores.dim() != 2 or scores.stride(1) != 1:
+        raise ValueError("ctc_lexicon_select: scores must be a 2-D float64 tensor with contiguous rows")
+    B, K = scores.shape
+    if record.dtype != torch.int32 or record.dim() != 2 or record.stride(1) != 1 or index.dtype != torch.int32 or index.numel() < B:
+        raise ValueError("ctc_lexicon_select: record must be a 2-D int32 tensor with contiguous rows, index an int32 tensor of B entries")
+    _check_nbest("ctc_lexicon_select", nbest)
+    if record.shape[1] < lexicon_record_words(nbest):
+        raise ValueError("ctc_lexicon_select: rows of %d words; nbest = %d needs %d" % (record.shape[1], nbest, lexicon_record_words(nbest)))
+    rc = LIB.tatt_ctc_lexicon_select(ops.P(scores), scores.stride(0), B, K, nbest, ops.P(index), ops.P(record), record.shape[0],
+                                     record.stride(0), ops.stream())
+    if rc == 1:
+        raise ValueError("tatt_ctc_lexicon_select refuses B = %d, K = %d, nbest = %d, rows of %d words" % (B, K, nbest, record.stride(0)))
+    if rc != 0:
+        raise RuntimeError("tatt_ctc_lexicon_select failed with code %d" % rc)
+    return record
+
+
+def parse_lexicon_records(record, nbest: int):
+    """record: the (n, >= lexicon_record_words(nbest)) int32 HOST tensor tatt_ctc_lexicon_select filled -> one LexiconDecoded per row.
+    Row, in 32-bit words: [0] entries written (<= nbest)  [1] flag  [2:4] the float64 logz as it is (low word first)  then per entry 4
+    words: the float64 logp, the word's index, 0."""
+    import struct
+    f64 = lambda lo, hi: struct.unpack("<d", struct.pack("<ii", lo, hi))[0]
+    out = []
+    for row in record.tolist():
+        n, flag = row[0], row[1]
+        if not 0 <= n <= nbest or flag not in (0, 1) or len(row) < lexicon_record_words(nbest):
+            raise ValueError("parse_lexicon_records: no lexicon record row: entries = %r, flag = %r" % (n, flag))
+        out.append(LexiconDecoded([(row[6 + 4 * i], f64(row[4 + 4 * i], row[5 + 4 * i])) for i in range(n)], f64(row[2], row[3]), flag))
+    return out
+
+
+def _lexicon_reading(dec: LexiconDecoded, lexicon: Lexicon, rw: int, squeezed: bool) -> LexiconReading:
+    import math
+    alts = [(lexicon.words[k], logp, math.exp(logp - dec.logz)) for k, logp in dec.entries]
+    text, logp, post = alts[0] if alts else ("", float("nan"), float("nan"))
+    return LexiconReading(text, logp, post, alts, rw, squeezed)
+
+
+class PendingReading:
+    """What `LineReader.read` started.  `result()` is the only host wait: -> one Reading (decode="beam": one BeamReading,
+    decode="lexicon": one LexiconReading) per line, in input order.  With keep_logits: `logits` [(line indices of the chunk, its
+    (T, n, C) logits on the device)]; with keep_scores (lexicon): `scores` [(line indices, the chunk's (n, K) float64 scores)]."""
+
+    def __init__(self, host, event, cap, plan, logits=None, nbest=None, lexicon=None, scores=None):
         self._host, self._event, self._cap, self._plan, self.logits, self._out = host, event, cap, plan, logits, None
         self._nbest = nbest                                          # None: greedy records
+        self._lexicon, self.scores = lexicon, scores                 # a Lexicon: lexicon records
 
     def result(self):
         if self._out is None:
@@ -451,6 +678,10 @@ class PendingReading:
                 self._event.synchronize()
                 self._out = [_reading(d, rw, sq) for d, rw, sq in zip(parse_records(self._host, self._cap), self._plan.rws,
                                                                        self._plan.squeezed)]
+            elif self._lexicon is not None:
+                self._event.synchronize()
+                self._out = [_lexicon_reading(d, self._lexicon, rw, sq) for d, rw, sq in zip(
+                    parse_lexicon_records(self._host, self._nbest), self._plan.rws, self._plan.squeezed)]
             else:
                 self._event.synchronize()
                 self._out = [_beam_reading(d, rw, sq) for d, rw, sq in zip(parse_beam_records(self._host, self._cap, self._nbest),
@@ -459,6 +690,14 @@ class PendingReading:
 
     def texts(self):
         return [r.text for r in self.result()]
+
+
+def _emitted_classes(crnn):
+    """the classes a CRNN's last layer emits, None where the module does not say"""
+    try:
+        return int(crnn.rnn[-1].embedding.out_features)
+    except (AttributeError, IndexError, TypeError):
+        return None
 
 
 class LineReader:
@@ -479,16 +718,32 @@ class LineReader:
     decode="beam" (with beam <= 16 and 1 <= nbest <= beam): every chunk gets ONE tatt_ctc_beam_read launch in place of the greedy one
     (the CTC prefix beam search, specification `ctc_beam_read_host`), the record buffer is sized for its rows and `result()` gives
     `BeamReading`s: the most probable string, its log-probability summed over its alignments in float64, and the `nbest` best strings
-    as `alternatives`.  Everything else of a call is the same; decode="greedy" is the default."""
+    as `alternatives`.  Everything else of a call is the same; decode="greedy" is the default.
+    decode="lexicon" (with lexicon = a `Lexicon` or a list of words, 1 <= nbest <= 16): every chunk gets the tatt_ctc_lexicon_score
+    launches (one per non-empty segment class of the lexicon) into an (n, K) float64 buffer of its own and ONE tatt_ctc_lexicon_select
+    launch in place of the greedy one (specification `ctc_lexicon_read_host`); `result()` gives `LexiconReading`s: the most probable
+    word of the list, its exact CTC log-probability, its posterior among the list's words, and the `nbest` best words as
+    `alternatives`.  keep_scores=True keeps every chunk's score buffer (`PendingReading.scores`)."""
 
     def __init__(self, crnn, batch_size: int = 48, device=None, keep_logits: bool = False, w: int = 64, decode: str = "greedy",
-                 beam: int = 8, nbest: int = 4):
+                 beam: int = 8, nbest: int = 4, lexicon=None, keep_scores: bool = False):
         from . import functional as Fh
         from .infer import _check_module, _crnn_folds
-        if decode not in ("greedy", "beam"):
-            raise ValueError("LineReader: decode is 'greedy' or 'beam'; got %r" % (decode,))
-        _check_beam("LineReader", beam, nbest, beam_limits()["beam"])
-        self.decode, self.beam, self.nbest = decode, beam, nbest
+        if decode not in ("greedy", "beam", "lexicon"):
+            raise ValueError("LineReader: decode is 'greedy', 'beam' or 'lexicon'; got %r" % (decode,))
+        if decode == "lexicon":
+            _check_nbest("LineReader", nbest)
+            if lexicon is None:
+                raise ValueError("LineReader: decode='lexicon' needs lexicon=, a Lexicon or a list of words")
+            lexicon = lexicon if isinstance(lexicon, Lexicon) else Lexicon(lexicon)
+            emits = _emitted_classes(crnn)
+            if emits is not None and lexicon.n_classes > emits:
+                raise ValueError("LineReader: the lexicon's alphabet has %d classes, the CRNN emits %d" % (lexicon.n_classes, emits))
+        else:
+            _check_beam("LineReader", beam, nbest, beam_limits()["beam"])
+            if lexicon is not None:
+                raise ValueError("LineReader: lexicon= goes with decode='lexicon'; got decode = %r" % (decode,))
+        self.decode, self.beam, self.nbest, self.lexicon, self.keep_scores = decode, beam, nbest, lexicon, bool(keep_scores)
         _check_module(crnn, "reader CRNN")
         if not (isinstance(batch_size, int) and batch_size > 0):
             raise ValueError("batch_size must be a positive int")
@@ -498,6 +753,8 @@ class LineReader:
         if want.type != "cuda" or (want.index is not None and want.index != self.device.index):
             raise ValueError("LineReader: the CRNN lives on %s, not on %s" % (self.device, want))
         self._limits = read_limits()
+        if lexicon is not None:
+            lexicon.device(self.device)                              # (the one upload of the packed words: no `read` makes it)
         with torch.cuda.device(self.device), torch.no_grad():
             Fh.sticky_word(self.device)
             self._folds = _crnn_folds(crnn)
@@ -565,8 +822,9 @@ class LineReader:
             head_dev.copy_(head, non_blocking=True)
             luma = torch.empty(plan.floats, dtype=torch.float32, device=self.device)
             line_luma(dev_bytes, head_dev, plan.desc, luma)
-            beam = self.decode == "beam"
-            words = beam_record_words(cap, self.nbest) if beam else 3 * cap + 2
+            beam, lex = self.decode == "beam", self.decode == "lexicon"
+            words = beam_record_words(cap, self.nbest) if beam else lexicon_record_words(self.nbest) if lex else 3 * cap + 2
+            kept_scores = [] if lex and self.keep_scores else None
             record = torch.empty(n, words, dtype=torch.int32, device=self.device)
             index, pos, foff = head_dev[n * READ_DESC:], 0, 0
             for rw, idx in plan.buckets:
@@ -577,6 +835,12 @@ class LineReader:
                     logits = self.forward(x[i:i + m])
                     if beam:
                         ctc_beam_read(logits, index[pos:pos + m], record, cap, self.beam, self.nbest)
+                    elif lex:
+                        scores = torch.empty(m, len(self.lexicon), dtype=torch.float64, device=self.device)
+                        ctc_lexicon_score(logits, self.lexicon, scores)
+                        ctc_lexicon_select(scores, index[pos:pos + m], record, self.nbest)
+                        if kept_scores is not None:
+                            kept_scores.append((idx[i:i + m], scores))
                     else:
                         ctc_greedy_read(logits, index[pos:pos + m], record, cap)
                     if keep:
@@ -586,4 +850,4 @@ class LineReader:
             host.copy_(record, non_blocking=True)
             ev = torch.cuda.Event()
             ev.record()
-        return PendingReading(host, ev, cap, plan, kept, self.nbest if beam else None)
+        return PendingReading(host, ev, cap, plan, kept, self.nbest if beam or lex else None, self.lexicon if lex else None, kept_scores)
