@@ -1002,6 +1002,28 @@ int tatt_ctc_lexicon_select(const double* scores, long st_sc, int B, int K, int 
                             long st_rec, hipStream_t st);
 /* out[0..4]: most steps T, most classes C, the longest word, most words K of a lexicon and most entries nbest.  Host only: needs no GPU. */
 int tatt_lexicon_limits(int* out);
+/* Word segmentation (csrc/ctcwords.hip; specification read.ctc_words_host): the most probable ALIGNMENT of image b whose collapsed
+ * string is a sequence of words of the closed list (of length >= 1), with the steps every word spans -- token passing in float64 over
+ * lp = log-soft-max of the logits (T,B,C) fp32 given by element strides, blank 0.  codes / words / K / k16 / k32 / k64: the packed list
+ * exactly as tatt_ctc_lexicon_score takes it.  The list is laid over packed lanes: 16 per word of the first class, then from the next
+ * multiple of 64 lanes 32 per word of the second, then from the next multiple of 64 lanes 64 per word of the third;
+ * tatt_words_limits()[2] is the most lanes a call takes.  word_penalty is added wherever a word is entered.  ONE launch, one work-group
+ * per image, which meets no other work-group.  Image b writes the record row index[b] (an index outside 0 .. n_rows - 1 writes
+ * nothing, neither record nor lp_out), rows st_rec ints apart, in 32-bit words:
+ *   [0] words written n <= cap  [1] flag  [2..3] the float64 logp as it is, low word first (-inf where no sequence of list words has an
+ *   alignment: n = 0)  then n entries of 2 words, left to right: [0] the caller's index of the word  [1] first | last << 16, the step
+ *   at which the word's first character was entered and the step at which it ended.  Words beyond the n entries are left as they were.
+ * flag 1, with [0] = 0 and logp = NaN: a NaN, a +inf or a step without a finite logit.
+ * lp_out, where not NULL: the (B, T, C) float64 log-soft-max the decoding ran on, image b at lp_out + b st_lp (NaN on a flagged image).
+ * Returns 1 before any launch for: a null pointer (lp_out may be NULL), T outside 1 .. 256, C outside 1 .. 64, B outside 1 .. 65535,
+ * K outside 1 .. 65536, n_codes < 0, a negative class count or k16 + k32 + k64 != K, more lanes than the limit, a word_penalty that is
+ * not finite, n_rows <= 0, cap < T, st_rec < 4 + 2 cap, st_lp < T C with a non-NULL lp_out. */
+int tatt_ctc_words_read(const float* logits, long st_t, long st_b, long st_c, int T, int B, int C, const int* codes, int n_codes,
+                        const int* words, int K, int k16, int k32, int k64, double word_penalty, const int* index, int* record,
+                        int n_rows, int cap, long st_rec, double* lp_out, long st_lp, hipStream_t st);
+/* out[0..4]: most steps T, most classes C, most packed lanes of a list, the threads of a work-group and the lanes a thread holds at that
+ * limit.  Host only: needs no GPU. */
+int tatt_words_limits(int* out);
 /* calculate_psnr (reference utils/ssim_psnr.py:9-15) of two (B,C,H,W) images in [0,1] given by element strides, first 3 channels */
 int tatt_psnr(const float* a, long a_n, long a_c, long a_h, long a_w, const float* b, long b_n, long b_c, long b_h, long b_w,
               float* out, int B, int C, int H, int W, hipStream_t st);

@@ -10,7 +10,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 HEADER = os.path.join(os.path.dirname(HERE), "include", "tatt_hip.h")
 LIB_PATH = os.path.join(HERE, "lib", "libtatt_hip.so")
 
-_CT = {"int": ctypes.c_int, "long": ctypes.c_long, "float": ctypes.c_float, "unsigned": ctypes.c_uint,
+_CT = {"int": ctypes.c_int, "long": ctypes.c_long, "float": ctypes.c_float, "double": ctypes.c_double, "unsigned": ctypes.c_uint,
        "hipStream_t": ctypes.c_void_p}
 
 

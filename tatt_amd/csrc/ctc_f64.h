@@ -1,5 +1,6 @@
-// Float64 helpers shared by the CTC decoders that sum path probabilities on the device (ctcbeam.hip, ctclex.hip): the log-sum-exp of
-// two terms as the host specification states it (tatt_amd/read.py `_beam_real`), and wave-wide maxima, minima and sums.
+// Float64 helpers shared by the CTC decoders that work on path probabilities on the device (ctcbeam.hip, ctclex.hip, ctcwords.hip): the
+// log-sum-exp of two terms as the host specification states it (tatt_amd/read.py `_beam_real`), wave-wide maxima, minima and sums, and
+// the move of a value to the lane above (`lx_below`, the neighbour states of ctclex.hip and ctcwords.hip).
 #pragma once
 #include "common.h"
 
@@ -70,4 +71,30 @@ __device__ __forceinline__ int cb_wave_mini(int v) {
     v = cb_mini<0x142>(v);
     v = cb_mini<0x143>(v);
     return __builtin_amdgcn_readlane(v, 63);
+}
+
+// the value the lane below holds (lane - 1), -inf in lane 0 of the wave; G == 16 never looks across a row of 16 lanes (a segment's
+// first lane takes no neighbour), so the row shift alone serves it
+template <int G>
+__device__ __forceinline__ double lx_below(double v, int lane) {
+    const int nh = (int)0xfff00000, nl = 0;                          // -inf
+    int hi = __builtin_amdgcn_update_dpp(nh, __double2hiint(v), 0x111, 0xf, 0xf, false);         // row_shr:1
+    int lo = __builtin_amdgcn_update_dpp(nl, __double2loint(v), 0x111, 0xf, 0xf, false);
+    if (G > 16) {
+        const int bh = __builtin_amdgcn_update_dpp(nh, __double2hiint(v), 0x142, 0xf, 0xf, false);   // row_bcast:15 into rows 1, 2, 3
+        const int bl = __builtin_amdgcn_update_dpp(nl, __double2loint(v), 0x142, 0xf, 0xf, false);
+        if ((lane & 15) == 0) {
+            hi = bh;
+            lo = bl;
+        }
+    }
+    return __hiloint2double(hi, lo);
+}
+
+// the same move for a 32-bit value (a token's start step in ctcwords.hip); lane 0 of the wave takes `fill`
+__device__ __forceinline__ int lx_below_i(int v, int lane, int fill) {
+    int r = __builtin_amdgcn_update_dpp(fill, v, 0x111, 0xf, 0xf, false);                        // row_shr:1
+    const int b = __builtin_amdgcn_update_dpp(fill, v, 0x142, 0xf, 0xf, false);                  // row_bcast:15 into rows 1, 2, 3
+    if ((lane & 15) == 0) r = b;
+    return r;
 }

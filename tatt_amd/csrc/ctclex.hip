@@ -14,7 +14,7 @@
 //                                 alpha'[s] = a + lp[c] -- the specification's operands in its order.  alpha[s - 1] and alpha[s - 2] come
 //                                 through data-parallel-primitive moves (a shift by one lane inside a row of 16; for G > 16 a row's lane 0
 //                                 takes lane 15 of the row below it through a row broadcast): no LDS in the step loop.
-//                                 The arithmetic of a word does not depend on G: the moves are exact.
+//                                 The arithmetic of a word does not depend on G: the moves (`lx_below`, ctc_f64.h) are exact.
 //   ctc_lexicon_select_kernel     one work-group per line: the nbest <= 16 largest finite scores (comparisons only: exact), ties to the
 //                                 lower word index, logz = m + log sum exp(score - m) in float64, one record row per line.
 // Every loop is bounded by T, C, K, LX_NBEST or a literal.  Nothing is indexed by lexicon DATA without a range check: a word whose length,
@@ -34,24 +34,6 @@
 #define LX_LDS_MAX (LX_MAX_T * (8 + 4 + 4 * LX_MAX_C))
 
 static_assert(2 * LX_MAX_L + 1 <= 64, "a word's states fit a wave");
-
-// the value the lane below holds (lane - 1), -inf in lane 0 of the wave; G == 16 never looks across a row of 16 lanes (a segment's
-// first lane takes no neighbour), so the row shift alone serves it
-template <int G>
-__device__ __forceinline__ double lx_below(double v, int lane) {
-    const int nh = (int)0xfff00000, nl = 0;                          // -inf
-    int hi = __builtin_amdgcn_update_dpp(nh, __double2hiint(v), 0x111, 0xf, 0xf, false);         // row_shr:1
-    int lo = __builtin_amdgcn_update_dpp(nl, __double2loint(v), 0x111, 0xf, 0xf, false);
-    if (G > 16) {
-        const int bh = __builtin_amdgcn_update_dpp(nh, __double2hiint(v), 0x142, 0xf, 0xf, false);   // row_bcast:15 into rows 1, 2, 3
-        const int bl = __builtin_amdgcn_update_dpp(nl, __double2loint(v), 0x142, 0xf, 0xf, false);
-        if ((lane & 15) == 0) {
-            hi = bh;
-            lo = bl;
-        }
-    }
-    return __hiloint2double(hi, lo);
-}
 
 template <int G>
 __global__ __launch_bounds__(LX_THREADS) void ctc_lexicon_score_kernel(const float* __restrict__ logits, long st_t, long st_b, long st_c,

@@ -776,11 +776,15 @@ class SuperResolver:
     chunk in place of the greedy one, and `readings()` gives `read.BeamReading`s (text, logp, alternatives); `texts()` as before.
     read_decode="lexicon" (read_lexicon = a `read.Lexicon` or a list of words, read_nbest <= 16) reads every line against that closed
     list: per chunk the tatt_ctc_lexicon_score launches and one tatt_ctc_lexicon_select launch in place of the greedy one, and
-    `readings()` gives `read.LexiconReading`s (text, logp, posterior, alternatives); every text is a word of the list."""
+    `readings()` gives `read.LexiconReading`s (text, logp, posterior, alternatives); every text is a word of the list.
+    read_decode="words" (read_lexicon, read_word_penalty = a finite float) reads every line as a SEQUENCE of list words: per chunk one
+    tatt_ctc_words_read launch in place of the greedy one, `readings()` gives `read.WordsReading`s (text: the words joined by spaces,
+    logp, words: one `read.WordSpan` per word with its steps and columns) and `texts()` the space-joined strings."""
 
     def __init__(self, generator, prior=None, recognizer=None, batch_size: int = 48, lr_size=(16, 64), mask: bool = True,
                  rule: str = "floor", keep_sr: bool = False, long_lines: bool = False, stride: int = 32, reader=None,
-                 read_decode: str = "greedy", read_beam: int = 8, read_nbest: int = 4, read_lexicon=None):
+                 read_decode: str = "greedy", read_beam: int = 8, read_nbest: int = 4, read_lexicon=None,
+                 read_word_penalty: float = 0.0):
         from .io import DeviceCollator, DeviceExporter
         _refuse_attention_recognizer(recognizer, "SuperResolver")
         _check_module(generator, "generator")
@@ -806,7 +810,7 @@ class SuperResolver:
         if reader is not None:
             from .read import LineReader
             self.reader = LineReader(reader, batch_size=batch_size, device=self.device, w=self.lr_size[1], decode=read_decode,
-                                     beam=read_beam, nbest=read_nbest, lexicon=read_lexicon)
+                                     beam=read_beam, nbest=read_nbest, lexicon=read_lexicon, word_penalty=read_word_penalty)
 
     def _texts(self, sr):
         """-> (pinned (n, T + 1) int32: decoded classes | length, its event)"""

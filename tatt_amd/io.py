@@ -1184,3 +1184,4 @@ from .read import (READ_MAX, READ_QUANTUM, BeamDecoded, BeamReading, Lexicon, Le
                    beam_limits, ctc_beam_read_host, ctc_greedy_read_host, ctc_lexicon_read_host,
                    ctc_string_logp_host, lexicon_limits, line_luma_host, read_limits, read_lines_host, read_plan, read_squeezed,
                    read_width)
+from .read import WordsDecoded, WordSpan, WordsReading, ctc_words_host, ctc_words_read_host, words_limits  # noqa: E402,F401

@@ -20,6 +20,9 @@ session and one tatt_ctc_greedy_read launch (decode="beam": one tatt_ctc_beam_re
 decode="lexicon": the score and select launches of csrc/ctclex.hip), one copy of the record buffer back.
 Reading against a closed list of words: `Lexicon` (the words as class ids, packed for the device), `ctc_lexicon_scores_host` /
 `ctc_lexicon_read_host` (the specification: `ctc_string_logp_host` of every word, the N best, the normaliser over the list).
+Reading a line of SEVERAL words against the list: `ctc_words_host` / `ctc_words_read_host` (the specification of csrc/ctcwords.hip: token
+passing, the most probable alignment that spells a sequence of list words, with the steps every word spans); decode="words": one
+tatt_ctc_words_read launch per bucket chunk in place of the greedy one.
 """
 from __future__ import annotations
 
@@ -41,6 +44,9 @@ BeamReading = namedtuple("BeamReading", "text logp alternatives rw squeezed")
 BeamDecoded = namedtuple("BeamDecoded", "entries flag margin reentry", defaults=(None, None))
 LexiconReading = namedtuple("LexiconReading", "text logp posterior alternatives rw squeezed")
 LexiconDecoded = namedtuple("LexiconDecoded", "entries logz flag margin", defaults=(None,))
+WordsDecoded = namedtuple("WordsDecoded", "words logp flag")          # words: [(the caller's word index, first step, last step)]
+WordSpan = namedtuple("WordSpan", "text index first last x0 x1")
+WordsReading = namedtuple("WordsReading", "text logp words rw squeezed")
 LEXICON_SEGMENTS = (16, 32, 64)   # lanes of a word's segment on the device: the smallest that holds its 2 L + 1 states
 ReadPlan = namedtuple("ReadPlan", "buckets desc offsets floats rws squeezed")
 
@@ -385,6 +391,144 @@ def ctc_lexicon_read_host(logits, lexicon: Lexicon, nbest: int = 4, details: boo
     return [_lexicon_decode(row, nbest, details, real) for row in scores]
 
 
+def _check_penalty(what, word_penalty) -> float:
+    import math
+    if isinstance(word_penalty, bool) or not isinstance(word_penalty, (int, float)) or not math.isfinite(word_penalty):
+        raise ValueError("%s: word_penalty must be a finite float; got %r" % (what, word_penalty))
+    return float(word_penalty)
+
+
+def ctc_words_host(lp, lexicon: Lexicon, word_penalty: float = 0.0) -> WordsDecoded:
+    """ONE line's float64 log-probabilities lp[t][c] (T x C, blank 0) -> WordsDecoded(words, logp, flag): the best sequence of the
+    lexicon's words the line spells, by token passing.  At word_penalty = 0 it is the most probable ALIGNMENT whose collapsed string is
+    a concatenation of list words; `words` is [(k, first, last)] left to right, k the caller's word index, `first` the step at which
+    the word's first character was entered and `last` the step at which it ended; `logp` the alignment's log-probability plus
+    word_penalty per word.  Only additions, comparisons and copies of float64.
+
+    Only words of length >= 1 take part ("" is ignored: the empty reading is always possible).  Word k with classes w[0 .. L - 1] has
+    the states ch[j] (j < L) and the in-word blanks bl[j] between j and j + 1 (j < L - 1); a state holds a token (score, start).
+    G[-1] = 0, X[-1][c] = -inf, all word states -inf.  "max in order": candidates are tried in the order given and only a STRICTLY
+    greater score replaces the current one.  For t = 0 .. T - 1:
+      enter[t][a], a >= 1   max in order of G[t - 1], then X[t - 1][c] for c = 1 .. C - 1, c != a; Esrc[t][a] the winner (0 for G);
+      ch[t][j]              lp[t][w[j]] + max in order of ch[t - 1][j]; j >= 1: bl[t - 1][j - 1]; j >= 1 and w[j] != w[j - 1]:
+                            ch[t - 1][j - 1]; j = 0: enter[t][w[0]] + word_penalty with start = t.  The token's start is the winner's;
+      bl[t][j]              lp[t][0] + max in order of bl[t - 1][j], ch[t - 1][j];
+      X[t][c]               the largest ch[t][L - 1] over the words whose last class is c, ties to the lower caller's word index;
+                            Xrec[t][c] that word and its token's start;
+      G[t]                  lp[t][0] + max in order of G[t - 1], X[t - 1][c] for c ascending; Gsrc[t] 0 (stay) or c.
+    logp = max in order of G[T - 1], X[T - 1][c] for c ascending.  Back-trace: a word ending at step e in class c is (k, start) =
+    Xrec[e][c], reported as (k, start, e); its predecessor is Esrc[start][w_k[0]]: a class c' is a word ending at start - 1 in c';
+    0 means: walk Gsrc back from start - 1 while it says stay, then take the class it names; reaching t < 0 ends the walk.
+    logp = -inf (no sequence of list words has an alignment of T steps) gives words = [], flag = 0.  So two words follow each other
+    without a blank only if the first one's last class differs from the second one's first class, and among segmentations of ONE
+    alignment (exact ties) the order of the list decides.  A negative word_penalty prefers fewer, longer words."""
+    wp = _check_penalty("ctc_words_host", word_penalty)
+    rows = lp.tolist() if hasattr(lp, "tolist") else [list(r) for r in lp]
+    if not rows or not rows[0] or any(len(r) != len(rows[0]) for r in rows):
+        raise ValueError("ctc_words_host takes the non-empty (T, C) log-probabilities of one line")
+    T, C = len(rows), len(rows[0])
+    if lexicon.n_classes > C:
+        raise ValueError("ctc_words_host: the lexicon's alphabet has %d classes, the line %d" % (lexicon.n_classes, C))
+    neg = float("-inf")
+    words = [(k, w) for k, w in enumerate(lexicon.classes) if w]
+    firsts = sorted({w[0] for _, w in words})
+    chs, chst = [[neg] * len(w) for _, w in words], [[0] * len(w) for _, w in words]
+    bls, blst = [[neg] * (len(w) - 1) for _, w in words], [[0] * (len(w) - 1) for _, w in words]
+    G, X = 0.0, [neg] * C
+    Xrec, Esrc, Gsrc = [], [], []
+    for t, row in enumerate(rows):
+        enter, esrc = {}, {}
+        for a in firsts:
+            m, src = G, 0
+            for c in range(1, C):
+                if c != a and X[c] > m:
+                    m, src = X[c], c
+            enter[a], esrc[a] = m, src
+        gm, gs = G, 0
+        for c in range(1, C):
+            if X[c] > gm:
+                gm, gs = X[c], c
+        lp0 = row[0]
+        Xn, rec = [neg] * C, [None] * C
+        for i, (k, w) in enumerate(words):
+            oc, ocs, ob, obs = chs[i], chst[i], bls[i], blst[i]
+            nc, ncs, nb, nbs = [], [], [], []
+            for j, c in enumerate(w):
+                m, ms = oc[j], ocs[j]
+                if j >= 1:
+                    if ob[j - 1] > m:
+                        m, ms = ob[j - 1], obs[j - 1]
+                    if c != w[j - 1] and oc[j - 1] > m:
+                        m, ms = oc[j - 1], ocs[j - 1]
+                else:
+                    e = enter[c] + wp
+                    if e > m:
+                        m, ms = e, t
+                nc.append(row[c] + m)
+                ncs.append(ms)
+            for j in range(len(w) - 1):
+                m, ms = ob[j], obs[j]
+                if oc[j] > m:
+                    m, ms = oc[j], ocs[j]
+                nb.append(lp0 + m)
+                nbs.append(ms)
+            chs[i], chst[i], bls[i], blst[i] = nc, ncs, nb, nbs
+            if nc[-1] > Xn[w[-1]]:
+                Xn[w[-1]], rec[w[-1]] = nc[-1], (k, ncs[-1])
+        G, X = lp0 + gm, Xn
+        Xrec.append(rec)
+        Esrc.append(esrc)
+        Gsrc.append(gs)
+    logp, c = G, 0
+    for a in range(1, C):
+        if X[a] > logp:
+            logp, c = X[a], a
+    if logp == neg:
+        return WordsDecoded([], neg, 0)
+    out, e, p = [], T - 1, T - 1
+    while True:
+        if c == 0:
+            while p >= 0 and Gsrc[p] == 0:
+                p -= 1
+            if p < 0:
+                break
+            c, e = Gsrc[p], p - 1
+        k, start = Xrec[e][c]
+        out.append((k, start, e))
+        c = Esrc[start][lexicon.classes[k][0]]
+        e = p = start - 1
+    return WordsDecoded(out[::-1], logp, 0)
+
+
+def ctc_words_read_host(logits, lexicon: Lexicon, word_penalty: float = 0.0):
+    """logits (T, B, C) -> one WordsDecoded per line: the log-soft-max of the other host decoders (`_log_softmax_row`, float64), then
+    `ctc_words_host`.  A line they would flag (a NaN, a +inf, a step without a finite logit) gives words = [], logp = nan, flag = 1."""
+    _check_penalty("ctc_words_read_host", word_penalty)
+    T, B, C, rows = _beam_rows(logits, "ctc_words_read_host")
+    if lexicon.n_classes > C:
+        raise ValueError("ctc_words_read_host: the lexicon's alphabet has %d classes, the logits %d" % (lexicon.n_classes, C))
+    real, exp, log, _ = _beam_real(None)
+    out = []
+    for row in rows:
+        lps = [_log_softmax_row(x, real, exp, log) for x in row]
+        out.append(WordsDecoded([], float("nan"), 1) if any(lp is None for lp in lps) else ctc_words_host(lps, lexicon, word_penalty))
+    return out
+
+
+def word_span_pixels(first: int, last: int, W: int, rw: int):
+    """-> (x0, x1): the columns of the line the caller gets back (width W, read at width rw) that the steps first .. last stand for, by
+    CONVENTION: a CTC step s sits at column 4 s of the rw-wide input and is given the 4 columns around it, x0 = max(0, (4 first - 2) W
+    // rw), x1 = min(W, ceil((4 last + 2) W / rw)) in integers.  The CRNN's receptive field is wider than that: the span says where a
+    word was read, not which pixels decided it."""
+    first, last, W, rw = int(first), int(last), int(W), int(rw)
+    return max(0, (4 * first - 2) * W // rw), min(W, -(-(4 * last + 2) * W // rw))
+
+
+def _words_reading(dec: WordsDecoded, lexicon: Lexicon, rw: int, squeezed: bool, W: int) -> WordsReading:
+    spans = [WordSpan(lexicon.words[k], k, first, last, *word_span_pixels(first, last, W, rw)) for k, first, last in dec.words]
+    return WordsReading(" ".join(sp.text for sp in spans), dec.logp, spans, rw, squeezed)
+
+
 def _reading(dec: Decoded, rw: int, squeezed: bool) -> Reading:
     d2a = _alphabet()
     return Reading("".join(d2a[c] for c in dec.classes), dec.conf, list(dec.classes), list(dec.char_conf), list(dec.steps), rw, squeezed)
@@ -660,20 +804,108 @@ def _lexicon_reading(dec: LexiconDecoded, lexicon: Lexicon, rw: int, squeezed: b
     return LexiconReading(text, logp, post, alts, rw, squeezed)
 
 
+def words_limits():
+    """tatt_words_limits: {'steps', 'classes', 'lanes', 'threads', 'slots'}: most steps T and classes C of tatt_ctc_words_read, the most
+    packed lanes of a lexicon (`words_lanes`), the threads of a work-group and the lanes a thread holds at that limit.  A host-only
+    entry: needs no GPU."""
+    from ._lib import LIB
+    out = (ctypes.c_int * 5)()
+    if LIB.tatt_words_limits(out) != 0:
+        raise RuntimeError("tatt_words_limits failed")
+    return dict(zip(("steps", "classes", "lanes", "threads", "slots"), (int(v) for v in out)))
+
+
+def words_lanes(lexicon: Lexicon) -> int:
+    """the packed lanes tatt_ctc_words_read lays the lexicon over: 16, 32 or 64 per word by its segment class, every class starting at
+    a multiple of 64 (a word's 2 L - 1 states run in the segment that holds the 2 L + 1 of lexicon decoding)"""
+    k16, k32, k64 = lexicon.counts
+    return -(-16 * k16 // 64) * 64 + -(-32 * k32 // 64) * 64 + 64 * k64
+
+
+def _check_lanes(what, lexicon: Lexicon):
+    lanes, limit = words_lanes(lexicon), words_limits()["lanes"]
+    if lanes > limit:
+        raise ValueError("%s: the lexicon needs %d lanes (%d, %d, %d words in segments of 16, 32, 64); decode='words' takes at most %d"
+                         % ((what, lanes) + tuple(lexicon.counts) + (limit,)))
+
+
+def words_record_words(cap: int) -> int:
+    """32-bit words of a words record row for lines of at most `cap` steps: [0] words written, [1] flag, [2:4] logp, then 2 per word"""
+    return 4 + 2 * int(cap)
+
+
+def ctc_words_read(logits, lexicon: Lexicon, index, record, cap: int, word_penalty: float = 0.0, lp_out=None):
+    """ONE tatt_ctc_words_read launch: logits (T, B, C) fp32 on the device (any strides), index (B,) int32 on the device: the record
+    row of every line, record (n_rows, >= words_record_words(cap)) int32 on the device, rows contiguous, cap >= T (see
+    `parse_words_records`); lp_out: None or a (B, T, C) float64 tensor on the device, every line contiguous, which receives the
+    log-soft-max the decoding ran on.  Specification `ctc_words_read_host`.  ValueError for what the entry refuses, before any launch."""
+    from . import ops
+    from ._lib import LIB
+    ops._check_dev(logits)
+    T, B, C = logits.shape
+    if record.dtype != torch.int32 or record.dim() != 2 or record.stride(1) != 1 or index.dtype != torch.int32 or index.numel() < B:
+        raise ValueError("ctc_words_read: record must be a 2-D int32 tensor with contiguous rows, index an int32 tensor of B entries")
+    wp = _check_penalty("ctc_words_read", word_penalty)
+    if lexicon.n_classes > C:
+        raise ValueError("ctc_words_read: the lexicon's alphabet has %d classes, the logits %d" % (lexicon.n_classes, C))
+    _check_lanes("ctc_words_read", lexicon)
+    if record.shape[1] < words_record_words(cap):
+        raise ValueError("ctc_words_read: rows of %d words; cap = %d needs %d" % (record.shape[1], cap, words_record_words(cap)))
+    st_lp = 0
+    if lp_out is not None:
+        if lp_out.dtype != torch.float64 or tuple(lp_out.shape) != (B, T, C) or lp_out.stride(2) != 1 or lp_out.stride(1) != C or \
+                lp_out.device != logits.device:
+            raise ValueError("ctc_words_read: lp_out must be a (%d, %d, %d) float64 tensor with contiguous lines on %s"
+                             % (B, T, C, logits.device))
+        st_lp = lp_out.stride(0)
+    codes, table = lexicon.device(logits.device)
+    rc = LIB.tatt_ctc_words_read(ops.P(logits), *logits.stride(), T, B, C, ops.P(codes), lexicon.n_codes, ops.P(table), len(lexicon),
+                                 *lexicon.counts, wp, ops.P(index), ops.P(record), record.shape[0], int(cap), record.stride(0),
+                                 ops.P(lp_out), st_lp, ops.stream())
+    if rc == 1:
+        raise ValueError("tatt_ctc_words_read refuses T = %d, B = %d, C = %d, K = %d, cap = %d, rows of %d words"
+                         % (T, B, C, len(lexicon), cap, record.stride(0)))
+    if rc != 0:
+        raise RuntimeError("tatt_ctc_words_read failed with code %d" % rc)
+    return record
+
+
+def parse_words_records(record, cap: int):
+    """record: the (n, >= words_record_words(cap)) int32 HOST tensor tatt_ctc_words_read filled -> one WordsDecoded per row.  Row, in
+    32-bit words: [0] words written (<= cap)  [1] flag  [2:4] the float64 logp as it is (low word first)  then per word 2 words: the
+    caller's word index, first | last << 16."""
+    import struct
+    out = []
+    for row in record.tolist():
+        n, flag = row[0], row[1]
+        if not 0 <= n <= cap or flag not in (0, 1) or len(row) < words_record_words(cap):
+            raise ValueError("parse_words_records: no words record row: words = %r, flag = %r" % (n, flag))
+        logp = struct.unpack("<d", struct.pack("<ii", row[2], row[3]))[0]
+        out.append(WordsDecoded([(row[4 + 2 * i], row[5 + 2 * i] & 0xffff, (row[5 + 2 * i] >> 16) & 0xffff) for i in range(n)], logp, flag))
+    return out
+
+
 class PendingReading:
     """What `LineReader.read` started.  `result()` is the only host wait: -> one Reading (decode="beam": one BeamReading,
     decode="lexicon": one LexiconReading) per line, in input order.  With keep_logits: `logits` [(line indices of the chunk, its
-    (T, n, C) logits on the device)]; with keep_scores (lexicon): `scores` [(line indices, the chunk's (n, K) float64 scores)]."""
+    (T, n, C) logits on the device)]; with keep_scores (lexicon): `scores` [(line indices, the chunk's (n, K) float64 scores)].
+    decode="words": one WordsReading per line (`texts()`: the words joined by spaces); with keep_lp: `lp` [(line indices, the chunk's
+    (n, T, C) float64 log-soft-max on the device)]."""
 
-    def __init__(self, host, event, cap, plan, logits=None, nbest=None, lexicon=None, scores=None):
+    def __init__(self, host, event, cap, plan, logits=None, nbest=None, lexicon=None, scores=None, words=False, lp=None):
         self._host, self._event, self._cap, self._plan, self.logits, self._out = host, event, cap, plan, logits, None
         self._nbest = nbest                                          # None: greedy records
         self._lexicon, self.scores = lexicon, scores                 # a Lexicon: lexicon records
+        self._words, self.lp = bool(words), lp                       # words records (of that Lexicon)
 
     def result(self):
         if self._out is None:
             if self._host is None:
                 self._out = []
+            elif self._words:
+                self._event.synchronize()
+                self._out = [_words_reading(d, self._lexicon, rw, sq, int(W)) for d, rw, sq, W in zip(
+                    parse_words_records(self._host, self._cap), self._plan.rws, self._plan.squeezed, self._plan.desc[:, 2])]
             elif self._nbest is None:
                 self._event.synchronize()
                 self._out = [_reading(d, rw, sq) for d, rw, sq in zip(parse_records(self._host, self._cap), self._plan.rws,
@@ -723,27 +955,42 @@ class LineReader:
     launches (one per non-empty segment class of the lexicon) into an (n, K) float64 buffer of its own and ONE tatt_ctc_lexicon_select
     launch in place of the greedy one (specification `ctc_lexicon_read_host`); `result()` gives `LexiconReading`s: the most probable
     word of the list, its exact CTC log-probability, its posterior among the list's words, and the `nbest` best words as
-    `alternatives`.  keep_scores=True keeps every chunk's score buffer (`PendingReading.scores`)."""
+    `alternatives`.  keep_scores=True keeps every chunk's score buffer (`PendingReading.scores`).
+    decode="words" (with lexicon = a `Lexicon` or a list of words, word_penalty a finite float): a line is read as a SEQUENCE of list
+    words.  Every chunk gets ONE tatt_ctc_words_read launch in place of the greedy one (token passing, specification
+    `ctc_words_read_host`); `result()` gives `WordsReading`s: `text` the words joined by spaces, `logp` the log-probability of the
+    best alignment (plus word_penalty per word), `words` one `WordSpan(text, index, first, last, x0, x1)` per word: its steps and, by
+    the convention of `word_span_pixels`, its columns in the line the caller gets back.  The lexicon must fit words_limits()["lanes"]
+    packed lanes (`words_lanes`): ValueError here otherwise.  keep_lp=True keeps every chunk's float64 log-soft-max
+    (`PendingReading.lp`)."""
 
     def __init__(self, crnn, batch_size: int = 48, device=None, keep_logits: bool = False, w: int = 64, decode: str = "greedy",
-                 beam: int = 8, nbest: int = 4, lexicon=None, keep_scores: bool = False):
+                 beam: int = 8, nbest: int = 4, lexicon=None, keep_scores: bool = False, word_penalty: float = 0.0,
+                 keep_lp: bool = False):
         from . import functional as Fh
         from .infer import _check_module, _crnn_folds
-        if decode not in ("greedy", "beam", "lexicon"):
-            raise ValueError("LineReader: decode is 'greedy', 'beam' or 'lexicon'; got %r" % (decode,))
-        if decode == "lexicon":
-            _check_nbest("LineReader", nbest)
+        if decode not in ("greedy", "beam", "lexicon", "words"):
+            raise ValueError("LineReader: decode is 'greedy', 'beam', 'lexicon' or 'words'; got %r" % (decode,))
+        word_penalty = _check_penalty("LineReader", word_penalty)
+        if decode != "words" and word_penalty != 0.0:
+            raise ValueError("LineReader: word_penalty= goes with decode='words'; got decode = %r" % (decode,))
+        if decode in ("lexicon", "words"):
+            if decode == "lexicon":
+                _check_nbest("LineReader", nbest)
             if lexicon is None:
-                raise ValueError("LineReader: decode='lexicon' needs lexicon=, a Lexicon or a list of words")
+                raise ValueError("LineReader: decode=%r needs lexicon=, a Lexicon or a list of words" % (decode,))
             lexicon = lexicon if isinstance(lexicon, Lexicon) else Lexicon(lexicon)
             emits = _emitted_classes(crnn)
             if emits is not None and lexicon.n_classes > emits:
                 raise ValueError("LineReader: the lexicon's alphabet has %d classes, the CRNN emits %d" % (lexicon.n_classes, emits))
+            if decode == "words":
+                _check_lanes("LineReader", lexicon)
         else:
             _check_beam("LineReader", beam, nbest, beam_limits()["beam"])
             if lexicon is not None:
-                raise ValueError("LineReader: lexicon= goes with decode='lexicon'; got decode = %r" % (decode,))
+                raise ValueError("LineReader: lexicon= goes with decode='lexicon' or decode='words'; got decode = %r" % (decode,))
         self.decode, self.beam, self.nbest, self.lexicon, self.keep_scores = decode, beam, nbest, lexicon, bool(keep_scores)
+        self.word_penalty, self.keep_lp = word_penalty, bool(keep_lp)
         _check_module(crnn, "reader CRNN")
         if not (isinstance(batch_size, int) and batch_size > 0):
             raise ValueError("batch_size must be a positive int")
@@ -822,9 +1069,11 @@ class LineReader:
             head_dev.copy_(head, non_blocking=True)
             luma = torch.empty(plan.floats, dtype=torch.float32, device=self.device)
             line_luma(dev_bytes, head_dev, plan.desc, luma)
-            beam, lex = self.decode == "beam", self.decode == "lexicon"
-            words = beam_record_words(cap, self.nbest) if beam else lexicon_record_words(self.nbest) if lex else 3 * cap + 2
+            beam, lex, wrd = self.decode == "beam", self.decode == "lexicon", self.decode == "words"
+            words = beam_record_words(cap, self.nbest) if beam else lexicon_record_words(self.nbest) if lex else \
+                words_record_words(cap) if wrd else 3 * cap + 2
             kept_scores = [] if lex and self.keep_scores else None
+            kept_lp = [] if wrd and self.keep_lp else None
             record = torch.empty(n, words, dtype=torch.int32, device=self.device)
             index, pos, foff = head_dev[n * READ_DESC:], 0, 0
             for rw, idx in plan.buckets:
@@ -841,6 +1090,12 @@ class LineReader:
                         ctc_lexicon_select(scores, index[pos:pos + m], record, self.nbest)
                         if kept_scores is not None:
                             kept_scores.append((idx[i:i + m], scores))
+                    elif wrd:
+                        lp = None
+                        if kept_lp is not None:
+                            lp = torch.empty(m, logits.shape[0], logits.shape[2], dtype=torch.float64, device=self.device)
+                            kept_lp.append((idx[i:i + m], lp))
+                        ctc_words_read(logits, self.lexicon, index[pos:pos + m], record, cap, self.word_penalty, lp)
                     else:
                         ctc_greedy_read(logits, index[pos:pos + m], record, cap)
                     if keep:
@@ -850,4 +1105,5 @@ class LineReader:
             host.copy_(record, non_blocking=True)
             ev = torch.cuda.Event()
             ev.record()
-        return PendingReading(host, ev, cap, plan, kept, self.nbest if beam or lex else None, self.lexicon if lex else None, kept_scores)
+        return PendingReading(host, ev, cap, plan, kept, self.nbest if beam or lex else None, self.lexicon if lex or wrd else None, kept_scores,
+                              wrd, kept_lp)
