@@ -716,9 +716,10 @@ int tatt_grid_sample_bwd(const float* x, long xsn, long xsc, long xsh, long xsw,
 /* ImageLoss(gradient=True, loss_weight=[w0, w1]).forward (reference loss/image_loss.py:19-34,50-58): per-sample
  * loss[b] = w0*mean((sr-hr)^2) + w1*mean|gradient_map(sr[:3]) - gradient_map(hr[:3])|; when loss_mean != NULL also
  * loss_mean[0] = scale * mean_b loss[b] (interfaces/super_resolution.py:889-894 uses scale 100).  sr / hr are (B,C,H,W) images
- * addressed by element strides (n, c, h, w). */
+ * addressed by element strides (n, c, h, w).  ws: workspace of B * 32 doubles (the fp64 wave sums of every image; the launch
+ * spreads an image over 16 work-groups). */
 int tatt_image_loss_fwd(const float* sr, long s_n, long s_c, long s_h, long s_w, const float* hr, long h_n, long h_c,
-                        long h_h, long h_w, float* loss, float* loss_mean, float scale, int B, int C, int H, int W,
+                        long h_h, long h_w, float* loss, float* loss_mean, float scale, double* ws, int B, int C, int H, int W,
                         float w0, float w1, hipStream_t st);
 /* its gradient w.r.t. sr (dsr has sr's strides); exactly one of gper (B per-sample upstream gradients) and gscalar (upstream
  * gradient of the scaled batch mean, 1 element) is non-NULL */

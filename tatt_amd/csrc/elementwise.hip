@@ -139,9 +139,47 @@ __global__ void pixel_shuffle_fwd_kernel(const float* __restrict__ in, float* __
     float v = in[(((long)b * H + h) * W + w) * (4 * C) + 4 * c + 2 * i + j];
     out[idx] = apply_act(v, act);
 }
+// The quad route (C % 4 == 0, 16-byte aligned maps, fewer than 2^31 elements): one thread owns output channels 4q .. 4q+3 of one LR
+// pixel p.  Their sources are the 16 consecutive input channels 16q .. 16q+15 (one 64-byte run, four 16-byte loads); element e of
+// load k is channel 4(4q+k) + e, i.e. output channel 4q+k of sub-pixel (i, j) = (e >> 1, e & 1), so a 4x4 transpose in registers
+// gives one 16-byte quad for each of the four HR pixels.  Item = p * Q + q (Q = C / 4) is also the index of the 64-byte input
+// run, and every index below is 32-bit: two unsigned divisions per 16 elements.
+__device__ __forceinline__ unsigned ps_hr_quad(unsigned item, unsigned Q, unsigned W, unsigned& q) {
+    const unsigned p = item / Q;
+    q = item - p * Q;
+    const unsigned r = p / W, w = p - r * W;              // r = b * H + h
+    return 4u * W * r + 2u * w;                           // HR pixel (b, 2h, 2w); (i, j) adds i * 2W + j
+}
+__global__ __launch_bounds__(256) void pixel_shuffle_fwd_quad_kernel(const f32x4* __restrict__ in, f32x4* __restrict__ out,
+                                                                     unsigned items, unsigned Q, unsigned W, int act) {
+    const unsigned item = blockIdx.x * 256u + threadIdx.x;
+    if (item >= items) return;
+    unsigned q;
+    const unsigned hp = ps_hr_quad(item, Q, W, q);
+    f32x4 x[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) x[k] = in[4u * item + k];
+#pragma unroll
+    for (int s = 0; s < 4; ++s) {
+        f32x4 y;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) y[k] = apply_act(x[k][s], act);
+        out[(hp + (s >> 1) * 2u * W + (s & 1)) * Q + q] = y;
+    }
+}
+static bool ps_quad_route(const void* a, const void* b, const void* c, int B, int H, int W, int C) {
+    const long total = (long)B * 4 * H * W * C;
+    return C > 0 && C % 4 == 0 && total > 0 && total < (1L << 31) && ((((uintptr_t)a) | ((uintptr_t)b) | ((uintptr_t)c)) & 15) == 0;
+}
 TATT_API int tatt_pixel_shuffle_fwd(const float* in, float* out, int B, int H, int W, int C, int act,
                                     hipStream_t st) {
     long total = (long)B * 4 * H * W * C;
+    if (ps_quad_route(in, out, nullptr, B, H, W, C)) {
+        const unsigned items = (unsigned)(total / 16);
+        hipLaunchKernelGGL(pixel_shuffle_fwd_quad_kernel, dim3(cdiv(items, 256)), dim3(256), 0, st,
+                           reinterpret_cast<const f32x4*>(in), reinterpret_cast<f32x4*>(out), items, (unsigned)(C / 4), (unsigned)W, act);
+        return LAUNCH_CHECK();
+    }
     hipLaunchKernelGGL(pixel_shuffle_fwd_kernel, EW_GRID(total), 0, st, in, out, B, H, W, C, act);
     return LAUNCH_CHECK();
 }
@@ -158,9 +196,37 @@ __global__ void pixel_shuffle_bwd_kernel(const float* __restrict__ in, const flo
     float g = dout[(((long)b * 2 * H + 2 * h + i) * (2 * W) + 2 * w + j) * C + c];
     din[idx] = g * act_grad(in[idx], act);
 }
+// the mirror of the quad route: four 16-byte dout quads (one per HR pixel), one 64-byte run of `in`, one 64-byte run of din
+__global__ __launch_bounds__(256) void pixel_shuffle_bwd_quad_kernel(const f32x4* __restrict__ in, const f32x4* __restrict__ dout,
+                                                                     f32x4* __restrict__ din, unsigned items, unsigned Q, unsigned W,
+                                                                     int act) {
+    const unsigned item = blockIdx.x * 256u + threadIdx.x;
+    if (item >= items) return;
+    unsigned q;
+    const unsigned hp = ps_hr_quad(item, Q, W, q);
+    f32x4 g[4], x[4];
+#pragma unroll
+    for (int s = 0; s < 4; ++s) g[s] = dout[(hp + (s >> 1) * 2u * W + (s & 1)) * Q + q];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) x[k] = in[4u * item + k];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        f32x4 d;
+#pragma unroll
+        for (int s = 0; s < 4; ++s) d[s] = g[s][k] * act_grad(x[k][s], act);
+        din[4u * item + k] = d;
+    }
+}
 TATT_API int tatt_pixel_shuffle_bwd(const float* in, const float* dout, float* din, int B, int H, int W, int C,
                                     int act, hipStream_t st) {
     long total = (long)B * H * W * 4 * C;
+    if (ps_quad_route(in, dout, din, B, H, W, C)) {
+        const unsigned items = (unsigned)(total / 16);
+        hipLaunchKernelGGL(pixel_shuffle_bwd_quad_kernel, dim3(cdiv(items, 256)), dim3(256), 0, st,
+                           reinterpret_cast<const f32x4*>(in), reinterpret_cast<const f32x4*>(dout), reinterpret_cast<f32x4*>(din), items,
+                           (unsigned)(C / 4), (unsigned)W, act);
+        return LAUNCH_CHECK();
+    }
     hipLaunchKernelGGL(pixel_shuffle_bwd_kernel, EW_GRID(total), 0, st, in, dout, din, B, H, W, C, act);
     return LAUNCH_CHECK();
 }

@@ -618,14 +618,18 @@ __global__ __launch_bounds__(512, 5) void stn_fc_bwd_kernel(SnFcBwdP p) {
     float dbn[4] = {0.f, 0.f, 0.f, 0.f}, uh[4] = {0.f, 0.f, 0.f, 0.f};
     if (t < 256) {
         const float mu = p.mean1[j0 + j], rs = p.rstd1[j0 + j];
+        float ub[4];                                                // the thread's U values travel together, ahead of the dS chains
+#pragma unroll
+        for (int mt = 0; mt < 4; ++mt) ub[mt] = mt * 16 + m < B ? p.U[(long)(mt * 16 + m) * FC_H + j0 + j] : 0.f;
         double s1 = 0.0, s2 = 0.0;
-        for (int mt = 0; mt < MT; ++mt) {
+#pragma unroll
+        for (int mt = 0; mt < 4; ++mt) {
             const int b = mt * 16 + m;
             if (b >= B) break;
             float ds = 0.f;
             for (int o = 0; o < NO; ++o) ds += dcs[b][o] * w2s[o][j];
             const float d = sS[b][j] > 0.f ? 0.1f * ds : 0.f;
-            const float h = (p.U[(long)b * FC_H + j0 + j] - mu) * rs;
+            const float h = (ub[mt] - mu) * rs;
             dbn[mt] = d; uh[mt] = h;
             s1 += (double)d; s2 += (double)d * (double)h;
         }
@@ -663,6 +667,12 @@ __global__ __launch_bounds__(512, 5) void stn_fc_bwd_kernel(SnFcBwdP p) {
         st16_sc1(p.dU, (b * FC_H + j0 + c4) * 4, &dus[b][c4]);
     }
     sn_publish(p.sync, g, ep * 4 + 1);
+    // phase B's W1 fragments depend on parameters alone: requested here, they travel under the parameter gradients and the wait
+    float bw[4][4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u)
+#pragma unroll
+        for (int v = 0; v < 4; ++v) bw[u][v] = p.W1[(long)(wave * 64 + 16 * u + 4 * q + v) * FC_H + 16 * g + i];
     // parameter gradients of this work-group's features while the others publish
     for (int idx = t; idx < NO * 16; idx += 512) {                  // dW2[o][j0 + j] = sum_b dctrl[b][o] S[b][j0 + j]
         const int o = idx >> 4, jj = idx & 15;
@@ -680,13 +690,33 @@ __global__ __launch_bounds__(512, 5) void stn_fc_bwd_kernel(SnFcBwdP p) {
 #pragma unroll
         for (int jj = 0; jj < 16; ++jj) a[jj] = 0.f;
         const int src = (t & 1) * 256 + (t >> 1);                   // F[b][k] = A6[b][k & 1][k >> 1]
-        for (int b = 0; b < B; ++b) {
+        int b = 0;
+#pragma unroll 1
+        for (; b + 8 <= B; b += 8) {                                // 8 rows of F requested at once; the sums still run over b in order
+            float f[8];
+#pragma unroll
+            for (int bb = 0; bb < 8; ++bb) f[bb] = p.A6[(long)(b + bb) * FC_H + src];
+#pragma unroll
+            for (int bb = 0; bb < 8; ++bb) {
+                // the row index passes through an empty statement that takes f[bb]: the row's LDS reads are issued once its F value has
+                // arrived, not 8 rows ahead of it (that would hold 8 x 16 more registers; the kernel stays below 96)
+                int row = b + bb;
+                asm volatile("" : "+s"(row) : "v"(f[bb]));
+#pragma unroll
+                for (int jq = 0; jq < 4; ++jq) {
+                    const f32x4 d4 = *reinterpret_cast<const f32x4*>(&dus[row][jq * 4]);
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) a[jq * 4 + e] = __builtin_fmaf(d4[e], f[bb], a[jq * 4 + e]);      // (fused whatever the unrolling)
+                }
+            }
+        }
+        for (; b < B; ++b) {                                        // the last B % 8 rows
             const float f = p.A6[(long)b * FC_H + src];
 #pragma unroll
             for (int jq = 0; jq < 4; ++jq) {
                 const f32x4 d4 = *reinterpret_cast<const f32x4*>(&dus[b][jq * 4]);
 #pragma unroll
-                for (int e = 0; e < 4; ++e) a[jq * 4 + e] += d4[e] * f;
+                for (int e = 0; e < 4; ++e) a[jq * 4 + e] = __builtin_fmaf(d4[e], f, a[jq * 4 + e]);
             }
         }
 #pragma unroll
@@ -701,17 +731,18 @@ __global__ __launch_bounds__(512, 5) void stn_fc_bwd_kernel(SnFcBwdP p) {
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
         const int jb = wave * 64 + 16 * u + 4 * q;
-        float bw[4];
+        u32x4_t raw[4];                                             // the round's dU quads are requested before its MFMAs
 #pragma unroll
-        for (int v = 0; v < 4; ++v) bw[v] = p.W1[(long)(jb + v) * FC_H + 16 * g + i];
+        for (int mt = 0; mt < 4; ++mt) {
+            raw[mt] = (u32x4_t){0u, 0u, 0u, 0u};
+            if (mt < MT) raw[mt] = ld16_sc1(p.dU, (min(mt * 16 + i, B - 1) * FC_H + jb) * 4);
+        }
 #pragma unroll
         for (int mt = 0; mt < 4; ++mt) {
             if (mt >= MT) break;
-            const int b = min(mt * 16 + i, B - 1);
-            const u32x4_t raw = ld16_sc1(p.dU, (b * FC_H + jb) * 4);
-            const f32x4 a4 = *reinterpret_cast<const f32x4*>(&raw);
+            const f32x4 a4 = *reinterpret_cast<const f32x4*>(&raw[mt]);
 #pragma unroll
-            for (int v = 0; v < 4; ++v) acc[mt] = __builtin_amdgcn_mfma_f32_16x16x4f32(a4[v], bw[v], acc[mt], 0, 0, 0);
+            for (int v = 0; v < 4; ++v) acc[mt] = __builtin_amdgcn_mfma_f32_16x16x4f32(a4[v], bw[u][v], acc[mt], 0, 0, 0);
         }
     }
     {

@@ -2177,8 +2177,9 @@ class ImageLossFn(Function):
         assert hr.shape == sr.shape
         per = ops.new(sr, B)
         mean = ops.new(sr, 1) if scale is not None else None
+        ws = torch.empty(B * 32, dtype=torch.float64, device=sr.device)      # the 16 wave sums (squared error, gradient prior) per image
         ops.call("tatt_image_loss_fwd", ops.P(sr), *sr.stride(), ops.P(hr), *hr.stride(), ops.P(per), ops.P(mean),
-                 0.0 if scale is None else float(scale), B, C, H, W, w0, w1, ops.stream())
+                 0.0 if scale is None else float(scale), ops.P(ws), B, C, H, W, w0, w1, ops.stream())
         ctx.save_for_backward(sr, hr)
         ctx.cfg = (w0, w1, scale)
         return per if scale is None else mean.reshape(())
