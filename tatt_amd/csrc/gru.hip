@@ -10,7 +10,7 @@
 //     (reference InfoTransformer.forward, model/transformer_v2.py:201-221).  One launch
 //     per time step: h W_hh^T on v_mfma_f32_16x16x4_f32 with K split over the 4 waves of a work-group
 //     and the gate math fused in the epilogue.
-#include "common.h"
+#include "handoff.h"
 
 struct SeqGeom {
     int nseq, T, s_in;
@@ -887,16 +887,12 @@ TATT_API int tatt_qgru_bwd_fused(const float* dgh_cur0, const float* dgh_cur1, c
 // dgh (this step's recurrent-side gate gradients): a tile's contraction needs the 16 x 3*HID rows its ROW BLOCK's HID/16 work-groups
 // produced one step earlier -- so synchronisation is per (row block, direction) GROUP of HID/16 members, not grid-wide.  Block b is
 // member b / NG of group b % NG: with NG = 8 groups (W = 64) a group's members are the blocks HIP places on ONE XCD (observed
-// placement b % 8, MI355X_MICROARCH.md) -- a speed bonus only; correctness uses the agent-scope forms of that guide:
-//   producer: 16-byte `sc1` (write-through) stores of its dgh tile -> s_waitcnt vmcnt(0) -> barrier -> ONE `sc1` flag store
-//             (flags[group][member] = number of steps published);
-//   consumer: wave 0 polls the group's flags (one 4-byte `sc1` load per lane = per member) -> barrier -> `sc1` loads of the rows.
-// Every spin is bounded by the wall clock: on expiry the kernel raises flags[QCH_ERR] and runs on without waiting (results are then
-// garbage but the launch ends); tatt_qgru_bwd_chain's caller reads the word when it next synchronises.
+// placement b % 8, MI355X_MICROARCH.md) -- a speed bonus only; correctness is the hand-off of handoff.h, with
+// flags[group * 64 + member] = number of steps published, the dgh tile stored (and drained) by threads 0..191 only, error word
+// flags[QCH_ERR] and sticky code TATT_STICKY_QGRU; tatt_qgru_bwd_chain's caller reads the word when it next synchronises.
 // Residency: the NG * HID/16 <= 256 work-groups must be co-resident (one per CU at 512 threads / <= 128 VGPRs leaves room beside it).
 // ------------------------------------------------------------------------------------------------
 #define QCH_ERR 1023                       // index of the error word in the sync buffer (1024 words)
-#define QCH_SPIN_TICKS 200000000L          // 2 s of the 100 MHz wall clock: far beyond any stall another launch (a collective waiting for a late rank) can cause
 struct QChainP {
     float* dgh[2]; const float* whhT[2]; const float* dhseq[2]; const float* gsave[2]; const float* hbuf[2];
     float* dhcarry[2]; float* dgi_acc[2];
@@ -905,7 +901,6 @@ struct QChainP {
     float* xch[2];      // SB: the exchanged tensor in matrix-core operand form, (T, Wb, 3*HID / 8) x {8 bf16 hi, 8 bf16 lo}
     unsigned* sticky;   // the device's sticky error word (common.h), may be null
 };
-typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
 typedef __bf16 qc_bf16x8 __attribute__((ext_vector_type(8)));
 __device__ __forceinline__ void qc_split8(const float* v, qc_bf16x8& hi, qc_bf16x8& lo) {
     hi = __builtin_bit_cast(qc_bf16x8, gr_split8(v, false));
@@ -989,20 +984,7 @@ __global__ __launch_bounds__(512) void qgru_bwd_chain_kernel(QChainP p) {
             hp = p.hbuf[d][(long)(d ? nxt + 1 : nxt) * plane + e];
         }
         if (s > p.s0) {                                                         // the group's members have published step s-1
-            if (wave == 0 && !s_dead) {
-                const long t0 = wall_clock64();
-                int it = 0;
-                for (;;) {
-                    const unsigned f = lane < NM ? __hip_atomic_load(flags + lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0xffffffffu;
-                    if (__builtin_amdgcn_ballot_w64(f < (unsigned)s) == 0) break;
-                    __builtin_amdgcn_s_sleep(1);
-                    if ((++it & 63) == 0 && wall_clock64() - t0 > QCH_SPIN_TICKS) {
-                        if (lane == 0) { s_dead = 1; __hip_atomic_store(p.flags + QCH_ERR, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); tatt_raise_sticky(p.sticky, TATT_STICKY_QGRU); }
-                        break;
-                    }
-                }
-            }
-            __syncthreads();
+            HANDOFF_WAIT(wave == 0, lane, 1, flags, NM, (unsigned)s, s_dead, p.flags + QCH_ERR, p.sticky, TATT_STICKY_QGRU)
         }
         f32x4 acc0 = (f32x4){0.f, 0.f, 0.f, 0.f}, acc1 = acc0;
         if constexpr (SB) {
@@ -1024,12 +1006,12 @@ __global__ __launch_bounds__(512) void qgru_bwd_chain_kernel(QChainP p) {
                     qc_split8(v, ah[tt], al[tt]);
                 }
             } else {
-                const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(p.xch[d] + (long)cur * p.Wb * K, 0, p.Wb * K * 4, 0x00020000);
+                const float* src = p.xch[d] + (long)cur * p.Wb * K;
                 const int off = (m0 + i) * K * 4 + (wave * 24 + q) * 32;
 #pragma unroll
                 for (int tt = 0; tt < 6; ++tt) {
-                    ah[tt] = __builtin_bit_cast(qc_bf16x8, __builtin_amdgcn_raw_buffer_load_b128(rs, off + 128 * tt, 0, 16 /* sc1 */));
-                    al[tt] = __builtin_bit_cast(qc_bf16x8, __builtin_amdgcn_raw_buffer_load_b128(rs, off + 128 * tt + 16, 0, 16 /* sc1 */));
+                    ah[tt] = __builtin_bit_cast(qc_bf16x8, ld16_sc1(src, p.Wb * K * 4, off + 128 * tt));
+                    al[tt] = __builtin_bit_cast(qc_bf16x8, ld16_sc1(src, p.Wb * K * 4, off + 128 * tt + 16));
                 }
             }
             __builtin_amdgcn_sched_barrier(0);
@@ -1040,12 +1022,9 @@ __global__ __launch_bounds__(512) void qgru_bwd_chain_kernel(QChainP p) {
             }
         } else {
             f32x4 a[KS];
-            {
-                const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(p.dgh[d] + (long)cur * p.Wb * K, 0, p.Wb * K * 4, 0x00020000);
+            const float* src = p.dgh[d] + (long)cur * p.Wb * K;
 #pragma unroll
-                for (int u = 0; u < KS; ++u)
-                    a[u] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, a_off + 64 * u, 0, 16 /* sc1 */));
-            }
+            for (int u = 0; u < KS; ++u) a[u] = __builtin_bit_cast(f32x4, ld16_sc1(src, p.Wb * K * 4, a_off + 64 * u));
             __builtin_amdgcn_sched_barrier(0);                                  // all twelve loads in flight before the first MFMA
 #pragma unroll
             for (int u = 0; u < KS; ++u)
@@ -1088,18 +1067,17 @@ __global__ __launch_bounds__(512) void qgru_bwd_chain_kernel(QChainP p) {
             if constexpr (SB) {
                 const int row = t / 12, gate = (t % 12) >> 2, grp8 = (t >> 1) & 1, hl = t & 1;
                 const u32x4_t v = *reinterpret_cast<const u32x4_t*>(hl ? &stage_l[row][gate][grp8 * 8] : &stage_h[row][gate][grp8 * 8]);
-                const __amdgpu_buffer_rsrc_t ws = __builtin_amdgcn_make_buffer_rsrc(p.xch[d] + (long)nxt * p.Wb * K, 0, p.Wb * K * 4, 0x00020000);
-                __builtin_amdgcn_raw_buffer_store_b128(v, ws, (m0 + row) * K * 4 + ((gate * HID + j0) / 8 + grp8) * 32 + hl * 16, 0, 16 /* sc1 */);
+                float* dst = p.xch[d] + (long)nxt * p.Wb * K;
+                st16_sc1(dst, p.Wb * K * 4, (m0 + row) * K * 4 + ((gate * HID + j0) / 8 + grp8) * 32 + hl * 16, &v);
             } else {
                 const int row = t / 12, gate = (t % 12) >> 2, j4 = (t & 3) * 4;
                 const f32x4 v = *reinterpret_cast<const f32x4*>(&stage[row][gate][j4]);
-                const __amdgpu_buffer_rsrc_t ws = __builtin_amdgcn_make_buffer_rsrc(p.dgh[d] + (long)nxt * p.Wb * K, 0, p.Wb * K * 4, 0x00020000);
-                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4_t, v), ws, ((m0 + row) * K + gate * HID + j0 + j4) * 4, 0, 16 /* sc1 */);
+                float* dst = p.dgh[d] + (long)nxt * p.Wb * K;
+                st16_sc1(dst, p.Wb * K * 4, ((m0 + row) * K + gate * HID + j0 + j4) * 4, &v);
             }
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            handoff_drain();                                                    // the storing waves only: the others' prefetched loads stay in flight
         }
-        __syncthreads();
-        if (t == 0) __hip_atomic_store(flags + mem, (unsigned)(s + 1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        handoff_post(flags + mem, (unsigned)(s + 1));
     }
     if (t < 256) { p.dhcarry[d][e] = dhc; p.dgi_acc[d][g3] = ga0; p.dgi_acc[d][g3 + HID] = ga1; p.dgi_acc[d][g3 + 2 * HID] = ga2; }
 }
@@ -1229,26 +1207,14 @@ __global__ __launch_bounds__(512) void qgru_fwd_chain_kernel(QFChainP p) {
     for (int s = p.s0; s < p.s1; ++s) {
         const int slot_prev = d ? p.T - s : s, slot_new = d ? p.T - 1 - s : s + 1, tcur = d ? p.T - 1 - s : s;
         if (s > p.s0) {
-            if (wave == 0 && !s_dead) {
-                const long t0 = wall_clock64();
-                int it = 0;
-                for (;;) {
-                    const unsigned f = lane < NM ? __hip_atomic_load(flags + lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0xffffffffu;
-                    if (__builtin_amdgcn_ballot_w64(f < (unsigned)s) == 0) break;
-                    __builtin_amdgcn_s_sleep(1);
-                    if ((++it & 63) == 0 && wall_clock64() - t0 > QCH_SPIN_TICKS) {
-                        if (lane == 0) { s_dead = 1; __hip_atomic_store(p.flags + QCH_ERR, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); tatt_raise_sticky(p.sticky, TATT_STICKY_QGRU); }
-                        break;
-                    }
-                }
-            }
-            __syncthreads();
+            HANDOFF_WAIT(wave == 0, lane, 1, flags, NM, (unsigned)s, s_dead, p.flags + QCH_ERR, p.sticky, TATT_STICKY_QGRU)
         }
         f32x4 acc[3];
 #pragma unroll
         for (int g = 0; g < 3; ++g) acc[g] = (f32x4){0.f, 0.f, 0.f, 0.f};
         if constexpr (SB) {
             if (s > 0) {                                                        // (h_prev of the first time step is zero: nothing to add)
+                // (ld16_sc1 written out: through the helper two instructions of this kernel's prologue change places)
                 const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(p.xch[d] + (long)slot_prev * plane, 0, p.Wb * HID * 4, 0x00020000);
                 const int off = (m0 + i) * HID * 4 + (wave * 8 + q) * 32;
                 qc_bf16x8 ah[2], al[2];
@@ -1265,12 +1231,9 @@ __global__ __launch_bounds__(512) void qgru_fwd_chain_kernel(QFChainP p) {
             }
         } else {
             f32x4 a[4];
-            {
-                const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(p.hbuf[d] + (long)slot_prev * plane, 0, p.Wb * HID * 4, 0x00020000);
+            const float* src = p.hbuf[d] + (long)slot_prev * plane;
 #pragma unroll
-                for (int u = 0; u < 4; ++u)
-                    a[u] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, a_off + 64 * u, 0, 16 /* sc1 */));
-            }
+            for (int u = 0; u < 4; ++u) a[u] = __builtin_bit_cast(f32x4, ld16_sc1(src, p.Wb * HID * 4, a_off + 64 * u));
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
             for (int u = 0; u < 4; ++u)
@@ -1317,18 +1280,17 @@ __global__ __launch_bounds__(512) void qgru_fwd_chain_kernel(QFChainP p) {
             if constexpr (SB) {
                 const int row = t >> 2, grp8 = (t >> 1) & 1, hl = t & 1;
                 const u32x4_t v = *reinterpret_cast<const u32x4_t*>(hl ? &stage_l[row][grp8 * 8] : &stage_h[row][grp8 * 8]);
-                const __amdgpu_buffer_rsrc_t ws = __builtin_amdgcn_make_buffer_rsrc(p.xch[d] + (long)slot_new * plane, 0, p.Wb * HID * 4, 0x00020000);
-                __builtin_amdgcn_raw_buffer_store_b128(v, ws, (m0 + row) * HID * 4 + (j0 / 8 + grp8) * 32 + hl * 16, 0, 16 /* sc1 */);
+                float* dst = p.xch[d] + (long)slot_new * plane;
+                st16_sc1(dst, p.Wb * HID * 4, (m0 + row) * HID * 4 + (j0 / 8 + grp8) * 32 + hl * 16, &v);
             } else {
                 const int row = t >> 2, j4 = (t & 3) * 4;
                 const f32x4 v = *reinterpret_cast<const f32x4*>(&stage[row][j4]);
-                const __amdgpu_buffer_rsrc_t ws = __builtin_amdgcn_make_buffer_rsrc(p.hbuf[d] + (long)slot_new * plane, 0, p.Wb * HID * 4, 0x00020000);
-                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4_t, v), ws, ((m0 + row) * HID + j0 + j4) * 4, 0, 16 /* sc1 */);
+                float* dst = p.hbuf[d] + (long)slot_new * plane;
+                st16_sc1(dst, p.Wb * HID * 4, ((m0 + row) * HID + j0 + j4) * 4, &v);
             }
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            handoff_drain();                                                    // the storing waves only: the others' prefetched loads stay in flight
         }
-        __syncthreads();
-        if (t == 0) __hip_atomic_store(flags + mem, (unsigned)(s + 1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        handoff_post(flags + mem, (unsigned)(s + 1));
     }
 }
 // gi* (Wb, 3*HID) incl. b_ih -- or NULL with x (Wb, IN), wih* (3*HID, IN), bih*: the projection is then computed by the launch itself

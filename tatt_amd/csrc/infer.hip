@@ -1,7 +1,7 @@
 // Eval-only kernels of the inference session (tatt_amd/infer.py): the CRNN's bidirectional LSTM layer as one launch, eval BatchNorm
 // folded into the preceding convolution, greedy CTC decoding compared with the labels on the device, and the attention recognisers' id
 // sequences scored against the same labels (tatt_amd/recog.py).
-#include "common.h"
+#include "handoff.h"
 
 // ------------------------------------------------------------------------------------------------
 // One bidirectional LSTM layer, forward only, all T steps in ONE launch (H = 256).
@@ -13,15 +13,12 @@
 // writes nothing but `out` (no cell sequence, no gate saves: there is no backward).
 //
 // What crosses work-groups per step is h_{t-1}: a tile's contraction reads the 16 rows x 256 units its (row block, direction) GROUP
-// of 16 members produced one step earlier.  Hand-off as in qgru_fwd_chain_kernel (gru.hip): the producer writes its h tile with
-// 16-byte `sc1` (write-through) stores -> s_waitcnt vmcnt(0) -> barrier -> ONE relaxed agent-scope flag store (flags[group][member] =
-// steps published); the consumer's wave 0 polls the group's 16 flags -> barrier -> `sc1` loads of the rows.  Every spin is bounded
-// by the wall clock: on expiry the launch raises flags[LCH_ERR] and the device's sticky word (TATT_STICKY_LSTM) and runs on.
-// No grid-wide barrier: only the members of one group wait on one another.  Residency: the whole grid (cdiv(Bt,16) x 16 x 2 <= 256
-// work-groups of 256 threads) must be co-resident -- tatt_lstm_fwd_chain refuses larger grids (the caller takes the step kernels).
+// of 16 members produced one step earlier.  The hand-off is the protocol of handoff.h: flags[group * 64 + member] = steps published,
+// only wave 0 stores (and drains), and only the members of one group wait on one another -- no grid-wide barrier.
+// Error word flags[LCH_ERR], sticky code TATT_STICKY_LSTM.  Residency: the whole grid (cdiv(Bt,16) x 16 x 2 <= 256 work-groups of 256
+// threads) must be co-resident -- tatt_lstm_fwd_chain refuses larger grids (the caller takes the step kernels).
 // ------------------------------------------------------------------------------------------------
 #define LCH_ERR 1023                       // index of the error word in the sync buffer (1024 words)
-#define LCH_SPIN_TICKS 200000000L          // 2 s of the 100 MHz wall clock
 #define LCH_H 256
 struct LstmChainP {
     const float* gi;            // (T, Bt, 8H): [dir][gate][H] along the last axis, b_ih included
@@ -32,7 +29,6 @@ struct LstmChainP {
     unsigned* sticky;           // the device's sticky error word (common.h), may be null
     int T, Bt;
 };
-typedef unsigned lch_u32x4 __attribute__((ext_vector_type(4)));
 __global__ __launch_bounds__(256) void lstm_fwd_chain_kernel(LstmChainP p) {
     constexpr int H = LCH_H;
     __shared__ float red[4][4][16][17];
@@ -69,32 +65,12 @@ __global__ __launch_bounds__(256) void lstm_fwd_chain_kernel(LstmChainP p) {
 #pragma unroll
         for (int g = 0; g < 4; ++g) acc[g] = (f32x4){0.f, 0.f, 0.f, 0.f};
         if (s > 0) {
-            if (wave == 0 && !s_dead) {
-                const long t0 = wall_clock64();
-                int it = 0;
-                for (;;) {
-                    const unsigned f = lane < 16 ? __hip_atomic_load(flags + lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0xffffffffu;
-                    if (__builtin_amdgcn_ballot_w64(f < (unsigned)s) == 0) break;
-                    __builtin_amdgcn_s_sleep(1);
-                    if ((++it & 63) == 0 && wall_clock64() - t0 > LCH_SPIN_TICKS) {
-                        if (lane == 0) {
-                            s_dead = 1;
-                            __hip_atomic_store(p.flags + LCH_ERR, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                            tatt_raise_sticky(p.sticky, TATT_STICKY_LSTM);
-                        }
-                        break;
-                    }
-                }
-            }
-            __syncthreads();
+            HANDOFF_WAIT(wave == 0, lane, 1, flags, 16, (unsigned)s, s_dead, p.flags + LCH_ERR, p.sticky, TATT_STICKY_LSTM)
             f32x4 a[4];
-            {
-                const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(p.out + (long)tp * plane, 0, (int)(plane * 4), 0x00020000);
-                const int off = (arow * 2 * H + d * H + kb + 4 * q) * 4;
+            const int off = (arow * 2 * H + d * H + kb + 4 * q) * 4;
 #pragma unroll
-                for (int ss = 0; ss < 4; ++ss)
-                    a[ss] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, off + 64 * ss, 0, 16 /* sc1 */));
-            }
+            for (int ss = 0; ss < 4; ++ss)
+                a[ss] = __builtin_bit_cast(f32x4, ld16_sc1(p.out + (long)tp * plane, (int)(plane * 4), off + 64 * ss));
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
             for (int ss = 0; ss < 4; ++ss)
@@ -127,13 +103,11 @@ __global__ __launch_bounds__(256) void lstm_fwd_chain_kernel(LstmChainP p) {
             const int r = t >> 2, j4 = (t & 3) * 4;
             if (m0 + r < Bt) {
                 const f32x4 v = *reinterpret_cast<const f32x4*>(&stage[r][j4]);
-                const __amdgpu_buffer_rsrc_t ws = __builtin_amdgcn_make_buffer_rsrc(p.out + (long)tt * plane, 0, (int)(plane * 4), 0x00020000);
-                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(lch_u32x4, v), ws, ((m0 + r) * 2 * H + d * H + j0 + j4) * 4, 0, 16 /* sc1 */);
+                st16_sc1(p.out + (long)tt * plane, (int)(plane * 4), ((m0 + r) * 2 * H + d * H + j0 + j4) * 4, &v);
             }
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            handoff_drain();                                         // the storing wave only
         }
-        __syncthreads();
-        if (t == 0) __hip_atomic_store(flags + mem, (unsigned)(s + 1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        handoff_post(flags + mem, (unsigned)(s + 1));
     }
 }
 

@@ -9,57 +9,28 @@
 //   stn_fc_bwd_kernel        the backward of that, every parameter gradient included
 //
 // A BatchNorm is a reduction over the whole map between two passes over it -- the reason the operator chain needs 3-4 launches per
-// layer.  These kernels keep it inside one launch: the G <= 128 work-groups of a launch publish partial sums with write-through (sc1)
-// stores, raise a flag word each, and wait for the others' flags (the agent-scope hand-off forms of MI355X_MICROARCH.md, validated on
-// this chip by the persistent query-GRU launches in gru.hip); every work-group then reduces the G partials in the same fixed order, so
-// all of them -- and every run -- compute bit-identical statistics.  Flags are epoch-stamped: a site's 256-word sync buffer is zeroed
-// once when it is allocated and reused by every later launch of that site (word 254 = epoch, word 255 = error); launches of one site
-// must not overlap (they are issued on one stream).  Spins are bounded by the wall clock: on expiry word 63 is raised and the launch
-// runs on (results invalid, reported by the host when it next synchronises).
-#include "common.h"
+// layer.  These kernels keep it inside one launch: the G <= 128 work-groups of a launch hand their partial sums to one another (the
+// protocol of handoff.h: what crosses work-groups is the partials, one flag word per work-group, and EVERY work-group waits for ALL
+// of them); every work-group then reduces the G partials in the same fixed order, so all of them -- and every run -- compute
+// bit-identical statistics.  Flags are epoch-stamped: a site's 256-word sync buffer is zeroed once when it is allocated and reused by
+// every later launch of that site (word 254 = epoch, word 255 = error; a phase's flag value is epoch * 4 + phase, compared wrap-safe);
+// launches of one site must not overlap (they are issued on one stream).
+#include "handoff.h"
 
-typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
 #define SN_WORDS 256                      // words of a site's sync buffer: flags 0 .. SN_MAXG-1, epoch, error
 #define SN_EPOCH 254
 #define SN_ERR 255
-#define SN_SPIN_TICKS 200000000L          // 2 s of the 100 MHz wall clock
 #define SN_MAXG 128
 #define SN_MAXW 4                         // pool windows per thread (they stay in registers between the two passes over the map)
+#define SN_ANY 0x7ffffff0                 // descriptor range of st16_sc1 / ld16_sc1 here (offsets are in range by construction)
 
-// 16-byte write-through store / L1-bypassing load at base + off bytes (base wave-uniform: the descriptor stays in SGPRs)
-__device__ __forceinline__ void st16_sc1(void* base, int off, const void* v16) {
-    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(base, 0, 0x7ffffff0, 0x00020000);
-    __builtin_amdgcn_raw_buffer_store_b128(*reinterpret_cast<const u32x4_t*>(v16), rs, off, 0, 16 /* sc1: write-through */);
-}
-__device__ __forceinline__ u32x4_t ld16_sc1(const void* base, int off) {
-    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, 0x7ffffff0, 0x00020000);
-    return __builtin_amdgcn_raw_buffer_load_b128(rs, off, 0, 16 /* sc1: not from this CU's L1 */);
-}
-
-// all of this launch's work-groups have published phase `phase` (1, 2, 3): called by every thread, ends with a barrier.
-// Publishing = stores (sc1) -> s_waitcnt vmcnt(0) -> barrier -> thread 0 raises the flag.
+// a launch's work-group g has published phase value `val` / all G work-groups have (handoff.h; every thread drains here: all store)
 __device__ __forceinline__ void sn_publish(unsigned* sync, int g, unsigned val) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (threadIdx.x == 0) __hip_atomic_store(sync + g, val, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    handoff_drain();
+    handoff_post(sync + g, val);
 }
 __device__ __forceinline__ void sn_wait(unsigned* sync, int G, unsigned val, int* s_dead, unsigned* sticky) {
-    if (threadIdx.x < 64 && !*s_dead) {
-        const int lane = threadIdx.x;
-        const long t0 = wall_clock64();
-        int it = 0;
-        for (;;) {
-            const unsigned f0 = lane < G ? __hip_atomic_load(sync + lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : val;
-            const unsigned f1 = lane + 64 < G ? __hip_atomic_load(sync + lane + 64, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : val;
-            if (__builtin_amdgcn_ballot_w64((int)(f0 - val) < 0 || (int)(f1 - val) < 0) == 0) break;
-            __builtin_amdgcn_s_sleep(1);
-            if ((++it & 63) == 0 && wall_clock64() - t0 > SN_SPIN_TICKS) {
-                if (lane == 0) { *s_dead = 1; __hip_atomic_store(sync + SN_ERR, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); tatt_raise_sticky(sticky, TATT_STICKY_STN); }
-                break;
-            }
-        }
-    }
-    __syncthreads();
+    HANDOFF_WAIT(threadIdx.x < 64, (int)threadIdx.x, 2, sync, G, val, *s_dead, sync + SN_ERR, sticky, TATT_STICKY_STN)
 }
 
 struct SnGeom { int B, H, W, C, G; };   // (B, H, W, C) map split over G work-groups
@@ -168,10 +139,10 @@ __global__ __launch_bounds__(256) void stn_bn_pool_fwd_kernel(SnFwdP p) {
     if (rl == 0) {
         const int d = (g * 2 * C + cq * 4) * 8;
         double v[2];
-        v[0] = acc[0]; v[1] = acc[1]; st16_sc1(p.part, d, v);
-        v[0] = acc[2]; v[1] = acc[3]; st16_sc1(p.part, d + 16, v);
-        v[0] = acc[4]; v[1] = acc[5]; st16_sc1(p.part, d + C * 8, v);
-        v[0] = acc[6]; v[1] = acc[7]; st16_sc1(p.part, d + C * 8 + 16, v);
+        v[0] = acc[0]; v[1] = acc[1]; st16_sc1(p.part, SN_ANY, d, v);
+        v[0] = acc[2]; v[1] = acc[3]; st16_sc1(p.part, SN_ANY, d + 16, v);
+        v[0] = acc[4]; v[1] = acc[5]; st16_sc1(p.part, SN_ANY, d + C * 8, v);
+        v[0] = acc[6]; v[1] = acc[7]; st16_sc1(p.part, SN_ANY, d + C * 8 + 16, v);
     }
     sn_publish(p.sync, g, ep * 4 + 1);
     sn_wait(p.sync, G, ep * 4 + 1, &s_dead, p.sticky);
@@ -184,8 +155,8 @@ __global__ __launch_bounds__(256) void stn_bn_pool_fwd_kernel(SnFwdP p) {
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
             const int gg = min(g0 + u * RL, G - 1), d = (gg * 2 * C + cq * 4) * 8;
-            raw[u][0] = ld16_sc1(p.part, d); raw[u][1] = ld16_sc1(p.part, d + 16);
-            raw[u][2] = ld16_sc1(p.part, d + C * 8); raw[u][3] = ld16_sc1(p.part, d + C * 8 + 16);
+            raw[u][0] = ld16_sc1(p.part, SN_ANY, d); raw[u][1] = ld16_sc1(p.part, SN_ANY, d + 16);
+            raw[u][2] = ld16_sc1(p.part, SN_ANY, d + C * 8); raw[u][3] = ld16_sc1(p.part, SN_ANY, d + C * 8 + 16);
         }
 #pragma unroll
         for (int u = 0; u < 4; ++u)
@@ -348,10 +319,10 @@ __global__ __launch_bounds__(256) void stn_bn_pool_bwd_kernel(SnBwdP p) {
     if (rl == 0) {
         const int d = (g * 3 * C + cq * 4) * 8;
         double v[2];
-        v[0] = acc[0]; v[1] = acc[1]; st16_sc1(p.part, d, v);
-        v[0] = acc[2]; v[1] = acc[3]; st16_sc1(p.part, d + 16, v);
-        v[0] = acc[4]; v[1] = acc[5]; st16_sc1(p.part, d + C * 8, v);
-        v[0] = acc[6]; v[1] = acc[7]; st16_sc1(p.part, d + C * 8 + 16, v);
+        v[0] = acc[0]; v[1] = acc[1]; st16_sc1(p.part, SN_ANY, d, v);
+        v[0] = acc[2]; v[1] = acc[3]; st16_sc1(p.part, SN_ANY, d + 16, v);
+        v[0] = acc[4]; v[1] = acc[5]; st16_sc1(p.part, SN_ANY, d + C * 8, v);
+        v[0] = acc[6]; v[1] = acc[7]; st16_sc1(p.part, SN_ANY, d + C * 8 + 16, v);
     }
     sn_publish(p.sync, g, ep * 4 + 1);
     sn_wait(p.sync, G, ep * 4 + 1, &s_dead, p.sticky);
@@ -363,8 +334,8 @@ __global__ __launch_bounds__(256) void stn_bn_pool_bwd_kernel(SnBwdP p) {
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
             const int gg = min(g0 + u * RL, G - 1), d = (gg * 3 * C + cq * 4) * 8;
-            raw[u][0] = ld16_sc1(p.part, d); raw[u][1] = ld16_sc1(p.part, d + 16);
-            raw[u][2] = ld16_sc1(p.part, d + C * 8); raw[u][3] = ld16_sc1(p.part, d + C * 8 + 16);
+            raw[u][0] = ld16_sc1(p.part, SN_ANY, d); raw[u][1] = ld16_sc1(p.part, SN_ANY, d + 16);
+            raw[u][2] = ld16_sc1(p.part, SN_ANY, d + C * 8); raw[u][3] = ld16_sc1(p.part, SN_ANY, d + C * 8 + 16);
         }
 #pragma unroll
         for (int u = 0; u < 4; ++u)
@@ -405,8 +376,8 @@ __global__ __launch_bounds__(256) void stn_bn_pool_bwd_kernel(SnBwdP p) {
     if (rl == 0) {
         const int d = (g * 3 * C + 2 * C + cq * 4) * 8;
         double v[2];
-        v[0] = cs[0]; v[1] = cs[1]; st16_sc1(p.part, d, v);
-        v[0] = cs[2]; v[1] = cs[3]; st16_sc1(p.part, d + 16, v);
+        v[0] = cs[0]; v[1] = cs[1]; st16_sc1(p.part, SN_ANY, d, v);
+        v[0] = cs[2]; v[1] = cs[3]; st16_sc1(p.part, SN_ANY, d + 16, v);
     }
     sn_publish(p.sync, g, ep * 4 + 2);
     if (g != 0) return;
@@ -414,7 +385,7 @@ __global__ __launch_bounds__(256) void stn_bn_pool_bwd_kernel(SnBwdP p) {
     double s[4] = {0, 0, 0, 0};
     for (int gg = rl; gg < G; gg += RL) {
         const int d = (gg * 3 * C + 2 * C + cq * 4) * 8;
-        const u32x4_t r0 = ld16_sc1(p.part, d), r1 = ld16_sc1(p.part, d + 16);
+        const u32x4_t r0 = ld16_sc1(p.part, SN_ANY, d), r1 = ld16_sc1(p.part, SN_ANY, d + 16);
         const double* d0 = reinterpret_cast<const double*>(&r0); const double* d1 = reinterpret_cast<const double*>(&r1);
         s[0] += d0[0]; s[1] += d0[1]; s[2] += d1[0]; s[3] += d1[1];
     }
@@ -556,7 +527,7 @@ __global__ __launch_bounds__(512) void stn_fc_fwd_kernel(SnFcFwdP p) {
 #pragma unroll
             for (int e = 0; e < 4; ++e) r[e] += sv * w2s[o + e][jj];
         }
-        st16_sc1(p.part, ((g * B * NO) + idx * 4) * 4, &r);
+        st16_sc1(p.part, SN_ANY, ((g * B * NO) + idx * 4) * 4, &r);
     }
     sn_publish(p.sync, g, ep * 4 + 1);
     if (g != 0) return;
@@ -566,7 +537,7 @@ __global__ __launch_bounds__(512) void stn_fc_fwd_kernel(SnFcFwdP p) {
         const int o = (idx * 4) % NO;
         f32x4 r = *reinterpret_cast<const f32x4*>(p.b2 + o);
         for (int gg = 0; gg < 32; ++gg) {
-            const u32x4_t raw = ld16_sc1(p.part, ((gg * B * NO) + idx * 4) * 4);
+            const u32x4_t raw = ld16_sc1(p.part, SN_ANY, ((gg * B * NO) + idx * 4) * 4);
             r += *reinterpret_cast<const f32x4*>(&raw);
         }
         *reinterpret_cast<f32x4*>(p.ctrl + idx * 4) = r;
@@ -664,7 +635,7 @@ __global__ __launch_bounds__(512, 5) void stn_fc_bwd_kernel(SnFcBwdP p) {
     }
     if (t < B * 4) {                                                // dU rows of this work-group: 16 floats = 4 x 16 bytes per sample
         const int b = t >> 2, c4 = (t & 3) * 4;
-        st16_sc1(p.dU, (b * FC_H + j0 + c4) * 4, &dus[b][c4]);
+        st16_sc1(p.dU, SN_ANY, (b * FC_H + j0 + c4) * 4, &dus[b][c4]);
     }
     sn_publish(p.sync, g, ep * 4 + 1);
     // phase B's W1 fragments depend on parameters alone: requested here, they travel under the parameter gradients and the wait
@@ -735,7 +706,7 @@ __global__ __launch_bounds__(512, 5) void stn_fc_bwd_kernel(SnFcBwdP p) {
 #pragma unroll
         for (int mt = 0; mt < 4; ++mt) {
             raw[mt] = (u32x4_t){0u, 0u, 0u, 0u};
-            if (mt < MT) raw[mt] = ld16_sc1(p.dU, (min(mt * 16 + i, B - 1) * FC_H + jb) * 4);
+            if (mt < MT) raw[mt] = ld16_sc1(p.dU, SN_ANY, (min(mt * 16 + i, B - 1) * FC_H + jb) * 4);
         }
 #pragma unroll
         for (int mt = 0; mt < 4; ++mt) {

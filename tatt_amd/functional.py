@@ -1479,19 +1479,27 @@ class TPStackFn(Function):
 
 # --------------------------------------------------------------------------------------------------
 # Query GRU recurrences as persistent launches (tatt_qgru_fwd_chain / tatt_qgru_bwd_chain) instead of one launch per time step.  Every spin in them is bounded
-# by the wall clock; qgru_chain_check() reads the error words of the most recent launches (synchronises: call it outside a capture).
+# by the wall clock (csrc/handoff.h); qgru_chain_check() reads the error words of the most recent launches (synchronises: call it outside a capture).
 QGRU_CHAIN_FWD = True
 QGRU_CHAIN_BWD = True
 # their recurrent products on the bf16 matrix cores with split operands (hi hi + hi lo + lo hi, fp32 accumulation) instead of fp32 MFMA:
 # the fp32 form takes a third of the chip's fp32 matrix throughput while the chain runs and slows the lane beside it
 QGRU_CHAIN_SB = True
 QGRU_WGRAD_SB = True            # the recurrent weight gradient (dgh^T h_prev over all steps) in split bf16 too (tatt_qgru_wgrad_sb)
-QGRU_CHAIN_SYNC = []
 
 
 # ---- residency and the sticky error word of the launches that synchronise their work-groups in flight --------------------------------
-_CAPACITY = {}           # device index -> (query-GRU chain capacities x4, STN map launches, STN fully connected launches)
+_CAPACITY = {}           # device index -> (query-GRU chain capacities x4, STN map launches, STN fully connected launches, LSTM chain)
 _STICKY = {}             # device index -> the device's sticky error word (int32 x 4; word 0 is registered with the library)
+# The sync buffers handed to those launches, ONE list: (reference to the buffer: a callable -> the tensor or None, index of its error
+# word, the name sync_check's message uses).  The lifetimes differ for a reason.  A query-GRU buffer is allocated per launch, possibly
+# inside a graph capture, and nothing else holds it: the last SYNC_KEEP of them are held STRONGLY so that their words stay readable.
+# An STN-head or LSTM-chain buffer belongs to a module or a session and goes with it: held weakly.
+_SYNC = []
+SYNC_KEEP = 8
+SYNC_QGRU = (1023, "a persistent query-GRU launch")
+SYNC_STN = (255, "an STN-head launch")
+SYNC_LSTM = (1023, "a one-launch LSTM layer (tatt_lstm_fwd_chain)")
 
 
 def _has_gpu():
@@ -1508,12 +1516,31 @@ def sync_capacity(device=None):
         idx = torch.cuda.current_device()
     if idx not in _CAPACITY:
         import ctypes
-        q, s = (ctypes.c_int * 4)(), (ctypes.c_int * 2)()
+        q, s, l = (ctypes.c_int * 4)(), (ctypes.c_int * 2)(), (ctypes.c_int * 1)()
         with torch.cuda.device(idx):
             ops.call("tatt_qgru_chain_capacity", q)
             ops.call("tatt_stn_capacity", s)
-        _CAPACITY[idx] = (q[0], q[1], q[2], q[3], s[0], s[1])
+            ops.call("tatt_lstm_chain_capacity", l)
+        _CAPACITY[idx] = (q[0], q[1], q[2], q[3], s[0], s[1], l[0])
     return _CAPACITY[idx]
+
+
+def _sync_register(buf, kind):
+    """`buf` joins the registry as a buffer of `kind` (SYNC_QGRU: held strongly, the last SYNC_KEEP of them; SYNC_STN, SYNC_LSTM: held
+    weakly) unless it is there already; entries whose buffer is gone leave."""
+    if not any(r() is buf for r, _, _ in _SYNC):
+        ref = (lambda: buf) if kind is SYNC_QGRU else weakref.ref(buf)
+        _SYNC[:] = [e for e in _SYNC if e[0]() is not None] + [(ref,) + kind]
+        for e in [e for e in _SYNC if e[2] == SYNC_QGRU[1]][:-SYNC_KEEP]:
+            _SYNC.remove(e)
+    return buf
+
+
+def _sync_scan(kind=None):
+    for ref, err, name in _SYNC:
+        s = ref()
+        if s is not None and (kind is None or name == kind[1]) and int(s[err].item()) != 0:
+            raise RuntimeError("tatt_amd: %s gave up waiting for its neighbours (work-groups not co-resident?)" % name)
 
 
 def sticky_word(device):
@@ -1546,16 +1573,11 @@ def _qgru_chain_takes(W, HID, bwd=False, device=None):
 def _qgru_chain_sync(ref):
     if not torch.cuda.is_current_stream_capturing():
         sticky_word(ref.device)                  # (registered before the first launch that could raise it)
-    sync = torch.empty(1024, device=ref.device, dtype=torch.int32)
-    QGRU_CHAIN_SYNC.append(sync)
-    del QGRU_CHAIN_SYNC[:-8]
-    return sync
+    return _sync_register(torch.empty(1024, device=ref.device, dtype=torch.int32), SYNC_QGRU)
 
 
 def qgru_chain_check():
-    for s in QGRU_CHAIN_SYNC:
-        if int(s[1023].item()) != 0:
-            raise RuntimeError("tatt_amd: a persistent query-GRU launch gave up waiting for its neighbours (work-groups not co-resident?)")
+    _sync_scan(SYNC_QGRU)
 
 
 class QueryGruFn(Function):
@@ -1732,7 +1754,6 @@ def stamp(name, ref=None):
 # --------------------------------------------------------------------------------------------------
 STN_FOLD_SPLITS = True   # test / A-B hook: False -> every split convolution of the head is followed by its own tatt_splitk_reduce launch
 STN_FOLD_MAX = 9         # ... only up to this many partial maps: the consumer's few work-groups add them one dependent load after the other
-STN_SYNC = []            # every sync buffer handed to those launches (sync_check reads their error words)
 
 
 def _stn_sync(holder, site, ref):
@@ -1743,11 +1764,7 @@ def _stn_sync(holder, site, ref):
         if not torch.cuda.is_current_stream_capturing():
             sticky_word(ref.device)
         table[key] = torch.zeros(256, device=ref.device, dtype=torch.int32)
-    buf = table[key]
-    if not any(r() is buf for r in STN_SYNC):        # registered on LOOKUP: a deep-copied / unpickled module brings its buffers unregistered
-        STN_SYNC[:] = [r for r in STN_SYNC if r() is not None]      # (the buffers belong to their module and go with it)
-        STN_SYNC.append(weakref.ref(buf))
-    return buf
+    return _sync_register(table[key], SYNC_STN)      # registered on LOOKUP: a deep-copied / unpickled module brings its buffers unregistered
 
 
 def sync_check():
@@ -1759,17 +1776,7 @@ def sync_check():
             raise RuntimeError("tatt_amd: a launch that synchronises its work-groups in flight gave up waiting on cuda:%d (%s): its "
                                "results -- and everything computed from them since -- are invalid (work-groups not co-resident?)" % (
                                    idx, " + ".join(n for b, n in ((1, "query-GRU chain"), (2, "STN head"), (4, "LSTM chain")) if code & b)))
-    qgru_chain_check()
-    from . import infer as _infer
-    for r in _infer.LSTM_SYNC:
-        s = r()
-        if s is not None and int(s[1023].item()) != 0:
-            raise RuntimeError("tatt_amd: a one-launch LSTM layer (tatt_lstm_fwd_chain) gave up waiting for its neighbours (work-groups not "
-                               "co-resident?)")
-    for r in STN_SYNC:
-        s = r()
-        if s is not None and int(s[255].item()) != 0:
-            raise RuntimeError("tatt_amd: an STN-head launch gave up waiting for its neighbours (work-groups not co-resident?)")
+    _sync_scan()
 
 
 def stn_head_fusable(x, stn, B):

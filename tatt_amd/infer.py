@@ -21,8 +21,6 @@ the end.  Neither changes the modules' state (training flags, parameters, runnin
 """
 from __future__ import annotations
 
-import ctypes
-import weakref
 from typing import Iterable, Optional, Sequence
 
 import torch
@@ -35,7 +33,6 @@ from .io import ALPHABET, LABEL_CAP, str_filt
 
 # A/B hook: False -> the CRNN's LSTM layers run the per-step kernels (tatt_lstm_fwd_step) inside the session as well
 LSTM_CHAIN = True
-LSTM_SYNC = []           # weak references to the sync buffers handed to tatt_lstm_fwd_chain (functional.sync_check reads word 1023)
 LABEL_RING = 4           # pinned host slots the label encoding of consecutive batches rotates through
 CTC_T = 26               # steps of the recogniser's output for its 100-pixel input (parse_crnn_data): W / 4 + 1
 D2A = "-" + ALPHABET     # class c -> character (class 0 is the CTC blank)
@@ -147,17 +144,11 @@ def ned_from_stats(stats) -> float:
 
 
 def lstm_chain_capacity(device=None) -> int:
-    out = (ctypes.c_int * 1)()
-    with torch.cuda.device(device if device is not None else torch.cuda.current_device()):
-        ops.call("tatt_lstm_chain_capacity", out)
-    return int(out[0])
+    return Fh.sync_capacity(device)[6]
 
 
 def _lstm_sync(ref):
-    buf = torch.zeros(1024, dtype=torch.int32, device=ref.device)
-    LSTM_SYNC[:] = [r for r in LSTM_SYNC if r() is not None]
-    LSTM_SYNC.append(weakref.ref(buf))
-    return buf
+    return Fh._sync_register(torch.zeros(1024, dtype=torch.int32, device=ref.device), Fh.SYNC_LSTM)
 
 
 def lstm_input_projection(x, rnn):
