@@ -933,6 +933,34 @@ int tatt_warp_u8(const unsigned char* src, long src_bytes, const int* desc, cons
 /* out[0..5]: tile height, tile width, most items of one launch, largest side of a source or target, largest feather, ints per
  * descriptor row.  Host only: needs no GPU. */
 int tatt_quad_limits(int* out);
+/* ---- polygon text instances: curved text (csrc/polys.hip; tatt_amd/polys.py is the specification) -- */
+/* The finished lines of polygons of 2 N points (N - 1 strips each, every strip a quad with a projective map of its own) pasted into the
+ * polygons' bounding boxes, uint8 RGB in device memory to uint8 RGB in device memory, tiled over the output (grid: tile x item, one
+ * thread per destination pixel), byte for byte `poly_paste_host`.  items (n_items, 16) int32 in DEVICE memory, one row per polygon:
+ *   [0] byte offset of the line's first pixel in src  [1] H  [2] W  [3] line row pitch in bytes, >= 3 W
+ *   [4] byte offset of the target's first pixel in dst  [5] OH  [6] OW  [7] target row pitch in bytes, >= 3 OW
+ *   [8] feather F >= 0  [9] the item's first row in strips  [10] its strip count, 1 .. 15  [11..15] 0
+ * strips (n_strips, 32) int32 in DEVICE memory, one row per strip, the strips of an item consecutive:
+ *   [0] scale U_k, the strip's first column in the line  [1] scale w_k, its columns ([0] >= 0, [1] >= 1, [0] + [1] <= W)
+ *   [2..19] the nine entries of the strip's integer matrix m, row-major, each a 64-bit two's complement value as (low word, high word)
+ *   [20..25] A, B, C of the seam the strip begins at, alike (0 for an item's first strip)
+ *   [26..31] A, B, C of the seam the strip ends at (0 for an item's last strip)
+ * Destination pixel (i, j), J = 2 j + 1, I = 2 i + 1: the strips are tried in order and the first that claims the pixel paints it; a
+ * pixel none claims is left as it is.  Strip k of n claims it iff A J + B I + C >= 0 for its first seam (k >= 1), A J + B I + C < 0 for
+ * its last seam (k <= n - 2), Wd > 0, 0 <= gy < 256 H, gx >= 0 (k = 0) and gx < 256 [1] (k = n - 1), with X, Y, Wd, gx, gy as
+ * tatt_warp_u8 states them.  The sample: gxg = gx + 256 [0], fx = gxg - 128, fy = gy - 128, the four taps clamped to the (H, W) line, the
+ * bilinear sum of tatt_warp_u8; with F > 0, d = min(xi, W - 1 - xi, yi, H - 1 - yi) for xi = clamp(gxg >> 8, 0, W - 1), yi = gy >> 8 and
+ * the blend of tatt_warp_u8.  All in 64-bit integers.  src and dst may be one buffer; the target rectangles of one launch must be
+ * disjoint and must not overlap a line.  items_host / strips_host: the same rows in HOST memory, read before the launch only to refuse:
+ * 1 bad arguments, a reserved word or a negative feather, 2 a geometry beyond tatt_poly_limits (a side, the feather, the strip count, a
+ * strip's columns outside the line, more than 65535 items), 3 a line or target rectangle that leaves src (src_bytes) / dst (dst_bytes),
+ * 4 an item whose strip rows leave the table of n_strips rows.  The kernel reads only device memory (the launch can be captured),
+ * re-checks every item (it writes nothing for an item it refuses) and clamps every tap whatever the matrices say. */
+int tatt_poly_paste_u8(const unsigned char* src, long src_bytes, const int* items, const int* items_host, int n_items,
+                       const int* strips, const int* strips_host, int n_strips, unsigned char* dst, long dst_bytes, hipStream_t st);
+/* out[0..7]: tile height, tile width, most items of one launch, largest side of a line or target, largest feather, ints per item row,
+ * ints per strip row, most strips of one polygon.  Host only: needs no GPU. */
+int tatt_poly_limits(int* out);
 /* ---- reading super-resolved lines at their own width (csrc/read.hip; tatt_amd/read.py is the specification) -- */
 /* ONE launch for all lines of a call: every uint8 RGB line canvas in src (where tatt_line_blend left it) goes through Pillow's 8-bit
  * bicubic Image.resize((rw, 32), BICUBIC) (horizontal pass first, its result rounded to uint8, a pass whose sizes agree skipped), then

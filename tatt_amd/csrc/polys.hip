@@ -1,0 +1,66 @@
+// Scene images with polygon text instances: curved text (tatt_amd/polys.py is the specification, tests/test_polys*.py hold the kernel to
+// it).  A polygon of 2 N points is cut into N - 1 strips, each a quad with the projective map of quads.hip.  Straightening a polygon is
+// tatt_warp_u8 (mode 0) with one row per strip and needs nothing new; this file is the way back:
+//   poly_paste_u8_kernel  the finished line -> the polygon's bounding box of the canvas.  Grid (tile, polygon), 256 threads, one thread
+//                         per destination pixel of a tile of 8 x 32.  Per pixel the strips of the polygon are walked in order: the exact
+//                         edge functions of the strip's two seams first (E = A J + B I + C on the pixel centre in half-pixel units: two
+//                         64-bit multiply-adds each, no division), then, only for a strip whose edge tests pass -- one strip for nearly
+//                         every pixel --, the strip's matrix, the two emulated 64-bit floor divisions, the gy test and the gx test of an
+//                         outer side, the bilinear sample from the WHOLE line (taps clamped to the line: across a seam a tap reads the
+//                         neighbouring strip's columns), the feather against the line's sides, the store.  Two neighbouring strips
+//                         evaluate the same integers for the seam they share, so every pixel between the outer sides belongs to exactly
+//                         one strip.
+// All of it is 64-bit integer arithmetic (csrc/poly_pixel.h: the same text runs on the host), no floating point, no LDS, no atomics, no
+// traffic between work-groups; the item and strip rows are indexed by the block and by a uniform loop counter alone.  Every quantity is read
+// from DEVICE memory (the launch can be captured); the same check runs on the host before the launch and in the kernel, every tap is
+// clamped, every store lies in a rectangle the check accepted.
+#include "common.h"
+#include "poly_pixel.h"
+
+#define PLY_THREADS 256
+
+// (src_base and dst_base may be one buffer: the line rectangles and the canvas; the targets of a launch are disjoint and overlap no line)
+__global__ __launch_bounds__(PLY_THREADS) void poly_paste_u8_kernel(const unsigned char* src_base, long src_bytes, const int* __restrict__ items,
+                                                                    const int* __restrict__ strips, int n_strips, unsigned char* dst_base,
+                                                                    long dst_bytes) {
+    const int* d = items + (long)blockIdx.y * PLY_DESC;
+    // a replayed launch re-checks: nothing is written for an item the host entry would have refused
+    if (ply_check(d, strips, n_strips, src_bytes, dst_bytes) != 0) return;
+    int i, j;
+    if (!ply_place(blockIdx.x, (int)threadIdx.x, d[5], d[6], &i, &j)) return;
+    ply_pixel(d, strips + (long)d[9] * PLY_STRIP_DESC, src_base + d[0], i, j, dst_base + d[4] + i * (long)d[7] + j * 3L);
+}
+
+TATT_API int tatt_poly_paste_u8(const unsigned char* src, long src_bytes, const int* items, const int* items_host, int n_items,
+                                const int* strips, const int* strips_host, int n_strips, unsigned char* dst, long dst_bytes,
+                                hipStream_t st) {
+    if (!src || !items || !items_host || !strips || !strips_host || !dst || n_items <= 0 || n_strips <= 0 || src_bytes <= 0 ||
+        dst_bytes <= 0)
+        return 1;
+    if (n_items > PLY_MAX_ITEMS) return 2;
+    long tiles = 0;
+    for (int i = 0; i < n_items; ++i) {
+        const int* d = items_host + (long)i * PLY_DESC;
+        const int rc = ply_check(d, strips_host, n_strips, src_bytes, dst_bytes);
+        if (rc) return rc;
+        const long t = ply_tiles(d[5], d[6]);
+        if (t > tiles) tiles = t;
+    }
+    if (tiles > 0x7fffffffL) return 2;
+    hipLaunchKernelGGL(poly_paste_u8_kernel, dim3((unsigned)tiles, n_items), dim3(PLY_THREADS), 0, st, src, src_bytes, items, strips,
+                       n_strips, dst, dst_bytes);
+    return LAUNCH_CHECK();
+}
+
+TATT_API int tatt_poly_limits(int* out) {
+    if (!out) return 1;
+    out[0] = PLY_TH;
+    out[1] = PLY_TW;
+    out[2] = PLY_MAX_ITEMS;
+    out[3] = PLY_MAX_SIDE;
+    out[4] = PLY_MAX_FEATHER;
+    out[5] = PLY_DESC;
+    out[6] = PLY_STRIP_DESC;
+    out[7] = PLY_MAX_STRIPS;
+    return 0;
+}

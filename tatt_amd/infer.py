@@ -753,7 +753,8 @@ class SuperResolver:
 
     `scene(image, boxes, feather=0)` (any instance without a recogniser) takes a whole picture and a detector's boxes and returns the
     up-scaled picture with the text of every box super-resolved and pasted back: see the method.  `scene_quads(image, quads, feather=0)`
-    is the same for quadrilaterals (four corner points per text instance, rotated or under perspective).
+    is the same for quadrilaterals (four corner points per text instance, rotated or under perspective), `scene_polys(image, polys,
+    feather=0)` for polygons of 2 N points (curved text).
 
     reader=crnn (opt-in; images and pictures are byte for byte those without it) reads every tiled line at its OWN width
     (`read.LineReader`, specification `read.read_lines_host`): the blended uint8 line is resized to (32, rw), rw = `read.read_width(wl)`
@@ -884,9 +885,25 @@ class SuperResolver:
         return self._scene("scene_quads", image, quads, feather, self.collator.quad_windows, self.exporter.scene_quads,
                            lambda q: tuple((int(x), int(y)) for x, y in q), quad_layers)
 
+    def scene_polys(self, image, polys, feather: int = 0) -> PendingScene:
+        """`scene_quads` for a detector's POLYGONS, curved text: image: an RGB PIL image, polys: 2 N integer points per text instance,
+        2 <= N <= 8, N along the top of the text in reading direction, then N back along the bottom (`io.poly_check`; N = 2 is a quad)
+        -> PendingScene whose `result()` (the only host wait) is the RGB PIL image of size (scale * Ws, scale * Hs): the bicubic up-scale
+        of the picture with every polygon replaced by its super-resolved text, later polygons over earlier ones, only the pixels of the
+        polygon painted; feather = F > 0 fades the outer F pixels of every line, never a seam between two strips.
+        `DeviceCollator.poly_windows` straightens every polygon strip by strip into an upright crop and cuts all windows on the device,
+        the windows go through the sessions as `scene` runs them, `DeviceExporter.scene_polys` merges, up-scales and pastes every line
+        back along its polygon (csrc/polys.hip) and copies the canvas back once.  Byte for byte `io.super_resolve_polys_host` on the same
+        SR windows; polygons of four points give the bytes of `scene_quads`.  No polygons: the up-scaled picture, no session runs.  Not
+        with a recogniser (ValueError); a reader reads one line per polygon, in input order.  With keep_sr the PendingScene's `boxes` are
+        the checked polygons and `layers` their paste layers (`io.poly_layers`)."""
+        from .io import poly_layers
+        return self._scene("scene_polys", image, polys, feather, self.collator.poly_windows, self.exporter.scene_polys,
+                           lambda q: tuple((int(x), int(y)) for x, y in q), poly_layers)
+
     def _scene(self, who, image, boxes, feather, windows, export, norm, layers) -> PendingScene:
-        """`scene` and `scene_quads` (`who`): windows = the collator's method that cuts them, export = the exporter's that pastes them,
-        norm(box) = a box as the PendingScene keeps it, layers(boxes) = their paste layers"""
+        """`scene`, `scene_quads` and `scene_polys` (`who`): windows = the collator's method that cuts them, export = the exporter's that
+        pastes them, norm(box) = a box as the PendingScene keeps it, layers(boxes) = their paste layers"""
         from .io import line_plan
         if self.rec is not None:
             raise ValueError("SuperResolver: a recogniser cannot read tiled lines (%s); pass recognizer=None" % who)

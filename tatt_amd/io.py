@@ -29,6 +29,9 @@
 * `quad_check` / `quad_matrices` / `warp_u8_host` / `quad_compose_host` / `super_resolve_quads_host` (tatt_amd/quads.py, re-exported here)
   take a detector's QUADRILATERALS instead of boxes: every quad rectified into an upright crop, the finished line warped back into its
   place; `DeviceCollator.quad_windows` and `DeviceExporter.scene_quads` are the same on the GPU (csrc/quads.hip), byte for byte.
+* `poly_check` / `poly_matrices` / `poly_paste_host` / `poly_compose_host` / `super_resolve_polys_host` (tatt_amd/polys.py, re-exported
+  here) take POLYGONS of 2 N points, a detector's curved text: straightened strip by strip, the finished line pasted back with exact
+  seams; `DeviceCollator.poly_windows` and `DeviceExporter.scene_polys` are the same on the GPU (csrc/polys.hip), byte for byte.
 * `LmdbRecords` reads the reference's lmdb record layout (`lmdbDataset_real`, dataset/dataset.py:565-686): keys `num-samples`,
   `label-%09d`, `image_hr-%09d`, `image_lr-%09d` (1-based), image bytes decoded by PIL to RGB, the label filtered by `str_filt`.
   It takes any object with the lmdb transaction's `get(key)`; `open_lmdb` wraps a real environment when the `lmdb` package is there
@@ -716,9 +719,14 @@ class DeviceCollator(_Limits):
         launch resizes the crops beyond `line_limits()` to (wl, h) on the device (none in the common case: no launch), ONE
         tatt_scene_windows launch reads every window out of its crop (`quad_plan`).  No quads: the upload alone, an empty stack.  Never
         waits for the device."""
+        plan = quad_plan(scene, quads, self.lr_size[::-1], stride, self.mask, self._lim(line_limits), self._lim(scene_limits),
+                         self._lim(quad_limits))
+        return self._rectified_windows(plan)
+
+    def _rectified_windows(self, plan):
+        """a QuadPlan or PolyPlan (one layout, `quad_fill`) staged and enqueued: the rectify launch, the resize launch, the windows"""
         from . import ops
         w, h = self.lr_size
-        plan = quad_plan(scene, quads, (h, w), stride, self.mask, self._lim(line_limits), self._lim(scene_limits), self._lim(quad_limits))
         o_warp, o_resize, o_desc, pix, used, total = quad_fill(None, plan)
 
         def launch(base, hbase):
@@ -735,6 +743,16 @@ class DeviceCollator(_Limits):
             return out
         out = self._stage(total, used, lambda flat: quad_fill(flat, plan), launch)       # (the device buffer holds the crops behind the upload)
         return out.view(len(plan.desc), 3 + int(self.mask), h, w), plan.lines, self._scene_dev(pix, plan)
+
+    def poly_windows(self, scene, polys, stride: int = 32):
+        """`quad_windows` for polygons of 2 N points (`poly_check`): curved text, straightened strip by strip -> (stack, lines,
+        scene_dev), the stack bit for bit `poly_windows_host(scene, polys, (h, w), stride, mask)`.  The launches of `quad_windows`: ONE
+        tatt_warp_u8 launch, with one row per STRIP, writes the strips of every polygon side by side into its crop, ONE tatt_resize_u8
+        launch for the crops beyond `line_limits()` (none in the common case), ONE tatt_scene_windows launch (`poly_plan`).  No
+        polygons: the upload alone, an empty stack.  Never waits for the device."""
+        plan = poly_plan(scene, polys, self.lr_size[::-1], stride, self.mask, self._lim(line_limits), self._lim(scene_limits),
+                         self._lim(quad_limits))
+        return self._rectified_windows(plan)
 
 
 # ---- image export on the device (csrc/export.hip) -----------------------------------------------------------------------------------
@@ -1173,6 +1191,38 @@ class DeviceExporter(_Limits):
         return self._enqueue([], nbytes, views, head=head, launch=launch, canvases=canvases)
 
 
+    def scene_polys(self, scene_dev, sr_windows, lines, polys, scale: int, feather: int = 0, c0: int = 0) -> PendingExport:
+        """`scene_quads` for polygons of 2 N points (curved text): scene_dev, sr_windows and lines as `DeviceCollator.poly_windows` and
+        the sessions leave them, one Line per polygon -> a PendingExport whose `result()` is one RGB PIL image of size (scale * Ws,
+        scale * Hs), BYTE FOR BYTE `poly_compose_host(scene, polys, [blend_windows_host(..) per polygon], scale, feather)`.  The
+        launches of `scene_quads` with ONE tatt_poly_paste_u8 launch per layer (`poly_layers`) in place of its tatt_warp_u8 launches:
+        every pixel of a polygon's bounding box is painted by the one strip that claims it, sampled from the whole line, feathered
+        against the line's outer sides only.  Never waits for the device."""
+        import ctypes
+        from . import ops
+        from .polys import POLY_DESC
+        from .scene import RESIZE_DESC
+        (Hs, Ws), (bdesc, starts, bbytes, H), canvases, blend = self._scene("scene_polys", scene_dev, sr_windows, lines, scale, c0)
+        polys = list(polys)
+        plan = poly_paste_plan((Ws, Hs), polys, bdesc, bbytes, scale, H, feather, self._lim(scene_limits), self._lim(poly_limits))
+        head, (_, o_starts, o_rows, o_items, o_strips) = _tables(bdesc, starts, plan.resize, plan.items, plan.strips)
+        views = [(plan.canvas_off, scale * Hs, scale * Ws, plan.pitch, None)]
+        nbytes, src_bytes, n = plan.nbytes, Hs * Ws * 3, len(polys)
+
+        def launch(base, hbase, pix):
+            out = ctypes.c_void_p(base + pix)
+            blend(base, hbase, o_starts, pix)
+            row = lambda o: _ptrs(base, hbase, o * 4)
+            ops.call("tatt_resize_u8", ops.P(scene_dev), src_bytes, *row(o_rows), 1, out, nbytes, ops.stream())
+            if n:                                                      # the line canvases lie in front of the rectangles, in the same buffer
+                ops.call("tatt_resize_u8", out, max(bbytes, 1), *row(o_rows + RESIZE_DESC), n, out, plan.canvas_off, ops.stream())
+            r = 0
+            for c in plan.counts:                                      # the rectangles lie in front of the canvas; ONE strip table
+                ops.call("tatt_poly_paste_u8", out, plan.canvas_off, *row(o_items + r * POLY_DESC), c, *row(o_strips), len(plan.strips),
+                         out, nbytes, ops.stream())
+                r += c
+        return self._enqueue([], nbytes, views, head=head, launch=launch, canvases=canvases)
+
 from .lines import (LINE_MAX_WL, Line, blend_plan, blend_windows_host, line_limits, line_plan, line_windows_host, lines_fill,  # noqa: E402,F401
                     lines_plan, super_resolve_lines_host)
 from .scene import (SCENE_MIN_SIDE, paste_plan, scene_check, scene_compose_host, scene_fill, scene_layers, scene_limits,  # noqa: E402,F401
@@ -1180,6 +1230,9 @@ from .scene import (SCENE_MIN_SIDE, paste_plan, scene_check, scene_compose_host,
 from .quads import (QUAD_MAX_TAPER, QUAD_SHIFT, quad_bbox, quad_check, quad_compose_host, quad_fill, quad_layers,  # noqa: E402,F401
                     quad_limits, quad_matrices, quad_paste_plan, quad_plan, quad_rectify_host, quad_size, quad_windows_host,
                     super_resolve_quads_host, warp_inside_host, warp_u8_host)
+from .polys import (poly_bbox, poly_check, poly_columns, poly_compose_host, poly_fill, poly_layers, poly_limits,  # noqa: E402,F401
+                    poly_matrices, poly_owner_host, poly_paste_host, poly_paste_plan, poly_plan, poly_rectify_host, poly_size,
+                    poly_strips, poly_windows_host, super_resolve_polys_host)
 from .read import (READ_MAX, READ_QUANTUM, BeamDecoded, BeamReading, Lexicon, LexiconDecoded, LexiconReading, Reading,  # noqa: E402,F401
                    beam_limits, ctc_beam_read_host, ctc_greedy_read_host, ctc_lexicon_read_host,
                    ctc_string_logp_host, lexicon_limits, line_luma_host, read_limits, read_lines_host, read_plan, read_squeezed,
