@@ -1003,6 +1003,21 @@ int tatt_ctc_beam_read(const float* logits, long st_t, long st_b, long st_c, int
 /* out[0..4]: most steps T, most classes C and most beam entries of tatt_ctc_beam_read, the nodes of an image's trie (1 + 256 * 16) and
  * the slots of its lookup table.  Host only: needs no GPU. */
 int tatt_beam_limits(int* out);
+/* tatt_ctc_beam_read with a character n-gram language model fused into the search (the same kernel, instantiated with the LM statements;
+ * specification read.ctc_beam_lm_read_host).  lmw: the increments table W of read.CharLM.increments on the device, lm_classes^order
+ * float64 entries, W[h_1, .., h_{order-1}, c] with the most recent class of the history last and 0 for "before the line begins";
+ * column 0 is the end of the line.  Weight and bonus are in the table: the kernel only adds its entries, in the order of the string, so an
+ * entry's LM term equals the specification's bit for bit.  Candidates are ranked by (acoustic sum) + (LM term); after the last step the
+ * beam is ranked once more by (tot + lm) + W[history][0], descending, ties to the lower rank, and the first nbest are written.
+ * Record row: [0] entries  [1] flag  then per entry es = 6 + cap + (cap & 1) words: [0..1] float64 logp, the ACOUSTIC sum over the
+ * alignments kept  [2..3] float64 lm, the LM term with the end increment  [4] length  [5] 0  [6 ..) cap classes padded with -1.
+ * Returns 1 before any launch for everything tatt_ctc_beam_read refuses (with this es), a null table, order outside 1 .. 3,
+ * lm_classes != C. */
+int tatt_ctc_beam_lm_read(const float* logits, long st_t, long st_b, long st_c, int T, int B, int C, int beam, int nbest,
+                          const double* lmw, int order, int lm_classes, const int* index, int* record, int n_rows, int cap, long st_rec,
+                          hipStream_t st);
+/* out[0..1]: the largest order and the most classes of a table tatt_ctc_beam_lm_read takes.  Host only: needs no GPU. */
+int tatt_lm_limits(int* out);
 /* Lexicon decoding (csrc/ctclex.hip; specification read.ctc_lexicon_read_host): scores[b][k] = the exact CTC log-probability (blank 0,
  * the forward recursion of read.ctc_string_logp_host in float64) of word k of a closed list under the logits (T,B,C) fp32 of image b,
  * given by element strides.  The list is packed by the host (read.Lexicon): codes: the class ids of all words one after the other

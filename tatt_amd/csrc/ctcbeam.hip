@@ -14,6 +14,11 @@
 // Every loop is bounded by T, C, CB_BEAM, CB_TABLE or a literal; the candidate registers are indexed by unrolled loops only (no scratch).
 // Wave-wide maxima, minima and sums go through data-parallel-primitive moves (row shifts, row broadcasts) and a lane read: no LDS, and
 // the result is the same in every lane.  The kernel is instantiated for 4, 8 and 16 beam entries; a launch takes the smallest that fits.
+// LM = true (tatt_ctc_beam_lm_read; specification `ctc_beam_lm_read_host`) fuses a character n-gram model into the search: every entry
+// carries one more float64, the sum of the increments W[history][class] of its string (the host's table `CharLM.increments`: weight and
+// bonus are already in it, so the kernel only ADDS entries of the table, left to right, and the term is the specification's bit for bit);
+// candidates are ranked by acoustic + LM, the record keeps the two apart, and after the last step the beam is ranked once more with the
+// end-of-line increment W[history][0] added.  Every LM statement stands under `if constexpr (LM)`.
 #include "common.h"
 #include "ctc_f64.h"                                           // CB_NEG, cb_lse, the wave maxima / minima / sums
 
@@ -29,16 +34,21 @@ static_assert(CB_TABLE > 2 * CB_NODES && CB_TABLE == 1 << CB_TABLE_BITS && CB_NO
 
 // 32-bit words of one entry of a record row: float64 logp (2) | length | pad | cap classes, an even count
 static __host__ __device__ inline int cb_entry_words(int cap) { return 4 + cap + (cap & 1); }
+// with a language model: float64 logp (2) | float64 lm (2) | length | pad | cap classes, an even count
+static __host__ __device__ inline int cb_lm_entry_words(int cap) { return 6 + cap + (cap & 1); }
+#define CB_LM_ORDER 3                          // most classes of an n-gram: the table has C^order entries, at most 64^3 doubles = 2 MB
 
 __device__ __forceinline__ unsigned cb_hash(int parent, int c) {
     return ((unsigned)(parent * CB_MAX_C + c) * 2654435761u) >> (32 - CB_TABLE_BITS);
 }
 
 // BM: the beam entries the kernel keeps registers and unrolled loops for (beam <= BM <= CB_BEAM): a launch takes the smallest that fits.
-template <int BM>
+// LM: lmw is the table W of C^order doubles, row = the last order - 1 classes of a prefix (0: before the line begins), column = the class
+template <int BM, bool LM>
 __global__ __launch_bounds__(64) void ctc_beam_read_kernel(const float* __restrict__ logits, long st_t, long st_b, long st_c, int T,
                                                            int C, int beam, int nbest, const int* __restrict__ index,
-                                                           int* __restrict__ record, int n_rows, int cap, long st_rec) {
+                                                           int* __restrict__ record, int n_rows, int cap, long st_rec,
+                                                           const double* __restrict__ lmw, int order) {
     __shared__ double lp[CB_MAX_C];                                  // the step's log-soft-max
     __shared__ double pb[2][CB_BEAM], pnb[2][CB_BEAM], tot[2][CB_BEAM];      // the beam, by rank; [cur] is read, [cur ^ 1] written
     __shared__ int node[2][CB_BEAM];
@@ -51,6 +61,8 @@ __global__ __launch_bounds__(64) void ctc_beam_read_kernel(const float* __restri
     __shared__ int state_sh[2];                                      // nodes in use, flag
     __shared__ int len_sh[CB_BEAM];
     __shared__ int last_sh[CB_BEAM];                                 // the last class of every entry's prefix, -1 for the empty one
+    __shared__ double lmv[2][LM ? CB_BEAM : 1];                      // LM: the LM term of every entry, by rank, buffered as the beam is
+    __shared__ int ctx[LM ? CB_BEAM : 1];                            // LM: the row of W that every entry's prefix selects
     const int lane = threadIdx.x;
     const float* x = logits + blockIdx.x * st_b + lane * st_c;
 
@@ -62,7 +74,9 @@ __global__ __launch_bounds__(64) void ctc_beam_read_kernel(const float* __restri
         if (lane < CB_BEAM) {
             stot[lane] = CB_NEG;
             last_sh[lane] = -1;
+            if constexpr (LM) ctx[lane] = 0;                         // (rows beyond the beam are loaded from, too: row 0)
         }
+        if constexpr (LM) (&lmv[0][0])[lane] = 0.0;                  // (the empty prefix: 0)
     }
     __syncthreads();
     if (lane == 0) {
@@ -100,6 +114,10 @@ __global__ __launch_bounds__(64) void ctc_beam_read_kernel(const float* __restri
             const double a = tot[cur][lane] + lp[0];
             double b = CB_NEG;
             last_sh[lane] = nd != 0 ? cls[nd] : -1;
+            if constexpr (LM) {                                      // (the root: cls[0] = par[0] = 0, "before the line begins")
+                const int c1 = cls[nd], c2 = cls[par[nd]];
+                ctx[lane] = order == 1 ? 0 : order == 2 ? c1 : c2 * C + c1;
+            }
             if (nd != 0) {
                 const int last = cls[nd], p = par[nd];
                 b = pnb[cur][lane] + lp[last];
@@ -120,11 +138,20 @@ __global__ __launch_bounds__(64) void ctc_beam_read_kernel(const float* __restri
         __syncthreads();
         // ---- lane c: the candidates (r, c) of every r ----
         double v[BM];                                                // (every load below is issued whatever nb is: no branch, one wait)
+        double w[LM ? BM : 1];
+        if constexpr (LM) {
+#pragma unroll
+            for (int r = 0; r < BM; ++r) w[r] = lmw[lane < C ? ctx[r] * C + lane : 0];       // (coalesced; the table lives in L2)
+        }
 #pragma unroll
         for (int r = 0; r < BM; ++r) {
             const double ext = (lane == last_sh[r] ? pb[cur][r] : tot[cur][r]) + lpc;
             const bool struck = kill[r * CB_MAX_C + lane] == (unsigned short)(t + 1);
-            const double val = lane == 0 ? stot[r] : (struck ? CB_NEG : ext);
+            double val;
+            if constexpr (LM)                                        // (first the LM term of the candidate, then the one sum)
+                val = lane == 0 ? stot[r] + lmv[cur][r] : (struck ? CB_NEG : ext + (lmv[cur][r] + w[r]));
+            else
+                val = lane == 0 ? stot[r] : (struck ? CB_NEG : ext);
             v[r] = r < nb && lane < C ? val : CB_NEG;
         }
         // ---- the `beam` largest, descending, ties to the lower key; lane i keeps the i-th ----
@@ -164,8 +191,16 @@ __global__ __launch_bounds__(64) void ctc_beam_read_kernel(const float* __restri
                 node[nxt][lane] = node[cur][r];
                 pb[nxt][lane] = spb[r];
                 pnb[nxt][lane] = spnb[r];
+                if constexpr (LM) {
+                    my_val = stot[r];                                // (my_val was the score: the acoustic sum again)
+                    lmv[nxt][lane] = lmv[cur][r];
+                }
             } else {
                 const int p = node[cur][r];
+                if constexpr (LM) {                                  // (the operations of the candidate phase on the same operands)
+                    my_val = (c == last_sh[r] ? pb[cur][r] : tot[cur][r]) + lp[c];
+                    lmv[nxt][lane] = lmv[cur][r] + lmw[ctx[r] * C + c];
+                }
                 pb[nxt][lane] = CB_NEG;
                 pnb[nxt][lane] = my_val;
                 const unsigned h = cb_hash(p, c);
@@ -232,20 +267,48 @@ __global__ __launch_bounds__(64) void ctc_beam_read_kernel(const float* __restri
         }
         return;
     }
-    const int n_out = nb < nbest ? nb : nbest, es = cb_entry_words(cap);
-    if (lane < n_out) {                                              // lane i walks entry i back to the root
+    constexpr int HD = LM ? 6 : 4;                                   // words of an entry before its classes
+    const int n_out = nb < nbest ? nb : nbest, es = LM ? cb_lm_entry_words(cap) : cb_entry_words(cap);
+    int src = lane;                                                  // the beam entry that record entry `lane` is
+    if constexpr (LM) {
+        // ---- the line ends here: final = (tot + lm) + W[history][0]; descending, ties to the lower rank.  The step loop is over, so
+        // stot takes the finals, spb the LM terms with the end increment, ext_par the beam entry of every position ----
+        if (lane < nb) {
+            const int nd = node[cur][lane], c1 = cls[nd], c2 = cls[par[nd]];
+            const double wend = lmw[(order == 1 ? 0 : order == 2 ? c1 : c2 * C + c1) * C];
+            stot[lane] = (tot[cur][lane] + lmv[cur][lane]) + wend;
+            spb[lane] = lmv[cur][lane] + wend;
+        }
+        __syncthreads();
+        if (lane < nb) {
+            const double f = stot[lane];
+            int pos = 0;
+#pragma unroll
+            for (int j = 0; j < BM; ++j)
+                if (j < nb && (stot[j] > f || (stot[j] == f && j < lane))) ++pos;
+            ext_par[pos] = lane;
+        }
+        __syncthreads();
+        if (lane < n_out) src = ext_par[lane];
+    }
+    if (lane < n_out) {                                              // lane i walks its entry back to the root
         int* e = rec + 2 + lane * es;
-        const int first = node[cur][lane];
+        const int first = node[cur][src];
         int len = 0;
         for (int nd = first; nd != 0 && len < T; nd = par[nd]) ++len;        // (a node's depth is at most the steps taken: len <= T <= cap)
-        const double lg = tot[cur][lane];
+        const double lg = tot[cur][src];
         e[0] = __double2loint(lg);
         e[1] = __double2hiint(lg);
-        e[2] = len;
-        e[3] = 0;
+        if constexpr (LM) {
+            const double lm = spb[src];
+            e[2] = __double2loint(lm);
+            e[3] = __double2hiint(lm);
+        }
+        e[HD - 2] = len;
+        e[HD - 1] = 0;
         int nd = first;
         for (int k = len - 1; k >= 0; --k) {
-            e[4 + k] = cls[nd];
+            e[HD + k] = cls[nd];
             nd = par[nd];
         }
         len_sh[lane] = len;
@@ -253,7 +316,7 @@ __global__ __launch_bounds__(64) void ctc_beam_read_kernel(const float* __restri
     __syncthreads();
     for (int i = 0; i < n_out; ++i) {
         int* e = rec + 2 + i * es;
-        for (int k = len_sh[i] + lane; k < es - 4; k += 64) e[4 + k] = -1;
+        for (int k = len_sh[i] + lane; k < es - HD; k += 64) e[HD + k] = -1;
     }
     if (lane == 0) {
         rec[0] = n_out;
@@ -261,21 +324,43 @@ __global__ __launch_bounds__(64) void ctc_beam_read_kernel(const float* __restri
     }
 }
 
-TATT_API int tatt_ctc_beam_read(const float* logits, long st_t, long st_b, long st_c, int T, int B, int C, int beam, int nbest,
-                                const int* index, int* record, int n_rows, int cap, long st_rec, hipStream_t st) {
+template <bool LM>
+static int cb_launch(const float* logits, long st_t, long st_b, long st_c, int T, int B, int C, int beam, int nbest, const int* index,
+                     int* record, int n_rows, int cap, long st_rec, const double* lmw, int order, hipStream_t st) {
     if (!logits || !index || !record) return 1;
     if (T <= 0 || T > CB_MAX_T || B <= 0 || C <= 0 || C > CB_MAX_C || n_rows <= 0 || cap < T) return 1;
-    if (nbest < 1 || nbest > beam || beam > CB_BEAM || st_rec < 2 + (long)nbest * cb_entry_words(cap)) return 1;
+    const int es = LM ? cb_lm_entry_words(cap) : cb_entry_words(cap);
+    if (nbest < 1 || nbest > beam || beam > CB_BEAM || st_rec < 2 + (long)nbest * es) return 1;
     if (beam <= 4)
-        hipLaunchKernelGGL(ctc_beam_read_kernel<4>, dim3(B), dim3(64), 0, st, logits, st_t, st_b, st_c, T, C, beam, nbest, index, record,
-                           n_rows, cap, st_rec);
+        hipLaunchKernelGGL((ctc_beam_read_kernel<4, LM>), dim3(B), dim3(64), 0, st, logits, st_t, st_b, st_c, T, C, beam, nbest, index,
+                           record, n_rows, cap, st_rec, lmw, order);
     else if (beam <= 8)
-        hipLaunchKernelGGL(ctc_beam_read_kernel<8>, dim3(B), dim3(64), 0, st, logits, st_t, st_b, st_c, T, C, beam, nbest, index, record,
-                           n_rows, cap, st_rec);
+        hipLaunchKernelGGL((ctc_beam_read_kernel<8, LM>), dim3(B), dim3(64), 0, st, logits, st_t, st_b, st_c, T, C, beam, nbest, index,
+                           record, n_rows, cap, st_rec, lmw, order);
     else
-        hipLaunchKernelGGL(ctc_beam_read_kernel<CB_BEAM>, dim3(B), dim3(64), 0, st, logits, st_t, st_b, st_c, T, C, beam, nbest, index,
-                           record, n_rows, cap, st_rec);
+        hipLaunchKernelGGL((ctc_beam_read_kernel<CB_BEAM, LM>), dim3(B), dim3(64), 0, st, logits, st_t, st_b, st_c, T, C, beam, nbest,
+                           index, record, n_rows, cap, st_rec, lmw, order);
     return LAUNCH_CHECK();
+}
+
+TATT_API int tatt_ctc_beam_read(const float* logits, long st_t, long st_b, long st_c, int T, int B, int C, int beam, int nbest,
+                                const int* index, int* record, int n_rows, int cap, long st_rec, hipStream_t st) {
+    return cb_launch<false>(logits, st_t, st_b, st_c, T, B, C, beam, nbest, index, record, n_rows, cap, st_rec, nullptr, 0, st);
+}
+
+// the search with the increments table `lmw` of lm_classes^order float64 entries on the device (read.CharLM.increments)
+TATT_API int tatt_ctc_beam_lm_read(const float* logits, long st_t, long st_b, long st_c, int T, int B, int C, int beam, int nbest,
+                                   const double* lmw, int order, int lm_classes, const int* index, int* record, int n_rows, int cap,
+                                   long st_rec, hipStream_t st) {
+    if (!lmw || order < 1 || order > CB_LM_ORDER || lm_classes != C) return 1;
+    return cb_launch<true>(logits, st_t, st_b, st_c, T, B, C, beam, nbest, index, record, n_rows, cap, st_rec, lmw, order, st);
+}
+
+TATT_API int tatt_lm_limits(int* out) {
+    if (!out) return 1;
+    out[0] = CB_LM_ORDER;
+    out[1] = CB_MAX_C;
+    return 0;
 }
 
 TATT_API int tatt_beam_limits(int* out) {

@@ -766,6 +766,9 @@ class SuperResolver:
     `out_sizes` and `feather` apply.  A plain call on an instance with `reader=` and no `recognizer=` raises ValueError.
     read_decode="beam" (read_beam, read_nbest) decodes with the CTC prefix beam search instead: one tatt_ctc_beam_read launch per
     chunk in place of the greedy one, and `readings()` gives `read.BeamReading`s (text, logp, alternatives); `texts()` as before.
+    With read_lm = a `read.CharLM` (read_lm_weight, read_lm_bonus: `LineReader`'s lm_weight, lm_bonus) a character n-gram model is fused
+    into that search: one tatt_ctc_beam_lm_read launch per chunk in place of the beam launch, `readings()` gives
+    `read.BeamLMReading`s (text, logp, lm, score, alternatives).
     read_decode="lexicon" (read_lexicon = a `read.Lexicon` or a list of words, read_nbest <= 16) reads every line against that closed
     list: per chunk the tatt_ctc_lexicon_score launches and one tatt_ctc_lexicon_select launch in place of the greedy one, and
     `readings()` gives `read.LexiconReading`s (text, logp, posterior, alternatives); every text is a word of the list.
@@ -776,7 +779,7 @@ class SuperResolver:
     def __init__(self, generator, prior=None, recognizer=None, batch_size: int = 48, lr_size=(16, 64), mask: bool = True,
                  rule: str = "floor", keep_sr: bool = False, long_lines: bool = False, stride: int = 32, reader=None,
                  read_decode: str = "greedy", read_beam: int = 8, read_nbest: int = 4, read_lexicon=None,
-                 read_word_penalty: float = 0.0):
+                 read_word_penalty: float = 0.0, read_lm=None, read_lm_weight=None, read_lm_bonus=None):
         from .io import DeviceCollator, DeviceExporter
         _refuse_attention_recognizer(recognizer, "SuperResolver")
         _check_module(generator, "generator")
@@ -802,7 +805,8 @@ class SuperResolver:
         if reader is not None:
             from .read import LineReader
             self.reader = LineReader(reader, batch_size=batch_size, device=self.device, w=self.lr_size[1], decode=read_decode,
-                                     beam=read_beam, nbest=read_nbest, lexicon=read_lexicon, word_penalty=read_word_penalty)
+                                     beam=read_beam, nbest=read_nbest, lexicon=read_lexicon, word_penalty=read_word_penalty,
+                                     lm=read_lm, lm_weight=read_lm_weight, lm_bonus=read_lm_bonus)
 
     def _texts(self, sr):
         """-> (pinned (n, T + 1) int32: decoded classes | length, its event)"""

@@ -1238,3 +1238,4 @@ from .read import (READ_MAX, READ_QUANTUM, BeamDecoded, BeamReading, Lexicon, Le
                    ctc_string_logp_host, lexicon_limits, line_luma_host, read_limits, read_lines_host, read_plan, read_squeezed,
                    read_width)
 from .read import WordsDecoded, WordSpan, WordsReading, ctc_words_host, ctc_words_read_host, words_limits  # noqa: E402,F401
+from .read import BeamLMDecoded, BeamLMReading, CharLM, char_lm_score_host, ctc_beam_lm_read_host, lm_limits  # noqa: E402,F401

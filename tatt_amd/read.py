@@ -13,6 +13,8 @@ passed in as a callable):
 * `ctc_greedy_read_host`: greedy CTC that says how sure it is (probabilities in float64).
 * `ctc_beam_read_host`: the CTC prefix beam search (N best strings, each with the log-probability summed over its alignments in float64),
   `ctc_string_logp_host`: the exact CTC log-probability of one string.
+* `CharLM`, `char_lm_score_host`, `ctc_beam_lm_read_host`: a character n-gram model and the beam search with it fused in (shallow
+  fusion: every step ranks by acoustic mass + LM term; the specification of tatt_ctc_beam_lm_read, `LineReader(decode="beam", lm=...)`).
 * `read_plan`: buckets, descriptor rows and float offsets -- the host half shared by both paths.
 * `read_lines_host`: the composition.
 `LineReader` is the device path: one tatt_line_luma launch for all lines of a call, per bucket chunk the folded eval forward of the
@@ -42,6 +44,8 @@ Reading = namedtuple("Reading", "text conf chars char_conf steps rw squeezed")
 Decoded = namedtuple("Decoded", "classes steps char_conf conf")
 BeamReading = namedtuple("BeamReading", "text logp alternatives rw squeezed")
 BeamDecoded = namedtuple("BeamDecoded", "entries flag margin reentry", defaults=(None, None))
+BeamLMReading = namedtuple("BeamLMReading", "text logp lm score alternatives rw squeezed")
+BeamLMDecoded = namedtuple("BeamLMDecoded", "entries flag margin reentry reranked", defaults=(None, None, None))
 LexiconReading = namedtuple("LexiconReading", "text logp posterior alternatives rw squeezed")
 LexiconDecoded = namedtuple("LexiconDecoded", "entries logz flag margin", defaults=(None,))
 WordsDecoded = namedtuple("WordsDecoded", "words logp flag")          # words: [(the caller's word index, first step, last step)]
@@ -336,6 +340,214 @@ class Lexicon:
         if device not in self._dev:
             self._dev[device] = (torch.from_numpy(self.codes).to(device), torch.from_numpy(self.table).to(device))
         return self._dev[device]
+
+
+class CharLM:
+    """A character n-gram language model for the beam search (`ctc_beam_lm_read_host`, `LineReader(decode="beam", lm=...)`).
+
+    `logp`: a float64 array of shape (C,) * order, 1 <= order <= 3, 2 <= C <= 64 (`lm_limits`): logp[h_1, .., h_{order-1}, c] is the
+    log-probability of class c after the history h, the most recent class LAST; history class 0 stands for "before the line begins",
+    c = 0 in the last axis for "the line ends here".  Every value must be finite (a smoothed model has no zeros): ValueError
+    otherwise, and for a wrong shape or an order or class count outside the limits.  `alphabet` (default: the reader's,
+    "-" + io.ALPHABET) names the classes for `from_corpus`; one that is given must have C characters."""
+    ORDER, CLASSES = 3, 64                                           # tatt_lm_limits, stated here so that a model needs no library
+    STEPS = 256                                                      # most steps of a line (read_limits), so most characters of a string
+
+    def __init__(self, logp, alphabet=None):
+        import numpy as np
+        try:
+            a = np.array(logp, dtype=np.float64)
+        except (TypeError, ValueError):
+            raise ValueError("CharLM: logp is a float64 array of shape (C,) * order") from None
+        if not 1 <= a.ndim <= self.ORDER:
+            raise ValueError("CharLM: an order of 1 .. %d expected (logp has shape (C,) * order); got %d axes" % (self.ORDER, a.ndim))
+        C = a.shape[-1]
+        if any(n != C for n in a.shape) or not 2 <= C <= self.CLASSES:
+            raise ValueError("CharLM: logp has shape (C,) * order with 2 <= C <= %d; got %s" % (self.CLASSES, a.shape))
+        if not bool(np.isfinite(a).all()):
+            raise ValueError("CharLM: every log-probability must be finite (smooth the model: it has no zeros)")
+        if alphabet is not None and len(str(alphabet)) != C:
+            raise ValueError("CharLM: the alphabet %r has %d classes, logp %d" % (str(alphabet), len(str(alphabet)), C))
+        a.setflags(write=False)
+        self.logp, self.order, self.n_classes = a, a.ndim, int(C)
+        self.alphabet = str(alphabet) if alphabet is not None else _alphabet() if len(_alphabet()) == C else None
+
+    @classmethod
+    def from_corpus(cls, strings, order: int = 3, alphabet=None, smoothing: float = 1.0):
+        """Count and smooth: every string is lower-cased and mapped through the alphabet (ValueError, naming the string, for a character
+        outside it); n-grams of every order up to `order` are counted with begin padding (class 0) and ONE end event (class 0) per
+        string.  P_0(c) = 1 / C and P_n(c | h) = (count(h, c) + smoothing P_{n-1}(c | h')) / (count(h) + smoothing), h' = h without its
+        oldest class; in float64, in this order, so the table is deterministic and every row sums to 1."""
+        import math
+
+        import numpy as np
+        if isinstance(strings, str):
+            raise ValueError("CharLM.from_corpus takes a list of strings, not one string")
+        alphabet = _alphabet() if alphabet is None else str(alphabet)
+        C = len(alphabet)
+        if not (isinstance(order, int) and 1 <= order <= cls.ORDER) or not 2 <= C <= cls.CLASSES:
+            raise ValueError("CharLM.from_corpus: 1 <= order <= %d and 2 <= classes <= %d expected; got order = %r, %d classes"
+                             % (cls.ORDER, cls.CLASSES, order, C))
+        smoothing = float(smoothing)
+        if not (math.isfinite(smoothing) and smoothing > 0.0):
+            raise ValueError("CharLM.from_corpus: smoothing is a positive finite float; got %r" % (smoothing,))
+        a2d = {ch: i for i, ch in enumerate(alphabet) if i >= 1}
+        counts = [np.zeros((C,) * n, np.float64) for n in range(1, order + 1)]
+        for s in strings:
+            low = str(s).lower()
+            for ch in low:
+                if ch not in a2d:
+                    raise ValueError("CharLM.from_corpus: the string %r has the character %r, which the alphabet %r lacks"
+                                     % (s, ch, alphabet[1:]))
+            padded = [0] * (order - 1) + [a2d[ch] for ch in low] + [0]
+            for i in range(order - 1, len(padded)):
+                for n in range(1, order + 1):
+                    counts[n - 1][tuple(padded[i - n + 1:i + 1])] += 1.0
+        p = np.full((), 1.0 / C, np.float64)
+        for cnt in counts:
+            p = (cnt + smoothing * p) / (cnt.sum(-1, keepdims=True) + smoothing)       # (p broadcasts over the new, oldest class)
+        return cls(np.log(p), alphabet)
+
+    def increments(self, weight: float = 0.5, bonus: float = 0.0):
+        """-> the table W the decoders add, float64, the shape of `logp`: W[h, c] = weight logp[h, c] + bonus for c >= 1 (a character),
+        W[h, 0] = weight logp[h, 0] (the end of the line gets no bonus).  Worked out ONCE here, in numpy; the host specification and the
+        device read this table and only ever add its entries.  ValueError, too, where max |W| x (256 + 1) is not finite: the sum over
+        the longest line and its end term must not overflow."""
+        import math
+
+        import numpy as np
+        try:
+            weight, bonus = float(weight), float(bonus)
+        except (TypeError, ValueError):
+            raise ValueError("CharLM.increments: weight and bonus are finite floats; got %r, %r" % (weight, bonus)) from None
+        if not (math.isfinite(weight) and math.isfinite(bonus)):
+            raise ValueError("CharLM.increments: weight and bonus are finite floats; got %r, %r" % (weight, bonus))
+        with np.errstate(over="ignore"):
+            w = np.float64(weight) * self.logp
+            out = w + np.float64(bonus)
+        out[..., 0] = w[..., 0]
+        # a line adds at most STEPS entries and the end term: that sum must stay finite whatever the string, or a score could become
+        # +-inf and, added to an acoustic -inf, a NaN
+        if not bool(np.isfinite(out).all()) or not np.isfinite(float(np.abs(out).max()) * (self.STEPS + 1)):
+            raise ValueError("CharLM.increments: with weight = %r and bonus = %r the LM term of a line of %d characters is not finite"
+                             % (weight, bonus, self.STEPS))
+        return np.ascontiguousarray(out)
+
+
+def lm_limits():
+    """tatt_lm_limits: {'order', 'classes'}: the largest order and the most classes of a `CharLM` table the beam kernel takes.  A
+    host-only entry: needs no GPU."""
+    from ._lib import LIB
+    out = (ctypes.c_int * 2)()
+    if LIB.tatt_lm_limits(out) != 0:
+        raise RuntimeError("tatt_lm_limits failed")
+    return dict(zip(("order", "classes"), (int(v) for v in out)))
+
+
+def _lm_row(W, prefix, order):
+    """the row of the nested-list table W (`order` axes) that `prefix` selects: its last order - 1 classes, left-padded with 0"""
+    if order == 1:
+        return W
+    if order == 2:
+        return W[prefix[-1] if prefix else 0]
+    return W[prefix[-2] if len(prefix) > 1 else 0][prefix[-1] if prefix else 0]
+
+
+def char_lm_score_host(W, classes):
+    """W: the increments table of `CharLM.increments`; classes: a string as class ids >= 1 -> (the left-to-right sum, from 0.0, of
+    W[h(prefix), c] over the string's characters, the end term W[h(string), 0]); h(p): the last order - 1 classes of p, left-padded
+    with 0.  Python floats: float64."""
+    import numpy as np
+    W = np.asarray(W, np.float64)
+    classes = [int(c) for c in classes]
+    if not 1 <= W.ndim <= CharLM.ORDER or any(not 1 <= c < W.shape[-1] for c in classes):
+        raise ValueError("char_lm_score_host: a table of 1 .. %d axes and class ids 1 .. %d expected" % (CharLM.ORDER, W.shape[-1] - 1))
+    Wl, total = W.tolist(), 0.0
+    for i, c in enumerate(classes):
+        total = total + _lm_row(Wl, classes[:i], W.ndim)[c]
+    return total, _lm_row(Wl, classes, W.ndim)[0]
+
+
+def ctc_beam_lm_read_host(logits, lm: CharLM, beam: int = 8, nbest: int = 4, weight: float = 0.5, bonus: float = 0.0,
+                          details: bool = False, real=None):
+    """`ctc_beam_read_host` with a character n-gram model fused into the search (shallow fusion), the specification of
+    tatt_ctc_beam_lm_read.  W = lm.increments(weight, bonus).  Every beam entry carries one more number, `lm`, 0.0 for the initial
+    empty prefix:
+      stay      lm' = lm (an extension that spells a prefix already in the beam adds acoustically into that prefix's stay candidate, as
+                in the plain search; the LM term is that prefix's own -- a function of the string alone, summed in the same order);
+      extend    rank r by c: lm' = lm_r + W[h(prefix_r), c].
+    A candidate whose lse(pb', pnb') is -inf is none.  The new beam: the `beam` candidates of largest score = lse(pb', pnb') + lm' (first
+    lm' is formed, then the one sum), descending, ties to the lower key r C + c.  After T steps final_i = (tot_i + lm_i) +
+    W[h(prefix_i), 0]; the beam is re-ranked by final, descending, ties to the lower rank, and the first `nbest` are returned:
+    BeamLMDecoded(entries=[(classes, logp, lm)], flag): logp the ACOUSTIC mass lse(pb, pnb), lm the LM term with the end term.
+    Flagged lines as in the plain search.  details=True adds `margin` (the smallest gap between a kept and a dropped score over all
+    steps, and between neighbours of the final list up to and including the first entry not returned), `reentry` (as in the plain
+    search) and `reranked` (whether the end term changed the order of the beam).  `real` as in the plain search; the LM term is float64
+    under both settings, since it is data.
+    The default weight and bonus are the usual shallow-fusion convention; they are not tuned on anything."""
+    beam, nbest = int(beam), int(nbest)
+    if not 1 <= nbest <= beam:
+        raise ValueError("ctc_beam_lm_read_host: 1 <= nbest <= beam expected; got beam = %r, nbest = %r" % (beam, nbest))
+    if not isinstance(lm, CharLM):
+        raise ValueError("ctc_beam_lm_read_host: lm is a CharLM; got %r" % (type(lm).__name__,))
+    T, B, C, rows = _beam_rows(logits, "ctc_beam_lm_read_host")
+    if lm.n_classes != C:
+        raise ValueError("ctc_beam_lm_read_host: the language model has %d classes, the logits %d" % (lm.n_classes, C))
+    W = lm.increments(weight, bonus).tolist()
+    real, exp, log, lse = _beam_real(real)
+    neg, inf = real("-inf"), float("inf")
+    out = []
+    for row in rows:
+        lps = [_log_softmax_row(x, real, exp, log) for x in row]
+        if any(lp is None for lp in lps):
+            out.append(BeamLMDecoded([], 1, inf, False, False) if details else BeamLMDecoded([], 1))
+            continue
+        cur, margin, reentry = [((), real(0.0), neg, real(0.0), 0.0)], inf, False    # (prefix, pb, pnb, tot, lm), by rank
+        for lp in lps:
+            where = {e[0]: r for r, e in enumerate(cur)}
+            child = {}                                               # (rank of the parent, class) -> rank of that string in the beam
+            for r, e in enumerate(cur):
+                q = where.get(e[0][:-1]) if e[0] else None
+                if q is not None:
+                    child[(q, e[0][-1])] = r
+            stay = [[e[3] + lp[0], e[2] + lp[e[0][-1]] if e[0] else neg] for e in cur]
+            cands = []                                               # (score, key, pb', pnb', tot', lm')
+            for r, (p, pb, pnb, tot, l) in enumerate(cur):
+                last = p[-1] if p else -1
+                w = _lm_row(W, p, lm.order)
+                for c in range(1, C):
+                    v = (pb if c == last else tot) + lp[c]
+                    q = child.get((r, c))
+                    if q is not None:
+                        stay[q][1] = lse(stay[q][1], v)
+                    elif v != neg:
+                        l2 = l + w[c]
+                        cands.append((v + l2, r * C + c, neg, v, v, l2))
+            for r, (a, b) in enumerate(stay):
+                v = lse(a, b)
+                if v != neg:
+                    cands.append((v + cur[r][4], r * C, a, b, v, cur[r][4]))
+            cands.sort(key=lambda e: (-e[0], e[1]))
+            if len(cands) > beam:
+                margin = min(margin, float(cands[beam - 1][0] - cands[beam][0]))
+            new = []
+            for s, key, a, b, v, l in cands[:beam]:
+                r, c = divmod(key, C)
+                new.append((cur[r][0] + (c,) if c else cur[r][0], a, b, v, l))
+            if details:
+                for e in new:
+                    p = e[0]
+                    if p not in where and any(len(o) > len(p) and o[:len(p)] == p for o in where):
+                        reentry = True
+            cur = new
+        ends = [_lm_row(W, e[0], lm.order)[0] for e in cur]
+        final = [(e[3] + e[4]) + w for e, w in zip(cur, ends)]
+        order = sorted(range(len(cur)), key=lambda i: (-final[i], i))
+        for i in range(min(nbest, len(cur) - 1)):
+            margin = min(margin, float(final[order[i]] - final[order[i + 1]]))
+        entries = [(list(cur[i][0]), cur[i][3], cur[i][4] + ends[i]) for i in order[:nbest]]
+        out.append(BeamLMDecoded(entries, 0, margin, reentry, order != list(range(len(cur)))) if details else BeamLMDecoded(entries, 0))
+    return out
 
 
 def ctc_lexicon_scores_host(logits, lexicon: Lexicon, real=None):
@@ -711,6 +923,79 @@ def _beam_reading(dec: BeamDecoded, rw: int, squeezed: bool) -> BeamReading:
     return BeamReading(text, logp, alts, rw, squeezed)
 
 
+def beam_lm_entry_words(cap: int) -> int:
+    """32-bit words of one entry of a beam record row with a language model: the float64 logp (2), the float64 lm (2), the length, a
+    pad word, then `cap` classes, rounded up to an even count"""
+    return 6 + int(cap) + (int(cap) & 1)
+
+
+def beam_lm_record_words(cap: int, nbest: int) -> int:
+    """32-bit words of such a row for `nbest` entries: [0] entries written, [1] flag, then the entries"""
+    return 2 + int(nbest) * beam_lm_entry_words(cap)
+
+
+def ctc_beam_lm_read(logits, table_dev, order: int, index, record, cap: int, beam: int = 8, nbest: int = 4):
+    """ONE tatt_ctc_beam_lm_read launch: `ctc_beam_read` with the increments table of a `CharLM` on the device: table_dev a contiguous
+    float64 tensor of C^order entries (`torch.from_numpy(lm.increments(weight, bonus))`, flat or in its own shape), record
+    (n_rows, >= beam_lm_record_words(cap, nbest)) int32 (see `parse_beam_lm_records`).  ValueError for what the entry refuses (what
+    `ctc_beam_read` refuses, an order outside lm_limits(), a table whose class count differs from the logits', the row width), before
+    any launch."""
+    from . import ops
+    from ._lib import LIB
+    ops._check_dev(logits)
+    T, B, C = logits.shape
+    if record.dtype != torch.int32 or record.dim() != 2 or record.stride(1) != 1 or index.dtype != torch.int32 or index.numel() < B:
+        raise ValueError("ctc_beam_lm_read: record must be a 2-D int32 tensor with contiguous rows, index an int32 tensor of B entries")
+    _check_beam("ctc_beam_lm_read", beam, nbest, beam_limits()["beam"])
+    lim = lm_limits()
+    if not (isinstance(order, int) and 1 <= order <= lim["order"]):
+        raise ValueError("ctc_beam_lm_read: an order of 1 .. %d expected; got %r" % (lim["order"], order))
+    if not (isinstance(table_dev, torch.Tensor) and table_dev.dtype == torch.float64 and table_dev.is_contiguous() and
+            table_dev.device == logits.device and table_dev.numel() > 0):
+        raise ValueError("ctc_beam_lm_read: the table is a contiguous float64 tensor on %s" % (logits.device,))
+    classes = next((k for k in range(1, lim["classes"] + 1) if k ** order == table_dev.numel()), 0)
+    if classes != C or (table_dev.dim() > 1 and tuple(table_dev.shape) != (C,) * order):
+        raise ValueError("ctc_beam_lm_read: a table of %s entries at order %d is none for the %d classes of the logits"
+                         % (tuple(table_dev.shape), order, C))
+    if record.shape[1] < beam_lm_record_words(cap, nbest):
+        raise ValueError("ctc_beam_lm_read: rows of %d words; cap = %d and nbest = %d need %d" % (record.shape[1], cap, nbest,
+                                                                                                beam_lm_record_words(cap, nbest)))
+    rc = LIB.tatt_ctc_beam_lm_read(ops.P(logits), *logits.stride(), T, B, C, beam, nbest, ops.P(table_dev), order, classes, ops.P(index),
+                                   ops.P(record), record.shape[0], int(cap), record.stride(0), ops.stream())
+    if rc == 1:
+        raise ValueError("tatt_ctc_beam_lm_read refuses T = %d, C = %d, beam = %d, nbest = %d, order = %d, cap = %d, rows of %d words"
+                         % (T, C, beam, nbest, order, cap, record.stride(0)))
+    if rc != 0:
+        raise RuntimeError("tatt_ctc_beam_lm_read failed with code %d" % rc)
+    return record
+
+
+def parse_beam_lm_records(record, cap: int, nbest: int):
+    """record: the (n, >= beam_lm_record_words(cap, nbest)) int32 HOST tensor tatt_ctc_beam_lm_read filled -> one BeamLMDecoded per row.
+    Row, in 32-bit words: [0] entries written (<= nbest)  [1] flag  then per entry, beam_lm_entry_words(cap) words: the float64 logp
+    (the acoustic mass) and the float64 lm (the LM term with the end term) as they are, low word first, the length, a pad word, `cap`
+    classes padded with -1."""
+    import struct
+    es, out = beam_lm_entry_words(cap), []
+    for row in record.tolist():
+        n, flag = row[0], row[1]
+        if not 0 <= n <= nbest or flag not in (0, 1):
+            raise ValueError("parse_beam_lm_records: no beam record row: entries = %r, flag = %r" % (n, flag))
+        entries = []
+        for i in range(n):
+            e = row[2 + i * es:2 + (i + 1) * es]
+            entries.append((e[6:6 + e[4]],) + struct.unpack("<dd", struct.pack("<iiii", *e[:4])))
+        out.append(BeamLMDecoded(entries, flag))
+    return out
+
+
+def _beam_lm_reading(dec: BeamLMDecoded, rw: int, squeezed: bool) -> BeamLMReading:
+    d2a = _alphabet()
+    alts = [("".join(d2a[c] for c in classes), logp, lm) for classes, logp, lm in dec.entries]
+    text, logp, lm = alts[0] if alts else ("", float("nan"), float("nan"))
+    return BeamLMReading(text, logp, lm, logp + lm, alts, rw, squeezed)
+
+
 def lexicon_limits():
     """tatt_lexicon_limits: {'steps', 'classes', 'length', 'words', 'nbest'}: most steps T and classes C of tatt_ctc_lexicon_score, the
     longest word and most words of a lexicon, most entries of tatt_ctc_lexicon_select.  A host-only entry: needs no GPU."""
@@ -886,13 +1171,15 @@ def parse_words_records(record, cap: int):
 
 
 class PendingReading:
-    """What `LineReader.read` started.  `result()` is the only host wait: -> one Reading (decode="beam": one BeamReading,
+    """What `LineReader.read` started.  `result()` is the only host wait: -> one Reading (decode="beam": one BeamReading, with lm=: one
+    BeamLMReading (text, logp: the acoustic mass, lm: the LM term, score = logp + lm, alternatives [(text, logp, lm)]),
     decode="lexicon": one LexiconReading) per line, in input order.  With keep_logits: `logits` [(line indices of the chunk, its
     (T, n, C) logits on the device)]; with keep_scores (lexicon): `scores` [(line indices, the chunk's (n, K) float64 scores)].
     decode="words": one WordsReading per line (`texts()`: the words joined by spaces); with keep_lp: `lp` [(line indices, the chunk's
     (n, T, C) float64 log-soft-max on the device)]."""
 
-    def __init__(self, host, event, cap, plan, logits=None, nbest=None, lexicon=None, scores=None, words=False, lp=None):
+    def __init__(self, host, event, cap, plan, logits=None, nbest=None, lexicon=None, scores=None, words=False, lp=None, lm=False):
+        self._lm = bool(lm)                                          # beam records with a language-model term
         self._host, self._event, self._cap, self._plan, self.logits, self._out = host, event, cap, plan, logits, None
         self._nbest = nbest                                          # None: greedy records
         self._lexicon, self.scores = lexicon, scores                 # a Lexicon: lexicon records
@@ -914,6 +1201,10 @@ class PendingReading:
                 self._event.synchronize()
                 self._out = [_lexicon_reading(d, self._lexicon, rw, sq) for d, rw, sq in zip(
                     parse_lexicon_records(self._host, self._nbest), self._plan.rws, self._plan.squeezed)]
+            elif self._lm:
+                self._event.synchronize()
+                self._out = [_beam_lm_reading(d, rw, sq) for d, rw, sq in zip(
+                    parse_beam_lm_records(self._host, self._cap, self._nbest), self._plan.rws, self._plan.squeezed)]
             else:
                 self._event.synchronize()
                 self._out = [_beam_reading(d, rw, sq) for d, rw, sq in zip(parse_beam_records(self._host, self._cap, self._nbest),
@@ -951,6 +1242,10 @@ class LineReader:
     (the CTC prefix beam search, specification `ctc_beam_read_host`), the record buffer is sized for its rows and `result()` gives
     `BeamReading`s: the most probable string, its log-probability summed over its alignments in float64, and the `nbest` best strings
     as `alternatives`.  Everything else of a call is the same; decode="greedy" is the default.
+    decode="beam" with lm = a `CharLM` (lm_weight, default 0.5, lm_bonus, default 0.0: the usual shallow-fusion convention, not tuned on
+    anything): the increments table `lm.increments(lm_weight, lm_bonus)` is built and uploaded once, here, and every chunk gets ONE
+    tatt_ctc_beam_lm_read launch in place of the beam launch (specification `ctc_beam_lm_read_host`); `result()` gives
+    `BeamLMReading`s.  A flagged line reads "" with logp = lm = score = nan.  Without lm= nothing of a call changes.
     decode="lexicon" (with lexicon = a `Lexicon` or a list of words, 1 <= nbest <= 16): every chunk gets the tatt_ctc_lexicon_score
     launches (one per non-empty segment class of the lexicon) into an (n, K) float64 buffer of its own and ONE tatt_ctc_lexicon_select
     launch in place of the greedy one (specification `ctc_lexicon_read_host`); `result()` gives `LexiconReading`s: the most probable
@@ -966,7 +1261,7 @@ class LineReader:
 
     def __init__(self, crnn, batch_size: int = 48, device=None, keep_logits: bool = False, w: int = 64, decode: str = "greedy",
                  beam: int = 8, nbest: int = 4, lexicon=None, keep_scores: bool = False, word_penalty: float = 0.0,
-                 keep_lp: bool = False):
+                 keep_lp: bool = False, lm=None, lm_weight=None, lm_bonus=None):
         from . import functional as Fh
         from .infer import _check_module, _crnn_folds
         if decode not in ("greedy", "beam", "lexicon", "words"):
@@ -989,6 +1284,24 @@ class LineReader:
             _check_beam("LineReader", beam, nbest, beam_limits()["beam"])
             if lexicon is not None:
                 raise ValueError("LineReader: lexicon= goes with decode='lexicon' or decode='words'; got decode = %r" % (decode,))
+        if lm is None:
+            if lm_weight is not None or lm_bonus is not None:
+                raise ValueError("LineReader: lm_weight= and lm_bonus= go with lm=, a CharLM")
+            table, self.lm_weight, self.lm_bonus = None, None, None
+        else:
+            if decode != "beam":
+                raise ValueError("LineReader: lm= goes with decode='beam'; got decode = %r" % (decode,))
+            if not isinstance(lm, CharLM):
+                raise ValueError("LineReader: lm is a CharLM; got %r" % (type(lm).__name__,))
+            emits = _emitted_classes(crnn)
+            if emits is not None and lm.n_classes != emits:
+                raise ValueError("LineReader: the language model has %d classes, the CRNN emits %d" % (lm.n_classes, emits))
+            try:
+                self.lm_weight, self.lm_bonus = 0.5 if lm_weight is None else float(lm_weight), 0.0 if lm_bonus is None else float(lm_bonus)
+                table = lm.increments(self.lm_weight, self.lm_bonus)
+            except (TypeError, ValueError):
+                raise ValueError("LineReader: lm_weight and lm_bonus are finite floats; got %r, %r" % (lm_weight, lm_bonus)) from None
+        self.lm = lm
         self.decode, self.beam, self.nbest, self.lexicon, self.keep_scores = decode, beam, nbest, lexicon, bool(keep_scores)
         self.word_penalty, self.keep_lp = word_penalty, bool(keep_lp)
         _check_module(crnn, "reader CRNN")
@@ -1002,6 +1315,7 @@ class LineReader:
         self._limits = read_limits()
         if lexicon is not None:
             lexicon.device(self.device)                              # (the one upload of the packed words: no `read` makes it)
+        self._lm_table = None if table is None else torch.from_numpy(table).to(self.device)          # (likewise: the one upload)
         with torch.cuda.device(self.device), torch.no_grad():
             Fh.sticky_word(self.device)
             self._folds = _crnn_folds(crnn)
@@ -1070,7 +1384,9 @@ class LineReader:
             luma = torch.empty(plan.floats, dtype=torch.float32, device=self.device)
             line_luma(dev_bytes, head_dev, plan.desc, luma)
             beam, lex, wrd = self.decode == "beam", self.decode == "lexicon", self.decode == "words"
-            words = beam_record_words(cap, self.nbest) if beam else lexicon_record_words(self.nbest) if lex else \
+            fused = beam and self._lm_table is not None
+            words = beam_lm_record_words(cap, self.nbest) if fused else beam_record_words(cap, self.nbest) if beam else \
+                lexicon_record_words(self.nbest) if lex else \
                 words_record_words(cap) if wrd else 3 * cap + 2
             kept_scores = [] if lex and self.keep_scores else None
             kept_lp = [] if wrd and self.keep_lp else None
@@ -1082,7 +1398,9 @@ class LineReader:
                 for i in range(0, len(idx), chunk):
                     m = min(chunk, len(idx) - i)
                     logits = self.forward(x[i:i + m])
-                    if beam:
+                    if fused:
+                        ctc_beam_lm_read(logits, self._lm_table, self.lm.order, index[pos:pos + m], record, cap, self.beam, self.nbest)
+                    elif beam:
                         ctc_beam_read(logits, index[pos:pos + m], record, cap, self.beam, self.nbest)
                     elif lex:
                         scores = torch.empty(m, len(self.lexicon), dtype=torch.float64, device=self.device)
@@ -1106,4 +1424,4 @@ class LineReader:
             ev = torch.cuda.Event()
             ev.record()
         return PendingReading(host, ev, cap, plan, kept, self.nbest if beam or lex else None, self.lexicon if lex or wrd else None, kept_scores,
-                              wrd, kept_lp)
+                              wrd, kept_lp, fused)
