@@ -1046,6 +1046,29 @@ int tatt_ctc_lexicon_select(const double* scores, long st_sc, int B, int K, int 
                             long st_rec, hipStream_t st);
 /* out[0..4]: most steps T, most classes C, the longest word, most words K of a lexicon and most entries nbest.  Host only: needs no GPU. */
 int tatt_lexicon_limits(int* out);
+/* Per-line lexicons (csrc/ctclexp.hip; specification read.ctc_line_lexicons_read_host): every image b of the chunk has a list of words of
+ * its own, and exactly the listed (image, word) pairs are scored.  codes / words: the UNION of all lists packed as tatt_ctc_lexicon_score
+ * takes a list (U rows of 4 ints [length, offset of its codes, union index, 0]).  tiles: n_tiles rows of 4 ints
+ *   [0] image b of the chunk  [1] segment class G = 16, 32 or 64  [2] first pair  [3] pairs of the tile, 1 .. 256 / G
+ * pairs: n_pairs rows of 2 ints [0] the word's row in `words`  [1] j, its position in the image's own list; counts: B ints, the words of
+ * every image's list.  ONE launch, one work-group per tile, which meets no other: scores[b * st_sc + j] = the exact CTC log-probability
+ * of the pair's word under the logits of image b, bit for bit what tatt_ctc_lexicon_score writes for that word and image (NaN for every
+ * pair of a flagged image, and for a word whose length, code offset or codes are out of range).  A tile whose image, class or pair range
+ * is out of range, a pair whose word row is outside 0 .. U - 1 or whose j is outside 0 .. min(counts[b], max_count) - 1 writes nothing.
+ * Returns 1 before any launch for: a null pointer, T outside 1 .. 256, C outside 1 .. 64, B outside 1 .. 65535, U outside 1 .. 1048576,
+ * n_codes < 0, n_tiles <= 0, n_pairs <= 0, n_tiles > n_pairs, n_pairs > 65536 B, max_count outside 1 .. 65536, st_sc < max_count. */
+int tatt_ctc_lexicon_score_pairs(const float* logits, long st_t, long st_b, long st_c, int T, int B, int C, const int* codes, int n_codes,
+                                 const int* words, int U, const int* tiles, int n_tiles, const int* pairs, int n_pairs, const int* counts,
+                                 int max_count, double* scores, long st_sc, hipStream_t st);
+/* tatt_ctc_lexicon_select with a count per image: image b has K_b = counts[b] scores, 0 <= K_b <= min(st_sc, 65536) (an image whose
+ * count is outside that writes nothing).  The record row, the order of the entries and the 64 bits of logz are what
+ * tatt_ctc_lexicon_select gives a (1, K_b) buffer.  K_b = 0: entries 0, flag 0, logz = -inf; flag 1 needs K_b >= 1 and every score a NaN.
+ * Returns 1 before any launch for: a null pointer, B or n_rows <= 0, st_sc < 1, nbest outside 1 .. 16, st_rec < 4 + 4 nbest. */
+int tatt_ctc_lexicon_select_rows(const double* scores, long st_sc, int B, const int* counts, int nbest, const int* index, int* record,
+                                 int n_rows, long st_rec, hipStream_t st);
+/* out[0..5]: most steps T, most classes C, the longest word, most words of ONE image's list, most distinct words of all lists (the
+ * union) and most entries nbest.  Host only: needs no GPU. */
+int tatt_line_lexicons_limits(int* out);
 /* Word segmentation (csrc/ctcwords.hip; specification read.ctc_words_host): the most probable ALIGNMENT of image b whose collapsed
  * string is a sequence of words of the closed list (of length >= 1), with the steps every word spans -- token passing in float64 over
  * lp = log-soft-max of the logits (T,B,C) fp32 given by element strides, blank 0.  codes / words / K / k16 / k32 / k64: the packed list

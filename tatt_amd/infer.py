@@ -774,7 +774,14 @@ class SuperResolver:
     `readings()` gives `read.LexiconReading`s (text, logp, posterior, alternatives); every text is a word of the list.
     read_decode="words" (read_lexicon, read_word_penalty = a finite float) reads every line as a SEQUENCE of list words: per chunk one
     tatt_ctc_words_read launch in place of the greedy one, `readings()` gives `read.WordsReading`s (text: the words joined by spaces,
-    logp, words: one `read.WordSpan` per word with its steps and columns) and `texts()` the space-joined strings."""
+    logp, words: one `read.WordSpan` per word with its steps and columns) and `texts()` the space-joined strings.
+    read_decode="lexicons" (read_nbest <= 16) reads every line against a list of words of its OWN: the call (`__call__` with
+    long_lines, `scene`, `scene_quads`, `scene_polys`) takes the keyword lexicons = a `read.LineLexicons` or one list of words per image,
+    box, quad or polygon, in input order (an empty list is legal: that line reads "").  Per call one more host-to-device copy (the
+    union of the lists and every chunk's tables), per chunk ONE tatt_ctc_lexicon_score_pairs launch and ONE
+    tatt_ctc_lexicon_select_rows launch in place of the greedy one; `readings()` gives `read.LexiconReading`s whose text and
+    alternatives are words of the line's own list and whose posterior is taken among them.  ValueError before anything is enqueued for
+    a wrong number of lists, a call without the keyword, and the keyword on an instance with another read_decode."""
 
     def __init__(self, generator, prior=None, recognizer=None, batch_size: int = 48, lr_size=(16, 64), mask: bool = True,
                  rule: str = "floor", keep_sr: bool = False, long_lines: bool = False, stride: int = 32, reader=None,
@@ -831,14 +838,24 @@ class SuperResolver:
         ev.record()
         return host, ev
 
-    def __call__(self, images, out_sizes=None) -> PendingUpscale:
+    def _lexicons(self, who, lexicons, n):
+        """the `lexicons=` keyword of a call over n lines, checked before anything is enqueued -> a `read.LineLexicons` or None"""
+        if self.reader is None:
+            if lexicons is not None:
+                raise ValueError("SuperResolver.%s: lexicons= needs an instance with reader=crnn, read_decode='lexicons'" % who)
+            return None
+        return self.reader.check_lexicons(lexicons, n, "SuperResolver.%s" % who)
+
+    def __call__(self, images, out_sizes=None, lexicons=None) -> PendingUpscale:
         images = list(images)
         if out_sizes is not None:
             out_sizes = [tuple(s) for s in out_sizes]
             if len(out_sizes) != len(images):
                 raise ValueError("%d out_sizes for %d images" % (len(out_sizes), len(images)))
         if self.long_lines:
-            return self._lines(images, out_sizes)
+            return self._lines(images, out_sizes, self._lexicons("__call__", lexicons, len(images)))
+        if lexicons is not None:
+            raise ValueError("SuperResolver: lexicons= reads tiled lines (long_lines=True, scene, scene_quads, scene_polys)")
         if self.reader is not None and self.rec is None:
             raise ValueError("SuperResolver: reader= reads tiled lines (long_lines=True, scene, scene_quads); a plain call squeezes every "
                              "crop into the LR size: pass recognizer= for its texts, or build the instance with long_lines=True")
@@ -861,7 +878,7 @@ class SuperResolver:
         from .tsrn import UpsampleBLock
         return 2 ** sum(isinstance(m, UpsampleBLock) for m in self.gen.modules())
 
-    def scene(self, image, boxes, feather: int = 0) -> PendingScene:
+    def scene(self, image, boxes, feather: int = 0, lexicons=None) -> PendingScene:
         """A whole picture: image: an RGB PIL image, boxes: integer (x0, y0, x1, y1) rectangles of text in it (`io.scene_check`) ->
         PendingScene whose `result()` (the only host wait) is the RGB PIL image of size (scale * Ws, scale * Hs): the bicubic up-scale of
         the picture with every box replaced by its super-resolved text, later boxes over earlier ones; feather = F > 0 fades the outer F
@@ -872,9 +889,9 @@ class SuperResolver:
         windows.  No boxes: the up-scaled picture, no session runs.  Not with a recogniser (ValueError)."""
         from .io import scene_layers
         return self._scene("scene", image, boxes, feather, self.collator.scene_windows, self.exporter.scene,
-                           lambda b: tuple(int(v) for v in b), scene_layers)
+                           lambda b: tuple(int(v) for v in b), scene_layers, lexicons)
 
-    def scene_quads(self, image, quads, feather: int = 0) -> PendingScene:
+    def scene_quads(self, image, quads, feather: int = 0, lexicons=None) -> PendingScene:
         """`scene` for a detector's QUADRILATERALS: image: an RGB PIL image, quads: four integer corner points per text instance,
         top-left, top-right, bottom-right, bottom-left in reading direction (`io.quad_check`) -> PendingScene whose `result()` (the only
         host wait) is the RGB PIL image of size (scale * Ws, scale * Hs): the bicubic up-scale of the picture with every quad replaced by
@@ -887,9 +904,9 @@ class SuperResolver:
         `boxes` are the checked quads and `layers` their paste layers (`io.quad_layers`)."""
         from .io import quad_layers
         return self._scene("scene_quads", image, quads, feather, self.collator.quad_windows, self.exporter.scene_quads,
-                           lambda q: tuple((int(x), int(y)) for x, y in q), quad_layers)
+                           lambda q: tuple((int(x), int(y)) for x, y in q), quad_layers, lexicons)
 
-    def scene_polys(self, image, polys, feather: int = 0) -> PendingScene:
+    def scene_polys(self, image, polys, feather: int = 0, lexicons=None) -> PendingScene:
         """`scene_quads` for a detector's POLYGONS, curved text: image: an RGB PIL image, polys: 2 N integer points per text instance,
         2 <= N <= 8, N along the top of the text in reading direction, then N back along the bottom (`io.poly_check`; N = 2 is a quad)
         -> PendingScene whose `result()` (the only host wait) is the RGB PIL image of size (scale * Ws, scale * Hs): the bicubic up-scale
@@ -903,9 +920,9 @@ class SuperResolver:
         the checked polygons and `layers` their paste layers (`io.poly_layers`)."""
         from .io import poly_layers
         return self._scene("scene_polys", image, polys, feather, self.collator.poly_windows, self.exporter.scene_polys,
-                           lambda q: tuple((int(x), int(y)) for x, y in q), poly_layers)
+                           lambda q: tuple((int(x), int(y)) for x, y in q), poly_layers, lexicons)
 
-    def _scene(self, who, image, boxes, feather, windows, export, norm, layers) -> PendingScene:
+    def _scene(self, who, image, boxes, feather, windows, export, norm, layers, lexicons=None) -> PendingScene:
         """`scene`, `scene_quads` and `scene_polys` (`who`): windows = the collator's method that cuts them, export = the exporter's that
         pastes them, norm(box) = a box as the PendingScene keeps it, layers(boxes) = their paste layers"""
         from .io import line_plan
@@ -916,12 +933,13 @@ class SuperResolver:
         h, w = self.lr_size
         line_plan((w, h), self.lr_size, self.stride)                 # (raises for a stride outside [w / 2, w])
         boxes = list(boxes)
+        lexicons = self._lexicons(who, lexicons, len(boxes))
         with torch.cuda.device(self.device):
             stack, lines, scene_dev = windows(image, boxes, self.stride)
             buf, scale = self._run_windows(stack)
             boxes = [norm(b) for b in boxes]                         # (checked by `windows`)
             pending = export(scene_dev, buf, lines, boxes, scale, feather)
-            reading = self._read(pending, scale)
+            reading = self._read(pending, scale, lexicons)
         if not self.keep_sr:
             return PendingScene(pending, reading=reading)
         return PendingScene(pending, buf, stack, lines, boxes, layers(boxes), reading)
@@ -943,12 +961,14 @@ class SuperResolver:
             return None, self._scale()
         return buf, sr_scale(*buf.shape[2:], *self.lr_size)
 
-    def _read(self, pending, scale):
+    def _read(self, pending, scale, lexicons=None):
         """with a reader: its launches on the blended lines of `pending` (a PendingExport of lines / scene / scene_quads), enqueued right
         behind the exporter's on the same stream -- the lines stay where they are until the exporter's next call"""
         if self.reader is None:
             return None
-        return self.reader.read(*pending.line_canvases, scale)
+        if lexicons is None:
+            return self.reader.read(*pending.line_canvases, scale)
+        return self.reader.read(*pending.line_canvases, scale, lexicons=lexicons)
 
     def _session(self, n, fresh):
         """the session of batch size n, captured on first use; refreshed once per call (`fresh`: the sizes this call has met)"""
@@ -970,16 +990,16 @@ class SuperResolver:
             self._zero_tp[n] = torch.zeros(n, 37, 1, 26, device=self.device)
         return self._zero_tp[n]
 
-    def _lines(self, images, out_sizes) -> PendingUpscale:
+    def _lines(self, images, out_sizes, lexicons=None) -> PendingUpscale:
         """the long_lines call: windows of all images -> sessions over batches of windows -> one SR buffer -> one blend launch"""
         with_text = self.reader is not None
         if not images:
-            return PendingUpscale([], with_text, None, reading=self.reader.read(None, [], 1) if with_text else None)
+            return PendingUpscale([], with_text, None, reading=self.reader.read(None, [], 1, lexicons=lexicons) if with_text else None)
         with torch.cuda.device(self.device):
             stack, lines = self.collator.windows(images, self.stride)
             buf, scale = self._run_windows(stack)
             pending = self.exporter.lines(buf, lines, scale, out_sizes=out_sizes)
-            reading = self._read(pending, scale)
+            reading = self._read(pending, scale, lexicons)
         keep = self.keep_sr
         return PendingUpscale([(pending, None, None)], with_text, buf if keep else None, stack if keep else None, lines if keep else None,
                               reading)

@@ -1239,3 +1239,4 @@ from .read import (READ_MAX, READ_QUANTUM, BeamDecoded, BeamReading, Lexicon, Le
                    read_width)
 from .read import WordsDecoded, WordSpan, WordsReading, ctc_words_host, ctc_words_read_host, words_limits  # noqa: E402,F401
 from .read import BeamLMDecoded, BeamLMReading, CharLM, char_lm_score_host, ctc_beam_lm_read_host, lm_limits  # noqa: E402,F401
+from .read import LineLexicons, ctc_line_lexicons_read_host, line_lexicons_limits  # noqa: E402,F401

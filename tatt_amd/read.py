@@ -25,6 +25,9 @@ Reading against a closed list of words: `Lexicon` (the words as class ids, packe
 Reading a line of SEVERAL words against the list: `ctc_words_host` / `ctc_words_read_host` (the specification of csrc/ctcwords.hip: token
 passing, the most probable alignment that spells a sequence of list words, with the steps every word spans); decode="words": one
 tatt_ctc_words_read launch per bucket chunk in place of the greedy one.
+Reading every line against a list of ITS OWN: `LineLexicons` (one list per line, their union packed for the device, `pack` the tile
+table and pairs of a launch), `ctc_line_lexicons_read_host` (the specification); decode="lexicons": per bucket chunk one
+tatt_ctc_lexicon_score_pairs launch and one tatt_ctc_lexicon_select_rows launch of csrc/ctclexp.hip in place of the greedy one.
 """
 from __future__ import annotations
 
@@ -342,6 +345,95 @@ class Lexicon:
         return self._dev[device]
 
 
+class LineLexicons:
+    """One closed list of words PER LINE, in the caller's line order (`ctc_line_lexicons_read_host`, `LineReader(decode="lexicons")`):
+    the 50-words-per-image protocol, a detector's box that arrives with candidates of its own.
+
+    Words are lower-cased and mapped through `alphabet` exactly as `Lexicon` does.  ValueError, naming the line and the word, for a
+    character outside the alphabet, a word longer than `Lexicon.LENGTH`, a duplicate WITHIN one line's list (after lower-casing), a
+    line with more than `Lexicon.WORDS` words and a union of more than `UNION` distinct words.  An EMPTY list is legal: that line
+    reads "".  The same word in several lines' lists is one entry of the union.
+    `lists` the lower-cased words per line, `classes` the same as class ids, `union` the distinct words in order of first appearance,
+    `index` per line the union index of every word; len() the number of lines.  For the device the union is packed like a `Lexicon`:
+    sorted once by segment class (`_segment`), `order` packed position -> union index, `packed` its inverse, `segments` the class of
+    every union word, `codes` the class ids of all union words in packed order, `table` (U, 4) int32 per packed word [length, offset of
+    its codes, union index, 0] (one zero row for an empty union: never an empty buffer).  `pack(lines)` makes the tables of one launch."""
+    UNION = 1048576                                                  # tatt_line_lexicons_limits, stated here so that lists need no library
+
+    def __init__(self, lists, alphabet=None, min_segment: int = 16):
+        import numpy as np
+        if isinstance(lists, str) or any(isinstance(ws, str) for ws in lists):
+            raise ValueError("LineLexicons takes one list of words per line, not strings")
+        self.alphabet = _alphabet() if alphabet is None else str(alphabet)
+        if min_segment not in LEXICON_SEGMENTS:
+            raise ValueError("LineLexicons: min_segment is one of %r; got %r" % (LEXICON_SEGMENTS, min_segment))
+        a2d = {ch: i for i, ch in enumerate(self.alphabet) if i >= 1}
+        self.lists, self.classes, self.index, self.union, where, union_classes = [], [], [], [], {}, []
+        for b, ws in enumerate(lists):
+            ws = [str(w).lower() for w in ws]
+            if len(ws) > Lexicon.WORDS:
+                raise ValueError("LineLexicons: line %d has %d words; at most %d" % (b, len(ws), Lexicon.WORDS))
+            seen, classes, index = set(), [], []
+            for w in ws:
+                if len(w) > Lexicon.LENGTH:
+                    raise ValueError("LineLexicons: line %d: the word %r has %d characters; at most %d" % (b, w, len(w), Lexicon.LENGTH))
+                for ch in w:
+                    if ch not in a2d:
+                        raise ValueError("LineLexicons: line %d: the word %r has the character %r, which the alphabet %r lacks"
+                                         % (b, w, ch, self.alphabet[1:]))
+                if w in seen:
+                    raise ValueError("LineLexicons: line %d: the word %r appears twice (after lower-casing)" % (b, w))
+                seen.add(w)
+                if w not in where:
+                    if len(self.union) == self.UNION:
+                        raise ValueError("LineLexicons: line %d: the word %r is distinct word %d of all lists; at most %d"
+                                         % (b, w, self.UNION + 1, self.UNION))
+                    where[w] = len(self.union)
+                    self.union.append(w)
+                    union_classes.append([a2d[ch] for ch in w])
+                index.append(where[w])
+                classes.append(union_classes[where[w]])
+            self.lists.append(ws)
+            self.classes.append(classes)
+            self.index.append(index)
+        self.min_segment, self.n_classes = int(min_segment), len(self.alphabet)
+        self.segments = [_segment(len(c), self.min_segment) for c in union_classes]
+        self.order = sorted(range(len(self.union)), key=lambda k: (self.segments[k], k))
+        self.packed, self._groups = [0] * len(self.union), {}
+        table, codes = np.zeros((max(1, len(self.union)), 4), np.int32), []
+        for p, k in enumerate(self.order):
+            self.packed[k] = p
+            table[p, :3] = (len(union_classes[k]), len(codes), k)
+            codes += union_classes[k]
+        self.table, self.codes, self.n_codes = table, np.asarray(codes + [0], np.int32), len(codes)
+
+    def __len__(self):
+        return len(self.lists)
+
+    def pack(self, lines):
+        """lines: the input indices of a chunk's lines, in the order of its logits -> (tiles (n_tiles, 4) int32, pairs (n_pairs, 2)
+        int32, counts (len(lines),) int32) as tatt_ctc_lexicon_score_pairs takes them: the pairs of line b (its row in the chunk) are
+        grouped by segment class, within a class by position j in the line's own list; one tile row (b, G, first pair, pairs <= 256 / G)
+        per non-empty tile, every pair in exactly one tile."""
+        import numpy as np
+        tiles, pairs, counts, n_pairs = [], [], [], 0
+        for b, i in enumerate(lines):
+            if i not in self._groups:                                # a line's pairs, grouped, are made once: (pairs, [(G, pairs of G)])
+                index = self.index[i]
+                groups = [[(self.packed[u], j) for j, u in enumerate(index) if self.segments[u] == G] for G in LEXICON_SEGMENTS]
+                self._groups[i] = (np.asarray([p for g in groups for p in g], np.int32).reshape(-1, 2),
+                                   [(G, len(g)) for G, g in zip(LEXICON_SEGMENTS, groups) if g])
+            mine, groups = self._groups[i]
+            counts.append(len(mine))
+            pairs.append(mine)
+            for G, n in groups:
+                for f in range(0, n, 256 // G):
+                    tiles.append((b, G, n_pairs + f, min(256 // G, n - f)))
+                n_pairs += n
+        pairs = np.concatenate(pairs) if pairs else np.zeros((0, 2), np.int32)
+        return np.asarray(tiles, np.int32).reshape(-1, 4), pairs, np.asarray(counts, np.int32)
+
+
 class CharLM:
     """A character n-gram language model for the beam search (`ctc_beam_lm_read_host`, `LineReader(decode="beam", lm=...)`).
 
@@ -601,6 +693,28 @@ def ctc_lexicon_read_host(logits, lexicon: Lexicon, nbest: int = 4, details: boo
     if scores is None:
         scores = ctc_lexicon_scores_host(logits, lexicon, real)
     return [_lexicon_decode(row, nbest, details, real) for row in scores]
+
+
+def ctc_line_lexicons_read_host(logits, lexicons: LineLexicons, nbest: int = 4, details: bool = False, real=None):
+    """logits (T, B, C), lexicons: one list per line -> one LexiconDecoded per line: line b read against ITS OWN list, exactly
+    `_lexicon_decode` of [ctc_string_logp_host(logits[:, b], c, real) for c in lexicons.classes[b]].  Word indices are positions in
+    line b's own list and logz runs over line b's own words.  A flagged line gives ([], nan, 1); an empty list on a clean line gives
+    ([], -inf, 0).  ValueError where len(lexicons) != B or the alphabet has more classes than the logits."""
+    nbest = int(nbest)
+    if nbest < 1:
+        raise ValueError("ctc_line_lexicons_read_host: nbest >= 1 expected; got %r" % (nbest,))
+    T, B, C, rows = _beam_rows(logits, "ctc_line_lexicons_read_host")
+    if len(lexicons) != B:
+        raise ValueError("ctc_line_lexicons_read_host: %d lists for %d lines" % (len(lexicons), B))
+    if lexicons.n_classes > C:
+        raise ValueError("ctc_line_lexicons_read_host: the lexicons' alphabet has %d classes, the logits %d" % (lexicons.n_classes, C))
+    real_, exp, log, lse = _beam_real(real)
+    out = []
+    for row, classes in zip(rows, lexicons.classes):
+        lps = [_log_softmax_row(x, real_, exp, log) for x in row]
+        scores = None if any(lp is None for lp in lps) else [_string_logp(lps, c, real_, lse) for c in classes]
+        out.append(_lexicon_decode(scores, nbest, details, real))
+    return out
 
 
 def _check_penalty(what, word_penalty) -> float:
@@ -1083,10 +1197,101 @@ def parse_lexicon_records(record, nbest: int):
 
 
 def _lexicon_reading(dec: LexiconDecoded, lexicon: Lexicon, rw: int, squeezed: bool) -> LexiconReading:
+    return _line_lexicon_reading(dec, lexicon.words, rw, squeezed)
+
+
+def _line_lexicon_reading(dec: LexiconDecoded, words, rw: int, squeezed: bool) -> LexiconReading:
+    """a decoded line as the caller sees it; words: the list the line was read against (a `Lexicon`'s, or the line's own)"""
     import math
-    alts = [(lexicon.words[k], logp, math.exp(logp - dec.logz)) for k, logp in dec.entries]
+    alts = [(words[k], logp, math.exp(logp - dec.logz)) for k, logp in dec.entries]
     text, logp, post = alts[0] if alts else ("", float("nan"), float("nan"))
     return LexiconReading(text, logp, post, alts, rw, squeezed)
+
+
+def line_lexicons_limits():
+    """tatt_line_lexicons_limits: {'steps', 'classes', 'length', 'words', 'union', 'nbest'}: `lexicon_limits()` with `words` the most
+    words of ONE line's list and `union` the most distinct words of all lists.  A host-only entry: needs no GPU."""
+    from ._lib import LIB
+    out = (ctypes.c_int * 6)()
+    if LIB.tatt_line_lexicons_limits(out) != 0:
+        raise RuntimeError("tatt_line_lexicons_limits failed")
+    return dict(zip(("steps", "classes", "length", "words", "union", "nbest"), (int(v) for v in out)))
+
+
+def _int32_on(what, name, t, device, cols=None):
+    if not (isinstance(t, torch.Tensor) and t.dtype == torch.int32 and t.device == device and t.is_contiguous() and
+            (t.dim() == 1 if cols is None else t.dim() == 2 and t.shape[1] == cols)):
+        raise ValueError("%s: %s must be a contiguous int32 tensor%s on %s" % (what, name, "" if cols is None else " of %d columns" % cols,
+                                                                               device))
+
+
+def ctc_lexicon_score_pairs(logits, codes, n_codes: int, table, tiles, pairs, counts, scores, max_count: int):
+    """ONE tatt_ctc_lexicon_score_pairs launch: logits (T, B, C) fp32 on the device (any strides); codes, table: the packed union of a
+    `LineLexicons` on the device (n_codes its code count); tiles (n_tiles, 4), pairs (n_pairs, 2), counts (B,): what
+    `LineLexicons.pack` gave for the B lines, on the device; scores (B, >= max_count) float64 on the device with contiguous rows,
+    max_count >= every count: scores[b][j] = the exact CTC log-probability of word j of line b's own list (NaN on a flagged line).
+    Only the listed pairs are written.  ValueError for what the entry refuses, before any launch."""
+    from . import ops
+    from ._lib import LIB
+    what = "ctc_lexicon_score_pairs"
+    ops._check_dev(logits)
+    if logits.dim() != 3:
+        raise ValueError("%s takes (T, B, C) logits; got %s" % (what, tuple(logits.shape)))
+    T, B, C = logits.shape
+    dev = logits.device
+    _int32_on(what, "codes", codes, dev)
+    _int32_on(what, "table", table, dev, 4)
+    _int32_on(what, "tiles", tiles, dev, 4)
+    _int32_on(what, "pairs", pairs, dev, 2)
+    _int32_on(what, "counts", counts, dev)
+    if not (isinstance(n_codes, int) and 0 <= n_codes <= codes.numel() and codes.numel() >= 1 and table.shape[0] >= 1):
+        raise ValueError("%s: n_codes = %r for %d codes" % (what, n_codes, codes.numel()))
+    if counts.numel() != B:
+        raise ValueError("%s: %d counts for %d lines" % (what, counts.numel(), B))
+    if not (isinstance(max_count, int) and max_count >= 1):
+        raise ValueError("%s: max_count >= 1 expected; got %r" % (what, max_count))
+    if scores.dtype != torch.float64 or scores.dim() != 2 or scores.stride(1) != 1 or scores.shape[0] != B or scores.shape[1] < max_count \
+            or scores.device != dev:
+        raise ValueError("%s: scores must be a (%d, >= %d) float64 tensor with contiguous rows on %s" % (what, B, max_count, dev))
+    rc = LIB.tatt_ctc_lexicon_score_pairs(ops.P(logits), *logits.stride(), T, B, C, ops.P(codes), n_codes, ops.P(table), table.shape[0],
+                                          ops.P(tiles), tiles.shape[0], ops.P(pairs), pairs.shape[0], ops.P(counts), max_count,
+                                          ops.P(scores), scores.stride(0), ops.stream())
+    if rc == 1:
+        raise ValueError("tatt_ctc_lexicon_score_pairs refuses T = %d, B = %d, C = %d, U = %d, %d tiles, %d pairs, max_count = %d"
+                         % (T, B, C, table.shape[0], tiles.shape[0], pairs.shape[0], max_count))
+    if rc != 0:
+        raise RuntimeError("tatt_ctc_lexicon_score_pairs failed with code %d" % rc)
+    return scores
+
+
+def ctc_lexicon_select_rows(scores, counts, index, record, nbest: int = 4):
+    """ONE tatt_ctc_lexicon_select_rows launch: `ctc_lexicon_select` with counts (B,) int32 on the device: line b has counts[b] <=
+    scores.shape[1] scores.  A line without words writes entries = 0, flag = 0, logz = -inf.  ValueError for what the entry refuses,
+    before any launch."""
+    from . import ops
+    from ._lib import LIB
+    what = "ctc_lexicon_select_rows"
+    if not scores.is_cuda:
+        raise RuntimeError("tatt_amd kernels need tensors on an AMD GPU (HIP device); got %s. There is no CPU fallback in the product "
+                           "path." % scores.device)
+    if scores.dtype != torch.float64 or scores.dim() != 2 or scores.stride(1) != 1 or scores.shape[1] < 1:
+        raise ValueError("%s: scores must be a 2-D float64 tensor with contiguous, non-empty rows" % what)
+    B = scores.shape[0]
+    _int32_on(what, "counts", counts, scores.device)
+    if counts.numel() != B:
+        raise ValueError("%s: %d counts for %d lines" % (what, counts.numel(), B))
+    if record.dtype != torch.int32 or record.dim() != 2 or record.stride(1) != 1 or index.dtype != torch.int32 or index.numel() < B:
+        raise ValueError("%s: record must be a 2-D int32 tensor with contiguous rows, index an int32 tensor of B entries" % what)
+    _check_nbest(what, nbest)
+    if record.shape[1] < lexicon_record_words(nbest):
+        raise ValueError("%s: rows of %d words; nbest = %d needs %d" % (what, record.shape[1], nbest, lexicon_record_words(nbest)))
+    rc = LIB.tatt_ctc_lexicon_select_rows(ops.P(scores), scores.stride(0), B, ops.P(counts), nbest, ops.P(index), ops.P(record),
+                                          record.shape[0], record.stride(0), ops.stream())
+    if rc == 1:
+        raise ValueError("tatt_ctc_lexicon_select_rows refuses B = %d, nbest = %d, rows of %d words" % (B, nbest, record.stride(0)))
+    if rc != 0:
+        raise RuntimeError("tatt_ctc_lexicon_select_rows failed with code %d" % rc)
+    return record
 
 
 def words_limits():
@@ -1176,10 +1381,15 @@ class PendingReading:
     decode="lexicon": one LexiconReading) per line, in input order.  With keep_logits: `logits` [(line indices of the chunk, its
     (T, n, C) logits on the device)]; with keep_scores (lexicon): `scores` [(line indices, the chunk's (n, K) float64 scores)].
     decode="words": one WordsReading per line (`texts()`: the words joined by spaces); with keep_lp: `lp` [(line indices, the chunk's
-    (n, T, C) float64 log-soft-max on the device)]."""
+    (n, T, C) float64 log-soft-max on the device)].
+    decode="lexicons": one LexiconReading per line, its words those of the line's OWN list and the posterior taken among them; an
+    empty list or a flagged line reads "" with logp = nan; with keep_scores: `scores` [(line indices, the chunk's (n, max count) float64
+    scores, the lines' counts)]."""
 
-    def __init__(self, host, event, cap, plan, logits=None, nbest=None, lexicon=None, scores=None, words=False, lp=None, lm=False):
+    def __init__(self, host, event, cap, plan, logits=None, nbest=None, lexicon=None, scores=None, words=False, lp=None, lm=False,
+                 lexicons=None):
         self._lm = bool(lm)                                          # beam records with a language-model term
+        self._lexicons = lexicons                                    # a LineLexicons: lexicon records, words of every line's own list
         self._host, self._event, self._cap, self._plan, self.logits, self._out = host, event, cap, plan, logits, None
         self._nbest = nbest                                          # None: greedy records
         self._lexicon, self.scores = lexicon, scores                 # a Lexicon: lexicon records
@@ -1197,6 +1407,10 @@ class PendingReading:
                 self._event.synchronize()
                 self._out = [_reading(d, rw, sq) for d, rw, sq in zip(parse_records(self._host, self._cap), self._plan.rws,
                                                                        self._plan.squeezed)]
+            elif self._lexicons is not None:
+                self._event.synchronize()
+                self._out = [_line_lexicon_reading(d, ws, rw, sq) for d, ws, rw, sq in zip(
+                    parse_lexicon_records(self._host, self._nbest), self._lexicons.lists, self._plan.rws, self._plan.squeezed)]
             elif self._lexicon is not None:
                 self._event.synchronize()
                 self._out = [_lexicon_reading(d, self._lexicon, rw, sq) for d, rw, sq in zip(
@@ -1257,19 +1471,33 @@ class LineReader:
     best alignment (plus word_penalty per word), `words` one `WordSpan(text, index, first, last, x0, x1)` per word: its steps and, by
     the convention of `word_span_pixels`, its columns in the line the caller gets back.  The lexicon must fit words_limits()["lanes"]
     packed lanes (`words_lanes`): ValueError here otherwise.  keep_lp=True keeps every chunk's float64 log-soft-max
-    (`PendingReading.lp`)."""
+    (`PendingReading.lp`).
+    decode="lexicons" (1 <= nbest <= 16; no lexicon=): every line is read against a list of words of its OWN, given with the call:
+    `read(..., lexicons=)`, a `LineLexicons` or one list per line by INPUT index (specification `ctc_line_lexicons_read_host`).  On
+    top of what greedy enqueues: ONE more host-to-device copy from pinned memory (the union's codes and table and every chunk's tile
+    table, pairs and counts in one int32 blob, the tables built from the plan's buckets), per chunk one (n, max count) float64 buffer,
+    ONE tatt_ctc_lexicon_score_pairs launch (none for a chunk whose lists are all empty) and ONE tatt_ctc_lexicon_select_rows launch
+    in place of the greedy one.  `result()` gives `LexiconReading`s: text and alternatives are words of the line's own list, the
+    posterior is taken among them; an empty list or a flagged line reads "" with logp = nan.  keep_scores=True keeps (line indices,
+    scores, counts) per chunk.  ValueError before anything is enqueued for a missing keyword, len(lexicons) != len(rows) and an
+    alphabet with more classes than the CRNN emits."""
 
     def __init__(self, crnn, batch_size: int = 48, device=None, keep_logits: bool = False, w: int = 64, decode: str = "greedy",
                  beam: int = 8, nbest: int = 4, lexicon=None, keep_scores: bool = False, word_penalty: float = 0.0,
                  keep_lp: bool = False, lm=None, lm_weight=None, lm_bonus=None):
         from . import functional as Fh
         from .infer import _check_module, _crnn_folds
-        if decode not in ("greedy", "beam", "lexicon", "words"):
-            raise ValueError("LineReader: decode is 'greedy', 'beam', 'lexicon' or 'words'; got %r" % (decode,))
+        if decode not in ("greedy", "beam", "lexicon", "words", "lexicons"):
+            raise ValueError("LineReader: decode is 'greedy', 'beam', 'lexicon', 'words' or 'lexicons'; got %r" % (decode,))
         word_penalty = _check_penalty("LineReader", word_penalty)
         if decode != "words" and word_penalty != 0.0:
             raise ValueError("LineReader: word_penalty= goes with decode='words'; got decode = %r" % (decode,))
-        if decode in ("lexicon", "words"):
+        if decode == "lexicons":
+            _check_nbest("LineReader", nbest)
+            if lexicon is not None:
+                raise ValueError("LineReader: lexicon= goes with decode='lexicon' or decode='words'; decode='lexicons' takes the lists "
+                                 "of a call as read(..., lexicons=)")
+        elif decode in ("lexicon", "words"):
             if decode == "lexicon":
                 _check_nbest("LineReader", nbest)
             if lexicon is None:
@@ -1356,12 +1584,31 @@ class LineReader:
         with torch.no_grad():
             return crnn_eval(self.crnn, self._folds, img, self._sync)
 
-    def read(self, dev_bytes, rows, scale, keep_logits=None) -> PendingReading:
+    def check_lexicons(self, lexicons, n: int, who: str = "LineReader.read"):
+        """the `lexicons=` of a call over n lines -> a `LineLexicons` (None for every decoding but "lexicons"); ValueError for the keyword
+        on another decoding, a missing one, a wrong number of lists, an alphabet with more classes than the CRNN emits.  Touches no device."""
+        if self.decode != "lexicons":
+            if lexicons is not None:
+                raise ValueError("%s: lexicons= goes with decode='lexicons'; got decode = %r" % (who, self.decode))
+            return None
+        if lexicons is None:
+            raise ValueError("%s: decode='lexicons' needs lexicons=, one list of words per line" % who)
+        lexicons = lexicons if isinstance(lexicons, LineLexicons) else LineLexicons(lexicons)
+        if len(lexicons) != n:
+            raise ValueError("%s: %d lists of words for %d lines" % (who, len(lexicons), n))
+        emits = _emitted_classes(self.crnn)
+        if emits is not None and lexicons.n_classes > emits:
+            raise ValueError("%s: the lexicons' alphabet has %d classes, the CRNN emits %d" % (who, lexicons.n_classes, emits))
+        return lexicons
+
+    def read(self, dev_bytes, rows, scale, keep_logits=None, lexicons=None) -> PendingReading:
         """dev_bytes: the uint8 device buffer holding the lines, rows: (byte offset, H, W, pitch) per line (what the `line_canvases` of a
-        `PendingExport` of `DeviceExporter.lines` / `.scene` / `.scene_quads` gives), scale: the SR factor -> PendingReading."""
+        `PendingExport` of `DeviceExporter.lines` / `.scene` / `.scene_quads` gives), scale: the SR factor -> PendingReading.
+        lexicons (decode="lexicons" only, and required there): a `LineLexicons` or one list of words per line, by INPUT index."""
         import numpy as np
         rows = list(rows)
         keep = self.keep_logits if keep_logits is None else bool(keep_logits)
+        lexicons = self.check_lexicons(lexicons, len(rows))
         if not rows:
             return PendingReading(None, None, 0, None, [] if keep else None)
         if not (isinstance(dev_bytes, torch.Tensor) and dev_bytes.dtype == torch.uint8 and dev_bytes.device == self.device and
@@ -1383,12 +1630,27 @@ class LineReader:
             head_dev.copy_(head, non_blocking=True)
             luma = torch.empty(plan.floats, dtype=torch.float32, device=self.device)
             line_luma(dev_bytes, head_dev, plan.desc, luma)
-            beam, lex, wrd = self.decode == "beam", self.decode == "lexicon", self.decode == "words"
+            beam, lex, wrd, per = self.decode == "beam", self.decode == "lexicon", self.decode == "words", lexicons is not None
             fused = beam and self._lm_table is not None
             words = beam_lm_record_words(cap, self.nbest) if fused else beam_record_words(cap, self.nbest) if beam else \
-                lexicon_record_words(self.nbest) if lex else \
+                lexicon_record_words(self.nbest) if lex or per else \
                 words_record_words(cap) if wrd else 3 * cap + 2
-            kept_scores = [] if lex and self.keep_scores else None
+            kept_scores = [] if (lex or per) and self.keep_scores else None
+            if per:
+                # the union and every chunk's tile table, pairs and counts: ONE int32 blob, one copy from pinned memory
+                packs, parts, at = [], [lexicons.codes, lexicons.table.reshape(-1)], lexicons.codes.size + lexicons.table.size
+                for rw, idx in plan.buckets:                         # (lists go by INPUT index, chunks in bucket order)
+                    for i in range(0, len(idx), chunk):
+                        tiles, pairs, counts = lexicons.pack(idx[i:i + chunk])
+                        packs.append((at, tiles.shape[0], pairs.shape[0], int(counts.max())))
+                        parts += [tiles.reshape(-1), pairs.reshape(-1), counts]
+                        at += tiles.size + pairs.size + counts.size
+                blob = torch.empty(at, dtype=torch.int32, pin_memory=True)
+                blob.numpy()[:] = np.concatenate(parts)
+                blob_dev = torch.empty(at, dtype=torch.int32, device=self.device)
+                blob_dev.copy_(blob, non_blocking=True)
+                u_codes, u_table = blob_dev[:lexicons.codes.size], blob_dev[lexicons.codes.size:packs[0][0]].view(-1, 4)
+                n_chunk = 0
             kept_lp = [] if wrd and self.keep_lp else None
             record = torch.empty(n, words, dtype=torch.int32, device=self.device)
             index, pos, foff = head_dev[n * READ_DESC:], 0, 0
@@ -1402,6 +1664,18 @@ class LineReader:
                         ctc_beam_lm_read(logits, self._lm_table, self.lm.order, index[pos:pos + m], record, cap, self.beam, self.nbest)
                     elif beam:
                         ctc_beam_read(logits, index[pos:pos + m], record, cap, self.beam, self.nbest)
+                    elif per:
+                        at, n_tiles, n_pairs, most = packs[n_chunk]
+                        n_chunk += 1
+                        counts = blob_dev[at + 4 * n_tiles + 2 * n_pairs:at + 4 * n_tiles + 2 * n_pairs + m]
+                        scores = torch.empty(m, max(1, most), dtype=torch.float64, device=self.device)
+                        if n_tiles:                                  # (a chunk of empty lists has nothing to score)
+                            ctc_lexicon_score_pairs(logits, u_codes, lexicons.n_codes, u_table, blob_dev[at:at + 4 * n_tiles].view(-1, 4),
+                                                    blob_dev[at + 4 * n_tiles:at + 4 * n_tiles + 2 * n_pairs].view(-1, 2), counts, scores,
+                                                    max(1, most))
+                        ctc_lexicon_select_rows(scores, counts, index[pos:pos + m], record, self.nbest)
+                        if kept_scores is not None:
+                            kept_scores.append((idx[i:i + m], scores, counts))
                     elif lex:
                         scores = torch.empty(m, len(self.lexicon), dtype=torch.float64, device=self.device)
                         ctc_lexicon_score(logits, self.lexicon, scores)
@@ -1423,5 +1697,5 @@ class LineReader:
             host.copy_(record, non_blocking=True)
             ev = torch.cuda.Event()
             ev.record()
-        return PendingReading(host, ev, cap, plan, kept, self.nbest if beam or lex else None, self.lexicon if lex or wrd else None, kept_scores,
-                              wrd, kept_lp, fused)
+        return PendingReading(host, ev, cap, plan, kept, self.nbest if beam or lex or per else None, self.lexicon if lex or wrd else None,
+                              kept_scores, wrd, kept_lp, fused, lexicons)
