@@ -242,7 +242,10 @@ __global__ __launch_bounds__(256) void gemm_mfma_kernel(GemmP p) {
 // with wave-uniform counters, and the row count M may be ragged (rows >= M load zeros and are not stored).
 // IM2COLT (requires !AKC, !BKC): the transposed im2col matrix of the weight gradient, A(i = (tap, ci), r = pixel), Cin % 64 == 0:
 // the 64 rows of a tile are 64 consecutive channels of ONE tap, so a K-chunk is 16 pixels x 64 contiguous channels.
-template <bool AKC, bool BKC, bool CAT, bool IM2COL, bool IM2COLT = false>
+// BLOCKED: the contraction is summed in blocks of ACC_BLOCK chunks (a second set of accumulators takes each finished block), as a
+// split contraction sums its partials: one fp32 chain over thousands of products is several times farther from the exact sum.
+#define ACC_BLOCK 32
+template <bool AKC, bool BKC, bool CAT, bool IM2COL, bool IM2COLT = false, bool BLOCKED = false>
 __global__ __launch_bounds__(256) void gemm_fast_kernel(GemmP p, int cvec) {
     constexpr int TKC = 64 * 20, TMC = 16 * 96;
     constexpr int TA = AKC ? TKC : TMC, TB = BKC ? TKC : TMC;
@@ -332,9 +335,9 @@ __global__ __launch_bounds__(256) void gemm_fast_kernel(GemmP p, int cvec) {
         *reinterpret_cast<f32x4*>(AsB + buf * TA + aslot) = ra;
         *reinterpret_cast<f32x4*>(BsB + buf * TB + bslot) = rb;
     };
-    f32x16 acc;
+    f32x16 acc, total;
 #pragma unroll
-    for (int i = 0; i < 16; ++i) acc[i] = 0.f;
+    for (int i = 0; i < 16; ++i) acc[i] = 0.f, total[i] = 0.f;
     const bool do_rs = !AKC && p.rowsum != nullptr && tile_n == 0;
     float rs_acc = 0.f;
     const int arow = wm * 32 + (lane & 31), bcol = wn * 32 + (lane & 31), kq = lane >> 5;
@@ -363,6 +366,10 @@ __global__ __launch_bounds__(256) void gemm_fast_kernel(GemmP p, int cvec) {
 #pragma unroll
                 for (int u = 0; u < 4; ++u) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(va[u], vb[u], acc, 0, 0, 0);
             }
+            if (BLOCKED && ((c - c_begin) & (ACC_BLOCK - 1)) == ACC_BLOCK - 1) {
+#pragma unroll
+                for (int i = 0; i < 16; ++i) { total[i] += acc[i]; acc[i] = 0.f; }
+            }
             if (do_rs) {
 #pragma unroll
                 for (int kk = 0; kk < 4; ++kk) rs_acc += As[((t >> 6) * 4 + kk) * 96 + (t & 63)];
@@ -370,6 +377,10 @@ __global__ __launch_bounds__(256) void gemm_fast_kernel(GemmP p, int cvec) {
             if (c + 1 < c_end) store_chunk(buf ^ 1);
             __syncthreads();
         }
+    }
+    if (BLOCKED) {
+#pragma unroll
+        for (int i = 0; i < 16; ++i) acc[i] += total[i];
     }
     if (do_rs) {
         smem[(t >> 6) * 64 + (t & 63)] = rs_acc;
@@ -616,7 +627,11 @@ static int try_conv_fast(const GemmP& p, hipStream_t st) {
     if (p.splitk > 1 && !al16(p.partial)) return -1;
     const int cvec = (p.scn == 1 && !(p.scm & 3) && al16(p.C) && (!p.bias || al16(p.bias))) ? 1 : 0;
     dim3 grid(cdiv(p.M, 64) * (p.N >> 6), p.splitk, 1), block(256);
-    hipLaunchKernelGGL((gemm_fast_kernel<true, false, false, true>), grid, block, 0, st, p, cvec);
+    // an UNSPLIT contraction of 2 blocks and more (K >= 1024: batch sizes with too many output tiles to split) sums in blocks
+    if (p.splitk == 1 && (p.K >> 4) >= 2 * ACC_BLOCK)
+        hipLaunchKernelGGL((gemm_fast_kernel<true, false, false, true, false, true>), grid, block, 0, st, p, cvec);
+    else
+        hipLaunchKernelGGL((gemm_fast_kernel<true, false, false, true>), grid, block, 0, st, p, cvec);
     return LAUNCH_CHECK();
 }
 

@@ -387,7 +387,8 @@ def repack_weight(w_oihw, mode, cache=True):
 
 # generic implicit-GEMM convolution: fewer output tiles than CONV_SPLIT_TILES and a deep contraction -> the contraction is split over
 # up to CONV_SPLIT_WGS work-groups (deterministic second-stage sum).  Round 5: 128 / 256 -> 256 / 768 (the data gradient of the STN
-# head's second convolution, 192 tiles x 36 K-chunks on the main lane of the last pass: 45 -> 30 us)
+# head's second convolution, 192 tiles x 36 K-chunks on the main lane of the last pass: 45 -> 30 us).  Unsplit, the im2col kernel sums a
+# contraction of 64 chunks and more in blocks of 32 chunks (csrc/gemm.hip, BLOCKED), so both sides of the threshold are equally accurate
 CONV_SPLIT_TILES, CONV_SPLIT_WGS = 256, 768
 
 

@@ -1,6 +1,8 @@
 """The MORAN recogniser on the GPU: the rectifier's one-launch tail (tatt_morn_rectify) alone, the stages (`offsets`, `rectify`, `encode`)
 under both arithmetic settings, and the whole recogniser (`read`, `forward`, `io.evaluate`) against what the reference recorded
 (tests/golden/moran_e2e.npz, tools/gen_golden_moran.py) and against the float64 specification of tests/moran_ref.py.
+Every convolution route as a single layer, and the stages at batch 1, 2, 5 and 48 with the contraction split on and off, are in
+tests/test_moran_routes_gpu.py.
 
 Error bars: 4 x the recorded distance of the reference's own fp32 result from its float64 run at that stage + 1e-7 x the largest |value|;
 for the sampler alone, 4 x the recorded distance of the reference's fp32 sampler from float64 sampling at the same recorded offsets."""
