@@ -147,8 +147,8 @@ TATT_API int tatt_colsum(const float* X, long ld, int M, int C, float* out, floa
 __global__ void bn_stats_stage1(const float* __restrict__ X, long ld, int M, int C, int rows_per_block,
                                 double* __restrict__ part) {
     __shared__ double sh[2][256];
-    const int cpb = C < 256 ? C : 256;           // channels per pass (C is a power of two <= 512 here)
-    const int rpar = 256 / cpb;                  // rows handled in parallel
+    const int cpb = C < 256 ? C : 256;           // channels per pass (any C: the last pass may be partial, c < C)
+    const int rpar = 256 / cpb;                  // rows handled in parallel (threads with rl >= rpar idle when cpb does not divide 256)
     const int t = threadIdx.x;
     const int cl = t % cpb, rl = t / cpb;
     const int m_begin = blockIdx.x * rows_per_block;

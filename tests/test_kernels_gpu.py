@@ -1,6 +1,7 @@
 """Per-kernel parity: each HIP operator (through the C ABI, forward and backward) against the CPU oracle /
 plain fp32 torch on the same seeded inputs.  Tolerances are fp32 round-off class (rtol 2e-4 / atol 2e-5 on
-values, 5e-4 on gradients)."""
+values, 5e-4 on gradients).  BatchNorm, LayerNorm, the attention core, the row softmax and TPS against float64 at every route of their
+dispatch: tests/test_norm_routes_gpu.py, tests/test_attn_routes_gpu.py, tests/test_tps_routes_gpu.py."""
 import math
 
 import numpy as np
