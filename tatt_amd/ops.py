@@ -960,10 +960,20 @@ def gru32_bwd(gates, out, dout, whh_f, whh_r, geom):
     return dgi, dgh, hprev
 
 
+def gru2_fits(nseq, T, s_in, stride_hi, stride_lo, stride_t):
+    """Do the second-generation recurrences take this geometry?  They address with 32-bit byte offsets: (largest token index + 1) x
+    1024 bytes (the gates rows) must fit.  The Python twin of gru2_fits in csrc/gru.hip: keep the two the same."""
+    if s_in <= 0 or stride_hi < 0 or stride_lo < 0 or stride_t <= 0:
+        return False
+    last = ((nseq - 1) // s_in) * stride_hi + (s_in - 1) * stride_lo + (T - 1) * stride_t
+    return last + 1 < (1 << 22)
+
+
 def gru_frag_ok(geom):
-    """Can tatt_gru32_bwd2 leave MFMA operand fragments for this sequence geometry?  (windows of 8 steps, K-steps of 4 windows)"""
+    """Can tatt_gru32_bwd2 leave MFMA operand fragments for this sequence geometry?  (windows of 8 steps, K-steps of 4 windows, and
+    the second generation itself: beyond `gru2_fits` the library runs the first generation, which leaves no fragments)"""
     nseq, T = geom[0], geom[1]
-    return GRU32_V2 and T % 8 == 0 and (nseq * (T // 8)) % 4 == 0
+    return GRU32_V2 and T % 8 == 0 and (nseq * (T // 8)) % 4 == 0 and gru2_fits(*geom)
 
 
 def gru32_bwd_frag(gates, out, dout, whh_f, whh_r, geom):
