@@ -8,40 +8,29 @@
 //                                 ctc_lexicon_score_kernel does, then a segment of G lanes runs that kernel's recursion for its pair and
 //                                 stores to scores[b][j].  G is the same in the whole work-group: a switch over the three bodies, so ONE
 //                                 launch per chunk serves all three segment classes.
-//                                 The staging and the step loop are ctclex.hip's, restated with the operands in the same order (that
-//                                 file's text is left as it is, and with it the resource report of its three kernels): a word's score
-//                                 is bit for bit the one-list path's (tests/test_line_lexicons_device_gpu.py).
-//   ctc_lexicon_select_rows_kernel   ctc_lexicon_select_kernel with a count per line: K_b = counts[b]; the per-thread strides and the
-//                                 reduction tree are that kernel's, so a line of K_b words gets the 64 bits of logz a (1, K_b) buffer
-//                                 gets there.  K_b = 0 writes entries = 0, flag = 0, logz = -inf (the flag rule "every score a NaN" is
-//                                 kept for K_b >= 1).
+//                                 The staging is ctc_lex.h's `lx_stage`, the function ctclex.hip calls too.  The recursion is that
+//                                 header's `lx_word` RESTATED in `lxp_body`, the operands in the same order: a word's score is bit for
+//                                 bit the one-list path's (tests/test_line_lexicons_device_gpu.py).  Calling `lx_word` here computes
+//                                 the same bytes with the same step loops, instruction for instruction, but moves them by 4 to 12
+//                                 bytes, and this kernel's time follows where they lie: tatt_ctc_lexicon_score_pairs then ran 0.2 to
+//                                 0.6 % slower than before the shared header, outside the run's spread (profiles/ctc_lex_core_ab.txt).
+//                                 A change to the recursion is made in ctc_lex.h AND here.
+//   ctc_lexicon_select_rows_kernel   ctc_lexicon_select_kernel with a count per line: K_b = counts[b] into the same `lx_select`, so a
+//                                 line of K_b words gets the 64 bits of logz a (1, K_b) buffer gets there.  K_b = 0 writes entries = 0,
+//                                 flag = 0, logz = -inf (the flag rule "every score a NaN" is kept for K_b >= 1).
 // Every loop is bounded by T, C, a tile's count (<= 256 / G), a line's count (<= 65536), LX_NBEST or a literal.  Nothing is indexed by
 // table DATA without a range check: a tile whose line, class or pair range is out of range, a pair whose union position or j (against
 // the line's count and the row stride) is out of range writes nothing; a word whose length, code offset or codes are out of range scores
 // NaN.  No atomics, no traffic between work-groups.
-#include "common.h"
-#include "ctc_f64.h"
+// Registers (hipcc's resource report, gfx950): pairs 99 VGPRs, 81 SGPRs, 4 waves per SIMD; select_rows 40 VGPRs, 8 waves per SIMD;
+// scratch = 0 in both (profiles/ctc_lex_core_ab.txt).
+#include "ctc_lex.h"
 
-#define LXP_MAX_T 256
-#define LXP_MAX_C 64
-#define LXP_MAX_L 31
-#define LXP_MAX_K 65536                         // words of one line
 #define LXP_MAX_U 1048576                       // distinct words of all lines
-#define LXP_NBEST 16
-#define LXP_THREADS 256
-#define LXP_WORD 4                              // ints per packed word, as in ctclex.hip
 #define LXP_TILE 4                              // ints per tile row: line | segment class | first pair | pairs
 #define LXP_PAIR 2                              // ints per pair: packed union position | position in the line's list
-#define LXP_STAGE 8
-#define LXP_LDS_MAX (LXP_MAX_T * (8 + 4 + 4 * LXP_MAX_C))
 
-#ifdef TATT_HOST_STANDIN                        // (tools/line_lexicons_host: work-groups run one after the other, a lane is a thread)
-#define LXP_SHARED static
-#else
-#define LXP_SHARED __shared__
-#endif
-
-// the recursion of one tile's pairs at segment class G; `flagged` and everything of the tile is the same in the whole work-group
+// the words of one tile's pairs at segment class G; `flagged` and everything of the tile is the same in the whole work-group
 template <int G>
 __device__ __forceinline__ void lxp_body(const double* ls, const float* mx, const float* xs, bool flagged, int T, int C,
                                          const int* __restrict__ codes, int n_codes, const int* __restrict__ words, int U,
@@ -58,14 +47,15 @@ __device__ __forceinline__ void lxp_body(const double* ls, const float* mx, cons
         const int u = p[0];
         j = p[1];
         if (u >= 0 && u < U) {
-            const int* w = words + (long)u * LXP_WORD;
+            const int* w = words + (long)u * LX_WORD;
             L = w[0];
             off = w[1];
         } else {
             live = false;                                            // no such word: nothing is written
         }
     }
-    const bool shape_ok = L >= 0 && L <= LXP_MAX_L && 2 * L + 1 <= G && off >= 0 && off <= n_codes - L;
+    // ---- ctc_lex.h's lx_word<G>(..., live, L, off, j, limit, row) RESTATED, the operands in its order (see the top) ----
+    const bool shape_ok = L >= 0 && L <= LX_MAX_L && 2 * L + 1 <= G && off >= 0 && off <= n_codes - L;
     const int S = shape_ok ? 2 * L + 1 : 1;
     const bool on = live && s < S;
     int c = 0, below2 = 0;                                           // ext[s], ext[s - 2]
@@ -103,54 +93,26 @@ __device__ __forceinline__ void lxp_body(const double* ls, const float* mx, cons
     if (out) *dst = word_bad ? __builtin_nan("") : (S == 1 ? a : cb_lse(a, a1));
 }
 
-__global__ __launch_bounds__(LXP_THREADS) void ctc_lexicon_pairs_kernel(const float* __restrict__ logits, long st_t, long st_b, long st_c,
-                                                                        int T, int B, int C, const int* __restrict__ codes, int n_codes,
-                                                                        const int* __restrict__ words, int U,
-                                                                        const int* __restrict__ tiles, const int* __restrict__ pairs,
-                                                                        int n_pairs, const int* __restrict__ counts, int max_count,
-                                                                        double* __restrict__ scores, long st_sc) {
+__global__ __launch_bounds__(LX_THREADS) void ctc_lexicon_pairs_kernel(const float* __restrict__ logits, long st_t, long st_b, long st_c,
+                                                                       int T, int B, int C, const int* __restrict__ codes, int n_codes,
+                                                                       const int* __restrict__ words, int U,
+                                                                       const int* __restrict__ tiles, const int* __restrict__ pairs,
+                                                                       int n_pairs, const int* __restrict__ counts, int max_count,
+                                                                       double* __restrict__ scores, long st_sc) {
     extern __shared__ double lxp_lds[];
     double* ls = lxp_lds;                                            // [T]
     float* mx = reinterpret_cast<float*>(ls + T);                    // [T]
     float* xs = mx + T;                                              // [T][C]
-    LXP_SHARED int flag_sh[LXP_THREADS / 64];
+    LX_SHARED int flag_sh[LX_THREADS / 64];
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
     const int* tile = tiles + (long)blockIdx.x * LXP_TILE;
     const int b = tile[0], G = tile[1], first = tile[2], count = tile[3];
-    if (b < 0 || b >= B || (G != 16 && G != 32 && G != 64) || count < 1 || count > LXP_THREADS / G || first < 0 || first > n_pairs - count)
+    if (b < 0 || b >= B || (G != 16 && G != 32 && G != 64) || count < 1 || count > LX_THREADS / G || first < 0 || first > n_pairs - count)
         return;                                                      // (the whole work-group: no such tile)
     const int kb = counts[b];
     const int limit = kb < max_count ? kb : max_count;               // j < the line's count and inside the row (max_count <= st_sc)
 
-    // ---- staging: a wave per step, lane = class, LXP_STAGE steps in flight ----
-    const float* x = logits + b * st_b + lane * st_c;
-    int flag = 0;
-    for (int t0 = wave; t0 < T && !flag; t0 += 4 * LXP_STAGE) {
-        float xv[LXP_STAGE];
-#pragma unroll
-        for (int u = 0; u < LXP_STAGE; ++u) {
-            const int t = t0 + 4 * u;
-            xv[u] = lane < C && t < T ? x[t * st_t] : -INFINITY;
-        }
-#pragma unroll
-        for (int u = 0; u < LXP_STAGE; ++u) {
-            const int t = t0 + 4 * u;
-            if (t < T && !flag) {                                    // (the same in every lane of the wave)
-                const float xc = xv[u];
-                const float m = cb_wave_max(xc);                     // (fmaxf skips a NaN: looked for on its own)
-                if (__ballot(xc != xc || xc == INFINITY) != 0 || m == -INFINITY) {
-                    flag = 1;
-                } else {
-                    const double sm = cb_wave_sum(lane < C ? exp((double)xc - (double)m) : 0.0);
-                    if (lane < C) xs[t * C + lane] = xc;
-                    if (lane == 0) {
-                        mx[t] = m;
-                        ls[t] = log(sm);
-                    }
-                }
-            }
-        }
-    }
+    const int flag = lx_stage<LX_STAGE>(logits + b * st_b, st_t, st_c, T, C, LX_THREADS / 64, ls, mx, xs);
     if (lane == 0) flag_sh[wave] = flag;
     __syncthreads();
     const bool flagged = (flag_sh[0] | flag_sh[1] | flag_sh[2] | flag_sh[3]) != 0;
@@ -163,131 +125,53 @@ __global__ __launch_bounds__(LXP_THREADS) void ctc_lexicon_pairs_kernel(const fl
     }
 }
 
-// 32-bit words of a record row: entries | flag | logz (2) | per entry logp (2), word index, 0 (ctclex.hip's layout)
-static inline long lxp_record_words(int nbest) { return 4 + 4 * (long)nbest; }
-
-__global__ __launch_bounds__(LXP_THREADS) void ctc_lexicon_select_rows_kernel(const double* __restrict__ scores, long st_sc,
-                                                                              const int* __restrict__ counts, int nbest,
-                                                                              const int* __restrict__ index, int* __restrict__ record,
-                                                                              int n_rows, long st_rec) {
-    LXP_SHARED double rv[LXP_THREADS];
-    LXP_SHARED int ri[LXP_THREADS];
-    const int tid = threadIdx.x;
+__global__ __launch_bounds__(LX_THREADS) void ctc_lexicon_select_rows_kernel(const double* __restrict__ scores, long st_sc,
+                                                                             const int* __restrict__ counts, int nbest,
+                                                                             const int* __restrict__ index, int* __restrict__ record,
+                                                                             int n_rows, long st_rec) {
     const int row = index[blockIdx.x];
     if (row < 0 || row >= n_rows) return;                            // (the whole work-group)
     const int K = counts[blockIdx.x];
-    if (K < 0 || K > LXP_MAX_K || K > st_sc) return;                 // (likewise: no such line)
-    const double* sc = scores + blockIdx.x * st_sc;
-    int* rec = record + row * st_rec;
-    const double inf = __builtin_inf();
-    double pv = inf, top = CB_NEG;                                   // the last pick (value, index); the first pick's value
-    int pi = -1, n_out = 0;
-    for (int i = 0; i < nbest; ++i) {
-        // the largest finite score after the last pick in the order (value descending, index ascending)
-        double bv = CB_NEG;
-        int bi = 0x7fffffff;
-        for (int k = tid; k < K; k += LXP_THREADS) {
-            const double v = sc[k];
-            const bool finite = v == v && v != CB_NEG && v != inf;
-            const bool after = v < pv || (v == pv && k > pi);
-            if (finite && after && (v > bv || (v == bv && k < bi))) {
-                bv = v;
-                bi = k;
-            }
-        }
-        rv[tid] = bv;
-        ri[tid] = bi;
-        __syncthreads();
-        for (int o = LXP_THREADS / 2; o > 0; o >>= 1) {
-            if (tid < o) {
-                const double ov = rv[tid + o];
-                const int oi = ri[tid + o];
-                if (oi != 0x7fffffff && (ri[tid] == 0x7fffffff || ov > rv[tid] || (ov == rv[tid] && oi < ri[tid]))) {
-                    rv[tid] = ov;
-                    ri[tid] = oi;
-                }
-            }
-            __syncthreads();
-        }
-        pv = rv[0];
-        pi = ri[0];
-        __syncthreads();                                             // (read before the next round writes)
-        if (pi == 0x7fffffff) break;                                 // fewer finite scores than nbest (the same in every thread)
-        if (i == 0) top = pv;
-        if (tid == 0) {
-            int* e = rec + 4 + 4 * i;
-            e[0] = __double2loint(pv);
-            e[1] = __double2hiint(pv);
-            e[2] = pi;
-            e[3] = 0;
-        }
-        ++n_out;
-    }
-    // ---- logz over ALL K words of the line, and whether every score is a NaN (a flagged line; never an empty one) ----
-    double sum = 0.0;
-    int nans = 0;
-    for (int k = tid; k < K; k += LXP_THREADS) {
-        const double v = sc[k];
-        if (v != v) ++nans;
-        else if (n_out > 0 && v != inf) sum += exp(v - top);         // (exp(-inf) = 0)
-    }
-    rv[tid] = sum;
-    ri[tid] = nans;
-    __syncthreads();
-    for (int o = LXP_THREADS / 2; o > 0; o >>= 1) {
-        if (tid < o) {
-            rv[tid] += rv[tid + o];
-            ri[tid] += ri[tid + o];
-        }
-        __syncthreads();
-    }
-    if (tid == 0) {
-        const int flag = K >= 1 && ri[0] == K;
-        const double logz = flag ? __builtin_nan("") : (n_out > 0 ? top + log(rv[0]) : CB_NEG);
-        rec[0] = n_out;
-        rec[1] = flag;
-        rec[2] = __double2loint(logz);
-        rec[3] = __double2hiint(logz);
-    }
+    if (K < 0 || K > LX_MAX_K || K > st_sc) return;                  // (likewise: no such line)
+    lx_select(scores + blockIdx.x * st_sc, K, nbest, record + row * st_rec);
 }
 
 TATT_API int tatt_ctc_lexicon_score_pairs(const float* logits, long st_t, long st_b, long st_c, int T, int B, int C, const int* codes,
                                           int n_codes, const int* words, int U, const int* tiles, int n_tiles, const int* pairs,
                                           int n_pairs, const int* counts, int max_count, double* scores, long st_sc, hipStream_t st) {
     if (!logits || !codes || !words || !tiles || !pairs || !counts || !scores) return 1;
-    if (T <= 0 || T > LXP_MAX_T || C <= 0 || C > LXP_MAX_C || B <= 0 || B > 65535 || U <= 0 || U > LXP_MAX_U || n_codes < 0) return 1;
-    if (n_tiles <= 0 || n_pairs <= 0 || n_tiles > n_pairs || (long)n_pairs > (long)B * LXP_MAX_K) return 1;
-    if (max_count < 1 || max_count > LXP_MAX_K || st_sc < max_count) return 1;
+    if (T <= 0 || T > LX_MAX_T || C <= 0 || C > LX_MAX_C || B <= 0 || B > 65535 || U <= 0 || U > LXP_MAX_U || n_codes < 0) return 1;
+    if (n_tiles <= 0 || n_pairs <= 0 || n_tiles > n_pairs || (long)n_pairs > (long)B * LX_MAX_K) return 1;
+    if (max_count < 1 || max_count > LX_MAX_K || st_sc < max_count) return 1;
     int rc = 0;
     static TattPerDevice attr_once;                                  // once per device, under the site lock (common.h)
     tatt_per_device(attr_once, [&] {
         rc = (int)hipFuncSetAttribute(reinterpret_cast<const void*>(ctc_lexicon_pairs_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                      LXP_LDS_MAX);
+                                      LX_LDS_MAX);
     });
     if (rc) return rc;                                               // (beyond 64 KB of LDS the launch depends on it)
-    const size_t lds = (size_t)T * (8 + 4 + 4 * (size_t)C);
-    hipLaunchKernelGGL(ctc_lexicon_pairs_kernel, dim3(n_tiles), dim3(LXP_THREADS), lds, st, logits, st_t, st_b, st_c, T, B, C, codes,
-                       n_codes, words, U, tiles, pairs, n_pairs, counts, max_count, scores, st_sc);
+    hipLaunchKernelGGL(ctc_lexicon_pairs_kernel, dim3(n_tiles), dim3(LX_THREADS), LX_STAGE_LDS(T, C), st, logits, st_t, st_b, st_c, T, B, C,
+                       codes, n_codes, words, U, tiles, pairs, n_pairs, counts, max_count, scores, st_sc);
     return LAUNCH_CHECK();
 }
 
 TATT_API int tatt_ctc_lexicon_select_rows(const double* scores, long st_sc, int B, const int* counts, int nbest, const int* index,
                                           int* record, int n_rows, long st_rec, hipStream_t st) {
     if (!scores || !counts || !index || !record) return 1;
-    if (B <= 0 || st_sc < 1 || nbest < 1 || nbest > LXP_NBEST || n_rows <= 0 || st_rec < lxp_record_words(nbest))
+    if (B <= 0 || st_sc < 1 || nbest < 1 || nbest > LX_NBEST || n_rows <= 0 || st_rec < lx_record_words(nbest))
         return 1;
-    hipLaunchKernelGGL(ctc_lexicon_select_rows_kernel, dim3(B), dim3(LXP_THREADS), 0, st, scores, st_sc, counts, nbest, index, record,
+    hipLaunchKernelGGL(ctc_lexicon_select_rows_kernel, dim3(B), dim3(LX_THREADS), 0, st, scores, st_sc, counts, nbest, index, record,
                        n_rows, st_rec);
     return LAUNCH_CHECK();
 }
 
 TATT_API int tatt_line_lexicons_limits(int* out) {
     if (!out) return 1;
-    out[0] = LXP_MAX_T;
-    out[1] = LXP_MAX_C;
-    out[2] = LXP_MAX_L;
-    out[3] = LXP_MAX_K;
+    out[0] = LX_MAX_T;
+    out[1] = LX_MAX_C;
+    out[2] = LX_MAX_L;
+    out[3] = LX_MAX_K;
     out[4] = LXP_MAX_U;
-    out[5] = LXP_NBEST;
+    out[5] = LX_NBEST;
     return 0;
 }

@@ -7,7 +7,13 @@
 //                         tid in registers: a token (float64 score, start step) and one word of constants.  Lane s of a word's segment
 //                         is the state ch[s / 2] (s even) or the in-word blank bl[s / 2] (s odd), s < 2 L - 1.
 //                         Staging as ctclex.hip: the line's T x C fp32 logits in LDS with mx (fp32) and ls (float64) per step, a wave per
-//                         step; lp = (double(x) - double(mx)) - ls, written to lp_out where the caller asks for it.
+//                         step; lp = (double(x) - double(mx)) - ls, written to lp_out where the caller asks for it.  The limits and
+//                         the packed word's layout are ctc_lex.h's; the staging loop is that header's `lx_stage` RESTATED here, with
+//                         WD_STAGE steps in flight and the work-group's own wave count.  Called as a function it computes the same
+//                         bytes and leaves the step loop's instructions as they are, but the staging comes out 16 bytes longer and the
+//                         29 KB step loop of <16>, which now starts on a 64-byte boundary, starts 16 bytes behind one:
+//                         tatt_ctc_words_read ran 0.85 % slower (padded back onto the boundary: at this text's speed;
+//                         profiles/ctc_lex_core_ab.txt).  A change to the staging rule is made in ctc_lex.h AND here.
 //                         One step t, two barriers (one behind A, one behind B and C):
 //                           A  every lane: m = own token; s >= 1: the token of lane s - 1; ch[j], j >= 1, w[j] != w[j - 1]: the token of
 //                              lane s - 2; s == 0: (enter[t][w[0]] + word_penalty, start t) -- each replaces m only where STRICTLY
@@ -29,25 +35,18 @@
 // take the report again when the compiler changes (tools/kres.sh tatt_amd/csrc/ctcwords.hip; ScratchSize must stay 0).
 // Every loop is bounded by T, C, R or a literal.  Nothing is indexed by lexicon DATA without a range check: a word whose length, code
 // offset, codes or own index are out of range takes no part.  No traffic between work-groups.
-#include "common.h"
-#include "ctc_f64.h"
+#include "ctc_lex.h"
 
-#define WD_MAX_T 256
-#define WD_MAX_C 64
-#define WD_MAX_L 31
-#define WD_MAX_K 65536
 #define WD_THREADS 1024
 #define WD_SLOTS 16                            // packed lanes a thread holds: 16 x (2 of score + start + constants) registers
 #define WD_LANES (WD_THREADS * WD_SLOTS)
-#define WD_WORD 4                              // ints per packed word, as ctclex.hip
 #define WD_STAGE 4                             // steps a wave has in flight while it stages
 #define WD_NONE 0xffffffffu
 
 static inline long wd_pad64(long v) { return (v + 63) / 64 * 64; }
-static inline size_t wd_lds(int T, int C) {
-    return (size_t)T * 8 + 2 * 64 * 8 + 64 * 8 + (size_t)T * 4 + (size_t)T * C * 4 + (size_t)T * C * 4 + (size_t)T * C + (size_t)T;
-}
-#define WD_LDS_MAX (WD_MAX_T * 8 + 2 * 64 * 8 + 64 * 8 + WD_MAX_T * 4 + WD_MAX_T * WD_MAX_C * 9 + WD_MAX_T)
+// the staged logits, then X [2][64] and enter [64] (float64), Xrec (4 T C), Esrc (T C) and Gsrc (T)
+static inline size_t wd_lds(int T, int C) { return LX_STAGE_LDS(T, C) + 2 * 64 * 8 + 64 * 8 + (size_t)T * C * 5 + (size_t)T; }
+#define WD_LDS_MAX (LX_LDS_MAX + 2 * 64 * 8 + 64 * 8 + LX_MAX_T * LX_MAX_C * 5 + LX_MAX_T)
 static_assert(WD_LDS_MAX <= 160 * 1024, "the tables of a line fit the LDS of a CU");
 
 // constants of a packed lane, one 32-bit word
@@ -98,7 +97,7 @@ __global__ __launch_bounds__(WD_THREADS) void ctc_words_kernel(const float* __re
     if (row < 0 || row >= n_rows) return;                            // (the whole work-group: nothing is written)
     int* rec = record + row * st_rec;
 
-    // ---- staging: a wave per step, lane = class, WD_STAGE steps in flight ----
+    // ---- staging: a wave per step, lane = class, WD_STAGE steps in flight (ctc_lex.h's lx_stage<WD_STAGE> restated: see the top) ----
     const float* x = logits + b * st_b + lane * st_c;
     int flag = 0;
     for (int t0 = wave; t0 < T && !flag; t0 += waves * WD_STAGE) {
@@ -161,12 +160,12 @@ __global__ __launch_bounds__(WD_THREADS) void ctc_words_kernel(const float* __re
         const bool live = slot < count;                              // (first + count <= K: the entry saw to it)
         int L = 0, off = 0, orig = -1;
         if (live) {
-            const int* w = words + (long)(first + slot) * WD_WORD;
+            const int* w = words + (long)(first + slot) * LX_WORD;
             L = w[0];
             off = w[1];
             orig = w[2];
         }
-        const bool shape_ok = L >= 1 && L <= WD_MAX_L && 2 * L + 1 <= G && off >= 0 && off <= n_codes - L && orig >= 0 && orig < K;
+        const bool shape_ok = L >= 1 && L <= LX_MAX_L && 2 * L + 1 <= G && off >= 0 && off <= n_codes - L && orig >= 0 && orig < K;
         const bool on = live && shape_ok && s < 2 * L - 1;
         const int j = s >> 1;
         int c = 0, below = 0, c0 = 0;                                // w[j], w[j - 1], w[0]
@@ -356,7 +355,7 @@ TATT_API int tatt_ctc_words_read(const float* logits, long st_t, long st_b, long
                                  const int* words, int K, int k16, int k32, int k64, double word_penalty, const int* index, int* record,
                                  int n_rows, int cap, long st_rec, double* lp_out, long st_lp, hipStream_t st) {
     if (!logits || !codes || !words || !index || !record) return 1;
-    if (T <= 0 || T > WD_MAX_T || C <= 0 || C > WD_MAX_C || B <= 0 || B > 65535 || K <= 0 || K > WD_MAX_K || n_codes < 0) return 1;
+    if (T <= 0 || T > LX_MAX_T || C <= 0 || C > LX_MAX_C || B <= 0 || B > 65535 || K <= 0 || K > LX_MAX_K || n_codes < 0) return 1;
     if (k16 < 0 || k32 < 0 || k64 < 0 || (long)k16 + k32 + k64 != K) return 1;
     const long lanes = wd_pad64(16L * k16) + wd_pad64(32L * k32) + 64L * k64;
     if (lanes > WD_LANES) return 1;
@@ -379,8 +378,8 @@ TATT_API int tatt_ctc_words_read(const float* logits, long st_t, long st_b, long
 
 TATT_API int tatt_words_limits(int* out) {
     if (!out) return 1;
-    out[0] = WD_MAX_T;
-    out[1] = WD_MAX_C;
+    out[0] = LX_MAX_T;
+    out[1] = LX_MAX_C;
     out[2] = WD_LANES;
     out[3] = WD_THREADS;
     out[4] = WD_SLOTS;

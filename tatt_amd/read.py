@@ -1155,23 +1155,33 @@ def ctc_lexicon_score(logits, lexicon: Lexicon, scores):
     return scores
 
 
+def _check_select(what, scores, index, record, nbest, counts=None):
+    """the argument checks of `ctc_lexicon_select` and, given counts, of `ctc_lexicon_select_rows` -> scores.shape"""
+    if not scores.is_cuda:
+        raise RuntimeError("tatt_amd kernels need tensors on an AMD GPU (HIP device); got %s. There is no CPU fallback in the product "
+                           "path." % scores.device)
+    if scores.dtype != torch.float64 or scores.dim() != 2 or scores.stride(1) != 1 or (counts is not None and scores.shape[1] < 1):
+        raise ValueError("%s: scores must be a 2-D float64 tensor with contiguous%s rows" % (what, "" if counts is None else ", non-empty"))
+    B = scores.shape[0]
+    if counts is not None:
+        _int32_on(what, "counts", counts, scores.device)
+        if counts.numel() != B:
+            raise ValueError("%s: %d counts for %d lines" % (what, counts.numel(), B))
+    if record.dtype != torch.int32 or record.dim() != 2 or record.stride(1) != 1 or index.dtype != torch.int32 or index.numel() < B:
+        raise ValueError("%s: record must be a 2-D int32 tensor with contiguous rows, index an int32 tensor of B entries" % what)
+    _check_nbest(what, nbest)
+    if record.shape[1] < lexicon_record_words(nbest):
+        raise ValueError("%s: rows of %d words; nbest = %d needs %d" % (what, record.shape[1], nbest, lexicon_record_words(nbest)))
+    return scores.shape
+
+
 def ctc_lexicon_select(scores, index, record, nbest: int = 4):
     """ONE tatt_ctc_lexicon_select launch: scores (B, K) float64 on the device with contiguous rows, index (B,) int32 on the device:
     the record row of every line, record (n_rows, >= lexicon_record_words(nbest)) int32 on the device, rows contiguous (see
     `parse_lexicon_records`).  ValueError for what the entry refuses, before any launch."""
     from . import ops
     from ._lib import LIB
-    if not scores.is_cuda:
-        raise RuntimeError("tatt_amd kernels need tensors on an AMD GPU (HIP device); got %s. There is no CPU fallback in the product "
-                           "path." % scores.device)
-    if scores.dtype != torch.float64 or scores.dim() != 2 or scores.stride(1) != 1:
-        raise ValueError("ctc_lexicon_select: scores must be a 2-D float64 tensor with contiguous rows")
-    B, K = scores.shape
-    if record.dtype != torch.int32 or record.dim() != 2 or record.stride(1) != 1 or index.dtype != torch.int32 or index.numel() < B:
-        raise ValueError("ctc_lexicon_select: record must be a 2-D int32 tensor with contiguous rows, index an int32 tensor of B entries")
-    _check_nbest("ctc_lexicon_select", nbest)
-    if record.shape[1] < lexicon_record_words(nbest):
-        raise ValueError("ctc_lexicon_select: rows of %d words; nbest = %d needs %d" % (record.shape[1], nbest, lexicon_record_words(nbest)))
+    B, K = _check_select("ctc_lexicon_select", scores, index, record, nbest)
     rc = LIB.tatt_ctc_lexicon_select(ops.P(scores), scores.stride(0), B, K, nbest, ops.P(index), ops.P(record), record.shape[0],
                                      record.stride(0), ops.stream())
     if rc == 1:
@@ -1270,21 +1280,7 @@ def ctc_lexicon_select_rows(scores, counts, index, record, nbest: int = 4):
     before any launch."""
     from . import ops
     from ._lib import LIB
-    what = "ctc_lexicon_select_rows"
-    if not scores.is_cuda:
-        raise RuntimeError("tatt_amd kernels need tensors on an AMD GPU (HIP device); got %s. There is no CPU fallback in the product "
-                           "path." % scores.device)
-    if scores.dtype != torch.float64 or scores.dim() != 2 or scores.stride(1) != 1 or scores.shape[1] < 1:
-        raise ValueError("%s: scores must be a 2-D float64 tensor with contiguous, non-empty rows" % what)
-    B = scores.shape[0]
-    _int32_on(what, "counts", counts, scores.device)
-    if counts.numel() != B:
-        raise ValueError("%s: %d counts for %d lines" % (what, counts.numel(), B))
-    if record.dtype != torch.int32 or record.dim() != 2 or record.stride(1) != 1 or index.dtype != torch.int32 or index.numel() < B:
-        raise ValueError("%s: record must be a 2-D int32 tensor with contiguous rows, index an int32 tensor of B entries" % what)
-    _check_nbest(what, nbest)
-    if record.shape[1] < lexicon_record_words(nbest):
-        raise ValueError("%s: rows of %d words; nbest = %d needs %d" % (what, record.shape[1], nbest, lexicon_record_words(nbest)))
+    B = _check_select("ctc_lexicon_select_rows", scores, index, record, nbest, counts)[0]
     rc = LIB.tatt_ctc_lexicon_select_rows(ops.P(scores), scores.stride(0), B, ops.P(counts), nbest, ops.P(index), ops.P(record),
                                           record.shape[0], record.stride(0), ops.stream())
     if rc == 1:

@@ -120,19 +120,25 @@ def make_cases(dev):
     return cases
 
 
-def main():
+def arguments():
     ap = argparse.ArgumentParser()
     ap.add_argument("--against", required=True, help="another build of libtatt_hip.so with the same C ABI")
     ap.add_argument("--repeats", type=int, default=9)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--window-ms", type=float, default=20.0)
     ap.add_argument("--out", default=None)
-    a = ap.parse_args()
+    return ap.parse_args()
+
+
+def run(bench, a, make_cases):
+    """the two libraries on {entry: [launch]} = make_cases(device) -> the result line, printed and written to a.out.  A launch is called
+    with a library and has `out` (the tensor it writes) and `init` (None, or what `out` holds before the compared pass); tools/
+    bench_lexicon_core.py measures its entries through this function too."""
     from tatt_amd._lib import LIB_PATH, parse_header
     protos = parse_header()
     libs = {"tree": load(LIB_PATH, protos), "against": load(os.path.abspath(a.against), protos)}
     dev = torch.device("cuda:0")
-    res = {"bench": "resamplers", "repeats": a.repeats, "window_ms": a.window_ms, "device": torch.cuda.get_device_name(0)}
+    res = {"bench": bench, "repeats": a.repeats, "window_ms": a.window_ms, "device": torch.cuda.get_device_name(0)}
 
     def once(lib, launches):
         """one pass from the initial bytes -> every output's bytes"""
@@ -183,7 +189,8 @@ def main():
     if a.out:
         with open(a.out, "w") as f:
             f.write(line + "\n")
+    return res
 
 
 if __name__ == "__main__":
-    main()
+    run("resamplers", arguments(), make_cases)

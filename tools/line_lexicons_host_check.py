@@ -40,7 +40,7 @@ def main():
     from tests.test_line_lexicons import CASES, compare_with_spec, corrupt_tables, line_case
     work = a.keep or tempfile.mkdtemp(prefix="line_lexicons_host_")
     os.makedirs(work, exist_ok=True)
-    for name in ("ctclexp.hip", "ctc_f64.h"):
+    for name in ("ctclexp.hip", "ctc_lex.h", "ctc_f64.h"):
         shutil.copy(os.path.join(ROOT, "tatt_amd", "csrc", name), work)
     shutil.copy(os.path.join(ROOT, "tools", "words_host", "common.h"), work)
     shutil.copy(os.path.join(ROOT, "tools", "line_lexicons_host", "main.cpp"), work)

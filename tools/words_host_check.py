@@ -40,7 +40,7 @@ def main():
     from tests.test_words import NEG, case_inputs, cases, degenerate_word_lines, log_softmax_rows, planted_lines
     work = a.keep or tempfile.mkdtemp(prefix="words_host_")
     os.makedirs(work, exist_ok=True)
-    for name in ("ctcwords.hip", "ctc_f64.h"):
+    for name in ("ctcwords.hip", "ctc_lex.h", "ctc_f64.h"):
         shutil.copy(os.path.join(ROOT, "tatt_amd", "csrc", name), work)
     for name in ("common.h", "main.cpp"):
         shutil.copy(os.path.join(ROOT, "tools", "words_host", name), work)
