@@ -1018,6 +1018,29 @@ int tatt_ctc_beam_lm_read(const float* logits, long st_t, long st_b, long st_c, 
                           hipStream_t st);
 /* out[0..1]: the largest order and the most classes of a table tatt_ctc_beam_lm_read takes.  Host only: needs no GPU. */
 int tatt_lm_limits(int* out);
+/* tatt_ctc_beam_read held to a FORMAT (the same kernel, instantiated with the pattern statements; specification
+ * read.ctc_beam_pattern_read_host).  The format is a DFA over the classes (read.Pattern): table: S rows of C bytes on the device,
+ * table[q C + c] the state after class c in state q, or 255 where no string of the format continues that way (column 0 is never
+ * read; an entry >= S is read as 255); accept: S bytes, non-zero for an accepting state; state 0 is the start state.  The state is kept
+ * per trie node.  The extension of a beam entry by c is a candidate only where the table has a state for it; keys, tie rule and order
+ * are the plain search's.  After the last step the entries in a non-accepting state are dropped and the first nbest of the rest are
+ * written, in their order: the record row is tatt_ctc_beam_read's, [0] may be 0 on a clean line.
+ * Returns 1 before any launch for everything tatt_ctc_beam_read refuses, a null table or accept, S outside 1 .. 64. */
+int tatt_ctc_beam_pattern_read(const float* logits, long st_t, long st_b, long st_c, int T, int B, int C, int beam, int nbest,
+                               const unsigned char* table, const unsigned char* accept, int S, const int* index, int* record,
+                               int n_rows, int cap, long st_rec, hipStream_t st);
+/* The exact log-probability that a line reads as ANY member of a format (csrc/ctcpat.hip; specification read.ctc_pattern_mass_host):
+ * the sum over ALL alignments whose collapsed string the DFA (table, accept, S as above) accepts, carried per (state, last class) in
+ * float64 probabilities with a power-of-two rescale per step; O(T S C) per line, one line per wave, no atomics, a fixed order of every
+ * sum.  Line b writes 4 words at out + index[b] st_out (an index outside 0 .. n_rows - 1 writes nothing): [0..1] the float64 mass as
+ * it is, low word first (-inf: nothing is accepted in T steps; NaN on a flagged line)  [2] flag (a NaN or +inf logit, a step without a
+ * finite logit)  [3] 0.
+ * Returns 1 before any launch, writing nothing, for: a null pointer, T outside 1 .. 256, C or S outside 1 .. 64, B or n_rows <= 0,
+ * st_out < 4. */
+int tatt_ctc_pattern_mass(const float* logits, long st_t, long st_b, long st_c, int T, int B, int C, const unsigned char* table,
+                          const unsigned char* accept, int S, const int* index, int* out, int n_rows, long st_out, hipStream_t st);
+/* out[0..3]: most steps T, most classes C and most DFA states S of the two entries above, most beam entries.  Host only: needs no GPU. */
+int tatt_pattern_limits(int* out);
 /* Lexicon decoding (csrc/ctclex.hip; specification read.ctc_lexicon_read_host): scores[b][k] = the exact CTC log-probability (blank 0,
  * the forward recursion of read.ctc_string_logp_host in float64) of word k of a closed list under the logits (T,B,C) fp32 of image b,
  * given by element strides.  The list is packed by the host (read.Lexicon): codes: the class ids of all words one after the other

@@ -98,3 +98,34 @@ __device__ __forceinline__ int lx_below_i(int v, int lane, int fill) {
     if ((lane & 15) == 0) r = b;
     return r;
 }
+
+// Exclusive scans of a wave's 64 values (ctcpat.hip: the sum over every lane but one's own is prefix + suffix, a sum of non-negative
+// terms, never total - own).  Inside a row of 16 lanes: four row shifts make the inclusive scan, one more shift makes it exclusive (the
+// row's first / last lane takes 0); across rows: the rows' totals are read from the rows' last / first lanes and the earlier / later
+// ones are added.  The order of the additions is fixed.
+template <int CTRL>
+__device__ __forceinline__ double cb_moved(double v) {               // the value CTRL moves here, 0 for a lane without a source
+    return __hiloint2double(__builtin_amdgcn_update_dpp(0, __double2hiint(v), CTRL, 0xf, 0xf, false),
+                            __builtin_amdgcn_update_dpp(0, __double2loint(v), CTRL, 0xf, 0xf, false));
+}
+__device__ __forceinline__ double cb_lane_value(double v, int k) {
+    return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), k), __builtin_amdgcn_readlane(__double2loint(v), k));
+}
+__device__ __forceinline__ double cb_wave_excl_prefix(double v, int lane) {
+    v = v + cb_moved<0x111>(v);                                      // row_shr:1, 2, 4, 8
+    v = v + cb_moved<0x112>(v);
+    v = v + cb_moved<0x114>(v);
+    v = v + cb_moved<0x118>(v);
+    const double t0 = cb_lane_value(v, 15), t1 = cb_lane_value(v, 31), t2 = cb_lane_value(v, 47);
+    const int row = lane >> 4;
+    return cb_moved<0x111>(v) + (row == 0 ? 0.0 : row == 1 ? t0 : row == 2 ? t0 + t1 : (t0 + t1) + t2);
+}
+__device__ __forceinline__ double cb_wave_excl_suffix(double v, int lane) {
+    v = v + cb_moved<0x101>(v);                                      // row_shl:1, 2, 4, 8
+    v = v + cb_moved<0x102>(v);
+    v = v + cb_moved<0x104>(v);
+    v = v + cb_moved<0x108>(v);
+    const double t1 = cb_lane_value(v, 16), t2 = cb_lane_value(v, 32), t3 = cb_lane_value(v, 48);
+    const int row = lane >> 4;
+    return cb_moved<0x101>(v) + (row == 3 ? 0.0 : row == 2 ? t3 : row == 1 ? t3 + t2 : (t3 + t2) + t1);
+}

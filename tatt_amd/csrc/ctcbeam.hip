@@ -19,6 +19,15 @@
 // bonus are already in it, so the kernel only ADDS entries of the table, left to right, and the term is the specification's bit for bit);
 // candidates are ranked by acoustic + LM, the record keeps the two apart, and after the last step the beam is ranked once more with the
 // end-of-line increment W[history][0] added.  Every LM statement stands under `if constexpr (LM)`.
+// PAT = true (tatt_ctc_beam_pattern_read; specification `ctc_beam_pattern_read_host`) holds the search to a format, a DFA over the classes
+// (`read.Pattern`: `ptab` S rows of C bytes, the next state or 255; `pacc` S bytes): the DFA state is a property of the trie NODE, one
+// byte written where the node is made (so a prefix that leaves the beam and comes back keeps its state; the byte is loaded by the lane
+// that selected the extension, beside its table look-up, and lane 0, which places the nodes one after the other, only copies it); lane c tests
+// ptab[state_r C + c] for its BM candidates where the LM loads stand, an extension the format does not continue with is no candidate,
+// and after the last step the entries in a non-accepting state are dropped, the rest keeping their order.  An extension that spells a
+// prefix already in the beam needs no test: that prefix's node was made through the same table entry.  A table entry >= S is read as
+// 255, so no content of the table can lead a load astray.  The record row is the plain search's.  Every statement of it stands under
+// `if constexpr (PAT)`; only <BM, false, true> is instantiated.
 #include "common.h"
 #include "ctc_f64.h"                                           // CB_NEG, cb_lse, the wave maxima / minima / sums
 
@@ -36,6 +45,7 @@ static_assert(CB_TABLE > 2 * CB_NODES && CB_TABLE == 1 << CB_TABLE_BITS && CB_NO
 static __host__ __device__ inline int cb_entry_words(int cap) { return 4 + cap + (cap & 1); }
 // with a language model: float64 logp (2) | float64 lm (2) | length | pad | cap classes, an even count
 static __host__ __device__ inline int cb_lm_entry_words(int cap) { return 6 + cap + (cap & 1); }
+#define CB_MAX_S 64                            // most states of a format's DFA (PAT): a state is a byte, 255 says "no such string"
 #define CB_LM_ORDER 3                          // most classes of an n-gram: the table has C^order entries, at most 64^3 doubles = 2 MB
 
 __device__ __forceinline__ unsigned cb_hash(int parent, int c) {
@@ -44,11 +54,13 @@ __device__ __forceinline__ unsigned cb_hash(int parent, int c) {
 
 // BM: the beam entries the kernel keeps registers and unrolled loops for (beam <= BM <= CB_BEAM): a launch takes the smallest that fits.
 // LM: lmw is the table W of C^order doubles, row = the last order - 1 classes of a prefix (0: before the line begins), column = the class
-template <int BM, bool LM>
+template <int BM, bool LM, bool PAT>
 __global__ __launch_bounds__(64) void ctc_beam_read_kernel(const float* __restrict__ logits, long st_t, long st_b, long st_c, int T,
                                                            int C, int beam, int nbest, const int* __restrict__ index,
                                                            int* __restrict__ record, int n_rows, int cap, long st_rec,
-                                                           const double* __restrict__ lmw, int order) {
+                                                           const double* __restrict__ lmw, int order,
+                                                           const unsigned char* __restrict__ ptab,
+                                                           const unsigned char* __restrict__ pacc, int S) {
     __shared__ double lp[CB_MAX_C];                                  // the step's log-soft-max
     __shared__ double pb[2][CB_BEAM], pnb[2][CB_BEAM], tot[2][CB_BEAM];      // the beam, by rank; [cur] is read, [cur ^ 1] written
     __shared__ int node[2][CB_BEAM];
@@ -63,6 +75,9 @@ __global__ __launch_bounds__(64) void ctc_beam_read_kernel(const float* __restri
     __shared__ int last_sh[CB_BEAM];                                 // the last class of every entry's prefix, -1 for the empty one
     __shared__ double lmv[2][LM ? CB_BEAM : 1];                      // LM: the LM term of every entry, by rank, buffered as the beam is
     __shared__ int ctx[LM ? CB_BEAM : 1];                            // LM: the row of W that every entry's prefix selects
+    __shared__ unsigned char nstate[PAT ? CB_NODES : 1];             // PAT: the DFA state of every node's string
+    __shared__ int pst[PAT ? CB_BEAM : 1];                           // PAT: the DFA state of every entry, by rank
+    __shared__ int ext_st[PAT ? CB_BEAM : 1];                        // PAT: the DFA state of a selected extension that needs its node
     const int lane = threadIdx.x;
     const float* x = logits + blockIdx.x * st_b + lane * st_c;
 
@@ -75,6 +90,7 @@ __global__ __launch_bounds__(64) void ctc_beam_read_kernel(const float* __restri
             stot[lane] = CB_NEG;
             last_sh[lane] = -1;
             if constexpr (LM) ctx[lane] = 0;                         // (rows beyond the beam are loaded from, too: row 0)
+            if constexpr (PAT) pst[lane] = 0;                        // (likewise: state 0)
         }
         if constexpr (LM) (&lmv[0][0])[lane] = 0.0;                  // (the empty prefix: 0)
     }
@@ -82,6 +98,7 @@ __global__ __launch_bounds__(64) void ctc_beam_read_kernel(const float* __restri
     if (lane == 0) {
         par[0] = 0;
         cls[0] = 0;
+        if constexpr (PAT) nstate[0] = 0;                            // the start state
         node[0][0] = 0;                                              // the empty prefix is the root
         pb[0][0] = 0.0;
         pnb[0][0] = CB_NEG;
@@ -114,6 +131,7 @@ __global__ __launch_bounds__(64) void ctc_beam_read_kernel(const float* __restri
             const double a = tot[cur][lane] + lp[0];
             double b = CB_NEG;
             last_sh[lane] = nd != 0 ? cls[nd] : -1;
+            if constexpr (PAT) pst[lane] = nstate[nd];
             if constexpr (LM) {                                      // (the root: cls[0] = par[0] = 0, "before the line begins")
                 const int c1 = cls[nd], c2 = cls[par[nd]];
                 ctx[lane] = order == 1 ? 0 : order == 2 ? c1 : c2 * C + c1;
@@ -143,6 +161,11 @@ __global__ __launch_bounds__(64) void ctc_beam_read_kernel(const float* __restri
 #pragma unroll
             for (int r = 0; r < BM; ++r) w[r] = lmw[lane < C ? ctx[r] * C + lane : 0];       // (coalesced; the table lives in L2)
         }
+        bool go[PAT ? BM : 1];                                       // PAT: the format continues from entry r with this lane's class
+        if constexpr (PAT) {
+#pragma unroll
+            for (int r = 0; r < BM; ++r) go[r] = ptab[lane < C ? pst[r] * C + lane : 0] < S;         // (at most 4 KB: it lives in L2)
+        }
 #pragma unroll
         for (int r = 0; r < BM; ++r) {
             const double ext = (lane == last_sh[r] ? pb[cur][r] : tot[cur][r]) + lpc;
@@ -150,6 +173,8 @@ __global__ __launch_bounds__(64) void ctc_beam_read_kernel(const float* __restri
             double val;
             if constexpr (LM)                                        // (first the LM term of the candidate, then the one sum)
                 val = lane == 0 ? stot[r] + lmv[cur][r] : (struck ? CB_NEG : ext + (lmv[cur][r] + w[r]));
+            else if constexpr (PAT)
+                val = lane == 0 ? stot[r] : (struck || !go[r] ? CB_NEG : ext);
             else
                 val = lane == 0 ? stot[r] : (struck ? CB_NEG : ext);
             v[r] = r < nb && lane < C ? val : CB_NEG;
@@ -217,6 +242,7 @@ __global__ __launch_bounds__(64) void ctc_beam_read_kernel(const float* __restri
                 node[nxt][lane] = miss ? 0 : found;
                 ext_par[lane] = p;
                 ext_cls[lane] = c;
+                if constexpr (PAT) ext_st[lane] = ptab[pst[r] * C + c];      // (lane i's own load, beside its look-up; < S: it was a candidate)
             }
             tot[nxt][lane] = my_val;
         }
@@ -236,6 +262,7 @@ __global__ __launch_bounds__(64) void ctc_beam_read_kernel(const float* __restri
                         if (table[slot] != CB_EMPTY) continue;       // (another key: this one is not in the table)
                         par[nn] = (unsigned short)p;
                         cls[nn] = (unsigned char)c;
+                        if constexpr (PAT) nstate[nn] = (unsigned char)ext_st[i];
                         table[slot] = (unsigned short)nn;
                         made = nn++;
                         break;
@@ -268,7 +295,8 @@ __global__ __launch_bounds__(64) void ctc_beam_read_kernel(const float* __restri
         return;
     }
     constexpr int HD = LM ? 6 : 4;                                   // words of an entry before its classes
-    const int n_out = nb < nbest ? nb : nbest, es = LM ? cb_lm_entry_words(cap) : cb_entry_words(cap);
+    int n_out = nb < nbest ? nb : nbest;
+    const int es = LM ? cb_lm_entry_words(cap) : cb_entry_words(cap);
     int src = lane;                                                  // the beam entry that record entry `lane` is
     if constexpr (LM) {
         // ---- the line ends here: final = (tot + lm) + W[history][0]; descending, ties to the lower rank.  The step loop is over, so
@@ -289,6 +317,26 @@ __global__ __launch_bounds__(64) void ctc_beam_read_kernel(const float* __restri
             ext_par[pos] = lane;
         }
         __syncthreads();
+        if (lane < n_out) src = ext_par[lane];
+    }
+    if constexpr (PAT) {
+        // ---- the line ends here: entries whose state does not accept are dropped, the rest keep their order.  The step loop is over,
+        // so ext_cls takes "entry r is accepted", ext_par the beam entry of every position ----
+        if (lane < nb) {
+            const int q = nstate[node[cur][lane]];
+            ext_cls[lane] = q < S && pacc[q] != 0;
+        }
+        __syncthreads();
+        int pos = 0, kept = 0;
+#pragma unroll
+        for (int j = 0; j < BM; ++j) {
+            const int a = j < nb ? ext_cls[j] : 0;
+            kept += a;
+            if (j < lane) pos += a;
+        }
+        if (lane < nb && ext_cls[lane] != 0) ext_par[pos] = lane;
+        __syncthreads();
+        n_out = kept < nbest ? kept : nbest;
         if (lane < n_out) src = ext_par[lane];
     }
     if (lane < n_out) {                                              // lane i walks its entry back to the root
@@ -324,28 +372,30 @@ __global__ __launch_bounds__(64) void ctc_beam_read_kernel(const float* __restri
     }
 }
 
-template <bool LM>
+template <bool LM, bool PAT>
 static int cb_launch(const float* logits, long st_t, long st_b, long st_c, int T, int B, int C, int beam, int nbest, const int* index,
-                     int* record, int n_rows, int cap, long st_rec, const double* lmw, int order, hipStream_t st) {
+                     int* record, int n_rows, int cap, long st_rec, const double* lmw, int order, const unsigned char* ptab,
+                     const unsigned char* pacc, int S, hipStream_t st) {
     if (!logits || !index || !record) return 1;
     if (T <= 0 || T > CB_MAX_T || B <= 0 || C <= 0 || C > CB_MAX_C || n_rows <= 0 || cap < T) return 1;
     const int es = LM ? cb_lm_entry_words(cap) : cb_entry_words(cap);
     if (nbest < 1 || nbest > beam || beam > CB_BEAM || st_rec < 2 + (long)nbest * es) return 1;
     if (beam <= 4)
-        hipLaunchKernelGGL((ctc_beam_read_kernel<4, LM>), dim3(B), dim3(64), 0, st, logits, st_t, st_b, st_c, T, C, beam, nbest, index,
-                           record, n_rows, cap, st_rec, lmw, order);
+        hipLaunchKernelGGL((ctc_beam_read_kernel<4, LM, PAT>), dim3(B), dim3(64), 0, st, logits, st_t, st_b, st_c, T, C, beam, nbest, index,
+                           record, n_rows, cap, st_rec, lmw, order, ptab, pacc, S);
     else if (beam <= 8)
-        hipLaunchKernelGGL((ctc_beam_read_kernel<8, LM>), dim3(B), dim3(64), 0, st, logits, st_t, st_b, st_c, T, C, beam, nbest, index,
-                           record, n_rows, cap, st_rec, lmw, order);
+        hipLaunchKernelGGL((ctc_beam_read_kernel<8, LM, PAT>), dim3(B), dim3(64), 0, st, logits, st_t, st_b, st_c, T, C, beam, nbest, index,
+                           record, n_rows, cap, st_rec, lmw, order, ptab, pacc, S);
     else
-        hipLaunchKernelGGL((ctc_beam_read_kernel<CB_BEAM, LM>), dim3(B), dim3(64), 0, st, logits, st_t, st_b, st_c, T, C, beam, nbest,
-                           index, record, n_rows, cap, st_rec, lmw, order);
+        hipLaunchKernelGGL((ctc_beam_read_kernel<CB_BEAM, LM, PAT>), dim3(B), dim3(64), 0, st, logits, st_t, st_b, st_c, T, C, beam, nbest,
+                           index, record, n_rows, cap, st_rec, lmw, order, ptab, pacc, S);
     return LAUNCH_CHECK();
 }
 
 TATT_API int tatt_ctc_beam_read(const float* logits, long st_t, long st_b, long st_c, int T, int B, int C, int beam, int nbest,
                                 const int* index, int* record, int n_rows, int cap, long st_rec, hipStream_t st) {
-    return cb_launch<false>(logits, st_t, st_b, st_c, T, B, C, beam, nbest, index, record, n_rows, cap, st_rec, nullptr, 0, st);
+    return cb_launch<false, false>(logits, st_t, st_b, st_c, T, B, C, beam, nbest, index, record, n_rows, cap, st_rec, nullptr, 0, nullptr,
+                                   nullptr, 0, st);
 }
 
 // the search with the increments table `lmw` of lm_classes^order float64 entries on the device (read.CharLM.increments)
@@ -353,7 +403,17 @@ TATT_API int tatt_ctc_beam_lm_read(const float* logits, long st_t, long st_b, lo
                                    const double* lmw, int order, int lm_classes, const int* index, int* record, int n_rows, int cap,
                                    long st_rec, hipStream_t st) {
     if (!lmw || order < 1 || order > CB_LM_ORDER || lm_classes != C) return 1;
-    return cb_launch<true>(logits, st_t, st_b, st_c, T, B, C, beam, nbest, index, record, n_rows, cap, st_rec, lmw, order, st);
+    return cb_launch<true, false>(logits, st_t, st_b, st_c, T, B, C, beam, nbest, index, record, n_rows, cap, st_rec, lmw, order, nullptr,
+                                  nullptr, 0, st);
+}
+
+// the search held to a format: table S rows of C bytes (the next state, or 255), accept S bytes, both on the device (read.Pattern)
+TATT_API int tatt_ctc_beam_pattern_read(const float* logits, long st_t, long st_b, long st_c, int T, int B, int C, int beam, int nbest,
+                                        const unsigned char* table, const unsigned char* accept, int S, const int* index, int* record,
+                                        int n_rows, int cap, long st_rec, hipStream_t st) {
+    if (!table || !accept || S < 1 || S > CB_MAX_S) return 1;
+    return cb_launch<false, true>(logits, st_t, st_b, st_c, T, B, C, beam, nbest, index, record, n_rows, cap, st_rec, nullptr, 0, table,
+                                  accept, S, st);
 }
 
 TATT_API int tatt_lm_limits(int* out) {

@@ -769,6 +769,9 @@ class SuperResolver:
     With read_lm = a `read.CharLM` (read_lm_weight, read_lm_bonus: `LineReader`'s lm_weight, lm_bonus) a character n-gram model is fused
     into that search: one tatt_ctc_beam_lm_read launch per chunk in place of the beam launch, `readings()` gives
     `read.BeamLMReading`s (text, logp, lm, score, alternatives).
+    With read_pattern = a `read.Pattern` or a regular expression (read_decode="beam"; not together with read_lm) every line is read
+    against that FORMAT: per chunk one tatt_ctc_beam_pattern_read launch and one tatt_ctc_pattern_mass launch in place of the greedy
+    one, `readings()` gives `read.PatternReading`s (text, logp, mass, posterior, alternatives); images and pictures are unchanged.
     read_decode="lexicon" (read_lexicon = a `read.Lexicon` or a list of words, read_nbest <= 16) reads every line against that closed
     list: per chunk the tatt_ctc_lexicon_score launches and one tatt_ctc_lexicon_select launch in place of the greedy one, and
     `readings()` gives `read.LexiconReading`s (text, logp, posterior, alternatives); every text is a word of the list.
@@ -786,7 +789,7 @@ class SuperResolver:
     def __init__(self, generator, prior=None, recognizer=None, batch_size: int = 48, lr_size=(16, 64), mask: bool = True,
                  rule: str = "floor", keep_sr: bool = False, long_lines: bool = False, stride: int = 32, reader=None,
                  read_decode: str = "greedy", read_beam: int = 8, read_nbest: int = 4, read_lexicon=None,
-                 read_word_penalty: float = 0.0, read_lm=None, read_lm_weight=None, read_lm_bonus=None):
+                 read_word_penalty: float = 0.0, read_lm=None, read_lm_weight=None, read_lm_bonus=None, read_pattern=None):
         from .io import DeviceCollator, DeviceExporter
         _refuse_attention_recognizer(recognizer, "SuperResolver")
         _check_module(generator, "generator")
@@ -809,11 +812,13 @@ class SuperResolver:
         self.sessions = {}
         self._ctc = {}                                               # batch size -> (keep, label, label_len) the decoding ignores
         self.reader = None
+        if reader is None and read_pattern is not None:
+            raise ValueError("SuperResolver: read_pattern= needs reader=crnn, read_decode='beam'")
         if reader is not None:
             from .read import LineReader
             self.reader = LineReader(reader, batch_size=batch_size, device=self.device, w=self.lr_size[1], decode=read_decode,
                                      beam=read_beam, nbest=read_nbest, lexicon=read_lexicon, word_penalty=read_word_penalty,
-                                     lm=read_lm, lm_weight=read_lm_weight, lm_bonus=read_lm_bonus)
+                                     lm=read_lm, lm_weight=read_lm_weight, lm_bonus=read_lm_bonus, pattern=read_pattern)
 
     def _texts(self, sr):
         """-> (pinned (n, T + 1) int32: decoded classes | length, its event)"""

@@ -186,47 +186,61 @@ def ctc_beam_read_host(logits, beam: int = 8, nbest: int = 4, details: bool = Fa
         if any(lp is None for lp in lps):
             out.append(BeamDecoded([], 1, inf, False) if details else BeamDecoded([], 1))
             continue
-        cur, margin, reentry = [((), real(0.0), neg, real(0.0))], inf, False          # (prefix, pb, pnb, tot), by rank
-        for lp in lps:
-            where = {e[0]: r for r, e in enumerate(cur)}
-            child = {}                                               # (rank of the parent, class) -> rank of that string in the beam
-            for r, e in enumerate(cur):
-                q = where.get(e[0][:-1]) if e[0] else None
-                if q is not None:
-                    child[(q, e[0][-1])] = r
-            stay = [[tot + lp[0], pnb + lp[p[-1]] if p else neg] for p, pb, pnb, tot in cur]
-            cands = []                                               # (total, key, pb', pnb')
-            for r, (p, pb, pnb, tot) in enumerate(cur):
-                last = p[-1] if p else -1
-                for c in range(1, C):
-                    v = (pb if c == last else tot) + lp[c]
-                    q = child.get((r, c))
-                    if q is not None:
-                        stay[q][1] = lse(stay[q][1], v)
-                    elif v != neg:
-                        cands.append((v, r * C + c, neg, v))
-            for r, (a, b) in enumerate(stay):
-                v = lse(a, b)
-                if v != neg:
-                    cands.append((v, r * C, a, b))
-            cands.sort(key=lambda e: (-e[0], e[1]))
-            if len(cands) > beam:
-                margin = min(margin, float(cands[beam - 1][0] - cands[beam][0]))
-            new = []
-            for v, key, a, b in cands[:beam]:
-                r, c = divmod(key, C)
-                new.append((cur[r][0] + (c,) if c else cur[r][0], a, b, v))
-            if details:
-                for e in new:
-                    p = e[0]
-                    if p not in where and any(len(o) > len(p) and o[:len(p)] == p for o in where):
-                        reentry = True
-            cur = new
-        for i in range(min(nbest, len(cur) - 1)):
-            margin = min(margin, float(cur[i][3] - cur[i + 1][3]))
-        entries = [(list(p), v) for p, pb, pnb, v in cur[:nbest]]
+        entries, margin, reentry = _beam_search(lps, C, beam, nbest, real, lse, details)
         out.append(BeamDecoded(entries, 0, margin, reentry) if details else BeamDecoded(entries, 0))
     return out
+
+
+def _beam_search(lps, C, beam, nbest, real, lse, details, table=None, accept=None):
+    """the search of `ctc_beam_read_host` on a clean line's log-soft-max rows -> (entries, margin, reentry).  With `table` (rows of C
+    next states, 255: none) and `accept` it is the search of `ctc_beam_pattern_read_host`: every entry carries the DFA state of its
+    prefix, an extension the table has no state for is no candidate, and after the last step the entries in a non-accepting state are
+    dropped before the first `nbest` are taken."""
+    neg, inf = real("-inf"), float("inf")
+    cur, margin, reentry = [((), real(0.0), neg, real(0.0), 0)], inf, False           # (prefix, pb, pnb, tot, state), by rank
+    for lp in lps:
+        where = {e[0]: r for r, e in enumerate(cur)}
+        child = {}                                                   # (rank of the parent, class) -> rank of that string in the beam
+        for r, e in enumerate(cur):
+            q = where.get(e[0][:-1]) if e[0] else None
+            if q is not None:
+                child[(q, e[0][-1])] = r
+        stay = [[tot + lp[0], pnb + lp[p[-1]] if p else neg] for p, pb, pnb, tot, st in cur]
+        cands = []                                                   # (total, key, pb', pnb')
+        for r, (p, pb, pnb, tot, st) in enumerate(cur):
+            last = p[-1] if p else -1
+            for c in range(1, C):
+                if table is not None and table[st][c] == 255:
+                    continue
+                v = (pb if c == last else tot) + lp[c]
+                q = child.get((r, c))
+                if q is not None:
+                    stay[q][1] = lse(stay[q][1], v)
+                elif v != neg:
+                    cands.append((v, r * C + c, neg, v))
+        for r, (a, b) in enumerate(stay):
+            v = lse(a, b)
+            if v != neg:
+                cands.append((v, r * C, a, b))
+        cands.sort(key=lambda e: (-e[0], e[1]))
+        if len(cands) > beam:
+            margin = min(margin, float(cands[beam - 1][0] - cands[beam][0]))
+        new = []
+        for v, key, a, b in cands[:beam]:
+            r, c = divmod(key, C)
+            st = cur[r][4]
+            new.append((cur[r][0] + (c,), a, b, v, table[st][c] if table is not None else 0) if c else (cur[r][0], a, b, v, st))
+        if details:
+            for e in new:
+                p = e[0]
+                if p not in where and any(len(o) > len(p) and o[:len(p)] == p for o in where):
+                    reentry = True
+        cur = new
+    if accept is not None:
+        cur = [e for e in cur if accept[e[4]]]
+    for i in range(min(nbest, len(cur) - 1)):
+        margin = min(margin, float(cur[i][3] - cur[i + 1][3]))
+    return [(list(e[0]), e[3]) for e in cur[:nbest]], margin, reentry
 
 
 def ctc_string_logp_host(logits_row, classes, real=None):
@@ -912,6 +926,453 @@ def read_lines_host(lines_u8, run_crnn, scale=2, w: int = 64):
     return out
 
 
+# ---- reading against a format --------------------------------------------------------------------------------------------------------------
+PatternMass = namedtuple("PatternMass", "mass flag")
+PatternDecoded = namedtuple("PatternDecoded", "entries mass flag margin reentry", defaults=(None, None))
+PatternReading = namedtuple("PatternReading", "text logp mass posterior alternatives rw squeezed")
+PATTERN_DEAD = 255        # table entry: no string of the format continues this way
+_PATTERN_SUBSETS = 4096   # most subsets the subset construction may make before minimisation
+
+
+class Pattern:
+    """A FORMAT to read lines against (`ctc_pattern_mass_host`, `ctc_beam_pattern_read_host`, `LineReader(decode="beam", pattern=...)`):
+    a regular expression over the reader's characters, compiled to a small DFA.  Registration plates, dates, prices, container codes:
+    open sets with a rigid shape, which no word list holds.
+
+    The characters are alphabet[1:]; alphabet[0] stands for the blank; the default is the reader's, "-" + io.ALPHABET.  The WHOLE line
+    must match (`re.fullmatch`).  The syntax is a strict subset of Python's `re`: literal alphabet characters, `.` (any alphabet
+    character), `[...]` with ranges and a leading `^`, `\\d`, `( )` and `(?: )`, `|`, and the quantifiers `?`, `*`, `+`, `{m}`, `{m,n}`
+    with n <= 256.  Upper-case letters are lower-cased.  Everything else -- anchors, back-references, look-around, lazy or possessive
+    quantifiers, flags, other escapes, a character outside the alphabet -- is a ValueError that names the position.
+    Compiled in four steps: an NFA, the subset construction, removal of every state from which no accepting state can be reached,
+    minimisation.  State 0 is the start state.  `n_states`; `table` (S, C) uint8: [q, c] the next state or 255 ("no string of the
+    format continues this way"; column 0 is all 255 and never read); `accept` (S,) uint8; `accepts(text)`; `device(device)` the one
+    upload.  ValueError for an empty language, a DFA of more than STATES states and an alphabet of more than CLASSES classes."""
+    STEPS, CLASSES, STATES, BEAM = 256, 64, 64, 16                   # tatt_pattern_limits, stated here so that a pattern needs no library
+    REPEAT = 256                                                     # the largest n of {m,n}
+
+    def __init__(self, spec, alphabet=None):
+        import numpy as np
+        if not isinstance(spec, str):
+            raise ValueError("Pattern takes a regular expression as a string; got %r" % (type(spec).__name__,))
+        self.spec, self.alphabet = spec, _alphabet() if alphabet is None else str(alphabet)
+        C = len(self.alphabet)
+        if not 2 <= C <= self.CLASSES:
+            raise ValueError("Pattern: an alphabet of 2 .. %d classes (the blank and the characters) expected; got %d" % (self.CLASSES, C))
+        if len(set(self.alphabet[1:])) != C - 1:
+            raise ValueError("Pattern: the alphabet %r names a character twice" % (self.alphabet[1:],))
+        self.n_classes = C
+        self._a2d = {ch: i for i, ch in enumerate(self.alphabet) if i >= 1}
+        ast = _PatternParser(spec, self._a2d).parse()
+        table, accept = _pattern_dfa(ast, C, spec)
+        if len(accept) > self.STATES:
+            raise ValueError("Pattern: %r needs a DFA of %d states; at most %d" % (spec, len(accept), self.STATES))
+        self.n_states = len(accept)
+        self.table, self.accept = np.asarray(table, np.uint8).reshape(self.n_states, C), np.asarray(accept, np.uint8)
+        self.table.setflags(write=False)
+        self.accept.setflags(write=False)
+        self._wide, self._dev = {C: self.table}, {}
+
+    def accepts(self, text) -> bool:
+        """whether the format holds `text` (lower-cased, as the spec was); a character outside the alphabet: no"""
+        q = 0
+        for ch in str(text).lower():
+            c = self._a2d.get(ch)
+            if c is None:
+                return False
+            q = int(self.table[q, c])
+            if q == PATTERN_DEAD:
+                return False
+        return bool(self.accept[q])
+
+    def table_for(self, classes: int):
+        """the table for logits of `classes` >= n_classes classes: the classes beyond the alphabet continue no string"""
+        import numpy as np
+        classes = int(classes)
+        if classes < self.n_classes:
+            raise ValueError("Pattern: the alphabet has %d classes, the logits %d" % (self.n_classes, classes))
+        if classes not in self._wide:
+            t = np.full((self.n_states, classes), PATTERN_DEAD, np.uint8)
+            t[:, :self.n_classes] = self.table
+            self._wide[classes] = t
+        return self._wide[classes]
+
+    def device(self, device, classes=None):
+        """-> (table, accept) uint8 tensors on `device`, uploaded once (per class count of the logits)"""
+        device = torch.device(device)
+        if device.type == "cuda" and device.index is None:           # ("cuda" and "cuda:0" are one upload)
+            device = torch.device("cuda", torch.cuda.current_device())
+        key = (device, self.n_classes if classes is None else int(classes))
+        if key not in self._dev:
+            self._dev[key] = (torch.from_numpy(self.table_for(key[1]).copy()).to(device), torch.from_numpy(self.accept.copy()).to(device))
+        return self._dev[key]
+
+
+class _PatternParser:
+    """recursive descent over the spec -> a tree of ("set", frozenset of classes), ("cat", [..]), ("alt", [..]), ("rep", node, m, n)
+    (n None: unbounded); ValueError with the position for everything outside the subset `Pattern` states"""
+
+    def __init__(self, spec, a2d):
+        self.s, self.i, self.a2d = spec, 0, a2d
+        self.all = frozenset(a2d.values())
+
+    def fail(self, what, at=None):
+        at = self.i if at is None else at
+        raise ValueError("Pattern: %s at position %d of %r" % (what, at, self.s))
+
+    def parse(self):
+        node = self.alt()
+        if self.i < len(self.s):
+            self.fail("an unbalanced ')'")
+        return node
+
+    def alt(self):
+        parts = [self.cat()]
+        while self.i < len(self.s) and self.s[self.i] == "|":
+            self.i += 1
+            parts.append(self.cat())
+        return parts[0] if len(parts) == 1 else ("alt", parts)
+
+    def cat(self):
+        parts = []
+        while self.i < len(self.s) and self.s[self.i] not in "|)":
+            parts.append(self.repeat())
+        return ("cat", parts)
+
+    def literal(self, ch, at):
+        c = self.a2d.get(ch.lower())
+        if c is None:
+            self.fail("the character %r, which the alphabet lacks," % ch, at)
+        return c
+
+    def repeat(self):
+        at, ch = self.i, self.s[self.i]
+        if ch in "*+?{":
+            self.fail("a quantifier with nothing to repeat")
+        if ch in "^$":
+            self.fail("an anchor (the whole line must match anyway)")
+        if ch in "]}":
+            self.fail("an unbalanced %r" % ch)
+        self.i += 1
+        if ch == ".":
+            node = ("set", self.all)
+        elif ch == "[":
+            node = ("set", self.char_class(at))
+        elif ch == "\\":
+            node = ("set", self.escape(at))
+        elif ch == "(":
+            if self.s.startswith("?", self.i):
+                if not self.s.startswith("?:", self.i):
+                    self.fail("a group extension other than (?: ) (look-around, flags and named groups are not taken)", at)
+                self.i += 2
+            node = self.alt()
+            if not self.s.startswith(")", self.i):
+                self.fail("a '(' that is never closed", at)
+            self.i += 1
+        else:
+            node = ("set", frozenset([self.literal(ch, at)]))
+        if self.i < len(self.s) and self.s[self.i] in "*+?{":
+            node = self.quantifier(node)
+            if self.i < len(self.s) and self.s[self.i] in "*+?{":
+                self.fail("a second quantifier (lazy, possessive and stacked quantifiers are not taken)")
+        return node
+
+    def escape(self, at):
+        if self.s.startswith("d", self.i):
+            self.i += 1
+            return frozenset(c for ch, c in self.a2d.items() if ch.isdecimal())
+        self.fail("an escape other than \\d", at)
+
+    def number(self):
+        j = self.i
+        while j < len(self.s) and self.s[j] in "0123456789":
+            j += 1
+        if j == self.i:
+            return None
+        v, self.i = int(self.s[self.i:j]), j
+        return v
+
+    def quantifier(self, node):
+        at, ch = self.i, self.s[self.i]
+        self.i += 1
+        if ch == "?":
+            return ("rep", node, 0, 1)
+        if ch == "*":
+            return ("rep", node, 0, None)
+        if ch == "+":
+            return ("rep", node, 1, None)
+        m = self.number()
+        n = m
+        if m is not None and self.s.startswith(",", self.i):
+            self.i += 1
+            n = self.number()
+        if m is None or n is None or not self.s.startswith("}", self.i):
+            self.fail("a quantifier that is neither {m} nor {m,n}", at)
+        self.i += 1
+        if n < m or n > Pattern.REPEAT:
+            self.fail("a quantifier {m,n} without m <= n <= %d" % Pattern.REPEAT, at)
+        return ("rep", node, m, n)
+
+    def char_class(self, at):
+        negate = self.s.startswith("^", self.i)
+        self.i += negate
+        members, first = set(), True
+        while True:
+            if self.i >= len(self.s):
+                self.fail("a '[' that is never closed", at)
+            j, ch = self.i, self.s[self.i]
+            self.i += 1
+            if ch == "]":
+                if first:
+                    self.fail("an empty character class", at)
+                break
+            first = False
+            if ch == "\\":
+                members |= self.escape(j)
+                continue
+            if ch in "[-":
+                self.fail("%r inside a character class (a range needs both ends)" % ch, j)
+            lo = self.literal(ch, j)
+            if self.s.startswith("-", self.i) and not self.s.startswith("-]", self.i):
+                k = self.i + 1
+                if k >= len(self.s) or self.s[k] in "\\[-":
+                    self.fail("a range without an end", self.i)
+                self.literal(self.s[k], k)
+                a, b = ch.lower(), self.s[k].lower()
+                if b < a:
+                    self.fail("a range that runs backwards", j)
+                members |= {c for x, c in self.a2d.items() if a <= x <= b}
+                self.i = k + 1
+            elif self.s.startswith("-]", self.i):
+                self.fail("'-' inside a character class (a range needs both ends)", self.i)
+            else:
+                members.add(lo)
+        return frozenset(self.all - members if negate else members)
+
+
+def _pattern_dfa(ast, C, spec):
+    """the tree of `_PatternParser` -> (table rows [S][C], accept [S]) of the minimal DFA without dead states, state 0 the start"""
+    eps, moves = [], []                                              # per NFA state: its epsilon targets, its (set, target) moves
+    limit = 1 << 16
+
+    def state():
+        if len(eps) >= limit:
+            raise ValueError("Pattern: %r unrolls into more than %d NFA states" % (spec, limit))
+        eps.append([])
+        moves.append([])
+        return len(eps) - 1
+
+    def build(node):                                                 # -> (entry, exit)
+        kind = node[0]
+        if kind == "set":
+            a, b = state(), state()
+            moves[a].append((node[1], b))
+            return a, b
+        if kind == "cat":
+            a = b = state()
+            for part in node[1]:
+                x, y = build(part)
+                eps[b].append(x)
+                b = y
+            return a, b
+        if kind == "alt":
+            a, b = state(), state()
+            for part in node[1]:
+                x, y = build(part)
+                eps[a].append(x)
+                eps[y].append(b)
+            return a, b
+        _, sub, m, n = node
+        a = b = state()
+        for _ in range(m):
+            x, y = build(sub)
+            eps[b].append(x)
+            b = y
+        if n is None:
+            x, y = build(sub)
+            z = state()
+            eps[b] += [x, z]
+            eps[y] += [x, z]
+            return a, z
+        z = state()
+        for _ in range(n - m):
+            x, y = build(sub)
+            eps[b] += [x, z]
+            b = y
+        eps[b].append(z)
+        return a, z
+
+    start, final = build(ast)
+
+    def closure(states):
+        seen, todo = set(states), list(states)
+        while todo:
+            for v in eps[todo.pop()]:
+                if v not in seen:
+                    seen.add(v)
+                    todo.append(v)
+        return frozenset(seen)
+
+    # the subset construction: only subsets reachable from the start are made
+    first = closure([start])
+    ids, rows, todo = {first: 0}, [], [first]
+    while todo:
+        sub = todo.pop(0)
+        row = [-1] * C
+        for c in range(1, C):
+            to = {t for s in sub for chars, t in moves[s] if c in chars}
+            if not to:
+                continue
+            to = closure(to)
+            if to not in ids:
+                if len(ids) >= _PATTERN_SUBSETS:
+                    raise ValueError("Pattern: %r needs more than %d DFA states before minimisation" % (spec, _PATTERN_SUBSETS))
+                ids[to] = len(ids)
+                todo.append(to)
+            row[c] = ids[to]
+        rows.append(row)                                             # (subsets are numbered in the order they are taken up)
+    acc = [final in sub for sub in ids]
+    # states from which no accepting state can be reached are removed
+    alive, grew = set(i for i, a in enumerate(acc) if a), True
+    while grew:
+        grew = False
+        for i, row in enumerate(rows):
+            if i not in alive and any(t in alive for t in row):
+                alive.add(i)
+                grew = True
+    if 0 not in alive:
+        raise ValueError("Pattern: %r matches no string over the alphabet" % (spec,))
+    rows = [[t if t in alive else -1 for t in row] for row in rows]
+    # minimisation: refine {accepting, not} by the blocks the moves lead to, until nothing splits (-1, "no move", is a block of its own)
+    block = {i: int(acc[i]) for i in alive}
+    while True:
+        sig = {i: (block[i],) + tuple(block[t] if t >= 0 else -1 for t in rows[i]) for i in alive}
+        names = {}
+        for i in sorted(alive):
+            names.setdefault(sig[i], len(names))
+        new = {i: names[sig[i]] for i in alive}
+        if len(names) == len(set(block.values())):
+            break
+        block = new
+    # the blocks are numbered in the order a breadth-first walk from the start meets them: state 0 is the start
+    rep = {}
+    for i in sorted(alive):
+        rep.setdefault(block[i], i)
+    number, todo = {block[0]: 0}, [block[0]]
+    while todo:
+        for t in rows[rep[todo.pop(0)]]:
+            if t >= 0 and block[t] not in number:
+                number[block[t]] = len(number)
+                todo.append(block[t])
+    order = sorted(number, key=number.get)
+    table = [[PATTERN_DEAD if t < 0 else number[block[t]] for t in rows[rep[b]]] for b in order]
+    return table, [int(acc[rep[b]]) for b in order]
+
+
+def pattern_limits():
+    """tatt_pattern_limits: {'steps', 'classes', 'states', 'beam'}: most steps T and classes C of tatt_ctc_pattern_mass and
+    tatt_ctc_beam_pattern_read, most states of a `Pattern`'s DFA, most beam entries.  A host-only entry: needs no GPU."""
+    from ._lib import LIB
+    out = (ctypes.c_int * 4)()
+    if LIB.tatt_pattern_limits(out) != 0:
+        raise RuntimeError("tatt_pattern_limits failed")
+    return dict(zip(("steps", "classes", "states", "beam"), (int(v) for v in out)))
+
+
+def _as_pattern(what, pattern, alphabet=None) -> "Pattern":
+    if isinstance(pattern, Pattern):
+        return pattern
+    if isinstance(pattern, str):
+        return Pattern(pattern, alphabet)
+    raise ValueError("%s: pattern is a Pattern or a regular expression as a string; got %r" % (what, type(pattern).__name__))
+
+
+def ctc_pattern_mass_host(logits, pattern, real=None):
+    """logits (T, B, C) -> one PatternMass(mass, flag) per line: mass = the log of the summed probability of ALL alignments whose
+    collapsed string the pattern's DFA accepts -- the exact probability that the line reads as any member of the format.  It is to a
+    format what `logz` is to a lexicon.  The specification of tatt_ctc_pattern_mass.
+
+    The arithmetic never subtracts.  A[q, e]: the mass of the alignments so far whose string has driven the DFA to q and that end in
+    the blank (e = 0) or in the class e; A[0, 0] = 1.  Per step, p = exp(x - max) / sum(exp(x - max)) (the sum class by class):
+      A'[q, 0] += p_0 sum_e A[q, e];   A'[q, c] += p_c A[q, c] for c >= 1 (the class repeats: same string, same state);
+      A'[table[q, c], c] += p_c sum_{e != c} A[q, e] where the target is not 255 (the sum is A @ (1 - I): non-negative terms).
+    After a step A is divided by the power of two 2^k, m = f 2^k the largest entry with 0.5 <= f < 1 (exact but for underflow), and k
+    is added to an integer exponent.  mass = log(sum over accepting q and all e of A[q, e]) + exponent log(2); -inf where nothing is
+    accepted in T steps.  A line with a NaN, a +inf or a step without a finite logit gives (nan, 1).
+    Classes of the logits beyond the pattern's alphabet continue no string.  `real` as in `ctc_beam_read_host`."""
+    import numpy as np
+    pattern = _as_pattern("ctc_pattern_mass_host", pattern)
+    x = logits.detach().cpu() if isinstance(logits, torch.Tensor) else torch.as_tensor(logits)
+    if x.dim() != 3 or x.shape[0] < 1 or x.shape[1] < 1 or x.shape[2] < 1:
+        raise ValueError("ctc_pattern_mass_host takes non-empty (T, B, C) logits; got %s" % (tuple(x.shape),))
+    x = x.to(torch.float32).numpy()
+    T, B, C = x.shape
+    table = pattern.table_for(C)
+    real = np.float64 if real is None else real
+    S, acc = pattern.n_states, pattern.accept.astype(bool)
+    qs, cs = np.nonzero(table[:, 1:] != PATTERN_DEAD)
+    cs = cs + 1
+    to = table[qs, cs].astype(np.int64)
+    others = (np.ones((C, C)) - np.eye(C)).astype(real)
+    out = []
+    with np.errstate(under="ignore", divide="ignore"):
+        for b in range(B):
+            row = x[:, b, :]
+            if bool(np.isnan(row).any()) or bool((row == np.inf).any()) or bool((row.max(1) == -np.inf).any()):
+                out.append(PatternMass(float("nan"), 1))
+                continue
+            A, expo = np.zeros((S, C), real), 0
+            A[0, 0] = 1
+            for t in range(T):
+                e = np.exp(row[t].astype(real) - real(row[t].max()))
+                s = real(0.0)
+                for v in e:
+                    s = s + v
+                p = e / s
+                N = np.zeros((S, C), real)
+                N[:, 0] = p[0] * A.sum(1)
+                N[:, 1:] = p[1:] * A[:, 1:]
+                np.add.at(N, (to, cs), (p * (A @ others))[qs, cs])
+                m = N.max()
+                if m > 0:
+                    k = int(np.frexp(m)[1])
+                    N = np.ldexp(N, -k)
+                    expo += k
+                A = N
+            total = A[acc].sum()
+            out.append(PatternMass(np.log(total) + real(expo) * np.log(real(2.0)) if total > 0 else real("-inf"), 0))
+    if real is np.float64:
+        out = [PatternMass(float(m.mass), m.flag) for m in out]
+    return out
+
+
+def ctc_beam_pattern_read_host(logits, pattern, beam: int = 8, nbest: int = 4, details: bool = False, real=None):
+    """`ctc_beam_read_host` held to a format, the specification of tatt_ctc_beam_pattern_read: every beam entry carries one more number,
+    the DFA state of its prefix (the root: 0).  The extension of the entry of rank r by c is a candidate only where
+    table[state_r, c] != 255; stay candidates and merged extensions are as before; keys, tie rule and order are unchanged.  After the
+    last step the entries in a non-accepting state are dropped, the rest keep their order, and the first `nbest` are the entries: there
+    may be fewer, or none.  -> one PatternDecoded(entries=[(classes, logp)], mass, flag[, margin, reentry]) per line; `mass` is
+    `ctc_pattern_mass_host`'s, so every logp <= mass.  A flagged line gives ([], nan, 1).  details, real: as in the plain search (the
+    margin over the final list runs over the entries that are left)."""
+    beam, nbest = int(beam), int(nbest)
+    if not 1 <= nbest <= beam:
+        raise ValueError("ctc_beam_pattern_read_host: 1 <= nbest <= beam expected; got beam = %r, nbest = %r" % (beam, nbest))
+    pattern = _as_pattern("ctc_beam_pattern_read_host", pattern)
+    T, B, C, rows = _beam_rows(logits, "ctc_beam_pattern_read_host")
+    table, accept = pattern.table_for(C).tolist(), pattern.accept.tolist()
+    masses = ctc_pattern_mass_host(logits, pattern, real)
+    real, exp, log, lse = _beam_real(real)
+    out = []
+    for row, m in zip(rows, masses):
+        lps = [_log_softmax_row(x, real, exp, log) for x in row]
+        if any(lp is None for lp in lps):
+            out.append(PatternDecoded([], float("nan"), 1, float("inf"), False) if details else PatternDecoded([], float("nan"), 1))
+            continue
+        entries, margin, reentry = _beam_search(lps, C, beam, nbest, real, lse, details, table, accept)
+        out.append(PatternDecoded(entries, m.mass, 0, margin, reentry) if details else PatternDecoded(entries, m.mass, 0))
+    return out
+
+
 # ---- device entry points ----------------------------------------------------------------------------------------------------------------
 def read_limits():
     """tatt_read_limits: {'height', 'rw', 'down', 'width', 'lines', 'steps', 'classes', 'desc'}.  A host-only entry: needs no GPU."""
@@ -1108,6 +1569,98 @@ def _beam_lm_reading(dec: BeamLMDecoded, rw: int, squeezed: bool) -> BeamLMReadi
     alts = [("".join(d2a[c] for c in classes), logp, lm) for classes, logp, lm in dec.entries]
     text, logp, lm = alts[0] if alts else ("", float("nan"), float("nan"))
     return BeamLMReading(text, logp, lm, logp + lm, alts, rw, squeezed)
+
+
+PATTERN_MASS_WORDS = 4    # 32-bit words tatt_ctc_pattern_mass writes per line: the float64 mass (2), the flag, 0
+
+
+def pattern_record_words(cap: int, nbest: int) -> int:
+    """32-bit words of a record row of `LineReader(pattern=...)`: the beam record row (an even count of words: the plain search's) and
+    the PATTERN_MASS_WORDS of the mass behind it"""
+    return beam_record_words(cap, nbest) + PATTERN_MASS_WORDS
+
+
+def _check_pattern(what, pattern, C):
+    if not isinstance(pattern, Pattern):
+        raise ValueError("%s: pattern is a Pattern; got %r" % (what, type(pattern).__name__))
+    lim = pattern_limits()
+    if pattern.n_states > lim["states"] or pattern.n_classes > lim["classes"]:
+        raise ValueError("%s: a pattern of %d states over %d classes; at most %d and %d" % (what, pattern.n_states, pattern.n_classes,
+                                                                                            lim["states"], lim["classes"]))
+    if pattern.n_classes > C:
+        raise ValueError("%s: the pattern's alphabet has %d classes, the logits %d" % (what, pattern.n_classes, C))
+
+
+def ctc_beam_pattern_read(logits, pattern: Pattern, index, record, cap: int, beam: int = 8, nbest: int = 4):
+    """ONE tatt_ctc_beam_pattern_read launch: `ctc_beam_read` held to the format `pattern` (its table and accepting states are uploaded
+    once per device); record and index as `ctc_beam_read` takes them, the rows are read by `parse_beam_records`.  Specification
+    `ctc_beam_pattern_read_host`.  ValueError for what the entry refuses and for an alphabet with more classes than the logits, before
+    any launch."""
+    from . import ops
+    from ._lib import LIB
+    ops._check_dev(logits)
+    T, B, C = logits.shape
+    if record.dtype != torch.int32 or record.dim() != 2 or record.stride(1) != 1 or index.dtype != torch.int32 or index.numel() < B:
+        raise ValueError("ctc_beam_pattern_read: record must be a 2-D int32 tensor with contiguous rows, index an int32 tensor of B entries")
+    _check_beam("ctc_beam_pattern_read", beam, nbest, pattern_limits()["beam"])
+    _check_pattern("ctc_beam_pattern_read", pattern, C)
+    if record.shape[1] < beam_record_words(cap, nbest):
+        raise ValueError("ctc_beam_pattern_read: rows of %d words; cap = %d and nbest = %d need %d" % (record.shape[1], cap, nbest,
+                                                                                                     beam_record_words(cap, nbest)))
+    table, accept = pattern.device(logits.device, C)
+    rc = LIB.tatt_ctc_beam_pattern_read(ops.P(logits), *logits.stride(), T, B, C, beam, nbest, ops.P(table), ops.P(accept), pattern.n_states,
+                                        ops.P(index), ops.P(record), record.shape[0], int(cap), record.stride(0), ops.stream())
+    if rc == 1:
+        raise ValueError("tatt_ctc_beam_pattern_read refuses T = %d, C = %d, beam = %d, nbest = %d, S = %d, cap = %d, rows of %d words"
+                         % (T, C, beam, nbest, pattern.n_states, cap, record.stride(0)))
+    if rc != 0:
+        raise RuntimeError("tatt_ctc_beam_pattern_read failed with code %d" % rc)
+    return record
+
+
+def ctc_pattern_mass(logits, pattern: Pattern, index, out):
+    """ONE tatt_ctc_pattern_mass launch: logits (T, B, C) fp32 on the device (any strides), index (B,) int32 on the device: the row of
+    every line, out (n_rows, >= PATTERN_MASS_WORDS) int32 on the device, its rows contiguous (a view of the columns of a wider buffer
+    will do): line b writes the float64 mass, its flag and a 0 (see `parse_pattern_mass`).  Specification `ctc_pattern_mass_host`.
+    ValueError for what the entry refuses and for an alphabet with more classes than the logits, before any launch."""
+    from . import ops
+    from ._lib import LIB
+    ops._check_dev(logits)
+    T, B, C = logits.shape
+    if out.dtype != torch.int32 or out.dim() != 2 or out.stride(1) != 1 or out.shape[1] < PATTERN_MASS_WORDS or out.device != logits.device \
+            or index.dtype != torch.int32 or index.numel() < B:
+        raise ValueError("ctc_pattern_mass: out must be a 2-D int32 tensor with contiguous rows of at least %d words on %s, index an "
+                         "int32 tensor of B entries" % (PATTERN_MASS_WORDS, logits.device))
+    _check_pattern("ctc_pattern_mass", pattern, C)
+    table, accept = pattern.device(logits.device, C)
+    rc = LIB.tatt_ctc_pattern_mass(ops.P(logits), *logits.stride(), T, B, C, ops.P(table), ops.P(accept), pattern.n_states, ops.P(index),
+                                   ops.P(out), out.shape[0], out.stride(0), ops.stream())
+    if rc == 1:
+        raise ValueError("tatt_ctc_pattern_mass refuses T = %d, B = %d, C = %d, S = %d, rows of %d words"
+                         % (T, B, C, pattern.n_states, out.stride(0)))
+    if rc != 0:
+        raise RuntimeError("tatt_ctc_pattern_mass failed with code %d" % rc)
+    return out
+
+
+def parse_pattern_mass(out):
+    """out: the (n, >= PATTERN_MASS_WORDS) int32 HOST tensor tatt_ctc_pattern_mass filled -> one PatternMass per row"""
+    import struct
+    res = []
+    for row in out.tolist():
+        if row[2] not in (0, 1):
+            raise ValueError("parse_pattern_mass: no mass row: flag = %r" % (row[2],))
+        res.append(PatternMass(struct.unpack("<d", struct.pack("<ii", row[0], row[1]))[0], row[2]))
+    return res
+
+
+def _pattern_reading(dec: BeamDecoded, mass: PatternMass, alphabet, rw: int, squeezed: bool) -> PatternReading:
+    import math
+    nan = float("nan")
+    m = nan if mass.flag or dec.flag else mass.mass
+    alts = [("".join(alphabet[c] for c in classes), logp, math.exp(logp - m)) for classes, logp in dec.entries]
+    text, logp, post = alts[0] if alts else ("", nan, nan)
+    return PatternReading(text, logp, m, post, alts, rw, squeezed)
 
 
 def lexicon_limits():
@@ -1380,10 +1933,14 @@ class PendingReading:
     (n, T, C) float64 log-soft-max on the device)].
     decode="lexicons": one LexiconReading per line, its words those of the line's OWN list and the posterior taken among them; an
     empty list or a flagged line reads "" with logp = nan; with keep_scores: `scores` [(line indices, the chunk's (n, max count) float64
-    scores, the lines' counts)]."""
+    scores, the lines' counts)].
+    decode="beam" with pattern=: one PatternReading per line (text, logp, mass: the log-probability that the line is ANY member of the
+    format, posterior = exp(logp - mass), alternatives [(text, logp, posterior)], best first).  A line without an accepting entry
+    reads "" with logp = nan while its mass stays meaningful; a flagged line has mass = nan as well."""
 
     def __init__(self, host, event, cap, plan, logits=None, nbest=None, lexicon=None, scores=None, words=False, lp=None, lm=False,
-                 lexicons=None):
+                 lexicons=None, pattern=None):
+        self._pattern = pattern                                      # a Pattern: beam records with the format's mass behind them
         self._lm = bool(lm)                                          # beam records with a language-model term
         self._lexicons = lexicons                                    # a LineLexicons: lexicon records, words of every line's own list
         self._host, self._event, self._cap, self._plan, self.logits, self._out = host, event, cap, plan, logits, None
@@ -1411,6 +1968,12 @@ class PendingReading:
                 self._event.synchronize()
                 self._out = [_lexicon_reading(d, self._lexicon, rw, sq) for d, rw, sq in zip(
                     parse_lexicon_records(self._host, self._nbest), self._plan.rws, self._plan.squeezed)]
+            elif self._pattern is not None:
+                self._event.synchronize()
+                at = beam_record_words(self._cap, self._nbest)
+                self._out = [_pattern_reading(d, m, self._pattern.alphabet, rw, sq) for d, m, rw, sq in zip(
+                    parse_beam_records(self._host, self._cap, self._nbest), parse_pattern_mass(self._host[:, at:]), self._plan.rws,
+                    self._plan.squeezed)]
             elif self._lm:
                 self._event.synchronize()
                 self._out = [_beam_lm_reading(d, rw, sq) for d, rw, sq in zip(
@@ -1456,6 +2019,14 @@ class LineReader:
     anything): the increments table `lm.increments(lm_weight, lm_bonus)` is built and uploaded once, here, and every chunk gets ONE
     tatt_ctc_beam_lm_read launch in place of the beam launch (specification `ctc_beam_lm_read_host`); `result()` gives
     `BeamLMReading`s.  A flagged line reads "" with logp = lm = score = nan.  Without lm= nothing of a call changes.
+    decode="beam" with pattern = a `Pattern` or a regular expression (see `Pattern` for the syntax): every line is read against that
+    FORMAT.  Every chunk gets ONE tatt_ctc_beam_pattern_read launch (the beam search with the format's DFA acting at every step,
+    specification `ctc_beam_pattern_read_host`) and ONE tatt_ctc_pattern_mass launch (the exact log-probability that the line is any
+    member of the format, specification `ctc_pattern_mass_host`) in place of the greedy launch; the mass lies behind the beam row of
+    the call's one record buffer and travels back in its one copy.  `result()` gives `PatternReading`s.  The table is uploaded once,
+    here, for the classes the CRNN emits: no `read` uploads anything for it.  ValueError here for pattern= with another decoding or with
+    lm=, an alphabet with more classes than the CRNN emits, a CRNN that does not state what it emits, and a pattern beyond
+    pattern_limits().  Without pattern= nothing of a call changes.
     decode="lexicon" (with lexicon = a `Lexicon` or a list of words, 1 <= nbest <= 16): every chunk gets the tatt_ctc_lexicon_score
     launches (one per non-empty segment class of the lexicon) into an (n, K) float64 buffer of its own and ONE tatt_ctc_lexicon_select
     launch in place of the greedy one (specification `ctc_lexicon_read_host`); `result()` gives `LexiconReading`s: the most probable
@@ -1480,7 +2051,7 @@ class LineReader:
 
     def __init__(self, crnn, batch_size: int = 48, device=None, keep_logits: bool = False, w: int = 64, decode: str = "greedy",
                  beam: int = 8, nbest: int = 4, lexicon=None, keep_scores: bool = False, word_penalty: float = 0.0,
-                 keep_lp: bool = False, lm=None, lm_weight=None, lm_bonus=None):
+                 keep_lp: bool = False, lm=None, lm_weight=None, lm_bonus=None, pattern=None):
         from . import functional as Fh
         from .infer import _check_module, _crnn_folds
         if decode not in ("greedy", "beam", "lexicon", "words", "lexicons"):
@@ -1525,7 +2096,19 @@ class LineReader:
                 table = lm.increments(self.lm_weight, self.lm_bonus)
             except (TypeError, ValueError):
                 raise ValueError("LineReader: lm_weight and lm_bonus are finite floats; got %r, %r" % (lm_weight, lm_bonus)) from None
-        self.lm = lm
+        if pattern is not None:
+            if decode != "beam":
+                raise ValueError("LineReader: pattern= goes with decode='beam'; got decode = %r" % (decode,))
+            if lm is not None:
+                raise ValueError("LineReader: pattern= and lm= do not go together")
+            pattern = _as_pattern("LineReader", pattern)             # (a pattern beyond the limits is refused where it is compiled)
+            emits = _emitted_classes(crnn)
+            if emits is None:                                        # (the table is uploaded here, once, for the classes of the logits)
+                raise ValueError("LineReader: pattern= needs a CRNN that states the classes it emits (rnn[-1].embedding.out_features)")
+            if pattern.n_classes > emits:
+                raise ValueError("LineReader: the pattern's alphabet has %d classes, the CRNN emits %d" % (pattern.n_classes, emits))
+            _check_pattern("LineReader", pattern, pattern.n_classes)
+        self.lm, self.pattern = lm, pattern
         self.decode, self.beam, self.nbest, self.lexicon, self.keep_scores = decode, beam, nbest, lexicon, bool(keep_scores)
         self.word_penalty, self.keep_lp = word_penalty, bool(keep_lp)
         _check_module(crnn, "reader CRNN")
@@ -1539,6 +2122,8 @@ class LineReader:
         self._limits = read_limits()
         if lexicon is not None:
             lexicon.device(self.device)                              # (the one upload of the packed words: no `read` makes it)
+        if pattern is not None:
+            pattern.device(self.device, _emitted_classes(crnn))      # (likewise: the table and the accepting states)
         self._lm_table = None if table is None else torch.from_numpy(table).to(self.device)          # (likewise: the one upload)
         with torch.cuda.device(self.device), torch.no_grad():
             Fh.sticky_word(self.device)
@@ -1627,8 +2212,9 @@ class LineReader:
             luma = torch.empty(plan.floats, dtype=torch.float32, device=self.device)
             line_luma(dev_bytes, head_dev, plan.desc, luma)
             beam, lex, wrd, per = self.decode == "beam", self.decode == "lexicon", self.decode == "words", lexicons is not None
-            fused = beam and self._lm_table is not None
-            words = beam_lm_record_words(cap, self.nbest) if fused else beam_record_words(cap, self.nbest) if beam else \
+            fused, fmt = beam and self._lm_table is not None, beam and self.pattern is not None
+            words = beam_lm_record_words(cap, self.nbest) if fused else pattern_record_words(cap, self.nbest) if fmt else \
+                beam_record_words(cap, self.nbest) if beam else \
                 lexicon_record_words(self.nbest) if lex or per else \
                 words_record_words(cap) if wrd else 3 * cap + 2
             kept_scores = [] if (lex or per) and self.keep_scores else None
@@ -1658,6 +2244,9 @@ class LineReader:
                     logits = self.forward(x[i:i + m])
                     if fused:
                         ctc_beam_lm_read(logits, self._lm_table, self.lm.order, index[pos:pos + m], record, cap, self.beam, self.nbest)
+                    elif fmt:
+                        ctc_beam_pattern_read(logits, self.pattern, index[pos:pos + m], record, cap, self.beam, self.nbest)
+                        ctc_pattern_mass(logits, self.pattern, index[pos:pos + m], record[:, beam_record_words(cap, self.nbest):])
                     elif beam:
                         ctc_beam_read(logits, index[pos:pos + m], record, cap, self.beam, self.nbest)
                     elif per:
@@ -1694,4 +2283,4 @@ class LineReader:
             ev = torch.cuda.Event()
             ev.record()
         return PendingReading(host, ev, cap, plan, kept, self.nbest if beam or lex or per else None, self.lexicon if lex or wrd else None,
-                              kept_scores, wrd, kept_lp, fused, lexicons)
+                              kept_scores, wrd, kept_lp, fused, lexicons, self.pattern)

@@ -22,6 +22,7 @@
 #define __device__
 #define __shared__
 #define __forceinline__ inline
+#define __host__
 #define __launch_bounds__(n)
 #define LAUNCH_CHECK() 0
 
@@ -64,8 +65,8 @@ static inline int __syncthreads_or(int p) {
     return r;
 }
 
-// update_dpp with the controls the CTC decoders use: row_shr:1 .. 15, row_bcast:15, row_bcast:31; bound_ctrl off: a lane without a source,
-// or in a row the row mask leaves out, keeps `old`
+// update_dpp with the controls the CTC decoders use: row_shr:1 .. 15, row_shl:1 .. 15 (the suffix scan of ctcpat.hip), row_bcast:15,
+// row_bcast:31; bound_ctrl off: a lane without a source, or in a row the row mask leaves out, keeps `old`
 static inline int standin_dpp(int old, int src, int ctrl, int row_mask, int bank_mask, bool bound_ctrl) {
     const int w = threadIdx.x >> 6, l = threadIdx.x & 63, row = l >> 4, i = l & 15;
     if (bank_mask != 0xf || bound_ctrl) abort();
@@ -74,6 +75,8 @@ static inline int standin_dpp(int old, int src, int ctrl, int row_mask, int bank
     int from = -1;
     if (ctrl >= 0x111 && ctrl <= 0x11f) {
         if (i >= ctrl - 0x110) from = l - (ctrl - 0x110);
+    } else if (ctrl >= 0x101 && ctrl <= 0x10f) {
+        if (i + (ctrl - 0x100) <= 15) from = l + (ctrl - 0x100);
     } else if (ctrl == 0x142) {
         if (row >= 1) from = (row - 1) * 16 + 15;
     } else if (ctrl == 0x143) {
