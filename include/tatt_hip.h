@@ -1114,6 +1114,30 @@ int tatt_ctc_words_read(const float* logits, long st_t, long st_b, long st_c, in
 /* out[0..4]: most steps T, most classes C, most packed lanes of a list, the threads of a work-group and the lanes a thread holds at that
  * limit.  Host only: needs no GPU. */
 int tatt_words_limits(int* out);
+/* CTC forced alignment (csrc/ctcalign.hip; specification read.ctc_align_host): the most probable ALIGNMENT of image b that spells a
+ * given string, with the steps every character spans -- the Viterbi recursion over the string's 2 L + 1 states in float64 over
+ * lp = log-soft-max of the logits (T,B,C) fp32 given by element strides, blank 0.  ONE launch, one work-group per image, which meets no
+ * other.  The string of image b is read ON THE DEVICE from row index[b] of the int32 buffer src (src_rows >= n_rows rows, src_stride
+ * words apart): its length L at word len_at, its classes from word cls_at; gate_at >= 0 names a word that must be >= 1 for a string to
+ * exist (gate_at = -1: none).  src may be `record` itself (a decode launch's row: the string is read before the row is written).
+ * Image b writes 4 + 4 cap_len words from word rec_at of the record row index[b] (an index outside 0 .. n_rows - 1 writes nothing,
+ * neither record nor lp_out), rows rec_stride ints apart; rec_at and rec_stride even, record 8-byte aligned:
+ *   [0] characters located n  [1] flag  [2..3] the float64 logp of the best alignment as it is, low word first (-inf where no
+ *   alignment of T steps spells the string: n = 0)  [4 ..) cap_len pairs (first step, last step) of which n are written
+ *   [4 + 2 cap_len ..) cap_len float64 of which n are written: the sum of lp[t][class] over the character's steps, left to right.
+ *   Words beyond the n stated characters are left as they were.
+ * flag 1, with n = 0 and logp = NaN: a NaN, a +inf or a step without a finite logit, or a gate word < 1.  flag 2, with n = 0 and
+ * logp = NaN: L < 0, L > cap_len, L > 127 or a class outside 1 .. C - 1.  Flag 1 wins over flag 2.
+ * lp_out: NULL or (B, T, C) float64, contiguous: the log-soft-max the recursion ran on, (double(x) - double(max)) - log sum exp (NaN on a
+ * flagged image).  Everything after it is float64 addition and comparison: the record equals the specification run on lp_out bit for bit.
+ * Returns 1 before any launch for: a null pointer (lp_out aside), T outside 1 .. 256, C outside 2 .. 64, B outside 1 .. 65535,
+ * cap_len outside 0 .. 127, n_rows <= 0, src_rows < n_rows, len_at or gate_at outside the row, cls_at + cap_len > src_stride, an odd
+ * rec_at or rec_stride, rec_at + 4 + 4 cap_len > rec_stride, a record that is not 8-byte aligned. */
+int tatt_ctc_align(const float* logits, long st_t, long st_b, long st_c, int T, int B, int C, const int* index, const int* src,
+                   int src_rows, long src_stride, int len_at, int cls_at, int gate_at, int* record, int n_rows, long rec_stride,
+                   int rec_at, int cap_len, double* lp_out, hipStream_t st);
+/* out[0..2]: most steps T, most classes C and the longest string.  Host only: needs no GPU. */
+int tatt_align_limits(int* out);
 /* calculate_psnr (reference utils/ssim_psnr.py:9-15) of two (B,C,H,W) images in [0,1] given by element strides, first 3 channels */
 int tatt_psnr(const float* a, long a_n, long a_c, long a_h, long a_w, const float* b, long b_n, long b_c, long b_h, long b_w,
               float* out, int B, int C, int H, int W, hipStream_t st);

@@ -14,7 +14,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIBDIR, "libtatt_hip.so")
-SOURCES = ["gemm.hip", "conv3.hip", "conv3w.hip", "conv9.hip", "norm.hip", "elementwise.hip", "gru.hip", "attn.hip", "sattn.hip", "sattn2.hip", "tplayer.hip", "tplayer2.hip", "tokgemm.hip", "tokwgrad.hip", "gruwgrad.hip", "tps.hip", "loss.hip", "lstm.hip", "ssim.hip", "stnhead.hip", "infer.hip", "ctc.hip", "collate.hip", "export.hip", "lines.hip", "scene.hip", "quads.hip", "polys.hip", "read.hip", "aster.hip", "moran.hip", "attndec.hip", "ctcbeam.hip", "ctclex.hip", "ctclexp.hip", "ctcwords.hip", "ctcpat.hip"]
+SOURCES = ["gemm.hip", "conv3.hip", "conv3w.hip", "conv9.hip", "norm.hip", "elementwise.hip", "gru.hip", "attn.hip", "sattn.hip", "sattn2.hip", "tplayer.hip", "tplayer2.hip", "tokgemm.hip", "tokwgrad.hip", "gruwgrad.hip", "tps.hip", "loss.hip", "lstm.hip", "ssim.hip", "stnhead.hip", "infer.hip", "ctc.hip", "collate.hip", "export.hip", "lines.hip", "scene.hip", "quads.hip", "polys.hip", "read.hip", "aster.hip", "moran.hip", "attndec.hip", "ctcbeam.hip", "ctclex.hip", "ctclexp.hip", "ctcwords.hip", "ctcpat.hip", "ctcalign.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden", "-ffp-contract=fast"]
 # per-source additions.  conv3.hip: the staging waves of the 3x3 kernels run beside MFMA waves on the same SIMD, and packed fp32 VALU forms
 # (what SLP vectorisation makes of adjacent scalar adds / fmas) take issue time from the matrix pipe (profiles/r06_conv3_sb4_roles.txt)
@@ -24,10 +24,10 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fvisibility=hi
 # multiply then one fp32 add, never a fused multiply-add
 # quads.hip, polys.hip: integer arithmetic only; built like their siblings so that nothing in them can contract
 # read.hip, further: its luma is one fp32 multiply that must stay one
-# ctcwords.hip: after the log-soft-max only float64 additions and comparisons, which the record must repeat bit for bit
+# ctcwords.hip, ctcalign.hip: after the log-soft-max only float64 additions and comparisons, which the record must repeat bit for bit
 EXTRA_FLAGS = {"conv3.hip": ["-fno-slp-vectorize"], "conv3w.hip": ["-fno-slp-vectorize"], "sattn2.hip": ["-fno-slp-vectorize"],
                "collate.hip": ["-ffp-contract=off"], "export.hip": ["-ffp-contract=off"], "lines.hip": ["-ffp-contract=off"],
-               "scene.hip": ["-ffp-contract=off"], "quads.hip": ["-ffp-contract=off"], "polys.hip": ["-ffp-contract=off"], "read.hip": ["-ffp-contract=off"], "ctcwords.hip": ["-ffp-contract=off"]}
+               "scene.hip": ["-ffp-contract=off"], "quads.hip": ["-ffp-contract=off"], "polys.hip": ["-ffp-contract=off"], "read.hip": ["-ffp-contract=off"], "ctcwords.hip": ["-ffp-contract=off"], "ctcalign.hip": ["-ffp-contract=off"]}
 _INCLUDE = re.compile(rb'^[ \t]*#[ \t]*include[ \t]+"([^"]+)"', re.M)
 
 

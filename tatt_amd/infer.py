@@ -678,7 +678,8 @@ class PendingUpscale:
     long_lines the ONE (n_windows, C, H, W) buffer of all SR windows, beside `lr` (the window stack the sessions read) and `lines`
     (`io.Line` records).  With a reader `readings()` gives the `read.Reading` record of every line (text, confidences, steps, rw)."""
 
-    def __init__(self, parts, with_text, sr, lr=None, lines=None, reading=None):
+    def __init__(self, parts, with_text, sr, lr=None, lines=None, reading=None, located=None):
+        self._located = located                                      # read_locate: (the (H, W) of every line canvas, out_sizes or None)
         self._parts, self._with_text, self.sr = parts, with_text, sr
         self.lr, self.lines = lr, lines                              # long_lines with keep_sr: the window stack and its Line records
         self._reading = reading                                      # long_lines with a reader: the PendingReading of the lines
@@ -701,6 +702,14 @@ class PendingUpscale:
             raise RuntimeError("readings() needs SuperResolver(..., reader=crnn, long_lines=True)")
         return self._reading.result()
 
+    def locations(self):
+        """one `read.LineLocation` per line, in input order (long_lines on an instance with `read_locate=True`); every character is a
+        `locate.LocatedChar`: the CharSpan's fields and `polygon`, its rectangle in the image `result()` returns for the line"""
+        from .locate import locate_lines
+        if self._reading is None or self._located is None:
+            raise RuntimeError("locations() needs SuperResolver(..., reader=crnn, read_locate=True, long_lines=True)")
+        return locate_lines(self._reading.locations(), *self._located)
+
 
 class PendingScene:
     """What `SuperResolver.scene` started.  `result()` is the only host wait: -> the RGB PIL image of size (scale * Ws, scale * Hs).
@@ -709,9 +718,10 @@ class PendingScene:
     On an instance with `reader=`: `texts()` / `readings()`, one string / `read.Reading` per box or quad in input order ([] without
     boxes), read from the blended lines BEFORE they were pasted (so `feather` does not reach them)."""
 
-    def __init__(self, pending, sr=None, lr=None, lines=None, boxes=None, layers=None, reading=None):
+    def __init__(self, pending, sr=None, lr=None, lines=None, boxes=None, layers=None, reading=None, located=None):
         self._pending, self.sr, self.lr, self.lines, self.boxes, self.layers = pending, sr, lr, lines, boxes, layers
         self._reading = reading
+        self._located = located                                      # read_locate: (the regions, the widths of their line canvases, scale)
 
     def result(self):
         return self._pending.result()[0]
@@ -723,6 +733,15 @@ class PendingScene:
 
     def texts(self):
         return [r.text for r in self.readings()]
+
+    def locations(self):
+        """one `read.LineLocation` per box, quad or polygon, in input order (an instance with `read_locate=True`); every character is a
+        `locate.LocatedChar`: the CharSpan's fields and `polygon`, its outline in the coordinates of the picture `result()` returns
+        (`locate.span_polygon`)"""
+        from .locate import locate_regions
+        if self._reading is None or self._located is None:
+            raise RuntimeError("locations() needs SuperResolver(..., reader=crnn, read_locate=True)")
+        return locate_regions(self._reading.locations(), *self._located)
 
 
 class SuperResolver:
@@ -784,12 +803,18 @@ class SuperResolver:
     union of the lists and every chunk's tables), per chunk ONE tatt_ctc_lexicon_score_pairs launch and ONE
     tatt_ctc_lexicon_select_rows launch in place of the greedy one; `readings()` gives `read.LexiconReading`s whose text and
     alternatives are words of the line's own list and whose posterior is taken among them.  ValueError before anything is enqueued for
-    a wrong number of lists, a call without the keyword, and the keyword on an instance with another read_decode."""
+    a wrong number of lists, a call without the keyword, and the keyword on an instance with another read_decode.
+    read_locate=True (needs reader=; read_decode "greedy" or "beam", plain or with read_lm / read_pattern: `LineReader(locate=True)`)
+    says WHERE every character was read: per chunk one tatt_ctc_align launch behind the decode launch, the alignment travelling back in
+    the reader's one copy.  `PendingUpscale.locations()` / `PendingScene.locations()` give one `read.LineLocation` per line whose
+    characters carry `polygon`, their outline in the image or picture the caller gets back (`tatt_amd/locate.py`); images and pictures
+    are byte for byte those without the keyword."""
 
     def __init__(self, generator, prior=None, recognizer=None, batch_size: int = 48, lr_size=(16, 64), mask: bool = True,
                  rule: str = "floor", keep_sr: bool = False, long_lines: bool = False, stride: int = 32, reader=None,
                  read_decode: str = "greedy", read_beam: int = 8, read_nbest: int = 4, read_lexicon=None,
-                 read_word_penalty: float = 0.0, read_lm=None, read_lm_weight=None, read_lm_bonus=None, read_pattern=None):
+                 read_word_penalty: float = 0.0, read_lm=None, read_lm_weight=None, read_lm_bonus=None, read_pattern=None,
+                 read_locate: bool = False):
         from .io import DeviceCollator, DeviceExporter
         _refuse_attention_recognizer(recognizer, "SuperResolver")
         _check_module(generator, "generator")
@@ -812,13 +837,16 @@ class SuperResolver:
         self.sessions = {}
         self._ctc = {}                                               # batch size -> (keep, label, label_len) the decoding ignores
         self.reader = None
+        if reader is None and read_locate:
+            raise ValueError("SuperResolver: read_locate=True needs reader=crnn")
         if reader is None and read_pattern is not None:
             raise ValueError("SuperResolver: read_pattern= needs reader=crnn, read_decode='beam'")
         if reader is not None:
             from .read import LineReader
             self.reader = LineReader(reader, batch_size=batch_size, device=self.device, w=self.lr_size[1], decode=read_decode,
                                      beam=read_beam, nbest=read_nbest, lexicon=read_lexicon, word_penalty=read_word_penalty,
-                                     lm=read_lm, lm_weight=read_lm_weight, lm_bonus=read_lm_bonus, pattern=read_pattern)
+                                     lm=read_lm, lm_weight=read_lm_weight, lm_bonus=read_lm_bonus, pattern=read_pattern,
+                                     **({"locate": True} if read_locate else {}))
 
     def _texts(self, sr):
         """-> (pinned (n, T + 1) int32: decoded classes | length, its event)"""
@@ -945,9 +973,10 @@ class SuperResolver:
             boxes = [norm(b) for b in boxes]                         # (checked by `windows`)
             pending = export(scene_dev, buf, lines, boxes, scale, feather)
             reading = self._read(pending, scale, lexicons)
+        located = (boxes, [r[2] for r in pending.line_canvases[1]], scale) if self.reader is not None and self.reader.locate else None
         if not self.keep_sr:
-            return PendingScene(pending, reading=reading)
-        return PendingScene(pending, buf, stack, lines, boxes, layers(boxes), reading)
+            return PendingScene(pending, reading=reading, located=located)
+        return PendingScene(pending, buf, stack, lines, boxes, layers(boxes), reading, located)
 
     def _run_windows(self, stack):
         """a window stack through the sessions in batches of `batch_size` -> (buf, scale): the ONE (n_windows, C, H, W) buffer of all SR
@@ -999,12 +1028,14 @@ class SuperResolver:
         """the long_lines call: windows of all images -> sessions over batches of windows -> one SR buffer -> one blend launch"""
         with_text = self.reader is not None
         if not images:
-            return PendingUpscale([], with_text, None, reading=self.reader.read(None, [], 1, lexicons=lexicons) if with_text else None)
+            return PendingUpscale([], with_text, None, reading=self.reader.read(None, [], 1, lexicons=lexicons) if with_text else None,
+                                  located=([], None) if with_text and self.reader.locate else None)
         with torch.cuda.device(self.device):
             stack, lines = self.collator.windows(images, self.stride)
             buf, scale = self._run_windows(stack)
             pending = self.exporter.lines(buf, lines, scale, out_sizes=out_sizes)
             reading = self._read(pending, scale, lexicons)
         keep = self.keep_sr
+        located = ([(r[1], r[2]) for r in pending.line_canvases[1]], out_sizes) if with_text and self.reader.locate else None
         return PendingUpscale([(pending, None, None)], with_text, buf if keep else None, stack if keep else None, lines if keep else None,
-                              reading)
+                              reading, located)

@@ -28,6 +28,10 @@ tatt_ctc_words_read launch per bucket chunk in place of the greedy one.
 Reading every line against a list of ITS OWN: `LineLexicons` (one list per line, their union packed for the device, `pack` the tile
 table and pairs of a launch), `ctc_line_lexicons_read_host` (the specification); decode="lexicons": per bucket chunk one
 tatt_ctc_lexicon_score_pairs launch and one tatt_ctc_lexicon_select_rows launch of csrc/ctclexp.hip in place of the greedy one.
+Locating what was read: `ctc_align_host` / `ctc_align_read_host` (the specification of csrc/ctcalign.hip: CTC forced alignment, the most
+probable alignment that spells a GIVEN string, with the steps every character spans); `LineReader(locate=True)`: one tatt_ctc_align
+launch per bucket chunk behind the decode launch, which reads the best string from the decode record on the device;
+`LineReader.align`: the same for strings the caller knows.  The geometry that carries the spans into the picture is tatt_amd/locate.py.
 """
 from __future__ import annotations
 
@@ -926,8 +930,137 @@ def read_lines_host(lines_u8, run_crnn, scale=2, w: int = 64):
     return out
 
 
+# ---- locating what was read: CTC forced alignment -------------------------------------------------------------------------------------
+Aligned = namedtuple("Aligned", "spans char_logp logp flag")          # spans: [(first step, last step)] per character
+CharSpan = namedtuple("CharSpan", "char cls first last x0 x1 logp")
+LineLocation = namedtuple("LineLocation", "text logp chars rw squeezed flag")
+ALIGN_STEPS, ALIGN_CLASSES, ALIGN_LENGTH = 256, 64, 127              # `align_limits` of the device entry (tests hold them equal)
+
+
+def ctc_align_host(lp, classes) -> Aligned:
+    """The specification of csrc/ctcalign.hip on ONE line.  lp: the (T, C) float64 log-soft-max rows (lists), classes: L ints in
+    1 .. C - 1 (blank 0) -> Aligned(spans, char_logp, logp, flag = 0): the most probable alignment that spells the string.
+
+    States s = 0 .. 2 L: an even state is a blank, an odd state the character classes[s // 2]; c(s) its class.  Start: v[0] = lp[0][0],
+    v[1] = lp[0][c(1)] (L >= 1), every other state -inf.  Step t >= 1: the candidate for state s is v[s]; then v[s - 1] is tried
+    (s >= 1); then v[s - 2] (s odd, s >= 3, c(s) != c(s - 2)); only a STRICTLY greater value replaces; the new v[s] is that value +
+    lp[t][c(s)] and the back-pointer 0, 1 or 2.  End: state 2 L; state 2 L - 1 only if strictly greater.  A best value of -inf: the
+    string cannot be spelled (T too short, repeats without room for the blank, -inf columns): logp = -inf, no spans.  Otherwise the
+    back-pointers are walked; character k has `first` / `last`, the first and last step in state 2 k + 1, and char_logp[k], the sum of
+    lp[t][classes[k]] over t = first .. last added left to right; logp is the best value itself.  Float64 additions and comparisons
+    only, no multiply."""
+    neg = float("-inf")
+    T, L = len(lp), len(classes)
+    if T < 1:
+        raise ValueError("ctc_align_host takes at least one step")
+    C = len(lp[0])
+    if any(not (isinstance(c, int) and 1 <= c < C) for c in classes):
+        raise ValueError("ctc_align_host: classes are ints in 1 .. %d; got %r" % (C - 1, list(classes)))
+    S = 2 * L + 1
+    cls = [classes[s // 2] if s & 1 else 0 for s in range(S)]
+    v = [neg] * S
+    v[0] = lp[0][0]
+    if L >= 1:
+        v[1] = lp[0][cls[1]]
+    back = [None]
+    for t in range(1, T):
+        row, nv, nb = lp[t], [neg] * S, [0] * S
+        for s in range(S):
+            best, p = v[s], 0
+            if s >= 1 and v[s - 1] > best:
+                best, p = v[s - 1], 1
+            if s & 1 and s >= 3 and cls[s] != cls[s - 2] and v[s - 2] > best:
+                best, p = v[s - 2], 2
+            nv[s], nb[s] = best + row[cls[s]], p
+        v = nv
+        back.append(nb)
+    logp, state = v[S - 1], S - 1
+    if L >= 1 and v[S - 2] > logp:
+        logp, state = v[S - 2], S - 2
+    if logp == neg:
+        return Aligned([], [], neg, 0)
+    first, last = [0] * L, [-1] * L
+    for t in range(T - 1, -1, -1):
+        if state & 1:
+            k = state // 2
+            if last[k] < 0:
+                last[k] = t
+            first[k] = t
+        if t >= 1:
+            state -= back[t][state]
+    sums = []
+    for k in range(L):
+        acc = lp[first[k]][classes[k]]
+        for t in range(first[k] + 1, last[k] + 1):
+            acc = acc + lp[t][classes[k]]
+        sums.append(acc)
+    return Aligned(list(zip(first, last)), sums, logp, 0)
+
+
+def ctc_align_read_host(logits, strings):
+    """logits (T, B, C) fp32, strings: one list of classes per line -> one Aligned per line: the log-soft-max of the other host decoders
+    (`_log_softmax_row`, float64), then `ctc_align_host`.  A line they would flag (a NaN, a +inf, a step without a finite logit) gives
+    spans = [], logp = nan, flag = 1."""
+    T, B, C, rows = _beam_rows(logits, "ctc_align_read_host")
+    if len(strings) != B:
+        raise ValueError("ctc_align_read_host: %d strings for %d lines" % (len(strings), B))
+    real, exp, log, _ = _beam_real(None)
+    out = []
+    for row, classes in zip(rows, strings):
+        lps = [_log_softmax_row(x, real, exp, log) for x in row]
+        out.append(Aligned([], [], float("nan"), 1) if any(lp is None for lp in lps) else ctc_align_host(lps, list(classes)))
+    return out
+
+
+def align_record_words(cap_len: int) -> int:
+    """32-bit words of the alignment part of a record row for strings of at most `cap_len` characters: [0] characters located, [1] flag,
+    [2:4] logp, cap_len pairs (first, last), cap_len float64 char_logp"""
+    return 4 + 4 * int(cap_len)
+
+
+def pack_strings(strings, cap_len: int):
+    """strings: one list of classes per line -> the (n, 2 + cap_len) int32 numpy table tatt_ctc_align reads them from with len_at = 0,
+    cls_at = 2, gate_at = -1: [0] the length, [1] 0, then the classes padded with -1.  ValueError for a cap_len outside
+    0 .. ALIGN_LENGTH and for a string longer than cap_len; the classes themselves are judged on the device (flag 2)."""
+    import numpy as np
+    if not (isinstance(cap_len, int) and 0 <= cap_len <= ALIGN_LENGTH):
+        raise ValueError("pack_strings: cap_len is an int in 0 .. %d; got %r" % (ALIGN_LENGTH, cap_len))
+    out = np.full((len(strings), 2 + cap_len), -1, np.int32)
+    for i, s in enumerate(strings):
+        s = [int(c) for c in s]
+        if len(s) > cap_len:
+            raise ValueError("pack_strings: line %d: %d characters, cap_len = %d" % (i, len(s), cap_len))
+        out[i, 0], out[i, 1] = len(s), 0
+        out[i, 2:2 + len(s)] = s
+    return out
+
+
+def parse_align_records(record, cap_len: int):
+    """record: the (n, >= align_record_words(cap_len)) int32 HOST tensor (or numpy array) holding the alignment parts tatt_ctc_align
+    wrote, from word 0 of every row -> one Aligned per row (flag 1 / 2: spans = [], logp = nan)."""
+    import struct
+    rows = record.tolist()
+    out = []
+    for row in rows:
+        n, flag = row[0], row[1]
+        if not 0 <= n <= cap_len or flag not in (0, 1, 2) or len(row) < align_record_words(cap_len):
+            raise ValueError("parse_align_records: no alignment record row: characters = %r, flag = %r" % (n, flag))
+        logp = struct.unpack("<d", struct.pack("<ii", row[2], row[3]))[0]
+        at = 4 + 2 * cap_len
+        sums = list(struct.unpack("<%dd" % n, struct.pack("<%di" % (2 * n), *row[at:at + 2 * n])))
+        out.append(Aligned([(row[4 + 2 * k], row[5 + 2 * k]) for k in range(n)], sums, logp, flag))
+    return out
+
+
+def _location(al: Aligned, classes, alphabet, rw: int, squeezed: bool, W: int) -> LineLocation:
+    """an Aligned of the string `classes` -> the LineLocation of a line of width W read at width rw"""
+    text = "".join(alphabet[c] for c in classes)
+    chars = [CharSpan(alphabet[c], c, f, l, *word_span_pixels(f, l, W, rw), lp) for c, (f, l), lp in zip(classes, al.spans, al.char_logp)]
+    return LineLocation(text, al.logp, chars, rw, squeezed, al.flag)
+
+
 # ---- reading against a format --------------------------------------------------------------------------------------------------------------
-PatternMass = namedtuple("PatternMass", "mass flag")
+PatternMass =namedtuple("PatternMass", "mass flag")
 PatternDecoded = namedtuple("PatternDecoded", "entries mass flag margin reentry", defaults=(None, None))
 PatternReading = namedtuple("PatternReading", "text logp mass posterior alternatives rw squeezed")
 PATTERN_DEAD = 255        # table entry: no string of the format continues this way
@@ -1924,6 +2057,70 @@ def parse_words_records(record, cap: int):
     return out
 
 
+def align_limits():
+    """tatt_align_limits: {'steps', 'classes', 'length'}: most steps T and classes C of tatt_ctc_align and the longest string it
+    aligns (2 length + 1 states, one thread each).  A host-only entry: needs no GPU."""
+    from ._lib import LIB
+    out = (ctypes.c_int * 3)()
+    if LIB.tatt_align_limits(out) != 0:
+        raise RuntimeError("tatt_align_limits failed")
+    return dict(zip(("steps", "classes", "length"), (int(v) for v in out)))
+
+
+def ctc_align(logits, index, src, len_at: int, cls_at: int, gate_at: int, record, rec_at: int, cap_len: int, lp_out=None):
+    """ONE tatt_ctc_align launch: logits (T, B, C) fp32 on the device (any strides), index (B,) int32 on the device: the row of every
+    line in `src` AND in `record`.  src: a 2-D int32 tensor on the device with contiguous rows, at least as many as `record`; line j's
+    string has its length at word len_at of row index[j], its classes from word cls_at, and -- gate_at >= 0 -- a word that must be >= 1
+    for a string to exist (-1: none).  src may be `record` itself (the row a decode launch wrote) or a table of `pack_strings`
+    (len_at = 0, cls_at = 2, gate_at = -1).  record: (n_rows, >= rec_at + align_record_words(cap_len)) int32 on the device, rows
+    contiguous with an even stride, rec_at even (see `parse_align_records`); lp_out: None or a contiguous (B, T, C) float64 tensor on the
+    device, which receives the log-soft-max the alignment ran on.  Specification `ctc_align_read_host`.  ValueError for what the entry
+    refuses (T, C or cap_len beyond align_limits() included: never truncated), before any launch."""
+    from . import ops
+    from ._lib import LIB
+    ops._check_dev(logits)
+    T, B, C = logits.shape
+    if record.dtype != torch.int32 or record.dim() != 2 or record.stride(1) != 1 or index.dtype != torch.int32 or index.numel() < B:
+        raise ValueError("ctc_align: record must be a 2-D int32 tensor with contiguous rows, index an int32 tensor of B entries")
+    if not (isinstance(src, torch.Tensor) and src.dtype == torch.int32 and src.dim() == 2 and src.stride(1) == 1 and
+            src.device == logits.device and record.device == logits.device and index.device == logits.device):
+        raise ValueError("ctc_align: src must be a 2-D int32 tensor with contiguous rows on %s, like record and index" % (logits.device,))
+    lim = align_limits()
+    if not all(isinstance(v, int) for v in (len_at, cls_at, gate_at, rec_at, cap_len)):
+        raise ValueError("ctc_align: len_at, cls_at, gate_at, rec_at and cap_len are ints")
+    if not 0 <= cap_len <= lim["length"]:
+        raise ValueError("ctc_align: cap_len = %d; strings of at most %d characters are aligned" % (cap_len, lim["length"]))
+    if T > lim["steps"] or C > lim["classes"] or C < 2:
+        raise ValueError("ctc_align: T = %d, C = %d; at most %d steps and 2 .. %d classes" % (T, C, lim["steps"], lim["classes"]))
+    if rec_at < 0 or rec_at % 2 or record.stride(0) % 2 or record.shape[1] < rec_at + align_record_words(cap_len):
+        raise ValueError("ctc_align: rows of %d words (stride %d); an even rec_at = %d and cap_len = %d need %d and an even stride"
+                         % (record.shape[1], record.stride(0), rec_at, cap_len, rec_at + align_record_words(cap_len)))
+    if src.shape[0] < record.shape[0] or not 0 <= len_at < src.shape[1] or not -1 <= gate_at < src.shape[1] or cls_at < 0 or \
+            cls_at + cap_len > src.shape[1]:
+        raise ValueError("ctc_align: src of %s; len_at = %d, cls_at = %d, gate_at = %d, cap_len = %d and %d record rows do not fit it"
+                         % (tuple(src.shape), len_at, cls_at, gate_at, cap_len, record.shape[0]))
+    if lp_out is not None and (lp_out.dtype != torch.float64 or tuple(lp_out.shape) != (B, T, C) or not lp_out.is_contiguous() or
+                               lp_out.device != logits.device):
+        raise ValueError("ctc_align: lp_out must be a contiguous (%d, %d, %d) float64 tensor on %s" % (B, T, C, logits.device))
+    rc = LIB.tatt_ctc_align(ops.P(logits), *logits.stride(), T, B, C, ops.P(index), ops.P(src), src.shape[0], src.stride(0), len_at,
+                            cls_at, gate_at, ops.P(record), record.shape[0], record.stride(0), rec_at, cap_len, ops.P(lp_out),
+                            ops.stream())
+    if rc == 1:
+        raise ValueError("tatt_ctc_align refuses T = %d, B = %d, C = %d, cap_len = %d, rec_at = %d, rows of %d words"
+                         % (T, B, C, cap_len, rec_at, record.stride(0)))
+    if rc != 0:
+        raise RuntimeError("tatt_ctc_align failed with code %d" % rc)
+    return record
+
+
+def _align_source(cap: int, nbest, lm: bool):
+    """(len_at, cls_at, gate_at) of the best string in a decode record row: greedy (nbest None) has its classes at 0 and its length at
+    3 cap; a beam row's entry 0 lies behind [0] entries written (the gate) and [1] the flag"""
+    if nbest is None:
+        return 3 * cap, 0, -1
+    return (2 + 4, 2 + 6, 0) if lm else (2 + 2, 2 + 4, 0)
+
+
 class PendingReading:
     """What `LineReader.read` started.  `result()` is the only host wait: -> one Reading (decode="beam": one BeamReading, with lm=: one
     BeamLMReading (text, logp: the acoustic mass, lm: the LM term, score = logp + lm, alternatives [(text, logp, lm)]),
@@ -1936,10 +2133,14 @@ class PendingReading:
     scores, the lines' counts)].
     decode="beam" with pattern=: one PatternReading per line (text, logp, mass: the log-probability that the line is ANY member of the
     format, posterior = exp(logp - mass), alternatives [(text, logp, posterior)], best first).  A line without an accepting entry
-    reads "" with logp = nan while its mass stays meaningful; a flagged line has mass = nan as well."""
+    reads "" with logp = nan while its mass stays meaningful; a flagged line has mass = nan as well.
+    locate=True: `locations()`, one LineLocation per line; the alignment lies behind the decode part of every record row, and `lp`
+    (with keep_lp) holds the float64 log-soft-max it ran on."""
 
     def __init__(self, host, event, cap, plan, logits=None, nbest=None, lexicon=None, scores=None, words=False, lp=None, lm=False,
-                 lexicons=None, pattern=None):
+                 lexicons=None, pattern=None, align=None):
+        self._align = align                                          # (rec_at, cap_len, (len_at, cls_at, gate_at), alphabet): locate=True
+        self._located = None
         self._pattern = pattern                                      # a Pattern: beam records with the format's mass behind them
         self._lm = bool(lm)                                          # beam records with a language-model term
         self._lexicons = lexicons                                    # a LineLexicons: lexicon records, words of every line's own list
@@ -1986,6 +2187,51 @@ class PendingReading:
 
     def texts(self):
         return [r.text for r in self.result()]
+
+    def locations(self):
+        """locate=True: one LineLocation per line, in input order: the reading's own best string (`text`), the log-probability of its
+        most probable alignment (`logp`) and one CharSpan(char, cls, first, last, x0, x1, logp) per character: its steps, its columns
+        in the line the caller gets back by the convention of `word_span_pixels`, and the sum of its log-probabilities over its steps.
+        flag 1 (a flagged line, or a beam without an entry): "" with logp = nan; flag 2 (a string beyond align_limits()): the text
+        without characters.  A string no alignment spells has logp = -inf and no characters."""
+        if self._align is None:
+            raise ValueError("PendingReading.locations: the reader was made without locate=True")
+        if self._host is None:
+            return []
+        if self._located is not None:
+            return self._located
+        self._event.synchronize()
+        rec_at, cap_len, (len_at, cls_at, gate_at), alphabet = self._align
+        rows = self._host.tolist()
+        als = parse_align_records(self._host[:, rec_at:rec_at + align_record_words(cap_len)], cap_len)
+        out = []
+        for row, al, rw, sq, W in zip(rows, als, self._plan.rws, self._plan.squeezed, self._plan.desc[:, 2]):
+            stated = al.flag != 1 and (gate_at < 0 or row[gate_at] >= 1) and 0 <= row[len_at] <= self._cap
+            classes = row[cls_at:cls_at + row[len_at]] if stated else []
+            out.append(_location(al, classes, alphabet, rw, sq, int(W)))
+        self._located = out
+        return out
+
+
+class PendingAlignment:
+    """What `LineReader.align` started.  `locations()` is the only host wait: one LineLocation per line, in input order (see
+    `PendingReading.locations`; `text` is the caller's own, lower-cased).  With keep_logits / keep_lp: `logits` / `lp` as
+    `PendingReading` has them."""
+
+    def __init__(self, host, event, cap_len, plan, strings, alphabet, logits=None, lp=None):
+        self._host, self._event, self._cap_len, self._plan, self._strings, self._alphabet = host, event, cap_len, plan, strings, alphabet
+        self.logits, self.lp, self._out = logits, lp, None
+
+    def locations(self):
+        if self._out is None:
+            if self._host is None:
+                self._out = []
+            else:
+                self._event.synchronize()
+                self._out = [_location(al, classes if al.flag != 1 else [], self._alphabet, rw, sq, int(W)) for al, classes, rw, sq, W in zip(
+                    parse_align_records(self._host, self._cap_len), self._strings, self._plan.rws, self._plan.squeezed,
+                    self._plan.desc[:, 2])]
+        return self._out
 
 
 def _emitted_classes(crnn):
@@ -2047,15 +2293,28 @@ class LineReader:
     in place of the greedy one.  `result()` gives `LexiconReading`s: text and alternatives are words of the line's own list, the
     posterior is taken among them; an empty list or a flagged line reads "" with logp = nan.  keep_scores=True keeps (line indices,
     scores, counts) per chunk.  ValueError before anything is enqueued for a missing keyword, len(lexicons) != len(rows) and an
-    alphabet with more classes than the CRNN emits."""
+    alphabet with more classes than the CRNN emits.
+    locate=True (decode="greedy" or "beam", plain or with lm= or pattern=; ValueError here with "lexicon", "lexicons" and "words", whose
+    records hold word indices, not classes): says WHERE the characters are.  Per chunk ONE more launch right behind the decode
+    launch(es), tatt_ctc_align (CTC forced alignment, specification `ctc_align_host`): it reads the reading's best string from the
+    decode record ON THE DEVICE (greedy: the classes at word 0, the length at 3 cap; beam: entry 0 behind the "entries written" word,
+    with the LM layout's offsets where lm= is given) and appends the alignment to the same record row at the next even word
+    (`align_record_words(min(cap, 127))` words), so the call still makes its one copy back and waits for nothing.
+    `PendingReading.locations()` gives one `LineLocation` per line; `result()` / `texts()` are what they are without the keyword;
+    keep_lp=True keeps every chunk's float64 log-soft-max.  Without the keyword a call enqueues exactly what it enqueued before.
+    `align(dev_bytes, rows, scale, texts)` aligns strings the caller knows, with no decode launch."""
 
     def __init__(self, crnn, batch_size: int = 48, device=None, keep_logits: bool = False, w: int = 64, decode: str = "greedy",
                  beam: int = 8, nbest: int = 4, lexicon=None, keep_scores: bool = False, word_penalty: float = 0.0,
-                 keep_lp: bool = False, lm=None, lm_weight=None, lm_bonus=None, pattern=None):
+                 keep_lp: bool = False, lm=None, lm_weight=None, lm_bonus=None, pattern=None, locate: bool = False):
         from . import functional as Fh
         from .infer import _check_module, _crnn_folds
         if decode not in ("greedy", "beam", "lexicon", "words", "lexicons"):
             raise ValueError("LineReader: decode is 'greedy', 'beam', 'lexicon', 'words' or 'lexicons'; got %r" % (decode,))
+        if locate and decode not in ("greedy", "beam"):
+            raise ValueError("LineReader: locate=True goes with decode='greedy' or decode='beam' (their records hold the classes of "
+                             "the string; those of %r hold word indices)" % (decode,))
+        self.locate = bool(locate)
         word_penalty = _check_penalty("LineReader", word_penalty)
         if decode != "words" and word_penalty != 0.0:
             raise ValueError("LineReader: word_penalty= goes with decode='words'; got decode = %r" % (decode,))
@@ -2191,7 +2450,7 @@ class LineReader:
         keep = self.keep_logits if keep_logits is None else bool(keep_logits)
         lexicons = self.check_lexicons(lexicons, len(rows))
         if not rows:
-            return PendingReading(None, None, 0, None, [] if keep else None)
+            return PendingReading(None, None, 0, None, [] if keep else None, align=(0, 0, (0, 0, -1), "") if self.locate else None)
         if not (isinstance(dev_bytes, torch.Tensor) and dev_bytes.dtype == torch.uint8 and dev_bytes.device == self.device and
                 dev_bytes.is_contiguous()):
             raise ValueError("LineReader.read takes a contiguous uint8 tensor on %s" % (self.device,))
@@ -2233,7 +2492,14 @@ class LineReader:
                 blob_dev.copy_(blob, non_blocking=True)
                 u_codes, u_table = blob_dev[:lexicons.codes.size], blob_dev[lexicons.codes.size:packs[0][0]].view(-1, 4)
                 n_chunk = 0
-            kept_lp = [] if wrd and self.keep_lp else None
+            kept_lp = [] if (wrd or self.locate) and self.keep_lp else None
+            align = None
+            if self.locate:
+                # the alignment part lies behind the decode part of the same row, at the next even word; the row stride is even
+                rec_at, cap_len = words + (words & 1), min(cap, ALIGN_LENGTH)
+                words = rec_at + align_record_words(cap_len)
+                source = _align_source(cap, self.nbest if beam else None, fused)
+                align = (rec_at, cap_len, source, self.pattern.alphabet if fmt else _alphabet())
             record = torch.empty(n, words, dtype=torch.int32, device=self.device)
             index, pos, foff = head_dev[n * READ_DESC:], 0, 0
             for rw, idx in plan.buckets:
@@ -2275,6 +2541,12 @@ class LineReader:
                         ctc_words_read(logits, self.lexicon, index[pos:pos + m], record, cap, self.word_penalty, lp)
                     else:
                         ctc_greedy_read(logits, index[pos:pos + m], record, cap)
+                    if align is not None:                            # ONE more launch: the best string is aligned where the decode left it
+                        lp = None
+                        if kept_lp is not None:
+                            lp = torch.empty(m, logits.shape[0], logits.shape[2], dtype=torch.float64, device=self.device)
+                            kept_lp.append((idx[i:i + m], lp))
+                        ctc_align(logits, index[pos:pos + m], record, *source, record, rec_at, cap_len, lp)
                     if keep:
                         kept.append((idx[i:i + m], logits))
                     pos += m
@@ -2283,4 +2555,72 @@ class LineReader:
             ev = torch.cuda.Event()
             ev.record()
         return PendingReading(host, ev, cap, plan, kept, self.nbest if beam or lex or per else None, self.lexicon if lex or wrd else None,
-                              kept_scores, wrd, kept_lp, fused, lexicons, self.pattern)
+                              kept_scores, wrd, kept_lp, fused, lexicons, self.pattern, align)
+
+    def align(self, dev_bytes, rows, scale, texts, keep_logits=None) -> "PendingAlignment":
+        """Aligns KNOWN strings, one per line (a ground-truth label, a corrected reading): dev_bytes, rows, scale as `read` takes them,
+        texts: one string per line (lower-cased here) -> PendingAlignment.  Enqueues what `read` enqueues without any decode launch:
+        the descriptor copy (the packed strings travel in it), the luma launch, per chunk the forward and ONE tatt_ctc_align launch,
+        the copy back.  ValueError, naming the line, for a character outside the alphabet or a text beyond align_limits()["length"],
+        before anything is enqueued."""
+        rows, texts = list(rows), [str(t).lower() for t in texts]
+        keep = self.keep_logits if keep_logits is None else bool(keep_logits)
+        if len(texts) != len(rows):
+            raise ValueError("LineReader.align: %d texts for %d lines" % (len(texts), len(rows)))
+        alphabet = _alphabet()
+        a2d = {ch: i for i, ch in enumerate(alphabet) if i >= 1}
+        strings = []
+        for i, t in enumerate(texts):
+            if len(t) > ALIGN_LENGTH:
+                raise ValueError("LineReader.align: line %d: %d characters; at most %d are aligned" % (i, len(t), ALIGN_LENGTH))
+            for ch in t:
+                if ch not in a2d:
+                    raise ValueError("LineReader.align: line %d: the text %r has the character %r, which the alphabet %r lacks"
+                                     % (i, t, ch, alphabet[1:]))
+            strings.append([a2d[ch] for ch in t])
+        if not rows:
+            return PendingAlignment(None, None, 0, None, [], alphabet, [] if keep else None, [] if self.keep_lp else None)
+        if not (isinstance(dev_bytes, torch.Tensor) and dev_bytes.dtype == torch.uint8 and dev_bytes.device == self.device and
+                dev_bytes.is_contiguous()):
+            raise ValueError("LineReader.align takes a contiguous uint8 tensor on %s" % (self.device,))
+        plan = read_plan(rows, scale, self.w)
+        n = len(rows)
+        order = [i for _, idx in plan.buckets for i in idx]
+        cap_len = max(len(s) for s in strings)
+        table = pack_strings(strings, cap_len)
+        chunk = min(self.B, READ_CHUNK)
+        kept, kept_lp = [] if keep else None, [] if self.keep_lp else None
+        with torch.cuda.device(self.device):
+            self._check_weights()
+            head = torch.empty(n * READ_DESC + n + table.size, dtype=torch.int32, pin_memory=True)
+            hn = head.numpy()
+            hn[:n * READ_DESC] = plan.desc.reshape(-1)
+            hn[n * READ_DESC:n * READ_DESC + n] = order
+            hn[n * READ_DESC + n:] = table.reshape(-1)
+            head_dev = torch.empty(head.numel(), dtype=torch.int32, device=self.device)
+            head_dev.copy_(head, non_blocking=True)
+            luma = torch.empty(plan.floats, dtype=torch.float32, device=self.device)
+            line_luma(dev_bytes, head_dev, plan.desc, luma)
+            words = align_record_words(cap_len)
+            record = torch.empty(n, words, dtype=torch.int32, device=self.device)
+            index, src = head_dev[n * READ_DESC:n * READ_DESC + n], head_dev[n * READ_DESC + n:].view(n, 2 + cap_len)
+            pos, foff = 0, 0
+            for rw, idx in plan.buckets:
+                x = luma[foff:foff + len(idx) * READ_HEIGHT * rw].view(len(idx), 1, READ_HEIGHT, rw)
+                foff += len(idx) * READ_HEIGHT * rw
+                for i in range(0, len(idx), chunk):
+                    m = min(chunk, len(idx) - i)
+                    logits = self.forward(x[i:i + m])
+                    lp = None
+                    if kept_lp is not None:
+                        lp = torch.empty(m, logits.shape[0], logits.shape[2], dtype=torch.float64, device=self.device)
+                        kept_lp.append((idx[i:i + m], lp))
+                    ctc_align(logits, index[pos:pos + m], src, 0, 2, -1, record, 0, cap_len, lp)
+                    if keep:
+                        kept.append((idx[i:i + m], logits))
+                    pos += m
+            host = torch.empty(n, words, dtype=torch.int32, pin_memory=True)
+            host.copy_(record, non_blocking=True)
+            ev = torch.cuda.Event()
+            ev.record()
+        return PendingAlignment(host, ev, cap_len, plan, strings, alphabet, kept, kept_lp)
