@@ -36,8 +36,11 @@ launch per bucket chunk behind the decode launch, which reads the best string fr
 from __future__ import annotations
 
 import ctypes
+import math
+import struct
 from collections import namedtuple
 
+import numpy as np
 import torch
 
 READ_QUANTUM = 20         # rw is a multiple of it
@@ -80,7 +83,6 @@ def line_luma_host(line_u8, rw: int):
     """line_u8: the (H, Wl, 3) uint8 line, the very bytes the caller gets back -> the (32, rw) float32 input of the recogniser:
     Image.fromarray(line).resize((rw, 32), BICUBIC), then n = 299 R + 587 G + 114 B as int32 (at most 255000: exact in fp32) and
     float32(n) * float32(1 / 255000)."""
-    import numpy as np
     from PIL import Image
     a = np.asarray(line_u8)
     if a.ndim != 3 or a.shape[2] != 3 or a.dtype != np.uint8:
@@ -95,7 +97,6 @@ def ctc_greedy_read_host(logits):
     blank 0 dropped, every other class kept), `steps` the first time step of every emitted character's run, `char_conf` the soft-max
     probability of the arg-max at that step, `conf` the minimum over ALL T steps of the arg-max's probability (the weakest decision on
     the path; defined for an empty string too).  Probabilities are computed in float64 from the given logits."""
-    import numpy as np
     x = np.asarray(logits.detach().cpu().numpy() if isinstance(logits, torch.Tensor) else logits)
     if x.ndim != 3:
         raise ValueError("ctc_greedy_read_host takes (T, B, C) logits; got %s" % (x.shape,))
@@ -121,10 +122,8 @@ def _beam_real(real):
     """the arithmetic of the beam specification: Python floats (float64), or a numpy scalar type such as np.longdouble, with which the
     tests measure the specification's own rounding -> (real, exp, log, lse)"""
     if real is None:
-        import math
         real, exp, log, log1p = float, math.exp, math.log, math.log1p
     else:
-        import numpy as np
         exp, log, log1p = np.exp, np.log, np.log1p
     neg = real("-inf")
 
@@ -315,7 +314,6 @@ class Lexicon:
     LENGTH, WORDS = 31, 65536                                        # tatt_lexicon_limits, stated here so that a list needs no library
 
     def __init__(self, words, alphabet=None, min_segment: int = 16):
-        import numpy as np
         if isinstance(words, str):
             raise ValueError("Lexicon takes a list of words, not one string")
         words = [str(w).lower() for w in words]
@@ -379,7 +377,6 @@ class LineLexicons:
     UNION = 1048576                                                  # tatt_line_lexicons_limits, stated here so that lists need no library
 
     def __init__(self, lists, alphabet=None, min_segment: int = 16):
-        import numpy as np
         if isinstance(lists, str) or any(isinstance(ws, str) for ws in lists):
             raise ValueError("LineLexicons takes one list of words per line, not strings")
         self.alphabet = _alphabet() if alphabet is None else str(alphabet)
@@ -433,7 +430,6 @@ class LineLexicons:
         int32, counts (len(lines),) int32) as tatt_ctc_lexicon_score_pairs takes them: the pairs of line b (its row in the chunk) are
         grouped by segment class, within a class by position j in the line's own list; one tile row (b, G, first pair, pairs <= 256 / G)
         per non-empty tile, every pair in exactly one tile."""
-        import numpy as np
         tiles, pairs, counts, n_pairs = [], [], [], 0
         for b, i in enumerate(lines):
             if i not in self._groups:                                # a line's pairs, grouped, are made once: (pairs, [(G, pairs of G)])
@@ -464,7 +460,6 @@ class CharLM:
     STEPS = 256                                                      # most steps of a line (read_limits), so most characters of a string
 
     def __init__(self, logp, alphabet=None):
-        import numpy as np
         try:
             a = np.array(logp, dtype=np.float64)
         except (TypeError, ValueError):
@@ -488,9 +483,6 @@ class CharLM:
         outside it); n-grams of every order up to `order` are counted with begin padding (class 0) and ONE end event (class 0) per
         string.  P_0(c) = 1 / C and P_n(c | h) = (count(h, c) + smoothing P_{n-1}(c | h')) / (count(h) + smoothing), h' = h without its
         oldest class; in float64, in this order, so the table is deterministic and every row sums to 1."""
-        import math
-
-        import numpy as np
         if isinstance(strings, str):
             raise ValueError("CharLM.from_corpus takes a list of strings, not one string")
         alphabet = _alphabet() if alphabet is None else str(alphabet)
@@ -523,9 +515,6 @@ class CharLM:
         W[h, 0] = weight logp[h, 0] (the end of the line gets no bonus).  Worked out ONCE here, in numpy; the host specification and the
         device read this table and only ever add its entries.  ValueError, too, where max |W| x (256 + 1) is not finite: the sum over
         the longest line and its end term must not overflow."""
-        import math
-
-        import numpy as np
         try:
             weight, bonus = float(weight), float(bonus)
         except (TypeError, ValueError):
@@ -544,14 +533,19 @@ class CharLM:
         return np.ascontiguousarray(out)
 
 
+def _limits(entry: str, names):
+    """a limits entry of the library (host-only: needs no GPU) -> {name: value}"""
+    from ._lib import LIB
+    out = (ctypes.c_int * len(names))()
+    if getattr(LIB, entry)(out) != 0:
+        raise RuntimeError("%s failed" % entry)
+    return dict(zip(names, (int(v) for v in out)))
+
+
 def lm_limits():
     """tatt_lm_limits: {'order', 'classes'}: the largest order and the most classes of a `CharLM` table the beam kernel takes.  A
     host-only entry: needs no GPU."""
-    from ._lib import LIB
-    out = (ctypes.c_int * 2)()
-    if LIB.tatt_lm_limits(out) != 0:
-        raise RuntimeError("tatt_lm_limits failed")
-    return dict(zip(("order", "classes"), (int(v) for v in out)))
+    return _limits("tatt_lm_limits", ("order", "classes"))
 
 
 def _lm_row(W, prefix, order):
@@ -567,7 +561,6 @@ def char_lm_score_host(W, classes):
     """W: the increments table of `CharLM.increments`; classes: a string as class ids >= 1 -> (the left-to-right sum, from 0.0, of
     W[h(prefix), c] over the string's characters, the end term W[h(string), 0]); h(p): the last order - 1 classes of p, left-padded
     with 0.  Python floats: float64."""
-    import numpy as np
     W = np.asarray(W, np.float64)
     classes = [int(c) for c in classes]
     if not 1 <= W.ndim <= CharLM.ORDER or any(not 1 <= c < W.shape[-1] for c in classes):
@@ -736,7 +729,6 @@ def ctc_line_lexicons_read_host(logits, lexicons: LineLexicons, nbest: int = 4, 
 
 
 def _check_penalty(what, word_penalty) -> float:
-    import math
     if isinstance(word_penalty, bool) or not isinstance(word_penalty, (int, float)) or not math.isfinite(word_penalty):
         raise ValueError("%s: word_penalty must be a finite float; got %r" % (what, word_penalty))
     return float(word_penalty)
@@ -885,7 +877,6 @@ def read_plan(line_sizes, scale, w: int = 64):
     buckets [(rw, [line indices in input order])] in ascending rw; desc (n, READ_DESC) int32 rows [byte offset, H, W, pitch, rw, float
     offset of the (32, rw) target, 0, 0] in INPUT order; offsets = desc[:, 5]: the lines of one bucket lie one after the other, the
     buckets in ascending rw, so each bucket is a contiguous (n, 1, 32, rw) view of one buffer of `floats` floats."""
-    import numpy as np
     rows = [tuple(int(v) for v in r) for r in line_sizes]
     scales = [int(scale)] * len(rows) if not hasattr(scale, "__len__") else [int(s) for s in scale]
     if len(scales) != len(rows):
@@ -920,7 +911,6 @@ def read_plan(line_sizes, scale, w: int = 64):
 def read_lines_host(lines_u8, run_crnn, scale=2, w: int = 64):
     """The composition on the host: per (H, W, 3) uint8 line `line_luma_host` at rw = read_width(W / scale, w) -> `run_crnn` (a callable:
     the (1, 1, 32, rw) float tensor -> (T, 1, 37) logits) -> `ctc_greedy_read_host` -> one Reading per line."""
-    import numpy as np
     lines = [np.asarray(a) for a in lines_u8]
     plan = read_plan([a.shape[:2] for a in lines], scale, w)
     out = []
@@ -1022,7 +1012,6 @@ def pack_strings(strings, cap_len: int):
     """strings: one list of classes per line -> the (n, 2 + cap_len) int32 numpy table tatt_ctc_align reads them from with len_at = 0,
     cls_at = 2, gate_at = -1: [0] the length, [1] 0, then the classes padded with -1.  ValueError for a cap_len outside
     0 .. ALIGN_LENGTH and for a string longer than cap_len; the classes themselves are judged on the device (flag 2)."""
-    import numpy as np
     if not (isinstance(cap_len, int) and 0 <= cap_len <= ALIGN_LENGTH):
         raise ValueError("pack_strings: cap_len is an int in 0 .. %d; got %r" % (ALIGN_LENGTH, cap_len))
     out = np.full((len(strings), 2 + cap_len), -1, np.int32)
@@ -1038,7 +1027,6 @@ def pack_strings(strings, cap_len: int):
 def parse_align_records(record, cap_len: int):
     """record: the (n, >= align_record_words(cap_len)) int32 HOST tensor (or numpy array) holding the alignment parts tatt_ctc_align
     wrote, from word 0 of every row -> one Aligned per row (flag 1 / 2: spans = [], logp = nan)."""
-    import struct
     rows = record.tolist()
     out = []
     for row in rows:
@@ -1085,7 +1073,6 @@ class Pattern:
     REPEAT = 256                                                     # the largest n of {m,n}
 
     def __init__(self, spec, alphabet=None):
-        import numpy as np
         if not isinstance(spec, str):
             raise ValueError("Pattern takes a regular expression as a string; got %r" % (type(spec).__name__,))
         self.spec, self.alphabet = spec, _alphabet() if alphabet is None else str(alphabet)
@@ -1120,7 +1107,6 @@ class Pattern:
 
     def table_for(self, classes: int):
         """the table for logits of `classes` >= n_classes classes: the classes beyond the alphabet continue no string"""
-        import numpy as np
         classes = int(classes)
         if classes < self.n_classes:
             raise ValueError("Pattern: the alphabet has %d classes, the logits %d" % (self.n_classes, classes))
@@ -1405,11 +1391,7 @@ def _pattern_dfa(ast, C, spec):
 def pattern_limits():
     """tatt_pattern_limits: {'steps', 'classes', 'states', 'beam'}: most steps T and classes C of tatt_ctc_pattern_mass and
     tatt_ctc_beam_pattern_read, most states of a `Pattern`'s DFA, most beam entries.  A host-only entry: needs no GPU."""
-    from ._lib import LIB
-    out = (ctypes.c_int * 4)()
-    if LIB.tatt_pattern_limits(out) != 0:
-        raise RuntimeError("tatt_pattern_limits failed")
-    return dict(zip(("steps", "classes", "states", "beam"), (int(v) for v in out)))
+    return _limits("tatt_pattern_limits", ("steps", "classes", "states", "beam"))
 
 
 def _as_pattern(what, pattern, alphabet=None) -> "Pattern":
@@ -1433,7 +1415,6 @@ def ctc_pattern_mass_host(logits, pattern, real=None):
     is added to an integer exponent.  mass = log(sum over accepting q and all e of A[q, e]) + exponent log(2); -inf where nothing is
     accepted in T steps.  A line with a NaN, a +inf or a step without a finite logit gives (nan, 1).
     Classes of the logits beyond the pattern's alphabet continue no string.  `real` as in `ctc_beam_read_host`."""
-    import numpy as np
     pattern = _as_pattern("ctc_pattern_mass_host", pattern)
     x = logits.detach().cpu() if isinstance(logits, torch.Tensor) else torch.as_tensor(logits)
     if x.dim() != 3 or x.shape[0] < 1 or x.shape[1] < 1 or x.shape[2] < 1:
@@ -1509,11 +1490,7 @@ def ctc_beam_pattern_read_host(logits, pattern, beam: int = 8, nbest: int = 4, d
 # ---- device entry points ----------------------------------------------------------------------------------------------------------------
 def read_limits():
     """tatt_read_limits: {'height', 'rw', 'down', 'width', 'lines', 'steps', 'classes', 'desc'}.  A host-only entry: needs no GPU."""
-    from ._lib import LIB
-    out = (ctypes.c_int * 8)()
-    if LIB.tatt_read_limits(out) != 0:
-        raise RuntimeError("tatt_read_limits failed")
-    return dict(zip(("height", "rw", "down", "width", "lines", "steps", "classes", "desc"), (int(v) for v in out)))
+    return _limits("tatt_read_limits", ("height", "rw", "down", "width", "lines", "steps", "classes", "desc"))
 
 
 def line_luma(src, desc_dev, desc_host, out):
@@ -1532,14 +1509,33 @@ def line_luma(src, desc_dev, desc_host, out):
         raise RuntimeError("tatt_line_luma failed with code %d" % rc)
 
 
+def _launched(entry: str, rc: int, what: str, *values):
+    """the return code of a launch entry: ValueError for what the entry refuses (1, before any launch), RuntimeError for any other"""
+    if rc == 1:
+        raise ValueError("%s refuses %s" % (entry, what % values))
+    if rc != 0:
+        raise RuntimeError("%s failed with code %d" % (entry, rc))
+
+
+def _check_record(what, record, index, B):
+    """the record / index refusal every decode wrapper makes, under the wrapper's own name"""
+    if record.dtype != torch.int32 or record.dim() != 2 or record.stride(1) != 1 or index.dtype != torch.int32 or index.numel() < B:
+        raise ValueError("%s: record must be a 2-D int32 tensor with contiguous rows, index an int32 tensor of B entries" % what)
+
+
+def _greedy_best_at(cap: int):
+    """(len_at, cls_at, gate_at) of the string in a greedy record row: `cap` classes, `cap` steps, `cap` confidences, then the length;
+    no gate word (-1).  `parse_records` and the alignment behind a greedy launch both read the row through it."""
+    return 3 * int(cap), 0, -1
+
+
 def ctc_greedy_read(logits, index, record, cap: int):
     """ONE tatt_ctc_greedy_read launch: logits (T, B, C) fp32 on the device (any strides), index (B,) int32 on the device: the record row
     of every image, record (n_rows, >= 3 cap + 2) int32 on the device, rows contiguous, cap >= T (see `parse_records`)."""
     from . import ops
     ops._check_dev(logits)
     T, B, C = logits.shape
-    if record.dtype != torch.int32 or record.dim() != 2 or record.stride(1) != 1 or index.dtype != torch.int32 or index.numel() < B:
-        raise ValueError("ctc_greedy_read: record must be a 2-D int32 tensor with contiguous rows, index an int32 tensor of B entries")
+    _check_record("ctc_greedy_read", record, index, B)
     ops.call("tatt_ctc_greedy_read", ops.P(logits), *logits.stride(), T, B, C, ops.P(index), ops.P(record), record.shape[0], int(cap),
              record.stride(0), ops.stream())
     return record
@@ -1549,27 +1545,52 @@ def parse_records(record, cap: int):
     """record: the (n, 3 cap + 2) int32 HOST tensor tatt_ctc_greedy_read filled -> one Decoded per row"""
     ints = record.tolist()
     flts = record.view(torch.float32).tolist()
+    len_at, cls_at, _ = _greedy_best_at(cap)
     out = []
     for ri, rf in zip(ints, flts):
-        n = ri[3 * cap]
-        out.append(Decoded(ri[:n], ri[cap:cap + n], rf[2 * cap:2 * cap + n], rf[3 * cap + 1]))
+        n = ri[len_at]
+        out.append(Decoded(ri[cls_at:cls_at + n], ri[cap:cap + n], rf[2 * cap:2 * cap + n], rf[len_at + 1]))
     return out
 
 
 def beam_limits():
     """tatt_beam_limits: {'steps', 'classes', 'beam', 'nodes', 'table'}: most steps T, classes C and beam entries of
     tatt_ctc_beam_read, the nodes of a line's prefix trie and the slots of its lookup table.  A host-only entry: needs no GPU."""
-    from ._lib import LIB
-    out = (ctypes.c_int * 5)()
-    if LIB.tatt_beam_limits(out) != 0:
-        raise RuntimeError("tatt_beam_limits failed")
-    return dict(zip(("steps", "classes", "beam", "nodes", "table"), (int(v) for v in out)))
+    return _limits("tatt_beam_limits", ("steps", "classes", "beam", "nodes", "table"))
+
+
+def _beam_best_at(doubles: int):
+    """(len_at, cls_at, gate_at) of entry 0 of a beam record row whose entries begin with `doubles` float64s (1: the logp; 2: with a
+    language model, the logp and the lm): [0] entries written (the gate), [1] flag, then per entry the float64s, the length, a pad
+    word, the classes.  The entry sizes, the row parser and the alignment behind a beam launch all read the layout from here."""
+    return 2 + 2 * doubles, 2 + 2 * doubles + 2, 0
+
+
+def _beam_entry_words(cap: int, doubles: int) -> int:
+    return _beam_best_at(doubles)[1] - 2 + int(cap) + (int(cap) & 1)
+
+
+def _parse_beam_rows(what, record, cap: int, nbest: int, doubles: int, decoded):
+    """the rows of a beam record (see `parse_beam_records`), `doubles` float64s in front of every entry -> one `decoded` per row, its
+    entries (classes, the float64s...)"""
+    es, (len_at, cls_at, gate_at), out = _beam_entry_words(cap, doubles), _beam_best_at(doubles), []
+    for row in record.tolist():
+        n, flag = row[gate_at], row[1]
+        if not 0 <= n <= nbest or flag not in (0, 1):
+            raise ValueError("%s: no beam record row: entries = %r, flag = %r" % (what, n, flag))
+        entries = []
+        for i in range(n):
+            e = row[2 + i * es:2 + (i + 1) * es]                     # (the offsets are entry 0's in the row: 2 words further)
+            entries.append((e[cls_at - 2:cls_at - 2 + e[len_at - 2]],) +
+                           struct.unpack("<%dd" % doubles, struct.pack("<%di" % (2 * doubles), *e[:2 * doubles])))
+        out.append(decoded(entries, flag))
+    return out
 
 
 def beam_entry_words(cap: int) -> int:
     """32-bit words of one entry of a beam record row: the float64 logp (2), the length, a pad word, then `cap` classes, rounded up to
     an even count so that every entry's logp is 8-byte aligned within the row"""
-    return 4 + int(cap) + (int(cap) & 1)
+    return _beam_entry_words(cap, 1)
 
 
 def beam_record_words(cap: int, nbest: int) -> int:
@@ -1590,19 +1611,15 @@ def ctc_beam_read(logits, index, record, cap: int, beam: int = 8, nbest: int = 4
     from ._lib import LIB
     ops._check_dev(logits)
     T, B, C = logits.shape
-    if record.dtype != torch.int32 or record.dim() != 2 or record.stride(1) != 1 or index.dtype != torch.int32 or index.numel() < B:
-        raise ValueError("ctc_beam_read: record must be a 2-D int32 tensor with contiguous rows, index an int32 tensor of B entries")
+    _check_record("ctc_beam_read", record, index, B)
     _check_beam("ctc_beam_read", beam, nbest, beam_limits()["beam"])
     if record.shape[1] < beam_record_words(cap, nbest):
         raise ValueError("ctc_beam_read: rows of %d words; cap = %d and nbest = %d need %d" % (record.shape[1], cap, nbest,
                                                                                              beam_record_words(cap, nbest)))
     rc = LIB.tatt_ctc_beam_read(ops.P(logits), *logits.stride(), T, B, C, beam, nbest, ops.P(index), ops.P(record), record.shape[0],
                                 int(cap), record.stride(0), ops.stream())
-    if rc == 1:
-        raise ValueError("tatt_ctc_beam_read refuses T = %d, C = %d, beam = %d, nbest = %d, cap = %d, rows of %d words"
-                         % (T, C, beam, nbest, cap, record.stride(0)))
-    if rc != 0:
-        raise RuntimeError("tatt_ctc_beam_read failed with code %d" % rc)
+    _launched("tatt_ctc_beam_read", rc, "T = %d, C = %d, beam = %d, nbest = %d, cap = %d, rows of %d words",
+              T, C, beam, nbest, cap, record.stride(0))
     return record
 
 
@@ -1610,18 +1627,7 @@ def parse_beam_records(record, cap: int, nbest: int):
     """record: the (n, >= beam_record_words(cap, nbest)) int32 HOST tensor tatt_ctc_beam_read filled -> one BeamDecoded per row.  Row, in
     32-bit words: [0] entries written (<= nbest)  [1] flag  then per entry, beam_entry_words(cap) words: the float64 logp as it is (low
     word first), the length, a pad word, `cap` classes padded with -1."""
-    import struct
-    es, out = beam_entry_words(cap), []
-    for row in record.tolist():
-        n, flag = row[0], row[1]
-        if not 0 <= n <= nbest or flag not in (0, 1):
-            raise ValueError("parse_beam_records: no beam record row: entries = %r, flag = %r" % (n, flag))
-        entries = []
-        for i in range(n):
-            e = row[2 + i * es:2 + (i + 1) * es]
-            entries.append((e[4:4 + e[2]], struct.unpack("<d", struct.pack("<ii", e[0], e[1]))[0]))
-        out.append(BeamDecoded(entries, flag))
-    return out
+    return _parse_beam_rows("parse_beam_records", record, cap, nbest, 1, BeamDecoded)
 
 
 def _beam_reading(dec: BeamDecoded, rw: int, squeezed: bool) -> BeamReading:
@@ -1634,7 +1640,7 @@ def _beam_reading(dec: BeamDecoded, rw: int, squeezed: bool) -> BeamReading:
 def beam_lm_entry_words(cap: int) -> int:
     """32-bit words of one entry of a beam record row with a language model: the float64 logp (2), the float64 lm (2), the length, a
     pad word, then `cap` classes, rounded up to an even count"""
-    return 6 + int(cap) + (int(cap) & 1)
+    return _beam_entry_words(cap, 2)
 
 
 def beam_lm_record_words(cap: int, nbest: int) -> int:
@@ -1652,8 +1658,7 @@ def ctc_beam_lm_read(logits, table_dev, order: int, index, record, cap: int, bea
     from ._lib import LIB
     ops._check_dev(logits)
     T, B, C = logits.shape
-    if record.dtype != torch.int32 or record.dim() != 2 or record.stride(1) != 1 or index.dtype != torch.int32 or index.numel() < B:
-        raise ValueError("ctc_beam_lm_read: record must be a 2-D int32 tensor with contiguous rows, index an int32 tensor of B entries")
+    _check_record("ctc_beam_lm_read", record, index, B)
     _check_beam("ctc_beam_lm_read", beam, nbest, beam_limits()["beam"])
     lim = lm_limits()
     if not (isinstance(order, int) and 1 <= order <= lim["order"]):
@@ -1670,11 +1675,8 @@ def ctc_beam_lm_read(logits, table_dev, order: int, index, record, cap: int, bea
                                                                                                 beam_lm_record_words(cap, nbest)))
     rc = LIB.tatt_ctc_beam_lm_read(ops.P(logits), *logits.stride(), T, B, C, beam, nbest, ops.P(table_dev), order, classes, ops.P(index),
                                    ops.P(record), record.shape[0], int(cap), record.stride(0), ops.stream())
-    if rc == 1:
-        raise ValueError("tatt_ctc_beam_lm_read refuses T = %d, C = %d, beam = %d, nbest = %d, order = %d, cap = %d, rows of %d words"
-                         % (T, C, beam, nbest, order, cap, record.stride(0)))
-    if rc != 0:
-        raise RuntimeError("tatt_ctc_beam_lm_read failed with code %d" % rc)
+    _launched("tatt_ctc_beam_lm_read", rc, "T = %d, C = %d, beam = %d, nbest = %d, order = %d, cap = %d, rows of %d words",
+              T, C, beam, nbest, order, cap, record.stride(0))
     return record
 
 
@@ -1683,18 +1685,7 @@ def parse_beam_lm_records(record, cap: int, nbest: int):
     Row, in 32-bit words: [0] entries written (<= nbest)  [1] flag  then per entry, beam_lm_entry_words(cap) words: the float64 logp
     (the acoustic mass) and the float64 lm (the LM term with the end term) as they are, low word first, the length, a pad word, `cap`
     classes padded with -1."""
-    import struct
-    es, out = beam_lm_entry_words(cap), []
-    for row in record.tolist():
-        n, flag = row[0], row[1]
-        if not 0 <= n <= nbest or flag not in (0, 1):
-            raise ValueError("parse_beam_lm_records: no beam record row: entries = %r, flag = %r" % (n, flag))
-        entries = []
-        for i in range(n):
-            e = row[2 + i * es:2 + (i + 1) * es]
-            entries.append((e[6:6 + e[4]],) + struct.unpack("<dd", struct.pack("<iiii", *e[:4])))
-        out.append(BeamLMDecoded(entries, flag))
-    return out
+    return _parse_beam_rows("parse_beam_lm_records", record, cap, nbest, 2, BeamLMDecoded)
 
 
 def _beam_lm_reading(dec: BeamLMDecoded, rw: int, squeezed: bool) -> BeamLMReading:
@@ -1733,8 +1724,7 @@ def ctc_beam_pattern_read(logits, pattern: Pattern, index, record, cap: int, bea
     from ._lib import LIB
     ops._check_dev(logits)
     T, B, C = logits.shape
-    if record.dtype != torch.int32 or record.dim() != 2 or record.stride(1) != 1 or index.dtype != torch.int32 or index.numel() < B:
-        raise ValueError("ctc_beam_pattern_read: record must be a 2-D int32 tensor with contiguous rows, index an int32 tensor of B entries")
+    _check_record("ctc_beam_pattern_read", record, index, B)
     _check_beam("ctc_beam_pattern_read", beam, nbest, pattern_limits()["beam"])
     _check_pattern("ctc_beam_pattern_read", pattern, C)
     if record.shape[1] < beam_record_words(cap, nbest):
@@ -1743,11 +1733,8 @@ def ctc_beam_pattern_read(logits, pattern: Pattern, index, record, cap: int, bea
     table, accept = pattern.device(logits.device, C)
     rc = LIB.tatt_ctc_beam_pattern_read(ops.P(logits), *logits.stride(), T, B, C, beam, nbest, ops.P(table), ops.P(accept), pattern.n_states,
                                         ops.P(index), ops.P(record), record.shape[0], int(cap), record.stride(0), ops.stream())
-    if rc == 1:
-        raise ValueError("tatt_ctc_beam_pattern_read refuses T = %d, C = %d, beam = %d, nbest = %d, S = %d, cap = %d, rows of %d words"
-                         % (T, C, beam, nbest, pattern.n_states, cap, record.stride(0)))
-    if rc != 0:
-        raise RuntimeError("tatt_ctc_beam_pattern_read failed with code %d" % rc)
+    _launched("tatt_ctc_beam_pattern_read", rc, "T = %d, C = %d, beam = %d, nbest = %d, S = %d, cap = %d, rows of %d words",
+              T, C, beam, nbest, pattern.n_states, cap, record.stride(0))
     return record
 
 
@@ -1768,17 +1755,12 @@ def ctc_pattern_mass(logits, pattern: Pattern, index, out):
     table, accept = pattern.device(logits.device, C)
     rc = LIB.tatt_ctc_pattern_mass(ops.P(logits), *logits.stride(), T, B, C, ops.P(table), ops.P(accept), pattern.n_states, ops.P(index),
                                    ops.P(out), out.shape[0], out.stride(0), ops.stream())
-    if rc == 1:
-        raise ValueError("tatt_ctc_pattern_mass refuses T = %d, B = %d, C = %d, S = %d, rows of %d words"
-                         % (T, B, C, pattern.n_states, out.stride(0)))
-    if rc != 0:
-        raise RuntimeError("tatt_ctc_pattern_mass failed with code %d" % rc)
+    _launched("tatt_ctc_pattern_mass", rc, "T = %d, B = %d, C = %d, S = %d, rows of %d words", T, B, C, pattern.n_states, out.stride(0))
     return out
 
 
 def parse_pattern_mass(out):
     """out: the (n, >= PATTERN_MASS_WORDS) int32 HOST tensor tatt_ctc_pattern_mass filled -> one PatternMass per row"""
-    import struct
     res = []
     for row in out.tolist():
         if row[2] not in (0, 1):
@@ -1788,7 +1770,6 @@ def parse_pattern_mass(out):
 
 
 def _pattern_reading(dec: BeamDecoded, mass: PatternMass, alphabet, rw: int, squeezed: bool) -> PatternReading:
-    import math
     nan = float("nan")
     m = nan if mass.flag or dec.flag else mass.mass
     alts = [("".join(alphabet[c] for c in classes), logp, math.exp(logp - m)) for classes, logp in dec.entries]
@@ -1799,11 +1780,7 @@ def _pattern_reading(dec: BeamDecoded, mass: PatternMass, alphabet, rw: int, squ
 def lexicon_limits():
     """tatt_lexicon_limits: {'steps', 'classes', 'length', 'words', 'nbest'}: most steps T and classes C of tatt_ctc_lexicon_score, the
     longest word and most words of a lexicon, most entries of tatt_ctc_lexicon_select.  A host-only entry: needs no GPU."""
-    from ._lib import LIB
-    out = (ctypes.c_int * 5)()
-    if LIB.tatt_lexicon_limits(out) != 0:
-        raise RuntimeError("tatt_lexicon_limits failed")
-    return dict(zip(("steps", "classes", "length", "words", "nbest"), (int(v) for v in out)))
+    return _limits("tatt_lexicon_limits", ("steps", "classes", "length", "words", "nbest"))
 
 
 def lexicon_record_words(nbest: int) -> int:
@@ -1834,10 +1811,7 @@ def ctc_lexicon_score(logits, lexicon: Lexicon, scores):
     codes, table = lexicon.device(logits.device)
     rc = LIB.tatt_ctc_lexicon_score(ops.P(logits), *logits.stride(), T, B, C, ops.P(codes), lexicon.n_codes, ops.P(table), K,
                                     *lexicon.counts, ops.P(scores), scores.stride(0), ops.stream())
-    if rc == 1:
-        raise ValueError("tatt_ctc_lexicon_score refuses T = %d, B = %d, C = %d, K = %d" % (T, B, C, K))
-    if rc != 0:
-        raise RuntimeError("tatt_ctc_lexicon_score failed with code %d" % rc)
+    _launched("tatt_ctc_lexicon_score", rc, "T = %d, B = %d, C = %d, K = %d", T, B, C, K)
     return scores
 
 
@@ -1853,8 +1827,7 @@ def _check_select(what, scores, index, record, nbest, counts=None):
         _int32_on(what, "counts", counts, scores.device)
         if counts.numel() != B:
             raise ValueError("%s: %d counts for %d lines" % (what, counts.numel(), B))
-    if record.dtype != torch.int32 or record.dim() != 2 or record.stride(1) != 1 or index.dtype != torch.int32 or index.numel() < B:
-        raise ValueError("%s: record must be a 2-D int32 tensor with contiguous rows, index an int32 tensor of B entries" % what)
+    _check_record(what, record, index, B)
     _check_nbest(what, nbest)
     if record.shape[1] < lexicon_record_words(nbest):
         raise ValueError("%s: rows of %d words; nbest = %d needs %d" % (what, record.shape[1], nbest, lexicon_record_words(nbest)))
@@ -1870,10 +1843,7 @@ def ctc_lexicon_select(scores, index, record, nbest: int = 4):
     B, K = _check_select("ctc_lexicon_select", scores, index, record, nbest)
     rc = LIB.tatt_ctc_lexicon_select(ops.P(scores), scores.stride(0), B, K, nbest, ops.P(index), ops.P(record), record.shape[0],
                                      record.stride(0), ops.stream())
-    if rc == 1:
-        raise ValueError("tatt_ctc_lexicon_select refuses B = %d, K = %d, nbest = %d, rows of %d words" % (B, K, nbest, record.stride(0)))
-    if rc != 0:
-        raise RuntimeError("tatt_ctc_lexicon_select failed with code %d" % rc)
+    _launched("tatt_ctc_lexicon_select", rc, "B = %d, K = %d, nbest = %d, rows of %d words", B, K, nbest, record.stride(0))
     return record
 
 
@@ -1881,7 +1851,6 @@ def parse_lexicon_records(record, nbest: int):
     """record: the (n, >= lexicon_record_words(nbest)) int32 HOST tensor tatt_ctc_lexicon_select filled -> one LexiconDecoded per row.
     Row, in 32-bit words: [0] entries written (<= nbest)  [1] flag  [2:4] the float64 logz as it is (low word first)  then per entry 4
     words: the float64 logp, the word's index, 0."""
-    import struct
     f64 = lambda lo, hi: struct.unpack("<d", struct.pack("<ii", lo, hi))[0]
     out = []
     for row in record.tolist():
@@ -1898,7 +1867,6 @@ def _lexicon_reading(dec: LexiconDecoded, lexicon: Lexicon, rw: int, squeezed: b
 
 def _line_lexicon_reading(dec: LexiconDecoded, words, rw: int, squeezed: bool) -> LexiconReading:
     """a decoded line as the caller sees it; words: the list the line was read against (a `Lexicon`'s, or the line's own)"""
-    import math
     alts = [(words[k], logp, math.exp(logp - dec.logz)) for k, logp in dec.entries]
     text, logp, post = alts[0] if alts else ("", float("nan"), float("nan"))
     return LexiconReading(text, logp, post, alts, rw, squeezed)
@@ -1907,11 +1875,7 @@ def _line_lexicon_reading(dec: LexiconDecoded, words, rw: int, squeezed: bool) -
 def line_lexicons_limits():
     """tatt_line_lexicons_limits: {'steps', 'classes', 'length', 'words', 'union', 'nbest'}: `lexicon_limits()` with `words` the most
     words of ONE line's list and `union` the most distinct words of all lists.  A host-only entry: needs no GPU."""
-    from ._lib import LIB
-    out = (ctypes.c_int * 6)()
-    if LIB.tatt_line_lexicons_limits(out) != 0:
-        raise RuntimeError("tatt_line_lexicons_limits failed")
-    return dict(zip(("steps", "classes", "length", "words", "union", "nbest"), (int(v) for v in out)))
+    return _limits("tatt_line_lexicons_limits", ("steps", "classes", "length", "words", "union", "nbest"))
 
 
 def _int32_on(what, name, t, device, cols=None):
@@ -1952,11 +1916,8 @@ def ctc_lexicon_score_pairs(logits, codes, n_codes: int, table, tiles, pairs, co
     rc = LIB.tatt_ctc_lexicon_score_pairs(ops.P(logits), *logits.stride(), T, B, C, ops.P(codes), n_codes, ops.P(table), table.shape[0],
                                           ops.P(tiles), tiles.shape[0], ops.P(pairs), pairs.shape[0], ops.P(counts), max_count,
                                           ops.P(scores), scores.stride(0), ops.stream())
-    if rc == 1:
-        raise ValueError("tatt_ctc_lexicon_score_pairs refuses T = %d, B = %d, C = %d, U = %d, %d tiles, %d pairs, max_count = %d"
-                         % (T, B, C, table.shape[0], tiles.shape[0], pairs.shape[0], max_count))
-    if rc != 0:
-        raise RuntimeError("tatt_ctc_lexicon_score_pairs failed with code %d" % rc)
+    _launched("tatt_ctc_lexicon_score_pairs", rc, "T = %d, B = %d, C = %d, U = %d, %d tiles, %d pairs, max_count = %d",
+              T, B, C, table.shape[0], tiles.shape[0], pairs.shape[0], max_count)
     return scores
 
 
@@ -1969,10 +1930,7 @@ def ctc_lexicon_select_rows(scores, counts, index, record, nbest: int = 4):
     B = _check_select("ctc_lexicon_select_rows", scores, index, record, nbest, counts)[0]
     rc = LIB.tatt_ctc_lexicon_select_rows(ops.P(scores), scores.stride(0), B, ops.P(counts), nbest, ops.P(index), ops.P(record),
                                           record.shape[0], record.stride(0), ops.stream())
-    if rc == 1:
-        raise ValueError("tatt_ctc_lexicon_select_rows refuses B = %d, nbest = %d, rows of %d words" % (B, nbest, record.stride(0)))
-    if rc != 0:
-        raise RuntimeError("tatt_ctc_lexicon_select_rows failed with code %d" % rc)
+    _launched("tatt_ctc_lexicon_select_rows", rc, "B = %d, nbest = %d, rows of %d words", B, nbest, record.stride(0))
     return record
 
 
@@ -1980,11 +1938,7 @@ def words_limits():
     """tatt_words_limits: {'steps', 'classes', 'lanes', 'threads', 'slots'}: most steps T and classes C of tatt_ctc_words_read, the most
     packed lanes of a lexicon (`words_lanes`), the threads of a work-group and the lanes a thread holds at that limit.  A host-only
     entry: needs no GPU."""
-    from ._lib import LIB
-    out = (ctypes.c_int * 5)()
-    if LIB.tatt_words_limits(out) != 0:
-        raise RuntimeError("tatt_words_limits failed")
-    return dict(zip(("steps", "classes", "lanes", "threads", "slots"), (int(v) for v in out)))
+    return _limits("tatt_words_limits", ("steps", "classes", "lanes", "threads", "slots"))
 
 
 def words_lanes(lexicon: Lexicon) -> int:
@@ -2015,8 +1969,7 @@ def ctc_words_read(logits, lexicon: Lexicon, index, record, cap: int, word_penal
     from ._lib import LIB
     ops._check_dev(logits)
     T, B, C = logits.shape
-    if record.dtype != torch.int32 or record.dim() != 2 or record.stride(1) != 1 or index.dtype != torch.int32 or index.numel() < B:
-        raise ValueError("ctc_words_read: record must be a 2-D int32 tensor with contiguous rows, index an int32 tensor of B entries")
+    _check_record("ctc_words_read", record, index, B)
     wp = _check_penalty("ctc_words_read", word_penalty)
     if lexicon.n_classes > C:
         raise ValueError("ctc_words_read: the lexicon's alphabet has %d classes, the logits %d" % (lexicon.n_classes, C))
@@ -2034,11 +1987,8 @@ def ctc_words_read(logits, lexicon: Lexicon, index, record, cap: int, word_penal
     rc = LIB.tatt_ctc_words_read(ops.P(logits), *logits.stride(), T, B, C, ops.P(codes), lexicon.n_codes, ops.P(table), len(lexicon),
                                  *lexicon.counts, wp, ops.P(index), ops.P(record), record.shape[0], int(cap), record.stride(0),
                                  ops.P(lp_out), st_lp, ops.stream())
-    if rc == 1:
-        raise ValueError("tatt_ctc_words_read refuses T = %d, B = %d, C = %d, K = %d, cap = %d, rows of %d words"
-                         % (T, B, C, len(lexicon), cap, record.stride(0)))
-    if rc != 0:
-        raise RuntimeError("tatt_ctc_words_read failed with code %d" % rc)
+    _launched("tatt_ctc_words_read", rc, "T = %d, B = %d, C = %d, K = %d, cap = %d, rows of %d words",
+              T, B, C, len(lexicon), cap, record.stride(0))
     return record
 
 
@@ -2046,7 +1996,6 @@ def parse_words_records(record, cap: int):
     """record: the (n, >= words_record_words(cap)) int32 HOST tensor tatt_ctc_words_read filled -> one WordsDecoded per row.  Row, in
     32-bit words: [0] words written (<= cap)  [1] flag  [2:4] the float64 logp as it is (low word first)  then per word 2 words: the
     caller's word index, first | last << 16."""
-    import struct
     out = []
     for row in record.tolist():
         n, flag = row[0], row[1]
@@ -2060,11 +2009,7 @@ def parse_words_records(record, cap: int):
 def align_limits():
     """tatt_align_limits: {'steps', 'classes', 'length'}: most steps T and classes C of tatt_ctc_align and the longest string it
     aligns (2 length + 1 states, one thread each).  A host-only entry: needs no GPU."""
-    from ._lib import LIB
-    out = (ctypes.c_int * 3)()
-    if LIB.tatt_align_limits(out) != 0:
-        raise RuntimeError("tatt_align_limits failed")
-    return dict(zip(("steps", "classes", "length"), (int(v) for v in out)))
+    return _limits("tatt_align_limits", ("steps", "classes", "length"))
 
 
 def ctc_align(logits, index, src, len_at: int, cls_at: int, gate_at: int, record, rec_at: int, cap_len: int, lp_out=None):
@@ -2080,8 +2025,7 @@ def ctc_align(logits, index, src, len_at: int, cls_at: int, gate_at: int, record
     from ._lib import LIB
     ops._check_dev(logits)
     T, B, C = logits.shape
-    if record.dtype != torch.int32 or record.dim() != 2 or record.stride(1) != 1 or index.dtype != torch.int32 or index.numel() < B:
-        raise ValueError("ctc_align: record must be a 2-D int32 tensor with contiguous rows, index an int32 tensor of B entries")
+    _check_record("ctc_align", record, index, B)
     if not (isinstance(src, torch.Tensor) and src.dtype == torch.int32 and src.dim() == 2 and src.stride(1) == 1 and
             src.device == logits.device and record.device == logits.device and index.device == logits.device):
         raise ValueError("ctc_align: src must be a 2-D int32 tensor with contiguous rows on %s, like record and index" % (logits.device,))
@@ -2105,20 +2049,241 @@ def ctc_align(logits, index, src, len_at: int, cls_at: int, gate_at: int, record
     rc = LIB.tatt_ctc_align(ops.P(logits), *logits.stride(), T, B, C, ops.P(index), ops.P(src), src.shape[0], src.stride(0), len_at,
                             cls_at, gate_at, ops.P(record), record.shape[0], record.stride(0), rec_at, cap_len, ops.P(lp_out),
                             ops.stream())
-    if rc == 1:
-        raise ValueError("tatt_ctc_align refuses T = %d, B = %d, C = %d, cap_len = %d, rec_at = %d, rows of %d words"
-                         % (T, B, C, cap_len, rec_at, record.stride(0)))
-    if rc != 0:
-        raise RuntimeError("tatt_ctc_align failed with code %d" % rc)
+    _launched("tatt_ctc_align", rc, "T = %d, B = %d, C = %d, cap_len = %d, rec_at = %d, rows of %d words",
+              T, B, C, cap_len, rec_at, record.stride(0))
     return record
 
 
-def _align_source(cap: int, nbest, lm: bool):
-    """(len_at, cls_at, gate_at) of the best string in a decode record row: greedy (nbest None) has its classes at 0 and its length at
-    3 cap; a beam row's entry 0 lies behind [0] entries written (the gate) and [1] the flag"""
-    if nbest is None:
-        return 3 * cap, 0, -1
-    return (2 + 4, 2 + 6, 0) if lm else (2 + 2, 2 + 4, 0)
+# ---- the decodings of a LineReader ------------------------------------------------------------------------------------------------------
+class _ReadState:
+    """What one `read` holds for its decoding besides the record: `scores` / `lp`: the score and log-soft-max buffers of its chunks
+    (None: not kept); decode="lexicons" only: `lexicons` the call's LineLexicons, `union` its codes and table on the device, `chunks`
+    an iterator over (tiles, pairs, counts, most words of a line) per chunk, in the order the chunks are launched."""
+
+    def __init__(self, scores=None, lp=None):
+        self.scores, self.lp, self.lexicons, self.union, self.chunks = scores, lp, None, None, None
+
+
+def _lp_buffer(kept_lp, lines, logits):
+    """the (n, T, C) float64 buffer a launch leaves its log-soft-max in, kept with the chunk's line indices; None where none is kept"""
+    if kept_lp is None:
+        return None
+    T, n, C = logits.shape
+    lp = torch.empty(n, T, C, dtype=torch.float64, device=logits.device)
+    kept_lp.append((lines, lp))
+    return lp
+
+
+class _Decoding:
+    """One decoding of `LineReader`: what it was made with, the layout of its record row, its launches and its parser, in one place.
+    `_reader_decoding` makes it from the reader's keywords.  Every launch goes through this module's globals at call time.
+    record_words(cap): 32-bit words of its record row for lines of at most `cap` steps.  align_source(cap): (len_at, cls_at, gate_at)
+    of the best string in that row; None: the row holds word indices, nothing to locate.  upload(device, emits): the one upload of what
+    its launches read on the device (no `read` makes it).  launch(logits (T, n, C), index: the record rows of the chunk's lines, record,
+    cap, lines: their input indices, state): the decode launch(es) of one chunk.  readings(host, cap, plan, state): the host record of a
+    call -> one reading per line, in input order."""
+    keeps_scores = keeps_lp = False
+    alphabet = property(lambda self: _alphabet())                    # of the classes in its record: what `locations()` spells with
+    align_source = upload = lambda self, *args: None
+
+    def __init__(self, beam, nbest, lexicon=None, word_penalty=0.0, lm=None, lm_weight=None, lm_bonus=None, lm_table=None, pattern=None):
+        self.beam, self.nbest, self.lexicon, self.word_penalty, self.pattern = beam, nbest, lexicon, word_penalty, pattern
+        self.lm, self.lm_weight, self.lm_bonus, self.lm_table = lm, lm_weight, lm_bonus, lm_table
+
+    def begin(self, reader, plan, chunk: int, lexicons) -> _ReadState:
+        """the state of one call, made after the luma launch and before the first chunk"""
+        return _ReadState([] if self.keeps_scores and reader.keep_scores else None,
+                          [] if (self.keeps_lp or reader.locate) and reader.keep_lp else None)
+
+
+class _Greedy(_Decoding):
+    record_words = lambda self, cap: 3 * int(cap) + 2
+    align_source = lambda self, cap: _greedy_best_at(cap)
+
+    def launch(self, logits, index, record, cap, lines, state):
+        ctc_greedy_read(logits, index, record, cap)
+
+    def readings(self, host, cap, plan, state):
+        return [_reading(d, rw, sq) for d, rw, sq in zip(parse_records(host, cap), plan.rws, plan.squeezed)]
+
+
+class _Beam(_Decoding):
+    record_words = lambda self, cap: beam_record_words(cap, self.nbest)
+    align_source = lambda self, cap: _beam_best_at(1)
+
+    def launch(self, logits, index, record, cap, lines, state):
+        ctc_beam_read(logits, index, record, cap, self.beam, self.nbest)
+
+    def readings(self, host, cap, plan, state):
+        return [_beam_reading(d, rw, sq) for d, rw, sq in zip(parse_beam_records(host, cap, self.nbest), plan.rws, plan.squeezed)]
+
+
+class _BeamLM(_Decoding):
+    record_words = lambda self, cap: beam_lm_record_words(cap, self.nbest)
+    align_source = lambda self, cap: _beam_best_at(2)
+
+    def upload(self, device, emits):
+        self.lm_table = torch.from_numpy(self.lm_table).to(device)
+
+    def launch(self, logits, index, record, cap, lines, state):
+        ctc_beam_lm_read(logits, self.lm_table, self.lm.order, index, record, cap, self.beam, self.nbest)
+
+    def readings(self, host, cap, plan, state):
+        return [_beam_lm_reading(d, rw, sq) for d, rw, sq in zip(parse_beam_lm_records(host, cap, self.nbest), plan.rws, plan.squeezed)]
+
+
+class _BeamPattern(_Beam):
+    """the beam row of `_Beam`, held to the format, and the format's mass behind it"""
+    alphabet = property(lambda self: self.pattern.alphabet)
+    record_words = lambda self, cap: pattern_record_words(cap, self.nbest)
+    upload = lambda self, device, emits: self.pattern.device(device, emits)
+
+    def launch(self, logits, index, record, cap, lines, state):
+        ctc_beam_pattern_read(logits, self.pattern, index, record, cap, self.beam, self.nbest)
+        ctc_pattern_mass(logits, self.pattern, index, record[:, beam_record_words(cap, self.nbest):])
+
+    def readings(self, host, cap, plan, state):
+        at = beam_record_words(cap, self.nbest)
+        return [_pattern_reading(d, m, self.pattern.alphabet, rw, sq) for d, m, rw, sq in zip(
+            parse_beam_records(host, cap, self.nbest), parse_pattern_mass(host[:, at:]), plan.rws, plan.squeezed)]
+
+
+class _Lexicon(_Decoding):
+    keeps_scores = True
+    record_words = lambda self, cap: lexicon_record_words(self.nbest)
+    upload = lambda self, device, emits: self.lexicon.device(device)
+
+    def launch(self, logits, index, record, cap, lines, state):
+        scores = torch.empty(logits.shape[1], len(self.lexicon), dtype=torch.float64, device=logits.device)
+        ctc_lexicon_score(logits, self.lexicon, scores)
+        ctc_lexicon_select(scores, index, record, self.nbest)
+        if state.scores is not None:
+            state.scores.append((lines, scores))
+
+    def readings(self, host, cap, plan, state):
+        return [_lexicon_reading(d, self.lexicon, rw, sq) for d, rw, sq in zip(parse_lexicon_records(host, self.nbest), plan.rws,
+                                                                                plan.squeezed)]
+
+
+class _Words(_Decoding):
+    keeps_lp = True
+    record_words = lambda self, cap: words_record_words(cap)
+    upload = lambda self, device, emits: self.lexicon.device(device)
+
+    def launch(self, logits, index, record, cap, lines, state):
+        ctc_words_read(logits, self.lexicon, index, record, cap, self.word_penalty, _lp_buffer(state.lp, lines, logits))
+
+    def readings(self, host, cap, plan, state):
+        return [_words_reading(d, self.lexicon, rw, sq, int(W)) for d, rw, sq, W in zip(parse_words_records(host, cap), plan.rws,
+                                                                                         plan.squeezed, plan.desc[:, 2])]
+
+
+class _LineLexicons(_Decoding):
+    keeps_scores = True
+    record_words = lambda self, cap: lexicon_record_words(self.nbest)
+
+    def begin(self, reader, plan, chunk, lexicons):
+        """the union and every chunk's tile table, pairs and counts: ONE int32 blob, one copy from pinned memory"""
+        state = super().begin(reader, plan, chunk, lexicons)
+        parts, spans, at = [lexicons.codes, lexicons.table.reshape(-1)], [], lexicons.codes.size + lexicons.table.size
+        for _, idx in plan.buckets:                                  # (lists go by INPUT index, chunks in bucket order)
+            for i in range(0, len(idx), chunk):
+                tiles, pairs, counts = lexicons.pack(idx[i:i + chunk])
+                spans.append((at, at + tiles.size, at + tiles.size + pairs.size, at + tiles.size + pairs.size + counts.size,
+                              max(1, int(counts.max()))))
+                parts += [tiles.reshape(-1), pairs.reshape(-1), counts]
+                at = spans[-1][3]
+        blob = torch.empty(at, dtype=torch.int32, pin_memory=True)
+        blob.numpy()[:] = np.concatenate(parts)
+        dev = torch.empty(at, dtype=torch.int32, device=reader.device)
+        dev.copy_(blob, non_blocking=True)
+        state.lexicons = lexicons
+        state.union = dev[:lexicons.codes.size], dev[lexicons.codes.size:spans[0][0]].view(-1, 4)
+        state.chunks = iter([(dev[a:b].view(-1, 4), dev[b:c].view(-1, 2), dev[c:d], most) for a, b, c, d, most in spans])
+        return state
+
+    def launch(self, logits, index, record, cap, lines, state):
+        tiles, pairs, counts, most = next(state.chunks)
+        scores = torch.empty(logits.shape[1], most, dtype=torch.float64, device=logits.device)
+        if tiles.shape[0]:                                           # (a chunk of empty lists has nothing to score)
+            codes, table = state.union
+            ctc_lexicon_score_pairs(logits, codes, state.lexicons.n_codes, table, tiles, pairs, counts, scores, most)
+        ctc_lexicon_select_rows(scores, counts, index, record, self.nbest)
+        if state.scores is not None:
+            state.scores.append((lines, scores, counts))
+
+    def readings(self, host, cap, plan, state):
+        return [_line_lexicon_reading(d, ws, rw, sq) for d, ws, rw, sq in zip(parse_lexicon_records(host, self.nbest), state.lexicons.lists,
+                                                                              plan.rws, plan.squeezed)]
+
+
+def _reader_decoding(decode, beam, nbest, lexicon, word_penalty, lm, lm_weight, lm_bonus, pattern, locate, emits) -> _Decoding:
+    """The keywords of `LineReader` and `emits`, the classes its CRNN emits (None: it does not say) -> the decoding; ValueError for
+    every combination the reader refuses.  Touches no device.  A new decoding is one subclass of `_Decoding` and one line here."""
+    if decode not in ("greedy", "beam", "lexicon", "words", "lexicons"):
+        raise ValueError("LineReader: decode is 'greedy', 'beam', 'lexicon', 'words' or 'lexicons'; got %r" % (decode,))
+    if locate and decode not in ("greedy", "beam"):
+        raise ValueError("LineReader: locate=True goes with decode='greedy' or decode='beam' (their records hold the classes of "
+                         "the string; those of %r hold word indices)" % (decode,))
+    word_penalty = _check_penalty("LineReader", word_penalty)
+    if decode != "words" and word_penalty != 0.0:
+        raise ValueError("LineReader: word_penalty= goes with decode='words'; got decode = %r" % (decode,))
+    if decode == "lexicons":
+        _check_nbest("LineReader", nbest)
+        if lexicon is not None:
+            raise ValueError("LineReader: lexicon= goes with decode='lexicon' or decode='words'; decode='lexicons' takes the lists "
+                             "of a call as read(..., lexicons=)")
+    elif decode in ("lexicon", "words"):
+        if decode == "lexicon":
+            _check_nbest("LineReader", nbest)
+        if lexicon is None:
+            raise ValueError("LineReader: decode=%r needs lexicon=, a Lexicon or a list of words" % (decode,))
+        lexicon = lexicon if isinstance(lexicon, Lexicon) else Lexicon(lexicon)
+        if emits is not None and lexicon.n_classes > emits:
+            raise ValueError("LineReader: the lexicon's alphabet has %d classes, the CRNN emits %d" % (lexicon.n_classes, emits))
+        if decode == "words":
+            _check_lanes("LineReader", lexicon)
+    else:
+        _check_beam("LineReader", beam, nbest, beam_limits()["beam"])
+        if lexicon is not None:
+            raise ValueError("LineReader: lexicon= goes with decode='lexicon' or decode='words'; got decode = %r" % (decode,))
+    table = None
+    if lm is None:
+        if lm_weight is not None or lm_bonus is not None:
+            raise ValueError("LineReader: lm_weight= and lm_bonus= go with lm=, a CharLM")
+    else:
+        if decode != "beam":
+            raise ValueError("LineReader: lm= goes with decode='beam'; got decode = %r" % (decode,))
+        if not isinstance(lm, CharLM):
+            raise ValueError("LineReader: lm is a CharLM; got %r" % (type(lm).__name__,))
+        if emits is not None and lm.n_classes != emits:
+            raise ValueError("LineReader: the language model has %d classes, the CRNN emits %d" % (lm.n_classes, emits))
+        try:
+            weight, bonus = 0.5 if lm_weight is None else float(lm_weight), 0.0 if lm_bonus is None else float(lm_bonus)
+            table = lm.increments(weight, bonus)
+        except (TypeError, ValueError):
+            raise ValueError("LineReader: lm_weight and lm_bonus are finite floats; got %r, %r" % (lm_weight, lm_bonus)) from None
+        lm_weight, lm_bonus = weight, bonus
+    if pattern is not None:
+        if decode != "beam":
+            raise ValueError("LineReader: pattern= goes with decode='beam'; got decode = %r" % (decode,))
+        if lm is not None:
+            raise ValueError("LineReader: pattern= and lm= do not go together")
+        pattern = _as_pattern("LineReader", pattern)                 # (a pattern beyond the limits is refused where it is compiled)
+        if emits is None:                                            # (the table is uploaded once, for the classes of the logits)
+            raise ValueError("LineReader: pattern= needs a CRNN that states the classes it emits (rnn[-1].embedding.out_features)")
+        if pattern.n_classes > emits:
+            raise ValueError("LineReader: the pattern's alphabet has %d classes, the CRNN emits %d" % (pattern.n_classes, emits))
+        _check_pattern("LineReader", pattern, pattern.n_classes)
+    made = {"greedy": _Greedy, "lexicon": _Lexicon, "words": _Words, "lexicons": _LineLexicons,
+            "beam": _BeamLM if lm is not None else _BeamPattern if pattern is not None else _Beam}[decode]
+    return made(beam, nbest, lexicon, word_penalty, lm, lm_weight, lm_bonus, table, pattern)
+
+
+def _locations(host, cap_len: int, plan, alphabet, strings):
+    """host: the align records of a call on the host, strings: the classes that were aligned, per line -> one LineLocation per line"""
+    return [_location(al, classes if al.flag != 1 else [], alphabet, rw, sq, int(W)) for al, classes, rw, sq, W in zip(
+        parse_align_records(host, cap_len), strings, plan.rws, plan.squeezed, plan.desc[:, 2])]
 
 
 class PendingReading:
@@ -2137,52 +2302,19 @@ class PendingReading:
     locate=True: `locations()`, one LineLocation per line; the alignment lies behind the decode part of every record row, and `lp`
     (with keep_lp) holds the float64 log-soft-max it ran on."""
 
-    def __init__(self, host, event, cap, plan, logits=None, nbest=None, lexicon=None, scores=None, words=False, lp=None, lm=False,
-                 lexicons=None, pattern=None, align=None):
-        self._align = align                                          # (rec_at, cap_len, (len_at, cls_at, gate_at), alphabet): locate=True
-        self._located = None
-        self._pattern = pattern                                      # a Pattern: beam records with the format's mass behind them
-        self._lm = bool(lm)                                          # beam records with a language-model term
-        self._lexicons = lexicons                                    # a LineLexicons: lexicon records, words of every line's own list
-        self._host, self._event, self._cap, self._plan, self.logits, self._out = host, event, cap, plan, logits, None
-        self._nbest = nbest                                          # None: greedy records
-        self._lexicon, self.scores = lexicon, scores                 # a Lexicon: lexicon records
-        self._words, self.lp = bool(words), lp                       # words records (of that Lexicon)
+    def __init__(self, host, event, cap, plan, mode, state, logits=None, align=None):
+        self._host, self._event, self._cap, self._plan, self._mode, self._state = host, event, cap, plan, mode, state
+        self.logits, self.scores, self.lp = logits, state.scores, state.lp
+        self._align = align                                          # (rec_at, cap_len) of the align part of a row: locate=True
+        self._out, self._located = None, None
 
     def result(self):
         if self._out is None:
             if self._host is None:
                 self._out = []
-            elif self._words:
-                self._event.synchronize()
-                self._out = [_words_reading(d, self._lexicon, rw, sq, int(W)) for d, rw, sq, W in zip(
-                    parse_words_records(self._host, self._cap), self._plan.rws, self._plan.squeezed, self._plan.desc[:, 2])]
-            elif self._nbest is None:
-                self._event.synchronize()
-                self._out = [_reading(d, rw, sq) for d, rw, sq in zip(parse_records(self._host, self._cap), self._plan.rws,
-                                                                       self._plan.squeezed)]
-            elif self._lexicons is not None:
-                self._event.synchronize()
-                self._out = [_line_lexicon_reading(d, ws, rw, sq) for d, ws, rw, sq in zip(
-                    parse_lexicon_records(self._host, self._nbest), self._lexicons.lists, self._plan.rws, self._plan.squeezed)]
-            elif self._lexicon is not None:
-                self._event.synchronize()
-                self._out = [_lexicon_reading(d, self._lexicon, rw, sq) for d, rw, sq in zip(
-                    parse_lexicon_records(self._host, self._nbest), self._plan.rws, self._plan.squeezed)]
-            elif self._pattern is not None:
-                self._event.synchronize()
-                at = beam_record_words(self._cap, self._nbest)
-                self._out = [_pattern_reading(d, m, self._pattern.alphabet, rw, sq) for d, m, rw, sq in zip(
-                    parse_beam_records(self._host, self._cap, self._nbest), parse_pattern_mass(self._host[:, at:]), self._plan.rws,
-                    self._plan.squeezed)]
-            elif self._lm:
-                self._event.synchronize()
-                self._out = [_beam_lm_reading(d, rw, sq) for d, rw, sq in zip(
-                    parse_beam_lm_records(self._host, self._cap, self._nbest), self._plan.rws, self._plan.squeezed)]
             else:
                 self._event.synchronize()
-                self._out = [_beam_reading(d, rw, sq) for d, rw, sq in zip(parse_beam_records(self._host, self._cap, self._nbest),
-                                                                            self._plan.rws, self._plan.squeezed)]
+                self._out = self._mode.readings(self._host, self._cap, self._plan, self._state)
         return self._out
 
     def texts(self):
@@ -2201,16 +2333,12 @@ class PendingReading:
         if self._located is not None:
             return self._located
         self._event.synchronize()
-        rec_at, cap_len, (len_at, cls_at, gate_at), alphabet = self._align
-        rows = self._host.tolist()
-        als = parse_align_records(self._host[:, rec_at:rec_at + align_record_words(cap_len)], cap_len)
-        out = []
-        for row, al, rw, sq, W in zip(rows, als, self._plan.rws, self._plan.squeezed, self._plan.desc[:, 2]):
-            stated = al.flag != 1 and (gate_at < 0 or row[gate_at] >= 1) and 0 <= row[len_at] <= self._cap
-            classes = row[cls_at:cls_at + row[len_at]] if stated else []
-            out.append(_location(al, classes, alphabet, rw, sq, int(W)))
-        self._located = out
-        return out
+        (rec_at, cap_len), (len_at, cls_at, gate_at) = self._align, self._mode.align_source(self._cap)
+        strings = [row[cls_at:cls_at + row[len_at]] if (gate_at < 0 or row[gate_at] >= 1) and 0 <= row[len_at] <= self._cap else []
+                   for row in self._host.tolist()]
+        self._located = _locations(self._host[:, rec_at:rec_at + align_record_words(cap_len)], cap_len, self._plan, self._mode.alphabet,
+                                   strings)
+        return self._located
 
 
 class PendingAlignment:
@@ -2228,9 +2356,7 @@ class PendingAlignment:
                 self._out = []
             else:
                 self._event.synchronize()
-                self._out = [_location(al, classes if al.flag != 1 else [], self._alphabet, rw, sq, int(W)) for al, classes, rw, sq, W in zip(
-                    parse_align_records(self._host, self._cap_len), self._strings, self._plan.rws, self._plan.squeezed,
-                    self._plan.desc[:, 2])]
+                self._out = _locations(self._host, self._cap_len, self._plan, self._alphabet, self._strings)
         return self._out
 
 
@@ -2309,67 +2435,11 @@ class LineReader:
                  keep_lp: bool = False, lm=None, lm_weight=None, lm_bonus=None, pattern=None, locate: bool = False):
         from . import functional as Fh
         from .infer import _check_module, _crnn_folds
-        if decode not in ("greedy", "beam", "lexicon", "words", "lexicons"):
-            raise ValueError("LineReader: decode is 'greedy', 'beam', 'lexicon', 'words' or 'lexicons'; got %r" % (decode,))
-        if locate and decode not in ("greedy", "beam"):
-            raise ValueError("LineReader: locate=True goes with decode='greedy' or decode='beam' (their records hold the classes of "
-                             "the string; those of %r hold word indices)" % (decode,))
-        self.locate = bool(locate)
-        word_penalty = _check_penalty("LineReader", word_penalty)
-        if decode != "words" and word_penalty != 0.0:
-            raise ValueError("LineReader: word_penalty= goes with decode='words'; got decode = %r" % (decode,))
-        if decode == "lexicons":
-            _check_nbest("LineReader", nbest)
-            if lexicon is not None:
-                raise ValueError("LineReader: lexicon= goes with decode='lexicon' or decode='words'; decode='lexicons' takes the lists "
-                                 "of a call as read(..., lexicons=)")
-        elif decode in ("lexicon", "words"):
-            if decode == "lexicon":
-                _check_nbest("LineReader", nbest)
-            if lexicon is None:
-                raise ValueError("LineReader: decode=%r needs lexicon=, a Lexicon or a list of words" % (decode,))
-            lexicon = lexicon if isinstance(lexicon, Lexicon) else Lexicon(lexicon)
-            emits = _emitted_classes(crnn)
-            if emits is not None and lexicon.n_classes > emits:
-                raise ValueError("LineReader: the lexicon's alphabet has %d classes, the CRNN emits %d" % (lexicon.n_classes, emits))
-            if decode == "words":
-                _check_lanes("LineReader", lexicon)
-        else:
-            _check_beam("LineReader", beam, nbest, beam_limits()["beam"])
-            if lexicon is not None:
-                raise ValueError("LineReader: lexicon= goes with decode='lexicon' or decode='words'; got decode = %r" % (decode,))
-        if lm is None:
-            if lm_weight is not None or lm_bonus is not None:
-                raise ValueError("LineReader: lm_weight= and lm_bonus= go with lm=, a CharLM")
-            table, self.lm_weight, self.lm_bonus = None, None, None
-        else:
-            if decode != "beam":
-                raise ValueError("LineReader: lm= goes with decode='beam'; got decode = %r" % (decode,))
-            if not isinstance(lm, CharLM):
-                raise ValueError("LineReader: lm is a CharLM; got %r" % (type(lm).__name__,))
-            emits = _emitted_classes(crnn)
-            if emits is not None and lm.n_classes != emits:
-                raise ValueError("LineReader: the language model has %d classes, the CRNN emits %d" % (lm.n_classes, emits))
-            try:
-                self.lm_weight, self.lm_bonus = 0.5 if lm_weight is None else float(lm_weight), 0.0 if lm_bonus is None else float(lm_bonus)
-                table = lm.increments(self.lm_weight, self.lm_bonus)
-            except (TypeError, ValueError):
-                raise ValueError("LineReader: lm_weight and lm_bonus are finite floats; got %r, %r" % (lm_weight, lm_bonus)) from None
-        if pattern is not None:
-            if decode != "beam":
-                raise ValueError("LineReader: pattern= goes with decode='beam'; got decode = %r" % (decode,))
-            if lm is not None:
-                raise ValueError("LineReader: pattern= and lm= do not go together")
-            pattern = _as_pattern("LineReader", pattern)             # (a pattern beyond the limits is refused where it is compiled)
-            emits = _emitted_classes(crnn)
-            if emits is None:                                        # (the table is uploaded here, once, for the classes of the logits)
-                raise ValueError("LineReader: pattern= needs a CRNN that states the classes it emits (rnn[-1].embedding.out_features)")
-            if pattern.n_classes > emits:
-                raise ValueError("LineReader: the pattern's alphabet has %d classes, the CRNN emits %d" % (pattern.n_classes, emits))
-            _check_pattern("LineReader", pattern, pattern.n_classes)
-        self.lm, self.pattern = lm, pattern
-        self.decode, self.beam, self.nbest, self.lexicon, self.keep_scores = decode, beam, nbest, lexicon, bool(keep_scores)
-        self.word_penalty, self.keep_lp = word_penalty, bool(keep_lp)
+        emits = _emitted_classes(crnn)
+        mode = _reader_decoding(decode, beam, nbest, lexicon, word_penalty, lm, lm_weight, lm_bonus, pattern, locate, emits)
+        self._mode, self.decode, self.locate, self.keep_scores, self.keep_lp = mode, decode, bool(locate), bool(keep_scores), bool(keep_lp)
+        self.beam, self.nbest, self.lexicon, self.word_penalty, self.pattern = beam, nbest, mode.lexicon, mode.word_penalty, mode.pattern
+        self.lm, self.lm_weight, self.lm_bonus = lm, mode.lm_weight, mode.lm_bonus
         _check_module(crnn, "reader CRNN")
         if not (isinstance(batch_size, int) and batch_size > 0):
             raise ValueError("batch_size must be a positive int")
@@ -2379,11 +2449,7 @@ class LineReader:
         if want.type != "cuda" or (want.index is not None and want.index != self.device.index):
             raise ValueError("LineReader: the CRNN lives on %s, not on %s" % (self.device, want))
         self._limits = read_limits()
-        if lexicon is not None:
-            lexicon.device(self.device)                              # (the one upload of the packed words: no `read` makes it)
-        if pattern is not None:
-            pattern.device(self.device, _emitted_classes(crnn))      # (likewise: the table and the accepting states)
-        self._lm_table = None if table is None else torch.from_numpy(table).to(self.device)          # (likewise: the one upload)
+        mode.upload(self.device, emits)                              # (the packed words, the pattern's or the LM's table: once, here)
         with torch.cuda.device(self.device), torch.no_grad():
             Fh.sticky_word(self.device)
             self._folds = _crnn_folds(crnn)
@@ -2445,117 +2511,26 @@ class LineReader:
         """dev_bytes: the uint8 device buffer holding the lines, rows: (byte offset, H, W, pitch) per line (what the `line_canvases` of a
         `PendingExport` of `DeviceExporter.lines` / `.scene` / `.scene_quads` gives), scale: the SR factor -> PendingReading.
         lexicons (decode="lexicons" only, and required there): a `LineLexicons` or one list of words per line, by INPUT index."""
-        import numpy as np
-        rows = list(rows)
+        rows, mode = list(rows), self._mode
         keep = self.keep_logits if keep_logits is None else bool(keep_logits)
         lexicons = self.check_lexicons(lexicons, len(rows))
         if not rows:
-            return PendingReading(None, None, 0, None, [] if keep else None, align=(0, 0, (0, 0, -1), "") if self.locate else None)
-        if not (isinstance(dev_bytes, torch.Tensor) and dev_bytes.dtype == torch.uint8 and dev_bytes.device == self.device and
-                dev_bytes.is_contiguous()):
-            raise ValueError("LineReader.read takes a contiguous uint8 tensor on %s" % (self.device,))
-        plan = read_plan(rows, scale, self.w)
-        n = len(rows)
-        order = [i for _, idx in plan.buckets for i in idx]            # bucket order -> input index: the decode launches' row indices
+            return PendingReading(None, None, 0, None, mode, _ReadState(), [] if keep else None, (0, 0) if self.locate else None)
+        plan = self._lines_plan("LineReader.read", dev_bytes, rows, scale)
         cap = max(rw for rw, _ in plan.buckets) // 4 + 1
-        chunk = min(self.B, READ_CHUNK)
-        kept = [] if keep else None
-        with torch.cuda.device(self.device):
-            self._check_weights()
-            head = torch.empty(n * READ_DESC + n, dtype=torch.int32, pin_memory=True)
-            hn = head.numpy()
-            hn[:n * READ_DESC] = plan.desc.reshape(-1)
-            hn[n * READ_DESC:] = order
-            head_dev = torch.empty(head.numel(), dtype=torch.int32, device=self.device)
-            head_dev.copy_(head, non_blocking=True)
-            luma = torch.empty(plan.floats, dtype=torch.float32, device=self.device)
-            line_luma(dev_bytes, head_dev, plan.desc, luma)
-            beam, lex, wrd, per = self.decode == "beam", self.decode == "lexicon", self.decode == "words", lexicons is not None
-            fused, fmt = beam and self._lm_table is not None, beam and self.pattern is not None
-            words = beam_lm_record_words(cap, self.nbest) if fused else pattern_record_words(cap, self.nbest) if fmt else \
-                beam_record_words(cap, self.nbest) if beam else \
-                lexicon_record_words(self.nbest) if lex or per else \
-                words_record_words(cap) if wrd else 3 * cap + 2
-            kept_scores = [] if (lex or per) and self.keep_scores else None
-            if per:
-                # the union and every chunk's tile table, pairs and counts: ONE int32 blob, one copy from pinned memory
-                packs, parts, at = [], [lexicons.codes, lexicons.table.reshape(-1)], lexicons.codes.size + lexicons.table.size
-                for rw, idx in plan.buckets:                         # (lists go by INPUT index, chunks in bucket order)
-                    for i in range(0, len(idx), chunk):
-                        tiles, pairs, counts = lexicons.pack(idx[i:i + chunk])
-                        packs.append((at, tiles.shape[0], pairs.shape[0], int(counts.max())))
-                        parts += [tiles.reshape(-1), pairs.reshape(-1), counts]
-                        at += tiles.size + pairs.size + counts.size
-                blob = torch.empty(at, dtype=torch.int32, pin_memory=True)
-                blob.numpy()[:] = np.concatenate(parts)
-                blob_dev = torch.empty(at, dtype=torch.int32, device=self.device)
-                blob_dev.copy_(blob, non_blocking=True)
-                u_codes, u_table = blob_dev[:lexicons.codes.size], blob_dev[lexicons.codes.size:packs[0][0]].view(-1, 4)
-                n_chunk = 0
-            kept_lp = [] if (wrd or self.locate) and self.keep_lp else None
-            align = None
-            if self.locate:
-                # the alignment part lies behind the decode part of the same row, at the next even word; the row stride is even
-                rec_at, cap_len = words + (words & 1), min(cap, ALIGN_LENGTH)
-                words = rec_at + align_record_words(cap_len)
-                source = _align_source(cap, self.nbest if beam else None, fused)
-                align = (rec_at, cap_len, source, self.pattern.alphabet if fmt else _alphabet())
-            record = torch.empty(n, words, dtype=torch.int32, device=self.device)
-            index, pos, foff = head_dev[n * READ_DESC:], 0, 0
-            for rw, idx in plan.buckets:
-                x = luma[foff:foff + len(idx) * READ_HEIGHT * rw].view(len(idx), 1, READ_HEIGHT, rw)
-                foff += len(idx) * READ_HEIGHT * rw
-                for i in range(0, len(idx), chunk):
-                    m = min(chunk, len(idx) - i)
-                    logits = self.forward(x[i:i + m])
-                    if fused:
-                        ctc_beam_lm_read(logits, self._lm_table, self.lm.order, index[pos:pos + m], record, cap, self.beam, self.nbest)
-                    elif fmt:
-                        ctc_beam_pattern_read(logits, self.pattern, index[pos:pos + m], record, cap, self.beam, self.nbest)
-                        ctc_pattern_mass(logits, self.pattern, index[pos:pos + m], record[:, beam_record_words(cap, self.nbest):])
-                    elif beam:
-                        ctc_beam_read(logits, index[pos:pos + m], record, cap, self.beam, self.nbest)
-                    elif per:
-                        at, n_tiles, n_pairs, most = packs[n_chunk]
-                        n_chunk += 1
-                        counts = blob_dev[at + 4 * n_tiles + 2 * n_pairs:at + 4 * n_tiles + 2 * n_pairs + m]
-                        scores = torch.empty(m, max(1, most), dtype=torch.float64, device=self.device)
-                        if n_tiles:                                  # (a chunk of empty lists has nothing to score)
-                            ctc_lexicon_score_pairs(logits, u_codes, lexicons.n_codes, u_table, blob_dev[at:at + 4 * n_tiles].view(-1, 4),
-                                                    blob_dev[at + 4 * n_tiles:at + 4 * n_tiles + 2 * n_pairs].view(-1, 2), counts, scores,
-                                                    max(1, most))
-                        ctc_lexicon_select_rows(scores, counts, index[pos:pos + m], record, self.nbest)
-                        if kept_scores is not None:
-                            kept_scores.append((idx[i:i + m], scores, counts))
-                    elif lex:
-                        scores = torch.empty(m, len(self.lexicon), dtype=torch.float64, device=self.device)
-                        ctc_lexicon_score(logits, self.lexicon, scores)
-                        ctc_lexicon_select(scores, index[pos:pos + m], record, self.nbest)
-                        if kept_scores is not None:
-                            kept_scores.append((idx[i:i + m], scores))
-                    elif wrd:
-                        lp = None
-                        if kept_lp is not None:
-                            lp = torch.empty(m, logits.shape[0], logits.shape[2], dtype=torch.float64, device=self.device)
-                            kept_lp.append((idx[i:i + m], lp))
-                        ctc_words_read(logits, self.lexicon, index[pos:pos + m], record, cap, self.word_penalty, lp)
-                    else:
-                        ctc_greedy_read(logits, index[pos:pos + m], record, cap)
-                    if align is not None:                            # ONE more launch: the best string is aligned where the decode left it
-                        lp = None
-                        if kept_lp is not None:
-                            lp = torch.empty(m, logits.shape[0], logits.shape[2], dtype=torch.float64, device=self.device)
-                            kept_lp.append((idx[i:i + m], lp))
-                        ctc_align(logits, index[pos:pos + m], record, *source, record, rec_at, cap_len, lp)
-                    if keep:
-                        kept.append((idx[i:i + m], logits))
-                    pos += m
-            host = torch.empty(n, words, dtype=torch.int32, pin_memory=True)
-            host.copy_(record, non_blocking=True)
-            ev = torch.cuda.Event()
-            ev.record()
-        return PendingReading(host, ev, cap, plan, kept, self.nbest if beam or lex or per else None, self.lexicon if lex or wrd else None,
-                              kept_scores, wrd, kept_lp, fused, lexicons, self.pattern, align)
+        words, align = mode.record_words(cap), None
+        if self.locate:
+            # the alignment part lies behind the decode part of the same row, at the next even word; the row stride is even
+            rec_at, cap_len, source = words + (words & 1), min(cap, ALIGN_LENGTH), mode.align_source(cap)
+            words, align = rec_at + align_record_words(cap_len), (rec_at, cap_len)
+
+        def each(state, logits, index, record, lines):
+            mode.launch(logits, index, record, cap, lines, state)
+            if align is not None:                                    # ONE more launch: the best string is aligned where the decode left it
+                ctc_align(logits, index, record, *source, record, rec_at, cap_len, _lp_buffer(state.lp, lines, logits))
+        host, ev, kept, state = self._enqueue(dev_bytes, plan, None, words, keep,
+                                              lambda tail: mode.begin(self, plan, self._chunk, lexicons), each)
+        return PendingReading(host, ev, cap, plan, mode, state, kept, align)
 
     def align(self, dev_bytes, rows, scale, texts, keep_logits=None) -> "PendingAlignment":
         """Aligns KNOWN strings, one per line (a ground-truth label, a corrected reading): dev_bytes, rows, scale as `read` takes them,
@@ -2578,44 +2553,58 @@ class LineReader:
                     raise ValueError("LineReader.align: line %d: the text %r has the character %r, which the alphabet %r lacks"
                                      % (i, t, ch, alphabet[1:]))
             strings.append([a2d[ch] for ch in t])
+        kept_lp = [] if self.keep_lp else None
         if not rows:
-            return PendingAlignment(None, None, 0, None, [], alphabet, [] if keep else None, [] if self.keep_lp else None)
+            return PendingAlignment(None, None, 0, None, [], alphabet, [] if keep else None, kept_lp)
+        plan = self._lines_plan("LineReader.align", dev_bytes, rows, scale)
+        cap_len = max(len(s) for s in strings)
+
+        def each(src, logits, index, record, lines):
+            ctc_align(logits, index, src, 0, 2, -1, record, 0, cap_len, _lp_buffer(kept_lp, lines, logits))
+        host, ev, kept, _ = self._enqueue(dev_bytes, plan, pack_strings(strings, cap_len), align_record_words(cap_len), keep,
+                                          lambda tail: tail.view(len(rows), 2 + cap_len), each)
+        return PendingAlignment(host, ev, cap_len, plan, strings, alphabet, kept, kept_lp)
+
+    # -- the one chunk loop ----------------------------------------------------------------------------------------------------------
+    _chunk = property(lambda self: min(self.B, READ_CHUNK))          # most lines of one forward
+
+    def _lines_plan(self, who, dev_bytes, rows, scale):
         if not (isinstance(dev_bytes, torch.Tensor) and dev_bytes.dtype == torch.uint8 and dev_bytes.device == self.device and
                 dev_bytes.is_contiguous()):
-            raise ValueError("LineReader.align takes a contiguous uint8 tensor on %s" % (self.device,))
-        plan = read_plan(rows, scale, self.w)
-        n = len(rows)
-        order = [i for _, idx in plan.buckets for i in idx]
-        cap_len = max(len(s) for s in strings)
-        table = pack_strings(strings, cap_len)
-        chunk = min(self.B, READ_CHUNK)
-        kept, kept_lp = [] if keep else None, [] if self.keep_lp else None
+            raise ValueError("%s takes a contiguous uint8 tensor on %s" % (who, self.device))
+        return read_plan(rows, scale, self.w)
+
+    def _enqueue(self, dev_bytes, plan, extra, words, keep, begin, each):
+        """What `read` and `align` enqueue on the current stream: the pinned head (the descriptor rows, every line's record row in bucket
+        order, then `extra`: int32 words of the caller's, or None) and its one copy, the luma launch, `begin(extra on the device)` ->
+        the call's state, per bucket chunk the forward and `each(state, logits, the record rows of the chunk, the (n, words) record,
+        the line indices of the chunk)`, then the record's one copy to pinned memory and an event.  Nothing waits for the device.
+        -> (the host record, the event, [(line indices, logits)] per chunk or None, the state)"""
+        n = int(plan.desc.shape[0])
+        order = [i for _, idx in plan.buckets for i in idx]          # bucket order -> input index: the launches' row indices
+        chunk, kept, at = self._chunk, [] if keep else None, n * READ_DESC + n
         with torch.cuda.device(self.device):
             self._check_weights()
-            head = torch.empty(n * READ_DESC + n + table.size, dtype=torch.int32, pin_memory=True)
+            head = torch.empty(at + (0 if extra is None else extra.size), dtype=torch.int32, pin_memory=True)
             hn = head.numpy()
             hn[:n * READ_DESC] = plan.desc.reshape(-1)
-            hn[n * READ_DESC:n * READ_DESC + n] = order
-            hn[n * READ_DESC + n:] = table.reshape(-1)
+            hn[n * READ_DESC:at] = order
+            if extra is not None:
+                hn[at:] = extra.reshape(-1)
             head_dev = torch.empty(head.numel(), dtype=torch.int32, device=self.device)
             head_dev.copy_(head, non_blocking=True)
             luma = torch.empty(plan.floats, dtype=torch.float32, device=self.device)
             line_luma(dev_bytes, head_dev, plan.desc, luma)
-            words = align_record_words(cap_len)
+            state = begin(head_dev[at:])
             record = torch.empty(n, words, dtype=torch.int32, device=self.device)
-            index, src = head_dev[n * READ_DESC:n * READ_DESC + n], head_dev[n * READ_DESC + n:].view(n, 2 + cap_len)
-            pos, foff = 0, 0
+            index, pos, foff = head_dev[n * READ_DESC:at], 0, 0
             for rw, idx in plan.buckets:
                 x = luma[foff:foff + len(idx) * READ_HEIGHT * rw].view(len(idx), 1, READ_HEIGHT, rw)
                 foff += len(idx) * READ_HEIGHT * rw
                 for i in range(0, len(idx), chunk):
                     m = min(chunk, len(idx) - i)
                     logits = self.forward(x[i:i + m])
-                    lp = None
-                    if kept_lp is not None:
-                        lp = torch.empty(m, logits.shape[0], logits.shape[2], dtype=torch.float64, device=self.device)
-                        kept_lp.append((idx[i:i + m], lp))
-                    ctc_align(logits, index[pos:pos + m], src, 0, 2, -1, record, 0, cap_len, lp)
+                    each(state, logits, index[pos:pos + m], record, idx[i:i + m])
                     if keep:
                         kept.append((idx[i:i + m], logits))
                     pos += m
@@ -2623,4 +2612,4 @@ class LineReader:
             host.copy_(record, non_blocking=True)
             ev = torch.cuda.Event()
             ev.record()
-        return PendingAlignment(host, ev, cap_len, plan, strings, alphabet, kept, kept_lp)
+        return host, ev, kept, state
