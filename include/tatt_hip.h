@@ -950,8 +950,8 @@ int tatt_quad_limits(int* out);
  * its last seam (k <= n - 2), Wd > 0, 0 <= gy < 256 H, gx >= 0 (k = 0) and gx < 256 [1] (k = n - 1), with X, Y, Wd, gx, gy as
  * tatt_warp_u8 states them.  The sample: gxg = gx + 256 [0], fx = gxg - 128, fy = gy - 128, the four taps clamped to the (H, W) line, the
  * bilinear sum of tatt_warp_u8; with F > 0, d = min(xi, W - 1 - xi, yi, H - 1 - yi) for xi = clamp(gxg >> 8, 0, W - 1), yi = gy >> 8 and
- * the blend of tatt_warp_u8.  All in 64-bit integers.  src and dst may be one buffer; the target rectangles of one launch must be
- * disjoint and must not overlap a line.  items_host / strips_host: the same rows in HOST memory, read before the launch only to refuse:
+ * the blend of tatt_warp_u8 (one text for both entries: csrc/warp_pixel.h).  All in 64-bit integers.  src and dst may be one buffer;
+ * the target rectangles of one launch must be disjoint and must not overlap a line.  items_host / strips_host: the same rows in HOST memory, read before the launch only to refuse:
  * 1 bad arguments, a reserved word or a negative feather, 2 a geometry beyond tatt_poly_limits (a side, the feather, the strip count, a
  * strip's columns outside the line, more than 65535 items), 3 a line or target rectangle that leaves src (src_bytes) / dst (dst_bytes),
  * 4 an item whose strip rows leave the table of n_strips rows.  The kernel reads only device memory (the launch can be captured),

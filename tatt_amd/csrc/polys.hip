@@ -10,12 +10,12 @@
 //                         neighbouring strip's columns), the feather against the line's sides, the store.  Two neighbouring strips
 //                         evaluate the same integers for the seam they share, so every pixel between the outer sides belongs to exactly
 //                         one strip.
-// All of it is 64-bit integer arithmetic (csrc/poly_pixel.h: the same text runs on the host), no floating point, no LDS, no atomics, no
+// All of it is 64-bit integer arithmetic (csrc/warp_pixel.h: the same text runs on the host), no floating point, no LDS, no atomics, no
 // traffic between work-groups; the item and strip rows are indexed by the block and by a uniform loop counter alone.  Every quantity is read
 // from DEVICE memory (the launch can be captured); the same check runs on the host before the launch and in the kernel, every tap is
 // clamped, every store lies in a rectangle the check accepted.
 #include "common.h"
-#include "poly_pixel.h"
+#include "warp_pixel.h"
 
 #define PLY_THREADS 256
 
@@ -27,7 +27,7 @@ __global__ __launch_bounds__(PLY_THREADS) void poly_paste_u8_kernel(const unsign
     // a replayed launch re-checks: nothing is written for an item the host entry would have refused
     if (ply_check(d, strips, n_strips, src_bytes, dst_bytes) != 0) return;
     int i, j;
-    if (!ply_place(blockIdx.x, (int)threadIdx.x, d[5], d[6], &i, &j)) return;
+    if (!warp_place(blockIdx.x, (int)threadIdx.x, d[5], d[6], &i, &j)) return;
     ply_pixel(d, strips + (long)d[9] * PLY_STRIP_DESC, src_base + d[0], i, j, dst_base + d[4] + i * (long)d[7] + j * 3L);
 }
 
@@ -37,13 +37,13 @@ TATT_API int tatt_poly_paste_u8(const unsigned char* src, long src_bytes, const 
     if (!src || !items || !items_host || !strips || !strips_host || !dst || n_items <= 0 || n_strips <= 0 || src_bytes <= 0 ||
         dst_bytes <= 0)
         return 1;
-    if (n_items > PLY_MAX_ITEMS) return 2;
+    if (n_items > WARP_MAX_ITEMS) return 2;
     long tiles = 0;
     for (int i = 0; i < n_items; ++i) {
         const int* d = items_host + (long)i * PLY_DESC;
         const int rc = ply_check(d, strips_host, n_strips, src_bytes, dst_bytes);
         if (rc) return rc;
-        const long t = ply_tiles(d[5], d[6]);
+        const long t = warp_tiles(d[5], d[6]);
         if (t > tiles) tiles = t;
     }
     if (tiles > 0x7fffffffL) return 2;
@@ -54,11 +54,11 @@ TATT_API int tatt_poly_paste_u8(const unsigned char* src, long src_bytes, const 
 
 TATT_API int tatt_poly_limits(int* out) {
     if (!out) return 1;
-    out[0] = PLY_TH;
-    out[1] = PLY_TW;
-    out[2] = PLY_MAX_ITEMS;
-    out[3] = PLY_MAX_SIDE;
-    out[4] = PLY_MAX_FEATHER;
+    out[0] = WARP_TH;
+    out[1] = WARP_TW;
+    out[2] = WARP_MAX_ITEMS;
+    out[3] = WARP_MAX_SIDE;
+    out[4] = WARP_MAX_FEATHER;
     out[5] = PLY_DESC;
     out[6] = PLY_STRIP_DESC;
     out[7] = PLY_MAX_STRIPS;

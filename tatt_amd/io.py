@@ -1119,13 +1119,38 @@ class DeviceExporter(_Limits):
         return self._enqueue([], nbytes, views, head=head, launch=lambda base, hbase, pix: blend(base, hbase, o_starts, pix),
                              canvases=canvases)
 
-    def _scene(self, who, scene_dev, sr_windows, lines, scale, c0):
-        """what `scene` and `scene_quads` (`who`) share in front of their paste plans: the check of the scene tensor and the blend of
-        the lines -> (Hs, Ws), then what `_blend` returns"""
+    def _scene_paste(self, who, scene_dev, sr_windows, lines, scale, c0, make_plan, tables, paste) -> PendingExport:
+        """What `scene`, `scene_quads` and `scene_polys` (`who`) share, which is everything but their plans and their paste launches:
+        the check of the scene tensor, the ONE tatt_line_blend launch of the lines, plan = make_plan((Ws, Hs), blend rows, blend bytes,
+        H), the tables staged behind the blend's (tables(plan): the resize rows first), the ONE tatt_resize_u8 launch of the background,
+        where the plan has `rects` the ONE tatt_resize_u8 launch of all lines into them, then per layer paste(out, nbytes, row, offs, r,
+        c): the launch of the layer's c items from item r on, row(o) the (device, host) pointers of word o of the tables, offs the word
+        offsets of `tables(plan)`; ONE copy back."""
+        import ctypes
+        from . import ops
+        from .scene import RESIZE_DESC
         if not (isinstance(scene_dev, torch.Tensor) and scene_dev.dim() == 3 and scene_dev.shape[2] == 3 and
                 scene_dev.dtype == torch.uint8 and scene_dev.is_contiguous() and scene_dev.device.type == "cuda"):
             raise ValueError("DeviceExporter.%s takes the contiguous (Hs, Ws, 3) uint8 scene on the device" % who)
-        return (int(scene_dev.shape[0]), int(scene_dev.shape[1])), *self._blend(sr_windows, list(lines), scale, c0)
+        Hs, Ws = int(scene_dev.shape[0]), int(scene_dev.shape[1])
+        (bdesc, starts, bbytes, H), canvases, blend = self._blend(sr_windows, list(lines), scale, c0)
+        plan = make_plan((Ws, Hs), bdesc, bbytes, H)
+        head, (_, o_starts, *offs) = _tables(bdesc, starts, *tables(plan))
+        views = [(plan.canvas_off, scale * Hs, scale * Ws, plan.pitch, None)]
+        nbytes, src_bytes, n = plan.nbytes, Hs * Ws * 3, len(plan.order)
+
+        def launch(base, hbase, pix):
+            out = ctypes.c_void_p(base + pix)
+            blend(base, hbase, o_starts, pix)
+            row = lambda o: _ptrs(base, hbase, o * 4)
+            ops.call("tatt_resize_u8", ops.P(scene_dev), src_bytes, *row(offs[0]), 1, out, nbytes, ops.stream())
+            if n and hasattr(plan, "rects"):                           # the line canvases lie in front of the rectangles, in the same buffer
+                ops.call("tatt_resize_u8", out, max(bbytes, 1), *row(offs[0] + RESIZE_DESC), n, out, plan.canvas_off, ops.stream())
+            r = 0
+            for c in plan.counts:                                      # what a layer reads lies in front of the canvas
+                paste(plan, out, row, offs, r, c)
+                r += c
+        return self._enqueue([], nbytes, views, head=head, launch=launch, canvases=canvases)
 
     def scene(self, scene_dev, sr_windows, lines, boxes, scale: int, feather: int = 0, c0: int = 0) -> PendingExport:
         """The finished scene: scene_dev: the (Hs, Ws, 3) uint8 scene on the device (`DeviceCollator.scene_windows`), sr_windows
@@ -1136,25 +1161,15 @@ class DeviceExporter(_Limits):
         canvases that stay on the device, ONE tatt_resize_u8 launch up-scales the scene into the canvas, ONE tatt_resize_u8 launch per
         layer (`scene_layers`: boxes that do not intersect share a launch) resizes the line canvases into their rectangles, feathered
         against what the canvas holds, and ONE non-blocking copy brings the buffer into the pinned slot.  Never waits for the device."""
-        import ctypes
         from . import ops
         from .scene import RESIZE_DESC
-        (Hs, Ws), (bdesc, starts, bbytes, H), canvases, blend = self._scene("scene", scene_dev, sr_windows, lines, scale, c0)
-        plan = paste_plan((Ws, Hs), list(boxes), bdesc, bbytes, scale, H, feather, self._lim(scene_limits))
-        head, (_, o_starts, o_rows) = _tables(bdesc, starts, plan.rows)
-        views = [(plan.canvas_off, scale * Hs, scale * Ws, plan.pitch, None)]
-        nbytes, src_bytes = plan.nbytes, Hs * Ws * 3
 
-        def launch(base, hbase, pix):
-            out = ctypes.c_void_p(base + pix)
-            blend(base, hbase, o_starts, pix)
-            row = lambda r: _ptrs(base, hbase, (o_rows + r * RESIZE_DESC) * 4)
-            ops.call("tatt_resize_u8", ops.P(scene_dev), src_bytes, *row(0), 1, out, nbytes, ops.stream())
-            r = 1
-            for n in plan.counts:                                      # the line canvases lie in front of the canvas, in the same buffer
-                ops.call("tatt_resize_u8", out, plan.canvas_off, *row(r), n, out, nbytes, ops.stream())
-                r += n
-        return self._enqueue([], nbytes, views, head=head, launch=launch, canvases=canvases)
+        def paste(plan, out, row, offs, r, c):                         # the line canvases lie in front of the canvas, in the same buffer
+            ops.call("tatt_resize_u8", out, plan.canvas_off, *row(offs[0] + (1 + r) * RESIZE_DESC), c, out, plan.nbytes, ops.stream())
+        return self._scene_paste("scene", scene_dev, sr_windows, lines, scale, c0,
+                                 lambda size, bdesc, bbytes, H: paste_plan(size, list(boxes), bdesc, bbytes, scale, H, feather,
+                                                                           self._lim(scene_limits)),
+                                 lambda plan: (plan.rows,), paste)
 
     def scene_quads(self, scene_dev, sr_windows, lines, quads, scale: int, feather: int = 0, c0: int = 0) -> PendingExport:
         """`scene` for quadrilateral boxes: scene_dev: the (Hs, Ws, 3) uint8 scene on the device (`DeviceCollator.quad_windows`),
@@ -1166,30 +1181,15 @@ class DeviceExporter(_Limits):
         (scale * bh, scale * bw) rectangles (in the output buffer, in front of the canvas), ONE tatt_warp_u8 launch per layer
         (`quad_layers`: quads whose bounding boxes do not intersect share a launch) warps the rectangles into their quads, feathered
         against what the canvas holds, and ONE non-blocking copy brings the buffer into the pinned slot.  Never waits for the device."""
-        import ctypes
         from . import ops
         from .quads import QUAD_DESC
-        from .scene import RESIZE_DESC
-        (Hs, Ws), (bdesc, starts, bbytes, H), canvases, blend = self._scene("scene_quads", scene_dev, sr_windows, lines, scale, c0)
-        quads = list(quads)
-        plan = quad_paste_plan((Ws, Hs), quads, bdesc, bbytes, scale, H, feather, self._lim(scene_limits), self._lim(quad_limits))
-        head, (_, o_starts, o_rows, o_warp) = _tables(bdesc, starts, plan.resize, plan.warp)
-        views = [(plan.canvas_off, scale * Hs, scale * Ws, plan.pitch, None)]
-        nbytes, src_bytes, n = plan.nbytes, Hs * Ws * 3, len(quads)
 
-        def launch(base, hbase, pix):
-            out = ctypes.c_void_p(base + pix)
-            blend(base, hbase, o_starts, pix)
-            row = lambda o: _ptrs(base, hbase, o * 4)
-            ops.call("tatt_resize_u8", ops.P(scene_dev), src_bytes, *row(o_rows), 1, out, nbytes, ops.stream())
-            if n:                                                      # the line canvases lie in front of the rectangles, in the same buffer
-                ops.call("tatt_resize_u8", out, max(bbytes, 1), *row(o_rows + RESIZE_DESC), n, out, plan.canvas_off, ops.stream())
-            r = 0
-            for c in plan.counts:                                      # the rectangles lie in front of the canvas
-                ops.call("tatt_warp_u8", out, plan.canvas_off, *row(o_warp + r * QUAD_DESC), c, out, nbytes, ops.stream())
-                r += c
-        return self._enqueue([], nbytes, views, head=head, launch=launch, canvases=canvases)
-
+        def paste(plan, out, row, offs, r, c):                         # the rectangles lie in front of the canvas
+            ops.call("tatt_warp_u8", out, plan.canvas_off, *row(offs[1] + r * QUAD_DESC), c, out, plan.nbytes, ops.stream())
+        return self._scene_paste("scene_quads", scene_dev, sr_windows, lines, scale, c0,
+                                 lambda size, bdesc, bbytes, H: quad_paste_plan(size, list(quads), bdesc, bbytes, scale, H, feather,
+                                                                                self._lim(scene_limits), self._lim(quad_limits)),
+                                 lambda plan: (plan.resize, plan.warp), paste)
 
     def scene_polys(self, scene_dev, sr_windows, lines, polys, scale: int, feather: int = 0, c0: int = 0) -> PendingExport:
         """`scene_quads` for polygons of 2 N points (curved text): scene_dev, sr_windows and lines as `DeviceCollator.poly_windows` and
@@ -1198,30 +1198,17 @@ class DeviceExporter(_Limits):
         launches of `scene_quads` with ONE tatt_poly_paste_u8 launch per layer (`poly_layers`) in place of its tatt_warp_u8 launches:
         every pixel of a polygon's bounding box is painted by the one strip that claims it, sampled from the whole line, feathered
         against the line's outer sides only.  Never waits for the device."""
-        import ctypes
         from . import ops
         from .polys import POLY_DESC
-        from .scene import RESIZE_DESC
-        (Hs, Ws), (bdesc, starts, bbytes, H), canvases, blend = self._scene("scene_polys", scene_dev, sr_windows, lines, scale, c0)
-        polys = list(polys)
-        plan = poly_paste_plan((Ws, Hs), polys, bdesc, bbytes, scale, H, feather, self._lim(scene_limits), self._lim(poly_limits))
-        head, (_, o_starts, o_rows, o_items, o_strips) = _tables(bdesc, starts, plan.resize, plan.items, plan.strips)
-        views = [(plan.canvas_off, scale * Hs, scale * Ws, plan.pitch, None)]
-        nbytes, src_bytes, n = plan.nbytes, Hs * Ws * 3, len(polys)
 
-        def launch(base, hbase, pix):
-            out = ctypes.c_void_p(base + pix)
-            blend(base, hbase, o_starts, pix)
-            row = lambda o: _ptrs(base, hbase, o * 4)
-            ops.call("tatt_resize_u8", ops.P(scene_dev), src_bytes, *row(o_rows), 1, out, nbytes, ops.stream())
-            if n:                                                      # the line canvases lie in front of the rectangles, in the same buffer
-                ops.call("tatt_resize_u8", out, max(bbytes, 1), *row(o_rows + RESIZE_DESC), n, out, plan.canvas_off, ops.stream())
-            r = 0
-            for c in plan.counts:                                      # the rectangles lie in front of the canvas; ONE strip table
-                ops.call("tatt_poly_paste_u8", out, plan.canvas_off, *row(o_items + r * POLY_DESC), c, *row(o_strips), len(plan.strips),
-                         out, nbytes, ops.stream())
-                r += c
-        return self._enqueue([], nbytes, views, head=head, launch=launch, canvases=canvases)
+        def paste(plan, out, row, offs, r, c):                         # the rectangles lie in front of the canvas; ONE strip table
+            ops.call("tatt_poly_paste_u8", out, plan.canvas_off, *row(offs[1] + r * POLY_DESC), c, *row(offs[2]), len(plan.strips),
+                     out, plan.nbytes, ops.stream())
+        return self._scene_paste("scene_polys", scene_dev, sr_windows, lines, scale, c0,
+                                 lambda size, bdesc, bbytes, H: poly_paste_plan(size, list(polys), bdesc, bbytes, scale, H, feather,
+                                                                                self._lim(scene_limits), self._lim(poly_limits)),
+                                 lambda plan: (plan.resize, plan.items, plan.strips), paste)
+
 
 from .lines import (LINE_MAX_WL, Line, blend_plan, blend_windows_host, line_limits, line_plan, line_windows_host, lines_fill,  # noqa: E402,F401
                     lines_plan, super_resolve_lines_host)

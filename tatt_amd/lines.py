@@ -146,6 +146,51 @@ def _super_resolve_boxes_host(windows_host, compose_host, what, scene, boxes, ru
     return compose_host(scene, boxes, images, scale, feather)
 
 
+def _region_windows_host(regions, crop, lr_size, stride, mask):
+    """`scene_windows_host`, `quad_windows_host` and `poly_windows_host` around crop(region), the RGB PIL crop of one checked region:
+    -> (stack, lines), the concatenation of `line_windows_host(crop, ...)` over the regions and lines[k] = Line(wl, starts, first window
+    index) of region k"""
+    import torch
+    h, w = lr_size
+    parts, lines, first = [], [], 0
+    for region in regions:
+        image = crop(region)
+        wl, starts = line_plan(image.size, lr_size, stride)
+        parts.append(line_windows_host(image, lr_size, stride, mask))
+        lines.append(Line(wl, starts, first))
+        first += len(starts)
+    stack = torch.cat(parts) if parts else torch.zeros(0, 3 + int(bool(mask)), h, w)
+    return stack, lines
+
+
+def _scale_check(who, scale):
+    if not (isinstance(scale, int) and not isinstance(scale, bool) and scale >= 1):
+        raise ValueError("%s: scale must be a positive int; got %r" % (who, scale))
+
+
+def _compose_front(what, scene, n, line_images, scale, feather):
+    """`scene_compose_host`, `quad_compose_host` and `poly_compose_host` behind their checks of the regions and the scale, in front of
+    their own pastes; what as `_super_resolve_boxes_host` takes it, n regions -> (canvas, line): the (scale * Hs, scale * Ws, 3) uint8
+    array of the up-scaled scene and line(k, ow, oh), line image k (RGB PIL, or an (H, W, 3) uint8 array) brought to (ow, oh) by PIL
+    bicubic, as an array"""
+    import numpy as np
+    from PIL import Image
+    if not (isinstance(feather, int) and not isinstance(feather, bool) and feather >= 0):
+        raise ValueError("%s: feather must be an int >= 0; got %r" % (what[0], feather))
+    if len(line_images) != n:
+        raise ValueError("%s: %d line images for %d %s" % (what[0], len(line_images), n, what[1]))
+    if scene.mode != "RGB":
+        raise ValueError("%s: an RGB PIL image is taken; got %r" % (what[0], scene.mode))
+    ws, hs = scene.size
+    canvas = np.array(scene if scale == 1 else scene.resize((scale * ws, scale * hs), Image.BICUBIC))
+
+    def line(k, ow, oh):
+        im = line_images[k]
+        im = im if isinstance(im, Image.Image) else Image.fromarray(np.ascontiguousarray(im), "RGB")
+        return np.asarray(im if im.size == (ow, oh) else im.resize((ow, oh), Image.BICUBIC))
+    return canvas, line
+
+
 # ---- host halves of the launches ------------------------------------------------------------------------------------------------------
 def line_limits():
     """tatt_line_limits: {'rows', 'cols', 'wl', 'h', 'w', 'inter_bytes', 'table_bytes', 'windows'} -- the sources the device resampler

@@ -18,6 +18,10 @@ This module is the specification on the host, pure Python / numpy / PIL: integer
 * `poly_limits` / `poly_plan` / `poly_fill` / `poly_paste_plan`: the host halves of the launches (tatt_warp_u8 mode 0 with one row per
   strip, tatt_resize_u8, tatt_scene_windows, tatt_poly_paste_u8).
 
+A quad is the polygon of four points, so what `tatt_amd/quads.py` offers under its `quad_*` names runs the bodies of this module with the
+quad's wording (`_QUAD`): `_check`, `_maps`, `_window_plan`, `_paste_front`.  The projective arithmetic and the pixel rule on arrays
+(`_sample_host`) live in `quads.py`.
+
 Rectifying is `warp_u8_host` (mode 0) per strip with the strip's m_rect into columns [U_k, U_k + w_k) of the crop; the source is the
 scene, so no strip needs its neighbour.
 
@@ -43,15 +47,19 @@ import numbers
 from collections import namedtuple
 from fractions import Fraction
 
-from .lines import Line, _line_takes, _super_resolve_boxes_host, line_limits, line_plan, line_windows_host
-from .quads import (QUAD_DESC, QUAD_MAX_TAPER, _adjugate, _d2, _diag, _homography, _integer, _mul, _r, _resize_takes, _up, _warp_coords,
-                    quad_fill, quad_limits, warp_row, warp_u8_host)
-from .scene import RESIZE_DESC, SCENE_DESC, SCENE_MIN_SIDE, scene_layers, scene_limits
+from .lines import Line, _compose_front, _line_takes, _region_windows_host, _scale_check, _super_resolve_boxes_host, line_limits, line_plan
+from .quads import (QUAD_DESC, QUAD_MAX_TAPER, _adjugate, _d2, _diag, _homography, _integer, _mul, _r, _sample_host, _warp_coords, _words,
+                    quad_bbox, quad_fill, quad_limits, warp_row, warp_u8_host)
+from .scene import RESIZE_DESC, SCENE_DESC, SCENE_MIN_SIDE, _paste_order, _up, scene_layers, scene_limits
 
 POLY_MIN_POINTS = 4       # N = 2: a quad
 POLY_MAX_POINTS = 16      # N = 8: seven strips
 POLY_DESC = 16            # ints per item row of tatt_poly_paste_u8 (include/tatt_hip.h)
 POLY_STRIP_DESC = 32      # ints per strip row
+# how the messages name a kind of region and what it takes: (prefix, a region, its points, the most points, the order of the points)
+_QUAD = ("quads", "quad", "four (x, y) pairs of ints", POLY_MIN_POINTS, "top-left, top-right, bottom-right, bottom-left with y down")
+_POLY = ("polys", "polygon", "an even number of (x, y) pairs of ints, %d to %d" % (POLY_MIN_POINTS, POLY_MAX_POINTS), POLY_MAX_POINTS,
+         "top points in reading direction, then back along the bottom, with y down")
 
 PolyMaps = namedtuple("PolyMaps", "rect paste bbox seams widths bh scale")
 PolyPlan = namedtuple("PolyPlan", "arrays offsets warp resize desc lines upload nbytes out_floats polys")
@@ -88,10 +96,7 @@ def poly_size(poly):
     return sum(poly_columns(poly)[0]), max(_r(_d2(poly[s], poly[2 * n - 1 - s])) for s in range(n))
 
 
-def poly_bbox(poly):
-    """-> (x0, y0, x1, y1), the bounding box of the points"""
-    xs, ys = [p[0] for p in poly], [p[1] for p in poly]
-    return min(xs), min(ys), max(xs), max(ys)
+poly_bbox = quad_bbox     # -> (x0, y0, x1, y1), the bounding box of the points, however many
 
 
 def _cross(a, b, c):
@@ -114,46 +119,65 @@ def poly_check(size, polys, limits=None):
     with opposite sides within QUAD_MAX_TAPER of each other (exactly, on squared lengths) and at least 2 columns; bw and bh at least
     SCENE_MIN_SIDE; no two non-adjacent strips whose interiors overlap (the text may bend but not cross itself); at most
     scene_limits()['boxes'] polygons.  Anything else raises ValueError naming the polygon, and the strip where there is one."""
+    return _check(size, polys, limits, _POLY)
+
+
+def _check(size, regions, limits, kind):
+    """`quad_check` (kind = _QUAD) and `poly_check` (_POLY): a quad is the polygon of four points, named whole where a polygon names
+    its strip, and measured before its taper is looked at (the order of `quad_check`'s messages; the rules are the same: one strip of
+    w_0 = bw >= SCENE_MIN_SIDE columns, and no second strip to cross)"""
+    who, one, points, most, corners = kind
     lim = limits if limits is not None else scene_limits()
     ws, hs = int(size[0]), int(size[1])
     if ws < 1 or hs < 1 or ws > lim["side"] or hs > lim["side"]:
-        raise ValueError("polys: the image is %d x %d; sides from 1 to %d are taken" % (ws, hs, lim["side"]))
-    polys = list(polys)
-    if len(polys) > lim["boxes"]:
-        raise ValueError("polys: %d polygons; at most %d" % (len(polys), lim["boxes"]))
+        raise ValueError("%s: the image is %d x %d; sides from 1 to %d are taken" % (who, ws, hs, lim["side"]))
+    regions = list(regions)
+    if len(regions) > lim["boxes"]:
+        raise ValueError("%s: %d %ss; at most %d" % (who, len(regions), one, lim["boxes"]))
     out = []
-    for k, poly in enumerate(polys):
+    for k, region in enumerate(regions):
         try:
-            ok = all(len(p) == 2 and all(isinstance(v, numbers.Integral) and not isinstance(v, bool) for v in p) for p in poly)
-            count = len(poly)
+            ok = all(len(p) == 2 and all(isinstance(v, numbers.Integral) and not isinstance(v, bool) for v in p) for p in region)
+            count = len(region)
         except TypeError:
             ok, count = False, 0
-        if not ok or count % 2 or not POLY_MIN_POINTS <= count <= POLY_MAX_POINTS:
-            raise ValueError("polys: polygon %d must be an even number of (x, y) pairs of ints, %d to %d; got %r" % (
-                k, POLY_MIN_POINTS, POLY_MAX_POINTS, poly))
-        q = tuple((int(x), int(y)) for x, y in poly)
+        if not ok or count % 2 or not POLY_MIN_POINTS <= count <= most:
+            raise ValueError("%s: %s %d must be %s; got %r" % (who, one, k, points, region))
+        q = tuple((int(x), int(y)) for x, y in region)
         if not all(0 <= x <= ws and 0 <= y <= hs for x, y in q):
-            raise ValueError("polys: polygon %d = %s does not lie in the %d x %d image (0 <= x <= Ws, 0 <= y <= Hs)" % (k, q, ws, hs))
+            raise ValueError("%s: %s %d = %s does not lie in the %d x %d image (0 <= x <= Ws, 0 <= y <= Hs)" % (who, one, k, q, ws, hs))
         strips = poly_strips(q)
-        for n, s in enumerate(strips):
-            if any(_cross(s[i], s[(i + 1) % 4], s[(i + 2) % 4]) <= 0 for i in range(4)):
-                raise ValueError("polys: polygon %d, strip %d = %s is not strictly convex and clockwise (top points in reading direction, "
-                                 "then back along the bottom, with y down)" % (k, n, s))
+        whole = most == POLY_MIN_POINTS
+        name = lambda n: "%s %d = %s" % (one, k, q) if whole else "%s %d, strip %d = %s" % (one, k, n, strips[n])
+
+        def sized():
+            bw, bh = poly_size(q)
+            if bw < SCENE_MIN_SIDE or bh < SCENE_MIN_SIDE:
+                raise ValueError("%s: %s %d = %s rectifies to %d x %d; both sides must be at least SCENE_MIN_SIDE = %d" % (
+                    who, one, k, q, bw, bh, SCENE_MIN_SIDE))
+
+        def tapered(n):
+            s = strips[n]
             for a, b in ((_d2(s[1], s[0]), _d2(s[2], s[3])), (_d2(s[3], s[0]), _d2(s[2], s[1]))):
                 if max(a, b) > QUAD_MAX_TAPER ** 2 * min(a, b):
-                    raise ValueError("polys: polygon %d, strip %d = %s: opposite sides differ by more than QUAD_MAX_TAPER = %d" % (
-                        k, n, s, QUAD_MAX_TAPER))
-        for n, w in enumerate(poly_columns(q)[0]):
-            if w < 2:
-                raise ValueError("polys: polygon %d, strip %d = %s takes %d column; at least 2" % (k, n, strips[n], w))
-        bw, bh = poly_size(q)
-        if bw < SCENE_MIN_SIDE or bh < SCENE_MIN_SIDE:
-            raise ValueError("polys: polygon %d = %s rectifies to %d x %d; both sides must be at least SCENE_MIN_SIDE = %d" % (
-                k, q, bw, bh, SCENE_MIN_SIDE))
+                    raise ValueError("%s: %s: opposite sides differ by more than QUAD_MAX_TAPER = %d" % (who, name(n), QUAD_MAX_TAPER))
+        for n, s in enumerate(strips):
+            if any(_cross(s[i], s[(i + 1) % 4], s[(i + 2) % 4]) <= 0 for i in range(4)):
+                raise ValueError("%s: %s is not strictly convex and clockwise (%s)" % (who, name(n), corners))
+            if not whole:
+                tapered(n)
+        if whole:                                                    # (its one strip has w_0 = bw >= SCENE_MIN_SIDE columns)
+            sized()
+            tapered(0)
+        else:
+            for n, w in enumerate(poly_columns(q)[0]):
+                if w < 2:
+                    raise ValueError("%s: %s takes %d column; at least 2" % (who, name(n), w))
+            sized()
         for n in range(len(strips)):
             for m in range(n + 2, len(strips)):
                 if _interiors_overlap(strips[n], strips[m]):
-                    raise ValueError("polys: polygon %d = %s crosses itself: strip %d and strip %d overlap" % (k, q, n, m))
+                    raise ValueError("%s: %s %d = %s crosses itself: strip %d and strip %d overlap" % (who, one, k, q, n, m))
         out.append(q)
     return out
 
@@ -166,9 +190,13 @@ def poly_matrices(poly, scale: int = 1, rect: bool = True, paste: bool = True):
     the strip's centroid; its gx is local to the strip); bbox = (bx0, by0, bx1, by1); seams[s - 1] = (A, B, C) of E_s for the interior
     seams s = 1 .. N - 2; widths = the w_k.  For N = 2 rect[0] and paste[0] are `quad_matrices`'s.  ValueError when the integers do not
     fit."""
+    return _maps(poly, scale, rect, paste, _POLY)
+
+
+def _maps(poly, scale, rect, paste, kind):
+    """`poly_matrices`, and `quad_matrices` for the polygon of four points (kind = _QUAD: its one strip is named as the quad)"""
     poly = tuple((int(x), int(y)) for x, y in poly)
-    if not (isinstance(scale, int) and not isinstance(scale, bool) and scale >= 1):
-        raise ValueError("polys: scale must be a positive int; got %r" % (scale,))
+    _scale_check(kind[0], scale)
     n = len(poly) // 2
     widths, _ = poly_columns(poly)
     bh = poly_size(poly)[1]
@@ -176,10 +204,10 @@ def poly_matrices(poly, scale: int = 1, rect: bool = True, paste: bool = True):
     s = scale
     half = _diag(Fraction(1, 2), Fraction(1, 2))
     shift = [[Fraction(1), 0, Fraction(s * bx0)], [0, Fraction(1), Fraction(s * by0)], [0, 0, Fraction(1)]]
-    tail = _mul(_mul(_diag(Fraction(1, s), Fraction(1, s)), shift), half)      # (exact arithmetic: `quad_matrices`' product, bracketed anew)
+    tail = _mul(_mul(_diag(Fraction(1, s), Fraction(1, s)), shift), half)
     rects, pastes = [] if rect else None, [] if paste else None
     for k, strip in enumerate(poly_strips(poly)):
-        what = "polygon %s, strip %d" % (poly, k)
+        what = "quad %s" % (poly,) if kind is _QUAD else "polygon %s, strip %d" % (poly, k)
         hf = _homography(strip, widths[k], bh)
         if rect:
             rects.append(_integer(_mul(hf, half), widths[k], bh, bh, widths[k], True, what))
@@ -195,12 +223,22 @@ def poly_matrices(poly, scale: int = 1, rect: bool = True, paste: bool = True):
     return PolyMaps(rects, pastes, (bx0, by0, bx1, by1), seams, widths, bh, s)
 
 
+def _rectify(a, strips, bh):
+    """the (bh, bw, 3) crop of the (matrix, width) strips of a region, side by side"""
+    import numpy as np
+    return np.concatenate([warp_u8_host(a, m, bh, w) for m, w in strips], axis=1)
+
+
+def _rect_strips(poly):
+    """one checked polygon -> the (m_rect, w_k) of its strips"""
+    maps = poly_matrices(poly, 1, paste=False)
+    return list(zip(maps.rect, maps.widths))
+
+
 def poly_rectify_host(scene, poly):
     """RGB PIL image (or an (Hs, Ws, 3) uint8 array), one checked polygon -> the (bh, bw, 3) uint8 rectified crop"""
     import numpy as np
-    a = np.asarray(scene)
-    maps = poly_matrices(poly, 1, paste=False)
-    return np.concatenate([warp_u8_host(a, m, maps.bh, w) for m, w in zip(maps.rect, maps.widths)], axis=1)
+    return _rectify(np.asarray(scene), _rect_strips(poly), poly_size(poly)[1])
 
 
 def _strip_claims(maps, out_h, out_w, H):
@@ -253,7 +291,6 @@ def poly_paste_host(line, maps, dst, feather=None, strips=None):
     if F < 0 or dst.ndim != 3 or dst.shape[2] != 3 or dst.dtype != np.uint8 or dst.shape[0] < 1 or dst.shape[1] < 1:
         raise ValueError("poly_paste_host: dst must be (OH, OW, 3) uint8 and the feather >= 0")
     out_h, out_w = dst.shape[:2]
-    p = line.astype(np.int64)
     old = dst.astype(np.int64)
     done = np.zeros((out_h, out_w), bool)
     start = 0
@@ -265,18 +302,7 @@ def poly_paste_host(line, maps, dst, feather=None, strips=None):
             continue
         ok = ok & ~done
         done |= ok
-        fx, fy = gxg - 128, gy - 128
-        x0, y0, ax, ay = fx >> 8, fy >> 8, (fx & 255)[:, :, None], (fy & 255)[:, :, None]
-        xa, xb = np.clip(x0, 0, W - 1), np.clip(x0 + 1, 0, W - 1)
-        ya, yb = np.clip(y0, 0, H - 1), np.clip(y0 + 1, 0, H - 1)
-        top = (256 - ax) * p[ya, xa] + ax * p[ya, xb]
-        bot = (256 - ax) * p[yb, xa] + ax * p[yb, xb]
-        v = ((256 - ay) * top + ay * bot + 32768) >> 16
-        if F:
-            xi, yi, D = np.clip(gxg >> 8, 0, W - 1), gy >> 8, F + 1
-            a = (np.minimum(np.minimum(np.minimum(xi, W - 1 - xi), np.minimum(yi, H - 1 - yi)), F) + 1)[:, :, None]
-            v = (2 * (a * v + (D - a) * old) + D) // (2 * D)
-        dst[ok] = v[ok].astype(np.uint8)
+        dst[ok] = _sample_host(line, gxg, gy, F, old)[ok].astype(np.uint8)
     return dst
 
 
@@ -285,20 +311,10 @@ def poly_windows_host(scene, polys, lr_size=(16, 64), stride: int = 32, mask: bo
     """RGB PIL image, polygons -> (stack, lines): the concatenation of `line_windows_host(rectified crop, ...)` over the polygons, an
     (n_windows, 3 + mask, h, w) float stack, and lines[k] = Line(wl, starts, first window index) of polygon k."""
     import numpy as np
-    import torch
     from PIL import Image
-    polys = poly_check(scene.size, polys)
-    h, w = lr_size
     a = np.asarray(scene)
-    parts, lines, first = [], [], 0
-    for poly in polys:
-        crop = Image.fromarray(poly_rectify_host(a, poly), "RGB")
-        wl, starts = line_plan(crop.size, lr_size, stride)
-        parts.append(line_windows_host(crop, lr_size, stride, mask))
-        lines.append(Line(wl, starts, first))
-        first += len(starts)
-    stack = torch.cat(parts) if parts else torch.zeros(0, 3 + int(bool(mask)), h, w)
-    return stack, lines
+    return _region_windows_host(poly_check(scene.size, polys), lambda poly: Image.fromarray(poly_rectify_host(a, poly), "RGB"), lr_size,
+                                stride, mask)
 
 
 def poly_layers(polys):
@@ -311,28 +327,15 @@ def poly_compose_host(scene, polys, line_images, scale: int, feather: int = 0, o
     k's line image (RGB PIL, or an (H, W, 3) uint8 array) is resized with PIL bicubic to (scale * bw, scale * bh) and pasted
     (`poly_paste_host`) into the polygon's bounding box of the canvas, in input order (`order`: another order of the indices, e.g. layer
     after layer).  feather = F >= 0; a polygon of four points gets the bytes `quad_compose_host` gives its quad."""
-    import numpy as np
     from PIL import Image
     polys = poly_check(scene.size, polys)
-    if not (isinstance(scale, int) and not isinstance(scale, bool) and scale >= 1):
-        raise ValueError("polys: scale must be a positive int; got %r" % (scale,))
-    if not (isinstance(feather, int) and not isinstance(feather, bool) and feather >= 0):
-        raise ValueError("polys: feather must be an int >= 0; got %r" % (feather,))
-    if len(line_images) != len(polys):
-        raise ValueError("polys: %d line images for %d polygons" % (len(line_images), len(polys)))
-    if scene.mode != "RGB":
-        raise ValueError("polys: an RGB PIL image is taken; got %r" % (scene.mode,))
-    ws, hs = scene.size
-    canvas = np.array(scene if scale == 1 else scene.resize((scale * ws, scale * hs), Image.BICUBIC))
+    _scale_check("polys", scale)
+    canvas, line = _compose_front(("polys", "polygons"), scene, len(polys), line_images, scale, feather)
     for k in (range(len(polys)) if order is None else order):
         bw, bh = poly_size(polys[k])
         maps = poly_matrices(polys[k], scale, rect=False)
         x0, y0, x1, y1 = maps.bbox
-        im = line_images[k]
-        im = im if isinstance(im, Image.Image) else Image.fromarray(np.ascontiguousarray(im), "RGB")
-        ow, oh = scale * bw, scale * bh
-        new = np.asarray(im if im.size == (ow, oh) else im.resize((ow, oh), Image.BICUBIC))
-        poly_paste_host(new, maps, canvas[scale * y0:scale * y1, scale * x0:scale * x1], feather)
+        poly_paste_host(line(k, scale * bw, scale * bh), maps, canvas[scale * y0:scale * y1, scale * x0:scale * x1], feather)
     return Image.fromarray(canvas, "RGB")
 
 
@@ -346,13 +349,6 @@ def super_resolve_polys_host(scene, polys, run_windows, lr_size=(16, 64), stride
 
 
 # ---- host halves of the launches ------------------------------------------------------------------------------------------------------
-def _words(v):
-    """a 64-bit two's complement value as (low, high) int32 words"""
-    u = int(v) & 0xFFFFFFFFFFFFFFFF
-    lo, hi = u & 0xFFFFFFFF, u >> 32
-    return [lo - (1 << 32) if lo >= 1 << 31 else lo, hi - (1 << 32) if hi >= 1 << 31 else hi]
-
-
 def poly_item_row(src_off, hs, ws, sp, dst_off, oh, ow, dp, feather, first, count):
     """one POLY_DESC-int item row of tatt_poly_paste_u8: [line byte offset, H, W, line pitch, target byte offset, OH, OW, target pitch,
     feather, first strip row, strip count, 0 x 5]"""
@@ -375,6 +371,17 @@ def poly_plan(scene, polys, lr_size=(16, 64), stride: int = 32, mask: bool = Tru
     polygon is warped into the crop's region at byte offset + 3 U_k with OW = w_k and the crop's pitch 3 bw: still ONE launch for all
     strips of all polygons.  An over-size crop goes the ways of `quad_plan`: resized on the device, or rectified and resized on the host
     and uploaded."""
+    return PolyPlan(*_window_plan(scene, polys, lr_size, stride, mask, limits, slimits, qlimits, _POLY, _rect_strips))
+
+
+def _resize_takes(hs, ws, oh, ow, slim):
+    """what tatt_resize_u8 takes (`scene_limits`)"""
+    return max(hs, ws, oh, ow) <= slim["side"] and hs <= slim["down"] * oh and ws <= slim["down"] * ow
+
+
+def _window_plan(scene, regions, lr_size, stride, mask, limits, slimits, qlimits, kind, strips):
+    """`quad_plan` (kind = _QUAD) and `poly_plan` (_POLY) -> the fields of their plans, the checked regions last.  strips(region): the
+    (m_rect, width) of its strips, one mode-0 warp row each, side by side in the region's crop; a quad has one."""
     import numpy as np
     from PIL import Image
     lim = limits if limits is not None else line_limits()
@@ -383,42 +390,41 @@ def poly_plan(scene, polys, lr_size=(16, 64), stride: int = 32, mask: bool = Tru
     if getattr(scene, "mode", None) != "RGB":
         raise ValueError("DeviceCollator takes RGB PIL images (Image.open(..).convert('RGB')); the scene is %r" % (
             getattr(scene, "mode", type(scene).__name__),))
-    polys = poly_check(scene.size, polys, slim)
+    regions = _check(scene.size, regions, slim, kind)
     h, w = int(lr_size[0]), int(lr_size[1])
     if not (1 <= h <= lim["h"] and 1 <= w <= lim["w"]):
         raise ValueError("tatt_scene_windows takes windows up to %d x %d (got %d x %d)" % (lim["h"], lim["w"], h, w))
     a = np.asarray(scene)
     Hs, Ws = a.shape[:2]
-    if max(Hs, Ws) > qlim["side"] or sum(len(p) // 2 - 1 for p in polys) > qlim["items"]:
+    if max(Hs, Ws) > qlim["side"] or sum(len(p) // 2 - 1 for p in regions) > qlim["items"]:
         raise ValueError("tatt_warp_u8 takes sides up to %d and %d items" % (qlim["side"], qlim["items"]))
     geo = []
-    for k, poly in enumerate(polys):
-        bw, bh = poly_size(poly)
+    for k, region in enumerate(regions):
+        bw, bh = poly_size(region)
         wl, starts = line_plan((bw, bh), (h, w), stride)
         if wl > lim["wl"] or len(starts) > lim["windows"]:
-            raise ValueError("tatt_scene_windows takes lines up to %d columns and %d windows (polygon %d: %d, %d)" % (
-                lim["wl"], lim["windows"], k, wl, len(starts)))
+            raise ValueError("tatt_scene_windows takes lines up to %d columns and %d windows (%s %d: %d, %d)" % (
+                lim["wl"], lim["windows"], kind[1], k, wl, len(starts)))
         if max(bw, bh) > qlim["side"]:
-            raise ValueError("tatt_warp_u8 takes crops up to %d a side (polygon %d: %d x %d)" % (qlim["side"], k, bw, bh))
+            raise ValueError("tatt_warp_u8 takes crops up to %d a side (%s %d: %d x %d)" % (qlim["side"], kind[1], k, bw, bh))
         how = "crop" if _line_takes(bh, bw, h, wl, w, lim) else "device" if _resize_takes(bh, bw, h, wl, slim) else "host"
-        geo.append((poly, bw, bh, wl, starts, how))
+        geo.append((region, bw, bh, wl, starts, how))
     arrays, offsets, off = [a], [0], _up(a.size)
     src = {}
-    for k, (poly, bw, bh, wl, starts, how) in enumerate(geo):       # uploaded sources first: the upload is one contiguous copy
+    for k, (region, bw, bh, wl, starts, how) in enumerate(geo):     # uploaded sources first: the upload is one contiguous copy
         if how == "host":
-            small = np.asarray(Image.fromarray(poly_rectify_host(a, poly), "RGB").resize((wl, h), Image.BICUBIC))
+            small = np.asarray(Image.fromarray(_rectify(a, strips(region), bh), "RGB").resize((wl, h), Image.BICUBIC))
             arrays.append(small)
             offsets.append(off)
             src[k] = (off, h, wl, 3 * wl)
             off += _up(small.size)
     upload = off
     warp, resize = [], []
-    for k, (poly, bw, bh, wl, starts, how) in enumerate(geo):
+    for k, (region, bw, bh, wl, starts, how) in enumerate(geo):
         if how == "host":
             continue
-        maps = poly_matrices(poly, 1, paste=False)
         start = 0
-        for m, wk in zip(maps.rect, maps.widths):                    # one row per strip, side by side in the crop
+        for m, wk in strips(region):                                 # one row per strip, side by side in the crop
             warp.append(warp_row(0, Hs, Ws, 3 * Ws, off + 3 * start, bh, wk, 3 * bw, 0, 0, m))
             start += wk
         crop = (off, bh, bw, 3 * bw)
@@ -432,7 +438,7 @@ def poly_plan(scene, polys, lr_size=(16, 64), stride: int = 32, mask: bool = Tru
         if off >= 2 ** 31:
             raise ValueError("DeviceCollator: the scene does not fit 32-bit offsets")
     rows, lines, out_off, planes = [], [], 0, 3 + int(bool(mask))
-    for k, (poly, bw, bh, wl, starts, how) in enumerate(geo):
+    for k, (region, bw, bh, wl, starts, how) in enumerate(geo):
         o, sh, sw, sp = src[k]
         lines.append(Line(wl, starts, len(rows)))
         for x in starts:
@@ -440,14 +446,11 @@ def poly_plan(scene, polys, lr_size=(16, 64), stride: int = 32, mask: bool = Tru
             out_off += planes * h * w
     if off >= 2 ** 31 or out_off >= 2 ** 31:
         raise ValueError("DeviceCollator: the scene does not fit 32-bit offsets")
-    return PolyPlan(arrays, offsets, np.array(warp, np.int32).reshape(-1, QUAD_DESC), np.array(resize, np.int32).reshape(-1, RESIZE_DESC),
-                    np.array(rows, np.int32).reshape(-1, SCENE_DESC), lines, upload, off, out_off, polys)
+    return (arrays, offsets, np.array(warp, np.int32).reshape(-1, QUAD_DESC), np.array(resize, np.int32).reshape(-1, RESIZE_DESC),
+            np.array(rows, np.int32).reshape(-1, SCENE_DESC), lines, upload, off, out_off, regions)
 
 
-def poly_fill(flat, plan):
-    """Write one staging slot of a PolyPlan: `quad_fill`, whose layout it shares (warp rows | resize rows | window rows | sources) ->
-    (o_warp, o_resize, o_desc, pix, used, total).  `poly_fill(None, plan)` only computes the offsets."""
-    return quad_fill(flat, plan)
+poly_fill = quad_fill     # a PolyPlan shares the QuadPlan's layout: warp rows | resize rows | window rows | sources
 
 
 def poly_paste_plan(size, polys, blend_desc, blend_bytes, scale: int, H: int, feather: int = 0, limits=None, plimits=None):
@@ -459,44 +462,9 @@ def poly_paste_plan(size, polys, blend_desc, blend_bytes, scale: int, H: int, fe
     polygons in layer l: one launch each; strips: (total strips, POLY_STRIP_DESC), the ONE strip table all launches share, the strips
     of an item consecutive from its 'first strip row'."""
     import numpy as np
-    lim = limits if limits is not None else scene_limits()
-    plim = plimits if plimits is not None else poly_limits()
-    polys = poly_check(size, polys, lim)
-    ws, hs = int(size[0]), int(size[1])
-    side, fmax = min(lim["side"], plim["side"]), min(lim["feather"], plim["feather"])
-    if not (isinstance(scale, int) and not isinstance(scale, bool) and scale >= 1):
-        raise ValueError("polys: scale must be a positive int; got %r" % (scale,))
-    if not (isinstance(feather, int) and not isinstance(feather, bool) and 0 <= feather <= fmax):
-        raise ValueError("polys: feather must be an int in [0, %d]; got %r" % (fmax, feather))
-    if len(blend_desc) != len(polys):
-        raise ValueError("polys: %d lines for %d polygons" % (len(blend_desc), len(polys)))
-    if scale * max(ws, hs) > side:
-        raise ValueError("polys: the canvas %d x %d is beyond the largest side %d" % (scale * ws, scale * hs, side))
-    if len(polys) > plim["items"] or any(len(p) // 2 - 1 > plim["strips"] for p in polys):
-        raise ValueError("tatt_poly_paste_u8 takes %d items of up to %d strips" % (plim["items"], plim["strips"]))
-    off = _up(blend_bytes)
-    resize = np.zeros((1 + len(polys), RESIZE_DESC), np.int32)
-    rects, maps = [], []
-    for k, poly in enumerate(polys):
-        bw, bh = poly_size(poly)
-        d = blend_desc[k]
-        lw = int(d[3]) * int(d[2])                                   # scale * wl columns of the line canvas
-        oh, ow = scale * bh, scale * bw
-        if H > lim["down"] * oh or lw > lim["down"] * ow or max(oh, ow) > side:
-            raise ValueError("polys: polygon %d: resizing %d x %d into %d x %d is beyond the limits" % (k, H, lw, oh, ow))
-        resize[1 + k, :9] = (int(d[6]), H, lw, int(d[7]), off, oh, ow, 3 * ow, 0)
-        rects.append(off)
-        maps.append(poly_matrices(poly, scale, rect=False))
-        off += _up(oh * 3 * ow)
-        if off >= 2 ** 31:
-            raise ValueError("DeviceExporter: the scene does not fit 32-bit offsets")
-    canvas_off, pitch = off, 3 * scale * ws
-    nbytes = canvas_off + scale * hs * pitch
-    if nbytes >= 2 ** 31 or hs * ws * 3 >= 2 ** 31:
-        raise ValueError("DeviceExporter: the scene does not fit 32-bit offsets")
-    resize[0, :9] = (0, hs, ws, 3 * ws, canvas_off, scale * hs, scale * ws, pitch, 0)
-    layers = poly_layers(polys)
-    order = sorted(range(len(polys)), key=lambda k: (layers[k], k))
+    polys, maps, resize, rects, canvas_off, pitch, nbytes, layers, order, counts = _paste_front(
+        size, polys, blend_desc, blend_bytes, scale, H, feather, limits, plimits if plimits is not None else poly_limits(), _POLY,
+        lambda poly: poly_matrices(poly, scale, rect=False))
     items, strips = [], []
     for k in order:
         mp = maps[k]
@@ -509,6 +477,48 @@ def poly_paste_plan(size, polys, blend_desc, blend_bytes, scale: int, H: int, fe
             strips.append(poly_strip_row(scale * start, scale * mp.widths[n], m, mp.seams[n - 1] if n else None,
                                          mp.seams[n] if n < last else None))
             start += mp.widths[n]
-    counts = [layers.count(l) for l in range(max(layers) + 1)] if layers else []
     return PolyPastePlan(resize, np.array(items, np.int32).reshape(-1, POLY_DESC), np.array(strips, np.int32).reshape(-1, POLY_STRIP_DESC),
                          layers, order, counts, rects, canvas_off, pitch, nbytes)
+
+
+def _paste_front(size, regions, blend_desc, blend_bytes, scale, H, feather, limits, klimits, kind, maps):
+    """`quad_paste_plan` (kind = _QUAD, klimits = `quad_limits()`) and `poly_paste_plan` (_POLY, `poly_limits()`) in front of the rows
+    of their own paste launches -> (the checked regions, maps(region) of each, resize, rects, canvas_off, pitch, nbytes, layers, order,
+    counts) as both plans state them"""
+    import numpy as np
+    who, one = kind[:2]
+    lim = limits if limits is not None else scene_limits()
+    regions = _check(size, regions, lim, kind)
+    ws, hs = int(size[0]), int(size[1])
+    side, fmax = min(lim["side"], klimits["side"]), min(lim["feather"], klimits["feather"])
+    _scale_check(who, scale)
+    if not (isinstance(feather, int) and not isinstance(feather, bool) and 0 <= feather <= fmax):
+        raise ValueError("%s: feather must be an int in [0, %d]; got %r" % (who, fmax, feather))
+    if len(blend_desc) != len(regions):
+        raise ValueError("%s: %d lines for %d %ss" % (who, len(blend_desc), len(regions), one))
+    if scale * max(ws, hs) > side:
+        raise ValueError("%s: the canvas %d x %d is beyond the largest side %d" % (who, scale * ws, scale * hs, side))
+    if "strips" in klimits and (len(regions) > klimits["items"] or any(len(p) // 2 - 1 > klimits["strips"] for p in regions)):
+        raise ValueError("tatt_poly_paste_u8 takes %d items of up to %d strips" % (klimits["items"], klimits["strips"]))
+    off = _up(blend_bytes)
+    resize = np.zeros((1 + len(regions), RESIZE_DESC), np.int32)
+    rects, mats = [], []
+    for k, region in enumerate(regions):
+        bw, bh = poly_size(region)
+        d = blend_desc[k]
+        lw = int(d[3]) * int(d[2])                                   # scale * wl columns of the line canvas
+        oh, ow = scale * bh, scale * bw
+        if H > lim["down"] * oh or lw > lim["down"] * ow or max(oh, ow) > side:
+            raise ValueError("%s: %s %d: resizing %d x %d into %d x %d is beyond the limits" % (who, one, k, H, lw, oh, ow))
+        resize[1 + k, :9] = (int(d[6]), H, lw, int(d[7]), off, oh, ow, 3 * ow, 0)
+        rects.append(off)
+        mats.append(maps(region))
+        off += _up(oh * 3 * ow)
+        if off >= 2 ** 31:
+            raise ValueError("DeviceExporter: the scene does not fit 32-bit offsets")
+    canvas_off, pitch = off, 3 * scale * ws
+    nbytes = canvas_off + scale * hs * pitch
+    if nbytes >= 2 ** 31 or hs * ws * 3 >= 2 ** 31:
+        raise ValueError("DeviceExporter: the scene does not fit 32-bit offsets")
+    resize[0, :9] = (0, hs, ws, 3 * ws, canvas_off, scale * hs, scale * ws, pitch, 0)
+    return (regions, mats, resize, rects, canvas_off, pitch, nbytes) + _paste_order([poly_bbox(p) for p in regions])

@@ -16,6 +16,10 @@ division, so the device path equals it byte for byte.
 * `quad_limits` / `quad_plan` / `quad_fill` / `quad_paste_plan`: the host halves of the launches (tatt_warp_u8, tatt_resize_u8,
   tatt_scene_windows).
 
+A quad is the polygon of four points of `tatt_amd/polys.py`, and everything that is not projective arithmetic has ONE body there: the
+check, the matrices of a strip, the window plan, the front of the paste plan.  The `quad_*` functions below are entries onto those
+bodies under the quad's own names and wording (they import from `polys` when called: `polys` imports this module).
+
 A warp is stated per destination pixel (i, j) through a 3 x 3 integer matrix m applied to (J, I, 1), J = 2 j + 1, I = 2 i + 1 (the pixel
 centre in half-pixel units):
     X = m00 J + m01 I + m02;   Y = m10 J + m11 I + m12;   Wd = m20 J + m21 I + m22                     (int64)
@@ -29,18 +33,16 @@ the nearest side of the SOURCE rectangle, and leaves every other pixel as it is.
 from __future__ import annotations
 
 import math
-import numbers
 from collections import namedtuple
 from fractions import Fraction
 
-from .lines import Line, _line_takes, _super_resolve_boxes_host, line_limits, line_plan, line_windows_host
-from .scene import RESIZE_DESC, SCENE_DESC, SCENE_MIN_SIDE, scene_layers, scene_limits
+from .lines import _compose_front, _region_windows_host, _scale_check, _super_resolve_boxes_host
+from .scene import _up, scene_layers
 
 QUAD_MAX_TAPER = 2        # opposite sides of a quad differ in length by at most this factor (a two-tap sampler aliases beyond it)
 QUAD_SHIFT = 36           # fraction bits of the integer matrices
 QUAD_DESC = 32            # ints per item row of tatt_warp_u8 (include/tatt_hip.h)
 _BOUND = 1 << 62
-_ALIGN = 16
 
 QuadPlan = namedtuple("QuadPlan", "arrays offsets warp resize desc lines upload nbytes out_floats quads")
 QuadPastePlan = namedtuple("QuadPastePlan", "resize warp layers order counts rects canvas_off pitch nbytes")
@@ -83,39 +85,8 @@ def quad_check(size, quads, limits=None):
     bottom-left corner (clockwise with y down, reading direction p0 -> p1) -> the quads as a list of tuples of int pairs.  Every point in
     [0, Ws] x [0, Hs], strictly convex and clockwise, both rectified sides at least SCENE_MIN_SIDE, opposite sides within QUAD_MAX_TAPER
     of each other (exactly, on squared lengths), at most scene_limits()['boxes'] quads; anything else raises ValueError naming the quad."""
-    lim = limits if limits is not None else scene_limits()
-    ws, hs = int(size[0]), int(size[1])
-    if ws < 1 or hs < 1 or ws > lim["side"] or hs > lim["side"]:
-        raise ValueError("quads: the image is %d x %d; sides from 1 to %d are taken" % (ws, hs, lim["side"]))
-    quads = list(quads)
-    if len(quads) > lim["boxes"]:
-        raise ValueError("quads: %d quads; at most %d" % (len(quads), lim["boxes"]))
-    out = []
-    for k, quad in enumerate(quads):
-        try:
-            ok = len(quad) == 4 and all(len(p) == 2 and all(isinstance(v, numbers.Integral) and not isinstance(v, bool) for v in p)
-                                        for p in quad)
-        except TypeError:
-            ok = False
-        if not ok:
-            raise ValueError("quads: quad %d must be four (x, y) pairs of ints; got %r" % (k, quad))
-        q = tuple((int(x), int(y)) for x, y in quad)
-        if not all(0 <= x <= ws and 0 <= y <= hs for x, y in q):
-            raise ValueError("quads: quad %d = %s does not lie in the %d x %d image (0 <= x <= Ws, 0 <= y <= Hs)" % (k, q, ws, hs))
-        for i in range(4):
-            a, b, c = q[i], q[(i + 1) % 4], q[(i + 2) % 4]
-            if (b[0] - a[0]) * (c[1] - b[1]) - (b[1] - a[1]) * (c[0] - b[0]) <= 0:
-                raise ValueError("quads: quad %d = %s is not strictly convex and clockwise (top-left, top-right, bottom-right, "
-                                 "bottom-left with y down)" % (k, q))
-        bw, bh = quad_size(q)
-        if bw < SCENE_MIN_SIDE or bh < SCENE_MIN_SIDE:
-            raise ValueError("quads: quad %d = %s rectifies to %d x %d; both sides must be at least SCENE_MIN_SIDE = %d" % (
-                k, q, bw, bh, SCENE_MIN_SIDE))
-        for s, t in ((_d2(q[1], q[0]), _d2(q[2], q[3])), (_d2(q[3], q[0]), _d2(q[2], q[1]))):
-            if max(s, t) > QUAD_MAX_TAPER ** 2 * min(s, t):
-                raise ValueError("quads: quad %d = %s: opposite sides differ by more than QUAD_MAX_TAPER = %d" % (k, q, QUAD_MAX_TAPER))
-        out.append(q)
-    return out
+    from .polys import _QUAD, _check
+    return _check(size, quads, limits, _QUAD)
 
 
 # ---- the matrices ---------------------------------------------------------------------------------------------------------------------
@@ -171,20 +142,9 @@ def quad_matrices(quad, scale: int = 1):
     """one checked quad, the up-scaling factor -> (m_rectify, m_paste, (bx0, by0, bx1, by1)): nine ints each, row-major.
     m_rectify warps the scene into the (bh, bw) crop; m_paste warps the (scale * bh, scale * bw) line into the quad's bounding box
     [scale * bx0, scale * bx1) x [scale * by0, scale * by1) of the up-scaled canvas.  ValueError when the integers do not fit."""
-    quad = tuple((int(x), int(y)) for x, y in quad)
-    if not (isinstance(scale, int) and not isinstance(scale, bool) and scale >= 1):
-        raise ValueError("quads: scale must be a positive int; got %r" % (scale,))
-    bw, bh = quad_size(quad)
-    bx0, by0, bx1, by1 = quad_bbox(quad)
-    hf = _homography(quad, bw, bh)
-    half = _diag(Fraction(1, 2), Fraction(1, 2))
-    m_rect = _integer(_mul(hf, half), bw, bh, bh, bw, True, "quad %s" % (quad,))
-    s = scale
-    shift = [[Fraction(1), 0, Fraction(s * bx0)], [0, Fraction(1), Fraction(s * by0)], [0, 0, Fraction(1)]]
-    q = _mul(_mul(_mul(_mul(_diag(s, s), _adjugate(hf)), _diag(Fraction(1, s), Fraction(1, s))), shift), half)
-    mx, my = Fraction(sum(p[0] for p in quad), 4), Fraction(sum(p[1] for p in quad), 4)
-    m_paste = _integer(q, 2 * s * (mx - bx0), 2 * s * (my - by0), s * (by1 - by0), s * (bx1 - bx0), False, "quad %s" % (quad,))
-    return m_rect, m_paste, (bx0, by0, bx1, by1)
+    from .polys import _QUAD, _maps
+    maps = _maps(quad, scale, True, True, _QUAD)
+    return maps.rect[0], maps.paste[0], maps.bbox
 
 
 # ---- the warp -------------------------------------------------------------------------------------------------------------------------
@@ -207,6 +167,29 @@ def warp_inside_host(m, out_h, out_w, src_h, src_w):
     return ok & (gx >= 0) & (gx < 256 * src_w) & (gy >= 0) & (gy < 256 * src_h)
 
 
+def _sample_host(src, gx, gy, feather=0, old=None):
+    """The pixel rule of `warp_u8_host` and `poly_paste_host`, on whole arrays.  src: (H, W, 3) uint8; gx, gy: int64 source coordinates
+    in 1 / 256 pixels -> the int64 bilinear sample: fx = gx - 128, x0 = fx >> 8, ax = fx & 255 (fy alike), the four taps clamped to the
+    source, the sum rounded at 2^15.  feather = F > 0: blended with `old` (int64, what the target holds): a = min(d + 1, F + 1),
+    D = F + 1, d = min(xi, W - 1 - xi, yi, H - 1 - yi) for xi = gx >> 8 clamped to the source (a pixel that is painted has it inside
+    anyway, except a polygon's inner strips) and yi = gy >> 8, and the pixel becomes (2 (a new + (D - a) old) + D) // (2 D)."""
+    import numpy as np
+    hs, ws = src.shape[:2]
+    fx, fy = gx - 128, gy - 128
+    x0, y0, ax, ay = fx >> 8, fy >> 8, (fx & 255)[:, :, None], (fy & 255)[:, :, None]
+    xa, xb = np.clip(x0, 0, ws - 1), np.clip(x0 + 1, 0, ws - 1)
+    ya, yb = np.clip(y0, 0, hs - 1), np.clip(y0 + 1, 0, hs - 1)
+    p = src.astype(np.int64)
+    top = (256 - ax) * p[ya, xa] + ax * p[ya, xb]
+    bot = (256 - ax) * p[yb, xa] + ax * p[yb, xb]
+    v = ((256 - ay) * top + ay * bot + 32768) >> 16
+    if feather:
+        xi, yi, D = np.clip(gx >> 8, 0, ws - 1), gy >> 8, feather + 1
+        a = (np.minimum(np.minimum(np.minimum(xi, ws - 1 - xi), np.minimum(yi, hs - 1 - yi)), feather) + 1)[:, :, None]
+        v = (2 * (a * v + (D - a) * old) + D) // (2 * D)
+    return v
+
+
 def warp_u8_host(src, m, out_h, out_w, dst=None, feather=None):
     """src: (H_src, W_src, 3) uint8, m: nine ints.  dst None: mode 0 -> the (out_h, out_w, 3) uint8 warp, every pixel written.  dst an
     (out_h, out_w, 3) uint8 array: mode 1, the painted pixels are blended INTO dst (in place; also returned) with feather F
@@ -220,25 +203,13 @@ def warp_u8_host(src, m, out_h, out_w, dst=None, feather=None):
         raise ValueError("warp_u8_host takes nine matrix entries and a positive destination size")
     hs, ws = src.shape[:2]
     gx, gy, ok = _warp_coords(m, out_h, out_w)
-    fx, fy = gx - 128, gy - 128
-    x0, y0, ax, ay = fx >> 8, fy >> 8, (fx & 255)[:, :, None], (fy & 255)[:, :, None]
-    xa, xb = np.clip(x0, 0, ws - 1), np.clip(x0 + 1, 0, ws - 1)
-    ya, yb = np.clip(y0, 0, hs - 1), np.clip(y0 + 1, 0, hs - 1)
-    p = src.astype(np.int64)
-    top = (256 - ax) * p[ya, xa] + ax * p[ya, xb]
-    bot = (256 - ax) * p[yb, xa] + ax * p[yb, xb]
-    v = ((256 - ay) * top + ay * bot + 32768) >> 16
     if dst is None:
-        return np.where(ok[:, :, None], v, 0).astype(np.uint8)
+        return np.where(ok[:, :, None], _sample_host(src, gx, gy), 0).astype(np.uint8)
     F = 0 if feather is None else int(feather)
     if F < 0 or dst.shape != (out_h, out_w, 3) or dst.dtype != np.uint8:
         raise ValueError("warp_u8_host: dst must be (out_h, out_w, 3) uint8 and the feather >= 0")
     inside = ok & (gx >= 0) & (gx < 256 * ws) & (gy >= 0) & (gy < 256 * hs)
-    if F:
-        xi, yi, D = gx >> 8, gy >> 8, F + 1
-        a = (np.minimum(np.minimum(np.minimum(xi, ws - 1 - xi), np.minimum(yi, hs - 1 - yi)), F) + 1)[:, :, None]
-        v = (2 * (a * v + (D - a) * dst.astype(np.int64)) + D) // (2 * D)
-    dst[inside] = v[inside].astype(np.uint8)
+    dst[inside] = _sample_host(src, gx, gy, F, dst.astype(np.int64))[inside].astype(np.uint8)
     return dst
 
 
@@ -253,20 +224,10 @@ def quad_windows_host(scene, quads, lr_size=(16, 64), stride: int = 32, mask: bo
     """RGB PIL image, quads -> (stack, lines): the concatenation of `line_windows_host(rectified crop, ...)` over the quads, an
     (n_windows, 3 + mask, h, w) float stack, and lines[k] = Line(wl, starts, first window index) of quad k."""
     import numpy as np
-    import torch
     from PIL import Image
-    quads = quad_check(scene.size, quads)
-    h, w = lr_size
     a = np.asarray(scene)
-    parts, lines, first = [], [], 0
-    for quad in quads:
-        crop = Image.fromarray(quad_rectify_host(a, quad), "RGB")
-        wl, starts = line_plan(crop.size, lr_size, stride)
-        parts.append(line_windows_host(crop, lr_size, stride, mask))
-        lines.append(Line(wl, starts, first))
-        first += len(starts)
-    stack = torch.cat(parts) if parts else torch.zeros(0, 3 + int(bool(mask)), h, w)
-    return stack, lines
+    return _region_windows_host(quad_check(scene.size, quads), lambda quad: Image.fromarray(quad_rectify_host(a, quad), "RGB"), lr_size,
+                                stride, mask)
 
 
 def quad_layers(quads):
@@ -279,28 +240,15 @@ def quad_compose_host(scene, quads, line_images, scale: int, feather: int = 0, o
     line image (RGB PIL, or an (H, W, 3) uint8 array) is resized with PIL bicubic to (scale * bw, scale * bh) and warped (mode 1, m_paste
     of `quad_matrices`) into the quad's bounding box of the canvas, in quad order (`order`: another order of the indices, e.g. layer
     after layer).  feather = F >= 0 as `warp_u8_host` states it; an axis-aligned quad gets the bytes `scene_compose_host` gives its box."""
-    import numpy as np
     from PIL import Image
     quads = quad_check(scene.size, quads)
-    if not (isinstance(scale, int) and not isinstance(scale, bool) and scale >= 1):
-        raise ValueError("quads: scale must be a positive int; got %r" % (scale,))
-    if not (isinstance(feather, int) and not isinstance(feather, bool) and feather >= 0):
-        raise ValueError("quads: feather must be an int >= 0; got %r" % (feather,))
-    if len(line_images) != len(quads):
-        raise ValueError("quads: %d line images for %d quads" % (len(line_images), len(quads)))
-    if scene.mode != "RGB":
-        raise ValueError("quads: an RGB PIL image is taken; got %r" % (scene.mode,))
-    ws, hs = scene.size
-    canvas = np.array(scene if scale == 1 else scene.resize((scale * ws, scale * hs), Image.BICUBIC))
+    _scale_check("quads", scale)
+    canvas, line = _compose_front(("quads", "quads"), scene, len(quads), line_images, scale, feather)
     for k in (range(len(quads)) if order is None else order):
         bw, bh = quad_size(quads[k])
         _, m, (x0, y0, x1, y1) = quad_matrices(quads[k], scale)
-        im = line_images[k]
-        im = im if isinstance(im, Image.Image) else Image.fromarray(np.ascontiguousarray(im), "RGB")
-        ow, oh = scale * bw, scale * bh
-        new = np.asarray(im if im.size == (ow, oh) else im.resize((ow, oh), Image.BICUBIC))
         rect = canvas[scale * y0:scale * y1, scale * x0:scale * x1]
-        warp_u8_host(new, m, rect.shape[0], rect.shape[1], rect, feather)
+        warp_u8_host(line(k, scale * bw, scale * bh), m, rect.shape[0], rect.shape[1], rect, feather)
     return Image.fromarray(canvas, "RGB")
 
 
@@ -314,8 +262,11 @@ def super_resolve_quads_host(scene, quads, run_windows, lr_size=(16, 64), stride
 
 
 # ---- host halves of the launches ------------------------------------------------------------------------------------------------------
-def _up(n):
-    return -(-int(n) // _ALIGN) * _ALIGN
+def _words(v):
+    """a 64-bit two's complement value as (low, high) int32 words"""
+    u = int(v) & 0xFFFFFFFFFFFFFFFF
+    lo, hi = u & 0xFFFFFFFF, u >> 32
+    return [lo - (1 << 32) if lo >= 1 << 31 else lo, hi - (1 << 32) if hi >= 1 << 31 else hi]
 
 
 def warp_row(src_off, hs, ws, sp, dst_off, oh, ow, dp, feather, mode, m):
@@ -323,15 +274,8 @@ def warp_row(src_off, hs, ws, sp, dst_off, oh, ow, dp, feather, mode, m):
     feather, mode (0 rectify, 1 paste), the nine matrix entries as (low, high) int32 words, 0 x 4]"""
     row = [src_off, hs, ws, sp, dst_off, oh, ow, dp, feather, mode]
     for v in m:
-        u = int(v) & 0xFFFFFFFFFFFFFFFF
-        lo, hi = u & 0xFFFFFFFF, u >> 32
-        row += [lo - (1 << 32) if lo >= 1 << 31 else lo, hi - (1 << 32) if hi >= 1 << 31 else hi]
+        row += _words(v)
     return row + [0] * (QUAD_DESC - len(row))
-
-
-def _resize_takes(hs, ws, oh, ow, slim):
-    """what tatt_resize_u8 takes (`scene_limits`)"""
-    return max(hs, ws, oh, ow) <= slim["side"] and hs <= slim["down"] * oh and ws <= slim["down"] * ow
 
 
 def quad_plan(scene, quads, lr_size=(16, 64), stride: int = 32, mask: bool = True, limits=None, slimits=None, qlimits=None):
@@ -344,69 +288,9 @@ def quad_plan(scene, quads, lr_size=(16, 64), stride: int = 32, mask: bool = Tru
     (or its resized version) as a source of its own, origin (0, 0); quads in input order, windows left to right.  A crop that neither the
     window kernel nor the tiled resampler takes (`slimits` = `scene_limits()`: a down-scale beyond its factor) is rectified and resized
     on the host and uploaded (arrays[1:]): `scene_plan`'s fallback, the same bytes by construction."""
-    import numpy as np
-    from PIL import Image
-    lim = limits if limits is not None else line_limits()
-    slim = slimits if slimits is not None else scene_limits()
-    qlim = qlimits if qlimits is not None else quad_limits()
-    if getattr(scene, "mode", None) != "RGB":
-        raise ValueError("DeviceCollator takes RGB PIL images (Image.open(..).convert('RGB')); the scene is %r" % (
-            getattr(scene, "mode", type(scene).__name__),))
-    quads = quad_check(scene.size, quads, slim)
-    h, w = int(lr_size[0]), int(lr_size[1])
-    if not (1 <= h <= lim["h"] and 1 <= w <= lim["w"]):
-        raise ValueError("tatt_scene_windows takes windows up to %d x %d (got %d x %d)" % (lim["h"], lim["w"], h, w))
-    a = np.asarray(scene)
-    Hs, Ws = a.shape[:2]
-    if max(Hs, Ws) > qlim["side"] or len(quads) > qlim["items"]:
-        raise ValueError("tatt_warp_u8 takes sides up to %d and %d items" % (qlim["side"], qlim["items"]))
-    geo = []
-    for k, quad in enumerate(quads):
-        bw, bh = quad_size(quad)
-        wl, starts = line_plan((bw, bh), (h, w), stride)
-        if wl > lim["wl"] or len(starts) > lim["windows"]:
-            raise ValueError("tatt_scene_windows takes lines up to %d columns and %d windows (quad %d: %d, %d)" % (
-                lim["wl"], lim["windows"], k, wl, len(starts)))
-        if max(bw, bh) > qlim["side"]:
-            raise ValueError("tatt_warp_u8 takes crops up to %d a side (quad %d: %d x %d)" % (qlim["side"], k, bw, bh))
-        how = "crop" if _line_takes(bh, bw, h, wl, w, lim) else "device" if _resize_takes(bh, bw, h, wl, slim) else "host"
-        geo.append((quad, bw, bh, wl, starts, how))
-    arrays, offsets, off = [a], [0], _up(a.size)
-    src = {}
-    for k, (quad, bw, bh, wl, starts, how) in enumerate(geo):       # uploaded sources first: the upload is one contiguous copy
-        if how == "host":
-            small = np.asarray(Image.fromarray(quad_rectify_host(a, quad), "RGB").resize((wl, h), Image.BICUBIC))
-            arrays.append(small)
-            offsets.append(off)
-            src[k] = (off, h, wl, 3 * wl)
-            off += _up(small.size)
-    upload = off
-    warp, resize = [], []
-    for k, (quad, bw, bh, wl, starts, how) in enumerate(geo):
-        if how == "host":
-            continue
-        warp.append(warp_row(0, Hs, Ws, 3 * Ws, off, bh, bw, 3 * bw, 0, 0, quad_matrices(quad, 1)[0]))
-        crop = (off, bh, bw, 3 * bw)
-        off += _up(bh * 3 * bw)
-        if how == "device":
-            resize.append([crop[0], bh, bw, 3 * bw, off, h, wl, 3 * wl, 0] + [0] * (RESIZE_DESC - 9))
-            src[k] = (off, h, wl, 3 * wl)
-            off += _up(h * 3 * wl)
-        else:
-            src[k] = crop
-        if off >= 2 ** 31:
-            raise ValueError("DeviceCollator: the scene does not fit 32-bit offsets")
-    rows, lines, out_off, planes = [], [], 0, 3 + int(bool(mask))
-    for k, (quad, bw, bh, wl, starts, how) in enumerate(geo):
-        o, sh, sw, sp = src[k]
-        lines.append(Line(wl, starts, len(rows)))
-        for x in starts:
-            rows.append((o, sh, sw, h, wl, x, w, int(bool(mask)), out_off, sp, 0, 0, 0, 0, 0, 0))
-            out_off += planes * h * w
-    if off >= 2 ** 31 or out_off >= 2 ** 31:
-        raise ValueError("DeviceCollator: the scene does not fit 32-bit offsets")
-    return QuadPlan(arrays, offsets, np.array(warp, np.int32).reshape(-1, QUAD_DESC), np.array(resize, np.int32).reshape(-1, RESIZE_DESC),
-                    np.array(rows, np.int32).reshape(-1, SCENE_DESC), lines, upload, off, out_off, quads)
+    from .polys import _QUAD, _window_plan
+    return QuadPlan(*_window_plan(scene, quads, lr_size, stride, mask, limits, slimits, qlimits, _QUAD,
+                                  lambda quad: [(quad_matrices(quad, 1)[0], quad_size(quad)[0])]))
 
 
 def quad_fill(flat, plan):
@@ -437,46 +321,14 @@ def quad_paste_plan(size, quads, blend_desc, blend_bytes, scale: int, H: int, fe
     tatt_warp_u8 (mode 1, rectangle -> the quad's bounding box of the canvas, feathered) in paste order `order` = by (layer, index);
     counts[l] quads in layer l: one launch each."""
     import numpy as np
-    lim = limits if limits is not None else scene_limits()
-    qlim = qlimits if qlimits is not None else quad_limits()
-    quads = quad_check(size, quads, lim)
-    ws, hs = int(size[0]), int(size[1])
-    if not (isinstance(scale, int) and not isinstance(scale, bool) and scale >= 1):
-        raise ValueError("quads: scale must be a positive int; got %r" % (scale,))
-    if not (isinstance(feather, int) and not isinstance(feather, bool) and 0 <= feather <= min(lim["feather"], qlim["feather"])):
-        raise ValueError("quads: feather must be an int in [0, %d]; got %r" % (min(lim["feather"], qlim["feather"]), feather))
-    if len(blend_desc) != len(quads):
-        raise ValueError("quads: %d lines for %d quads" % (len(blend_desc), len(quads)))
-    if scale * max(ws, hs) > min(lim["side"], qlim["side"]):
-        raise ValueError("quads: the canvas %d x %d is beyond the largest side %d" % (scale * ws, scale * hs, min(lim["side"], qlim["side"])))
-    off = _up(blend_bytes)
-    resize = np.zeros((1 + len(quads), RESIZE_DESC), np.int32)
-    rects, mats = [], []
-    for k, quad in enumerate(quads):
-        bw, bh = quad_size(quad)
-        d = blend_desc[k]
-        lw = int(d[3]) * int(d[2])                                   # scale * wl columns of the line canvas
-        oh, ow = scale * bh, scale * bw
-        if H > lim["down"] * oh or lw > lim["down"] * ow or max(oh, ow) > min(lim["side"], qlim["side"]):
-            raise ValueError("quads: quad %d: resizing %d x %d into %d x %d is beyond the limits" % (k, H, lw, oh, ow))
-        resize[1 + k, :9] = (int(d[6]), H, lw, int(d[7]), off, oh, ow, 3 * ow, 0)
-        rects.append(off)
-        mats.append(quad_matrices(quad, scale))
-        off += _up(oh * 3 * ow)
-        if off >= 2 ** 31:
-            raise ValueError("DeviceExporter: the scene does not fit 32-bit offsets")
-    canvas_off, pitch = off, 3 * scale * ws
-    nbytes = canvas_off + scale * hs * pitch
-    if nbytes >= 2 ** 31 or hs * ws * 3 >= 2 ** 31:
-        raise ValueError("DeviceExporter: the scene does not fit 32-bit offsets")
-    resize[0, :9] = (0, hs, ws, 3 * ws, canvas_off, scale * hs, scale * ws, pitch, 0)
-    layers = quad_layers(quads)
-    order = sorted(range(len(quads)), key=lambda k: (layers[k], k))
+    from .polys import _QUAD, _paste_front
+    quads, mats, resize, rects, canvas_off, pitch, nbytes, layers, order, counts = _paste_front(
+        size, quads, blend_desc, blend_bytes, scale, H, feather, limits, qlimits if qlimits is not None else quad_limits(), _QUAD,
+        lambda quad: quad_matrices(quad, scale))
     warp = []
     for k in order:
         bw, bh = quad_size(quads[k])
         _, m, (x0, y0, x1, y1) = mats[k]
         warp.append(warp_row(rects[k], scale * bh, scale * bw, 3 * scale * bw, canvas_off + scale * y0 * pitch + 3 * scale * x0,
                              scale * (y1 - y0), scale * (x1 - x0), pitch, feather, 1, m))
-    counts = [layers.count(l) for l in range(max(layers) + 1)] if layers else []
     return QuadPastePlan(resize, np.array(warp, np.int32).reshape(-1, QUAD_DESC), layers, order, counts, rects, canvas_off, pitch, nbytes)

@@ -20,7 +20,7 @@ from __future__ import annotations
 import numbers
 from collections import namedtuple
 
-from .lines import Line, _line_takes, _super_resolve_boxes_host, line_limits, line_plan, line_windows_host
+from .lines import Line, _compose_front, _line_takes, _region_windows_host, _super_resolve_boxes_host, line_limits, line_plan
 
 SCENE_MIN_SIDE = 4        # shortest side of a box: with it no paste shrinks by more than 16 : 1 (one window is 4 : 1, a line 16 rows high)
 SCENE_DESC = 16           # ints per window row of tatt_scene_windows (include/tatt_hip.h)
@@ -29,6 +29,10 @@ _ALIGN = 16
 
 ScenePlan = namedtuple("ScenePlan", "arrays offsets desc lines nbytes out_floats")
 PastePlan = namedtuple("PastePlan", "rows layers order counts canvas_off pitch nbytes")
+
+
+def _up(n):
+    return -(-int(n) // _ALIGN) * _ALIGN
 
 
 def scene_limits():
@@ -77,18 +81,7 @@ def scene_windows_host(scene, boxes, lr_size=(16, 64), stride: int = 32, mask: b
     """RGB PIL image, boxes -> (stack, lines): the concatenation of `line_windows_host(scene.crop(box), ...)` over the boxes, an
     (n_windows, 3 + mask, h, w) float stack, and lines[k] = Line(wl, starts, first window index) of box k.  Every box is a line: a box no
     wider than the LR window's aspect ratio (4 : 1) is one window."""
-    import torch
-    boxes = scene_check(scene.size, boxes)
-    h, w = lr_size
-    parts, lines, first = [], [], 0
-    for box in boxes:
-        crop = scene.crop(box)
-        wl, starts = line_plan(crop.size, lr_size, stride)
-        parts.append(line_windows_host(crop, lr_size, stride, mask))
-        lines.append(Line(wl, starts, first))
-        first += len(starts)
-    stack = torch.cat(parts) if parts else torch.zeros(0, 3 + int(bool(mask)), h, w)
-    return stack, lines
+    return _region_windows_host(scene_check(scene.size, boxes), scene.crop, lr_size, stride, mask)
 
 
 def scene_layers(boxes):
@@ -100,6 +93,13 @@ def scene_layers(boxes):
         below = [layers[j] for j, (a0, b0, a1, b1) in enumerate(boxes[:k]) if x0 < a1 and a0 < x1 and y0 < b1 and b0 < y1]
         layers.append(1 + max(below) if below else 0)
     return layers
+
+
+def _paste_order(boxes):
+    """-> (layers, order, counts): `scene_layers` of the boxes, the paste order by (layer, index), the boxes of every layer"""
+    layers = scene_layers(boxes)
+    order = sorted(range(len(boxes)), key=lambda k: (layers[k], k))
+    return layers, order, [layers.count(l) for l in range(max(layers) + 1)] if layers else []
 
 
 def _feather_weight(oh, ow, feather):
@@ -122,22 +122,12 @@ def scene_compose_host(scene, boxes, line_images, scale: int, feather: int = 0, 
     boxes = scene_check(scene.size, boxes)
     if not (isinstance(scale, int) and scale >= 1):
         raise ValueError("scene: scale must be a positive int; got %r" % (scale,))
-    if not (isinstance(feather, int) and not isinstance(feather, bool) and feather >= 0):
-        raise ValueError("scene: feather must be an int >= 0; got %r" % (feather,))
-    if len(line_images) != len(boxes):
-        raise ValueError("scene: %d line images for %d boxes" % (len(line_images), len(boxes)))
-    if scene.mode != "RGB":
-        raise ValueError("scene: an RGB PIL image is taken; got %r" % (scene.mode,))
-    ws, hs = scene.size
-    full = (scale * ws, scale * hs)
-    canvas = np.array(scene if scale == 1 else scene.resize(full, Image.BICUBIC))
+    canvas, line = _compose_front(("scene", "boxes"), scene, len(boxes), line_images, scale, feather)
     D = feather + 1
     for k in (range(len(boxes)) if order is None else order):
         x0, y0, x1, y1 = boxes[k]
-        im = line_images[k]
-        im = im if isinstance(im, Image.Image) else Image.fromarray(np.ascontiguousarray(im), "RGB")
         ow, oh = scale * (x1 - x0), scale * (y1 - y0)
-        new = np.asarray(im if im.size == (ow, oh) else im.resize((ow, oh), Image.BICUBIC)).astype(np.int64)
+        new = line(k, ow, oh).astype(np.int64)
         rect = canvas[scale * y0:scale * y1, scale * x0:scale * x1]
         if feather:
             a = _feather_weight(oh, ow, feather)[:, :, None]
@@ -176,7 +166,7 @@ def scene_plan(scene, boxes, lr_size=(16, 64), stride: int = 32, mask: bool = Tr
     a = np.asarray(scene)
     Hs, Ws = a.shape[:2]
     arrays, offsets, rows, lines = [a], [0], [], []
-    off, out_off, planes = -(-a.size // _ALIGN) * _ALIGN, 0, 3 + int(bool(mask))
+    off, out_off, planes = _up(a.size), 0, 3 + int(bool(mask))
     for k, (x0, y0, x1, y1) in enumerate(boxes):
         bw, bh = x1 - x0, y1 - y0
         wl, starts = line_plan((bw, bh), (h, w), stride)
@@ -190,7 +180,7 @@ def scene_plan(scene, boxes, lr_size=(16, 64), stride: int = 32, mask: bool = Tr
             arrays.append(small)
             offsets.append(off)
             src = (off, h, wl, 3 * wl, 0, 0)
-            off += -(-small.size // _ALIGN) * _ALIGN
+            off += _up(small.size)
         lines.append(Line(wl, starts, len(rows)))
         for x in starts:
             rows.append((src[0], src[1], src[2], h, wl, x, w, int(bool(mask)), out_off, src[3], src[4], src[5], 0, 0, 0, 0))
@@ -206,7 +196,7 @@ def scene_fill(flat, plan):
     """Write one staging slot: flat: a writable 1-D uint8 array -> (pix, used).  Layout: descriptor table at 0 | source i at
     `pix + plan.offsets[i]` (the scene first), all 16-byte aligned; `scene_fill(None, plan)` only computes the offsets."""
     import numpy as np
-    pix = -(-plan.desc.nbytes // _ALIGN) * _ALIGN
+    pix = _up(plan.desc.nbytes)
     used = pix + plan.nbytes
     if flat is not None:
         flat[:plan.desc.nbytes].view(np.int32)[:] = plan.desc.reshape(-1)
@@ -235,13 +225,12 @@ def paste_plan(size, boxes, blend_desc, blend_bytes, scale: int, H: int, feather
         raise ValueError("scene: %d lines for %d boxes" % (len(blend_desc), len(boxes)))
     if scale * max(ws, hs) > lim["side"]:
         raise ValueError("scene: the canvas %d x %d is beyond the largest side %d" % (scale * ws, scale * hs, lim["side"]))
-    canvas_off = -(-int(blend_bytes) // _ALIGN) * _ALIGN
+    canvas_off = _up(blend_bytes)
     pitch = 3 * scale * ws
     nbytes = canvas_off + scale * hs * pitch
     if nbytes >= 2 ** 31 or hs * ws * 3 >= 2 ** 31:
         raise ValueError("DeviceExporter: the scene does not fit 32-bit offsets")
-    layers = scene_layers(boxes)
-    order = sorted(range(len(boxes)), key=lambda k: (layers[k], k))
+    layers, order, counts = _paste_order(boxes)
     rows = np.zeros((1 + len(boxes), RESIZE_DESC), np.int32)
     rows[0, :9] = (0, hs, ws, 3 * ws, canvas_off, scale * hs, scale * ws, pitch, 0)
     for r, k in enumerate(order):
@@ -252,5 +241,4 @@ def paste_plan(size, boxes, blend_desc, blend_bytes, scale: int, H: int, feather
         if H > lim["down"] * oh or lw > lim["down"] * ow:
             raise ValueError("scene: box %d: pasting %d x %d into %d x %d shrinks by more than %d" % (k, H, lw, oh, ow, lim["down"]))
         rows[1 + r, :9] = (int(d[6]), H, lw, int(d[7]), canvas_off + scale * y0 * pitch + 3 * scale * x0, oh, ow, pitch, feather)
-    counts = [layers.count(l) for l in range(max(layers) + 1)] if layers else []
     return PastePlan(rows, layers, order, counts, canvas_off, pitch, nbytes)

@@ -89,6 +89,34 @@ def test_four_points_give_what_the_quad_path_gives(quad, scale):
         assert not np.array_equal(got, before)
 
 
+def test_quad_plans_are_the_poly_plans_of_four_point_regions():
+    """the five quads of tests/test_quads.py as quads and as polygons of four points: the same window plan, the same paste plan up to
+    the rows of the paste launch, whose shared words and matrices agree"""
+    from tatt_amd import io
+    from tests.test_quads import FIVE
+    scene = _img(3, 97, 211)
+    polys = [_as_poly(q) for q in FIVE]
+    a, b = io.quad_plan(scene, FIVE, LR, 32, True), io.poly_plan(scene, polys, LR, 32, True)
+    for name in ("offsets", "lines", "upload", "nbytes", "out_floats"):
+        assert getattr(a, name) == getattr(b, name), name
+    for name in ("warp", "resize", "desc"):
+        assert np.array_equal(getattr(a, name), getattr(b, name)), name
+    assert len(a.arrays) == len(b.arrays) and all(np.array_equal(x, y) for x, y in zip(a.arrays, b.arrays))
+    lines = a.lines
+    n = lines[-1].first + len(lines[-1].starts)
+    for scale in (1, 2):
+        bdesc, _, bbytes = io.blend_plan(lines, n, 16 * scale, 64 * scale, scale, "floor", 0)
+        a = io.quad_paste_plan(SIZE, FIVE, bdesc, bbytes, scale, 16 * scale, 3)
+        b = io.poly_paste_plan(SIZE, polys, bdesc, bbytes, scale, 16 * scale, 3)
+        for name in ("layers", "order", "counts", "rects", "canvas_off", "pitch", "nbytes"):
+            assert getattr(a, name) == getattr(b, name), (scale, name)
+        assert np.array_equal(a.resize, b.resize)
+        assert len(a.warp) == len(b.items) == len(b.strips) == len(FIVE)
+        for r, (row, item) in enumerate(zip(a.warp, b.items)):
+            assert list(row[:9]) == list(item[:9]) and list(item[9:11]) == [r, 1], (scale, r)
+            assert list(row[10:28]) == list(b.strips[r][2:20]), (scale, r)
+
+
 # ---- the claim rule against exact rational geometry ---------------------------------------------------------------------------------
 def _cross(a, b, p):
     return (b[0] - a[0]) * (p[1] - a[1]) - (b[1] - a[1]) * (p[0] - a[0])
@@ -423,6 +451,12 @@ def test_poly_paste_entry_return_codes_on_host_rows():
     assert run(item(src=-1)) == 3 and run(item(sp=449)) == 3 and run(item(), s=sb - 1) == 3 and run(item(src=1)) == 3
     assert run(item(dst=-16)) == 3 and run(item(dp=899)) == 3 and run(item(), d=db - 13) == 3 and run(item(dst=32)) == 3
     assert run(item(first=1)) == 4 and run(item(first=-1)) == 4 and run(item(), n_strips=2) == 4 and run(item(first=3, count=1)) == 4
+    # two faults in one item: the first test in the entry's order decides (reserved words and feather sign; sides, feather and strip
+    # count; buffers; the strip table; the strips' columns)
+    assert run(item(r11=1, count=0)) == 1 and run(item(f=-1, hs=0)) == 1 and run(item(f=-1, src=-1)) == 1
+    assert run(item(count=0, src=-1)) == 2 and run(item(count=lim["strips"] + 1, dp=899)) == 2 and run(item(hs=0, first=-1)) == 2
+    assert run(item(count=0, first=-1)) == 2 and run(item(f=lim["feather"] + 1, dst=-16)) == 2
+    assert run(item(sp=449, first=1)) == 3 and run(item(ws=149, src=-1)) == 3 and run(item(ws=149, first=1)) == 4
 
 
 # ---- build --------------------------------------------------------------------------------------------------------------------------

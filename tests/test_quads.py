@@ -355,6 +355,10 @@ def test_warp_entry_return_codes_on_host_rows():
     assert rc([row()] * (lim["items"] + 1)) == 2
     assert run(row(src=-1)) == 3 and run(row(sp=449)) == 3 and run(row(), s=sb - 1) == 3 and run(row(src=1)) == 3
     assert run(row(dst=-16)) == 3 and run(row(dp=899)) == 3 and run(row(), d=db - 13) == 3 and run(row(dst=32)) == 3
+    # two faults in one row: the first test in the entry's order decides (reserved words, feather sign and mode; sides and feather; buffers)
+    assert run(row(mode=2, hs=0)) == 1 and run(row(mode=-1, sp=449)) == 1 and run(row(r28=1, src=-1)) == 1 and run(row(f=-1, dp=899)) == 1
+    assert run(row(mode=2, f=lim["feather"] + 1)) == 1 and run(row(hs=0, src=-1)) == 2 and run(row(f=lim["feather"] + 1, dst=-16)) == 2
+    assert run(row(oh=lim["side"] + 1, dp=899)) == 2 and run(row(src=-1, dst=-16)) == 3
 
 
 # ---- build --------------------------------------------------------------------------------------------------------------------------

@@ -37,7 +37,7 @@ def _diff(g, w):
 
 
 # ---- the kernel ---------------------------------------------------------------------------------------------------------------------
-def _warp_items():
+def warp_items():
     """[(source, matrix, OH, OW, mode, feather)]: identity, rotated and perspective matrices; destination heights and widths 1, tile - 1,
     tile, tile + 1; both modes; feather 0, 1 and 5"""
     from tatt_amd import io
@@ -63,10 +63,9 @@ def _warp_items():
     return items
 
 
-def _run_warp(dev, items, seed=1):
-    """-> (the targets cut out of the destination, what the host yardstick makes of them, whether every byte outside the targets kept its
-    value): every source and every target lies at a non-zero offset with a pitch wider than its rows"""
-    from tatt_amd import io, ops
+def warp_layout(items, seed=1):
+    """-> (the rows, the source buffer, the destination before the launch, [(offset, pitch, OH, OW)]): every source and every target lies
+    at a non-zero offset with a pitch wider than its rows"""
     from tatt_amd.quads import warp_row
     rows, soff, doff, srcs, rects = [], 16, 48, [], []
     for a, m, oh, ow, mode, f in items:
@@ -81,26 +80,41 @@ def _run_warp(dev, items, seed=1):
     for o, sp, a in srcs:
         np.lib.stride_tricks.as_strided(sbuf[o:], a.shape, (sp, 3, 1))[...] = a
     before = np.random.default_rng(seed).integers(0, 256, doff, dtype=np.uint8)
+    return np.array(rows, np.int32), sbuf, before, rects
+
+
+def warp_wants(items, before, rects):
+    """what the host yardstick makes of every target, and the mask of the bytes outside all targets"""
+    from tatt_amd import io
+    want, keep = [], np.ones(before.size, bool)
+    for (a, m, oh, ow, mode, f), (o, dp, _, _) in zip(items, rects):
+        old = np.lib.stride_tricks.as_strided(before[o:], (oh, ow, 3), (dp, 3, 1)).copy()
+        want.append(io.warp_u8_host(a, m, oh, ow, old, f) if mode else io.warp_u8_host(a, m, oh, ow))
+        for y in range(oh):
+            keep[o + y * dp:o + y * dp + 3 * ow] = False
+    return want, keep
+
+
+def _run_warp(dev, items, seed=1):
+    """-> (the targets cut out of the destination, what the host yardstick makes of them, whether every byte outside the targets kept its
+    value)"""
+    from tatt_amd import ops
+    rows, sbuf, before, rects = warp_layout(items, seed)
     s, d = torch.from_numpy(sbuf).to(dev), torch.from_numpy(before).to(dev)
-    host = torch.tensor(rows, dtype=torch.int32)
+    host = torch.from_numpy(rows)
     desc = host.to(dev)
     rc = ops.LIB.tatt_warp_u8(ops.P(s), s.numel(), ctypes.c_void_p(desc.data_ptr()), ctypes.c_void_p(host.data_ptr()), len(rows), ops.P(d),
                               d.numel(), ops.stream())
     assert rc == 0, rc
     out = d.cpu().numpy()
-    got, want, keep = [], [], np.ones(out.size, bool)
-    for (a, m, oh, ow, mode, f), (o, dp, _, _) in zip(items, rects):
-        got.append(np.lib.stride_tricks.as_strided(out[o:], (oh, ow, 3), (dp, 3, 1)).copy())
-        old = np.lib.stride_tricks.as_strided(before[o:], (oh, ow, 3), (dp, 3, 1)).copy()
-        want.append(io.warp_u8_host(a, m, oh, ow, old, f) if mode else io.warp_u8_host(a, m, oh, ow))
-        for y in range(oh):
-            keep[o + y * dp:o + y * dp + 3 * ow] = False
+    want, keep = warp_wants(items, before, rects)
+    got = [np.lib.stride_tricks.as_strided(out[o:], (oh, ow, 3), (dp, 3, 1)).copy() for o, dp, oh, ow in rects]
     return got, want, np.array_equal(out[keep], before[keep])
 
 
 def test_warp_equals_the_host_yardstick_in_one_launch_and_alone(dev):
     from tatt_amd import io
-    items = _warp_items()
+    items = warp_items()
     got, want, outside = _run_warp(dev, items)                       # all items in one launch
     for n, (g, w) in enumerate(zip(got, want)):
         assert np.array_equal(g, w), (n, items[n][2:], int((g != w).sum()), g.size)

@@ -1,5 +1,6 @@
 """The five Pillow-resampling entries of csrc/pil_resample.h's two bodies -- tatt_collate_images, tatt_line_windows, tatt_scene_windows
-(the window body), tatt_resize_u8, tatt_line_luma (the tile body) -- on TWO builds of the library in one process: the tree's
+(the window body), tatt_resize_u8, tatt_line_luma (the tile body) -- and the two entries of csrc/warp_pixel.h's pixel functions --
+tatt_warp_u8 in both modes, tatt_poly_paste_u8 -- on TWO builds of the library in one process: the tree's
 libtatt_hip.so and the one given by --against (the same C ABI, e.g. the parent commit's build), alternating the two.  Both are taken as built
 (`python -m tatt_amd.build` first).  Reports only (one JSON line), asserts nothing but that the two libraries write the same bytes.
 
@@ -11,6 +12,9 @@ Shapes, the defaults of the tools that measure the paths around these entries:
   scene_windows   tools/bench_scene.py: seeded scenes 720x1280 with 8 and with 40 boxes, 2160x3840 with 40 boxes (three launches)
   resize_u8       the same scenes: the 2 x background and one launch per paste layer, feather 2, from line canvases of seeded bytes
   line_luma       tools/bench_read.py: the line canvases (32 rows, 2 wl columns) of `lines16` and of the 40 boxes of the 720x1280 scene
+  warp_rectify    tools/bench_quads.py --cases 720x1280x40: the mode-0 rows of its 40 quads, scene -> crops (one launch)
+  warp_paste      the same quads: the mode-1 rows at scale 2, feather 2, rectangles of seeded bytes -> canvas (one launch per layer)
+  poly_paste      tools/bench_polys.py --cases 720x1280x40x7: the item and strip rows of its 40 polygons of N = 7, scale 2, feather 2, all layers
 The calls go through ctypes with the argument lists the Python layer builds (its `*_plan` functions), the same lists for both libraries.
 A timed window is `passes` passes over the entry's launches back to back between two device events, ending in a synchronise; `passes`
 is chosen once per entry so that a window lasts about --window-ms (far above the launch overhead) and `launches_<entry>` records
@@ -57,10 +61,29 @@ class Launch:
         assert rc == 0, (self.name, rc)
 
 
+class PolyLaunch(Launch):
+    """one call of tatt_poly_paste_u8: the items of a layer (`desc`) and the strip table all layers share"""
+
+    def __init__(self, dev, src, src_size, items, strips, out, init=None):
+        import numpy as np
+        Launch.__init__(self, dev, "tatt_poly_paste_u8", src, src_size, items, out, init)
+        self.strips_host = np.ascontiguousarray(strips, np.int32)
+        self.strips = torch.from_numpy(self.strips_host).to(dev)
+
+    def __call__(self, lib):
+        from tatt_amd import ops
+        rc = lib.tatt_poly_paste_u8(ops.P(self.src), self.src_size, ops.P(self.desc), ctypes.c_void_p(self.host.ctypes.data), len(self.host),
+                                    ops.P(self.strips), ctypes.c_void_p(self.strips_host.ctypes.data), len(self.strips_host),
+                                    ops.P(self.out), self.out.numel(), ops.stream())
+        assert rc == 0, (self.name, rc)
+
+
 def make_cases(dev):
     """-> {entry: [Launch]}"""
     import numpy as np
     from PIL import Image
+    from bench_polys import make_polys
+    from bench_quads import make_quads
     from bench_scene import make_boxes
     from tatt_amd import io, lines, read, scene
     from tests.pil_resample_ref import make_batch, make_image
@@ -117,6 +140,39 @@ def make_cases(dev):
         plan = read.read_plan([(int(d[6]), 32, int(d[3]) * int(d[2]), int(d[7])) for d in bdesc], 2)
         src = torch.randint(0, 256, (bbytes,), dtype=torch.uint8, device=dev, generator=torch.Generator(dev).manual_seed(bbytes))
         cases["line_luma"].append(Launch(dev, "tatt_line_luma", src, bbytes, plan.desc, floats(plan.floats)))
+
+    def seeded(n):
+        return torch.randint(0, 256, (n,), dtype=torch.uint8, device=dev, generator=torch.Generator(dev).manual_seed(n))
+
+    def pastes(regions, sizes, plan_of):
+        """the paste plan of the regions at scale 2, feather 2, and its buffer: the rectangles and the canvas hold seeded bytes"""
+        lns = []
+        for size in sizes:
+            wl, starts = io.line_plan(size)
+            lns.append(lines.Line(wl, starts, sum(len(ln.starts) for ln in lns)))
+        bdesc, _, bbytes = lines.blend_plan(lns, lns[-1].first + len(lns[-1].starts), 32, 128, 2)
+        plan = plan_of(regions, bdesc, bbytes, 2, 32, 2)
+        return plan, torch.empty(plan.nbytes, dtype=torch.uint8, device=dev), seeded(plan.nbytes)
+
+    rng = np.random.default_rng(7)                                   # (the quads and the polygons the two tools draw when given the one case)
+    img = Image.fromarray(make_image(rng, 720, 1280, 0), "RGB")
+    quads = make_quads(rng, 720, 1280, 40)
+    plan = io.quad_plan(img, quads)
+    buf = packed(plan.arrays, plan.offsets, plan.nbytes)             # the scene in front, the crops behind it in the same buffer
+    cases["warp_rectify"] = [Launch(dev, "tatt_warp_u8", buf, plan.nbytes, plan.warp, buf)]
+    paste, out, init = pastes(quads, [io.quad_size(q) for q in quads], lambda *a: io.quad_paste_plan(img.size, *a))
+    cases["warp_paste"], r = [], 0
+    for c in paste.counts:                                           # (only the first launch restores `init`, as for resize_u8)
+        cases["warp_paste"].append(Launch(dev, "tatt_warp_u8", out, paste.canvas_off, paste.warp[r:r + c], out, init if r == 0 else None))
+        r += c
+    rng = np.random.default_rng(7)
+    img = Image.fromarray(make_image(rng, 720, 1280, 0), "RGB")
+    polys = make_polys(rng, 720, 1280, 40, 7)
+    paste, out, init = pastes(polys, [io.poly_size(p) for p in polys], lambda *a: io.poly_paste_plan(img.size, *a))
+    cases["poly_paste"], r = [], 0
+    for c in paste.counts:
+        cases["poly_paste"].append(PolyLaunch(dev, out, paste.canvas_off, paste.items[r:r + c], paste.strips, out, init if r == 0 else None))
+        r += c
     return cases
 
 

@@ -1,8 +1,10 @@
-"""The polygon paste off the GPU: the check and the pixel function of tatt_poly_paste_u8 (csrc/poly_pixel.h, `__host__ __device__`: the
-very text the kernel runs) compiled with tools/polys_host/main.cpp into a STAND-ALONE program under -fsanitize=address,undefined and run
-over the items of tests/test_polys_device_gpu.py (N = 2, 4, 5 and 8; targets of 1, tile - 1, tile and tile + 1 rows and columns; feather
-0, 1 and 5; scale 1 and 2; lines and targets at non-zero offsets with wide pitches) against arrays the specification
-(`tatt_amd.polys.poly_paste_host`) writes.  Nothing is loaded into this process.  It is a check for the BUILD machine (CPUs, no GPU); it
+"""The polygon paste and the warp off the GPU: the checks and the pixel functions of tatt_poly_paste_u8 and tatt_warp_u8
+(csrc/warp_pixel.h, `__host__ __device__`: the very text the kernels run) compiled with tools/polys_host/main.cpp into a STAND-ALONE
+program under -fsanitize=address,undefined and run in two passes: over the items of tests/test_polys_device_gpu.py (N = 2, 4, 5 and 8;
+targets of 1, tile - 1, tile and tile + 1 rows and columns; feather 0, 1 and 5; scale 1 and 2; lines and targets at non-zero offsets with
+wide pitches) against arrays the specification (`tatt_amd.polys.poly_paste_host`) writes, and over the rows of tests/
+test_quads_device_gpu.py (identity, rotated and perspective matrices; the same target sizes; both modes; feather 0, 1 and 5) against
+arrays `tatt_amd.quads.warp_u8_host` writes.  Nothing is loaded into this process.  It is a check for the BUILD machine (CPUs, no GPU); it
 is not run on a GPU machine, and it stops where LD_PRELOAD is set: a sanitized program must be the first thing loaded, and the tool
 leaves that setting as it is.
 
@@ -31,16 +33,24 @@ def main():
               "nothing; it leaves the setting as it is.")
         return 2
     from tests.test_polys_device_gpu import paste_items, paste_layout, paste_wants
+    from tests.test_quads_device_gpu import warp_items, warp_layout, warp_wants
+
+    def expected(before, want, rects):
+        full = before.copy()
+        for w, (o, dp, oh, ow) in zip(want, rects):
+            np.lib.stride_tricks.as_strided(full[o:], (oh, ow, 3), (dp, 3, 1))[...] = w
+        return full
     items = paste_items()
     rows, strips, sbuf, before, rects = paste_layout(items)
-    want, _ = paste_wants(items, before, rects)
-    full = before.copy()
-    for w, (o, dp, oh, ow) in zip(want, rects):
-        np.lib.stride_tricks.as_strided(full[o:], (oh, ow, 3), (dp, 3, 1))[...] = w
+    full = expected(before, paste_wants(items, before, rects)[0], rects)
+    items = warp_items()
+    wrows, wsbuf, wbefore, wrects = warp_layout(items)
+    wfull = expected(wbefore, warp_wants(items, wbefore, wrects)[0], wrects)
     work = a.keep or tempfile.mkdtemp(prefix="polys_host_")
     os.makedirs(work, exist_ok=True)
     try:
-        for name, arr in (("rows", rows), ("strips", strips), ("src", sbuf), ("before", before), ("want", full)):
+        for name, arr in (("rows", rows), ("strips", strips), ("src", sbuf), ("before", before), ("want", full), ("warp_rows", wrows),
+                          ("warp_src", wsbuf), ("warp_before", wbefore), ("warp_want", wfull)):
             arr.tofile(os.path.join(work, name + ".bin"))
         cxx = os.environ.get("CXX", "/opt/rocm/llvm/bin/clang++")
         exe = os.path.join(work, "polys_host")
